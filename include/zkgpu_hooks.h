@@ -90,7 +90,9 @@ long long zkgpu_debug_force_regroup(zkgpu_ctx *ctx, int on);
  * GPU; world = 0 restores RCCL; world < 0 only asks.  Returns the all-gathers the mock has served.  A communicator keeps the function table it
  * was created with for its whole life, whatever the switch does afterwards.
  * (A second rehearsal aid lives in the environment: ZKGPU_TEST_COMM_STALL="init:<rank>|init:all|gather:<rank>|gather:all"
- * beside ZKGPU_TEST_HOOKS=1 makes ncclCommInitRank / the first ncclAllGather of the named rank never return.) */
+ * beside ZKGPU_TEST_HOOKS=1 makes ncclCommInitRank / the first ncclAllGather of the named rank never return.  A third:
+ * ZKGPU_TEST_ASSUME_QUEUES=<n> beside it is the queue count zkgpu_verifier_create judges for its second-verifier warning,
+ * in place of GPU_MAX_HW_QUEUES; it makes no queue.) */
 long long zkgpu_debug_comm_mock(zkgpu_ctx *ctx, int world, const uint8_t *peer_slots, size_t slot_bytes);
 /* Fault injection (csrc/fault_gate.hpp): the n-th HIP runtime call the library makes from now on -- allocation, copy, event,
  * stream, synchronisation, the hipGetLastError that collects a launch -- reports hipErrorUnknown WITHOUT being made (the device
