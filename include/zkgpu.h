@@ -263,6 +263,30 @@ int zkgpu_r1cs_verify_batch(zkgpu_ctx *ctx, const zkgpu_pointset *ps, const zkgp
                             size_t batch, const uint8_t *commitments, const uint8_t *proofs, size_t proof_len,
                             const uint8_t *r_bytes, uint8_t *accept_bitmap, int host_threads);
 
+/* Statements of DIFFERENT constraint systems in one device call (what Tx::verify hands over for transactions whose
+ * programs each build their own system; upstream's batch verification takes a list of verifiers, each with its own
+ * constraint system).  Statement i is checked against plans[plan_index[i]] (cloak and described plans alike: any label,
+ * m, n1, n, padded n, phases, second-phase challenges, IPA rounds); commitments: each statement's m x 32 bytes, back to
+ * back; proofs / proof_offsets: a CSR of R1CSProof encodings (batch + 1 offsets, the first 0), either wire form the
+ * statement's plan accepts (the library reads exactly 32 m bytes of commitments per statement: a binding checks what it
+ * was handed against that); r_bytes: 64 per statement, or NULL to draw them from the OS.  Bit i of accept_bitmap is what
+ * zkgpu_r1cs_verify_batch_gpu(ctx, ps, plans[plan_index[i]], 1, ..) gives for that statement alone with the same r; a
+ * malformed proof (wrong length, non-canonical scalar, forbidden identity) clears its own bit only.  ZKGPU_EINVAL with
+ * the bitmap zeroed, before any device work: a plan index out of range, a NULL plan, a plan that needs more generators
+ * than ps holds, decreasing offsets or a first offset other than 0.  batch = 0 is OK (accept_bitmap may then be NULL).
+ * The preparation is one launch per stage whatever the number of plans (the scalar preparation once per LDS class present:
+ * plans that leave room for two or more workgroups per CU, and those that do not), and the multiscalar multiplications
+ * cover each statement's own rows; statements are
+ * checked alone (no group checks).  *_submit: as zkgpu_cloak_verify_submit (host buffers free on return), collected by
+ * zkgpu_verify_wait. */
+int zkgpu_r1cs_verify_mixed(zkgpu_ctx *ctx, const zkgpu_pointset *ps, zkgpu_r1cs_plan *const *plans, size_t n_plans,
+                            size_t batch, const uint32_t *plan_index, const uint8_t *commitments,
+                            const uint8_t *proofs, const uint64_t *proof_offsets, const uint8_t *r_bytes,
+                            uint8_t *accept_bitmap);
+int zkgpu_r1cs_verify_mixed_submit(zkgpu_ctx *ctx, const zkgpu_pointset *ps, zkgpu_r1cs_plan *const *plans, size_t n_plans,
+                                   size_t batch, const uint32_t *plan_index, const uint8_t *commitments,
+                                   const uint8_t *proofs, const uint64_t *proof_offsets, const uint8_t *r_bytes);
+
 /* The prover for a described constraint system (BASELINE.json configs[4]: "R1CS proving -- Pedersen vector commits +
  * IPA -- for a 1024-constraint program"; replaces bulletproofs r1cs::Prover::{commit, constraint collection, prove}).
  * Beyond the description the prover needs the witness:

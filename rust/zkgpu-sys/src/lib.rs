@@ -158,6 +158,16 @@ extern "C" {
         batch: usize, commitments: *const u8, proofs: *const u8, proof_len: usize, r_bytes: *const u8,
         accept_bitmap: *mut u8, host_threads: c_int,
     ) -> c_int;
+    pub fn zkgpu_r1cs_verify_mixed(
+        ctx: *mut zkgpu_ctx, ps: *const zkgpu_pointset, plans: *const *mut zkgpu_cloak_plan, n_plans: usize,
+        batch: usize, plan_index: *const u32, commitments: *const u8, proofs: *const u8, proof_offsets: *const u64,
+        r_bytes: *const u8, accept_bitmap: *mut u8,
+    ) -> c_int;
+    pub fn zkgpu_r1cs_verify_mixed_submit(
+        ctx: *mut zkgpu_ctx, ps: *const zkgpu_pointset, plans: *const *mut zkgpu_cloak_plan, n_plans: usize,
+        batch: usize, plan_index: *const u32, commitments: *const u8, proofs: *const u8, proof_offsets: *const u64,
+        r_bytes: *const u8,
+    ) -> c_int;
     pub fn zkgpu_r1cs_prove_batch(
         ctx: *mut zkgpu_ctx, ps: *const zkgpu_pointset, desc: *const zkgpu_r1cs_desc, mult_def: *const u32,
         gens_capacity: usize, batch: usize, values: *const u8, blindings: *const u8, given: *const u8, n_given: usize,

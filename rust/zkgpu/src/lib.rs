@@ -482,6 +482,86 @@ impl GpuVerifier {
     }
 }
 
+/// A constraint system compiled for the device (`zkgpu_r1cs_plan_create`): what `verify_r1cs_mixed` checks statements
+/// against.  Cache plans by a hash of the description; a plan lives no longer than its verifier.
+pub struct R1csPlan<'v> {
+    p: *mut sys::zkgpu_cloak_plan,
+    m: usize, // commitments per statement: the library reads 32 m bytes of each statement's commitments
+    _v: std::marker::PhantomData<&'v GpuVerifier>,
+}
+
+impl Drop for R1csPlan<'_> {
+    fn drop(&mut self) {
+        unsafe { sys::zkgpu_r1cs_plan_destroy(self.p) };
+    }
+}
+
+/// One statement of a mixed call: `plan` indexes the call's plan list; `commitments`: that plan's m x 32 bytes.
+pub struct R1csStatement<'a> {
+    pub plan: u32,
+    pub commitments: &'a [u8],
+    pub proof: &'a [u8],
+}
+
+impl GpuVerifier {
+    /// Compiles the constraint system a program built (traced into `desc`).
+    pub fn r1cs_plan(&self, desc: &sys::zkgpu_r1cs_desc) -> Result<R1csPlan<'_>, Error> {
+        let mut p: *mut sys::zkgpu_cloak_plan = ptr::null_mut();
+        check(unsafe { sys::zkgpu_r1cs_plan_create(self.ctx, desc, self.gens.capacity, &mut p) }, || {
+            text(unsafe { sys::zkgpu_last_error(self.ctx) })
+        })?;
+        Ok(R1csPlan { p, m: desc.n_commitments as usize, _v: std::marker::PhantomData })
+    }
+
+    /// `r1cs::Verifier::verify` for statements of DIFFERENT constraint systems in one device call: one verdict per
+    /// statement, in order.  A malformed proof is a `false` of its own; `Err` = no verdicts at all.
+    pub fn verify_r1cs_mixed(&self, plans: &[&R1csPlan<'_>], stmts: &[R1csStatement<'_>], randomness: Option<&[u8]>) -> Result<Vec<bool>, Error> {
+        let n = stmts.len();
+        if let Some(r) = randomness {
+            if r.len() != 64 * n {
+                return Err(Error::InvalidArgument("randomness: 64 bytes per statement".into()));
+            }
+        }
+        let handles: Vec<*mut sys::zkgpu_cloak_plan> = plans.iter().map(|p| p.p).collect();
+        let mut index = Vec::with_capacity(n);
+        let mut com = Vec::new();
+        let mut proofs = Vec::new();
+        let mut offs = Vec::with_capacity(n + 1);
+        offs.push(0u64);
+        for s in stmts {
+            // the library reads exactly 32 m bytes per statement, m from its plan: what it is handed must be that
+            let plan = plans.get(s.plan as usize).ok_or_else(|| Error::InvalidArgument("plan index out of range".into()))?;
+            if s.commitments.len() != 32 * plan.m {
+                return Err(Error::InvalidArgument("commitments: 32 bytes per commitment of the statement's plan".into()));
+            }
+            index.push(s.plan);
+            com.extend_from_slice(s.commitments);
+            proofs.extend_from_slice(s.proof);
+            offs.push(proofs.len() as u64);
+        }
+        let mut bitmap = vec![0u8; (n + 7) / 8];
+        check(
+            unsafe {
+                sys::zkgpu_r1cs_verify_mixed(
+                    self.ctx,
+                    self.gens.ps,
+                    handles.as_ptr(),
+                    handles.len(),
+                    n,
+                    index.as_ptr(),
+                    com.as_ptr(),
+                    proofs.as_ptr(),
+                    offs.as_ptr(),
+                    randomness.map_or(ptr::null(), |r| r.as_ptr()),
+                    bitmap.as_mut_ptr(),
+                )
+            },
+            || text(unsafe { sys::zkgpu_last_error(self.ctx) }),
+        )?;
+        Ok(bits(&bitmap, n))
+    }
+}
+
 impl Drop for GpuVerifier {
     fn drop(&mut self) {
         unsafe {

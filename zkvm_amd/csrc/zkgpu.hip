@@ -143,7 +143,7 @@ struct zkgpu_ctx {
   std::vector<zkgpu_ctx*> pv_slices;    // helper contexts (one stream each) on which the slices 1.. of a prover call run (run_sliced)
   std::vector<uint32_t> pv_plan_host;   // the tables pv_plan holds (compared before uploading again)
   size_t pv_lay_batch = 0;              // batch size the scaffolding in pv_lay was built for (0: none)
-  Buffer prep_absorb, prep_raw;    // cooperative transcript: absorbed words per segment, raw challenge bytes
+  Buffer prep_absorb, prep_raw, mx_tab, mx_st_index;    // cooperative transcript: absorbed words per segment, raw challenge bytes | zkgpu_r1cs_verify_mixed: per-call tables, generator index
   int locate_mode = 0;             // failed groups: 0 automatic, 1 always re-check every transaction, 2 always locate the culprit
   int transcript_mode = 0;         // 0 automatic, 1 one lane per transaction, 2 one wavefront per transaction
   int forced_parts = 0;
@@ -1492,7 +1492,7 @@ void zkgpu_destroy(zkgpu_ctx* c) {
                     &c->digits, &c->st_partials, &c->dynsum, &c->accept2, &c->bin_order, &c->class_count, &c->part_hist, &c->part_entries, &c->part_lo, &c->dec_scratch, &c->heavy, &c->small_tbl, &c->recoded, &c->grp_sc, &c->grp_digits, &c->grp_partials, &c->grp_ok, &c->row_map, &c->grp_fail, &c->grp_fail_sum, &c->rechk_pts, &c->grp_ws, &c->grp_wf, &c->grp_dyn, &c->pv_plan, &c->pv_state, &c->pv_in, &c->pv_rows0, &c->pv_rows1, &c->pv_rows2, &c->pv_rows3, &c->pv_lay, &c->pv_pts, &c->pv_com, &c->pv_ab, &c->pv_proofs, &c->prep_com, &c->prep_proofs, &c->prep_r,
                     &c->prep_pw, &c->prep_ch, &c->prep_wf, &c->prep_dyn_sc, &c->prep_dyn_pt, &c->prep_st_sc,
                     &c->prep_absorb, &c->prep_raw, &c->ipa_lv, &c->ipa_rv, &c->ipa_cg, &c->ipa_ch, &c->ipa_w, &c->ipa_u,
-                    &c->coal_com, &c->coal_proofs, &c->coal_r};
+                    &c->coal_com, &c->coal_proofs, &c->coal_r, &c->mx_tab, &c->mx_st_index};
   for (Buffer* b : bufs) if (b->p) (void)hipFree(b->p);
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->pinned_in) (void)hipHostFree(c->pinned_in);
@@ -3446,3 +3446,262 @@ int zkgpu_set_window_bits(zkgpu_ctx* c, int w) {
 }  // extern "C"
 
 #include "session.hpp"
+
+#include "mixed_kernels.hpp"
+
+// ---- statements of several plans in one call (mixed_kernels.hpp) ----------------------------------------------------
+// zkgpu_r1cs_verify_mixed*: statement i is checked against plans[plan_index[i]].  The host lays out a per-call table
+// (one MixPlan per distinct plan, one MixStmt per statement) and one CSR of multiscalar-multiplication rows whose lengths
+// are the statements' own; the preparation is one launch per stage whatever the number of plans, and the rows go
+// through the same multiscalar-multiplication pipeline as zkgpu_verify_batch_ps_submit_dev.  Statements are checked
+// alone (no group checks): bit i is what a batch of that statement alone would give.
+namespace {
+int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* const* plans, size_t n_plans, size_t batch,
+                  const uint32_t* plan_index, const uint8_t* commitments, const uint8_t* proofs, const uint64_t* proof_offsets,
+                  const uint8_t* r_bytes) {
+  // every argument error is found here, before anything touches the device.  (The commitments' length is not an argument:
+  // 32 m bytes per statement, m from its plan, is what is read -- the bindings check it against what they were handed.)
+  if (!c) return ZKGPU_EINVAL;
+  if (!ps || ps->ctx->device != c->device) { c->last_error = "mixed verification: no point set, or one of another device"; return ZKGPU_EINVAL; }
+  if (batch >= (1ull << 24)) { c->last_error = "mixed verification: batch of 2^24 statements or more"; return ZKGPU_EINVAL; }
+  if (c->pending) { c->last_error = "a submitted batch is still waiting for zkgpu_verify_wait"; return ZKGPU_EINVAL; }
+  if (batch == 0) { park_sync_result(c, ZKGPU_OK, nullptr, 0); return ZKGPU_OK; }
+  if (!plans || n_plans == 0 || !plan_index || !commitments || !proofs || !proof_offsets) {
+    c->last_error = "mixed verification: null plan list, plan index, commitments, proofs or offsets";
+    return ZKGPU_EINVAL;
+  }
+  for (size_t p = 0; p < n_plans; ++p) {
+    const zkgpu_cloak_plan* pl = plans[p];
+    if (!pl || pl->device != c->device) { c->last_error = "mixed verification: null plan, or a plan of another device"; return ZKGPU_EINVAL; }
+    if (ps->n < 2 + 2 * pl->gens_capacity) { c->last_error = "mixed verification: a plan needs more generators than the set holds"; return ZKGPU_EINVAL; }
+  }
+  if (proof_offsets[0] != 0) { c->last_error = "mixed verification: proof_offsets[0] must be 0"; return ZKGPU_EINVAL; }
+  for (size_t i = 0; i < batch; ++i) {
+    if (plan_index[i] >= n_plans) { c->last_error = "mixed verification: plan index out of range"; return ZKGPU_EINVAL; }
+    if (proof_offsets[i + 1] < proof_offsets[i]) { c->last_error = "mixed verification: proof offsets decrease"; return ZKGPU_EINVAL; }
+  }
+  const uint32_t B = (uint32_t)batch;
+  // distinct plans (by handle) and the statements sorted by plan
+  std::vector<zkgpu_cloak_plan*> uniq;
+  std::vector<uint32_t> pid_of(n_plans, ~0u), pid(B);
+  for (uint32_t i = 0; i < B; ++i) {
+    uint32_t& slot = pid_of[plan_index[i]];
+    if (slot == ~0u) {
+      zkgpu_cloak_plan* pl = plans[plan_index[i]];
+      for (uint32_t u = 0; u < uniq.size() && slot == ~0u; ++u) if (uniq[u] == pl) slot = u;
+      if (slot == ~0u) { slot = (uint32_t)uniq.size(); uniq.push_back(pl); }
+    }
+    pid[i] = slot;
+  }
+  const uint32_t U = (uint32_t)uniq.size();
+  // LDS classes of k_mx_prepare: plans that leave room for two or more workgroups per CU, and those that take one alone.
+  // Statements are ordered by (class, plan); k_mx_prepare runs once per class present, each launch with its own class's
+  // largest LDS, so that one large program in a call does not cut every small statement to one workgroup per CU.
+  std::vector<uint32_t> count(U, 0), order(B), cls(U), by_class(U);
+  for (uint32_t u = 0; u < U; ++u) { cls[u] = uniq[u]->lds_bytes > MIX_LDS_SMALL ? 1u : 0u; by_class[u] = u; }
+  std::stable_sort(by_class.begin(), by_class.end(), [&](uint32_t a, uint32_t b) { return cls[a] < cls[b]; });
+  for (uint32_t i = 0; i < B; ++i) ++count[pid[i]];
+  uint32_t class_start[3] = {0, 0, B};
+  size_t class_lds[2] = {0, 0};
+  {
+    std::vector<uint32_t> at(U, 0);
+    uint32_t run = 0;
+    for (uint32_t u : by_class) {
+      at[u] = run;
+      if (cls[u] == 0) class_start[1] = run + count[u];
+      run += count[u];
+      class_lds[cls[u]] = std::max(class_lds[cls[u]], uniq[u]->lds_bytes);
+    }
+    for (uint32_t i = 0; i < B; ++i) order[at[pid[i]]++] = i;
+  }
+  bool coop = c->transcript_mode == 2 || (c->transcript_mode == 0 && batch <= COOP_TRANSCRIPT_MAX);
+  for (zkgpu_cloak_plan* pl : uniq) coop &= pl->n_seg != 0 && pl->shape.n_ch <= 0xffffu;
+  std::vector<uint32_t> lane_order;
+  if (!coop) {                           // each plan's run padded to whole wavefronts
+    lane_order.reserve(B + 64 * U);
+    for (uint32_t i = 0; i < B; ++i) {
+      lane_order.push_back(order[i]);
+      if (i + 1 == B || pid[order[i + 1]] != pid[order[i]])
+        while (lane_order.size() % 64) lane_order.push_back(~0u);
+    }
+  }
+  // the table
+  std::vector<MixPlan> mp(U);
+  size_t max_nch = 0;
+  for (uint32_t u = 0; u < U; ++u) {
+    const zkgpu_cloak_plan* pl = uniq[u];
+    MixPlan& m = mp[u];
+    memset(&m, 0, sizeof m);
+    m.sh = pl->shape;
+    m.init = pl->d_init; m.tape = (const uint4*)pl->d_tape; m.n_ops = pl->n_ops;
+    m.seg_info = pl->d_seg_info; m.seg_const = pl->d_seg_const; m.seg_map = pl->d_seg_map; m.n_seg = pl->n_seg;
+    m.mono_chal = pl->d_mono_chal; m.mono_pow = pl->d_mono_pow; m.tgt_off = pl->d_tgt_off; m.term_info = pl->d_term_q;
+    m.prod_qm = (const uint2*)pl->d_term_mono; m.prod_coef = pl->d_term_coef;
+    m.h_base = (uint32_t)(2 + pl->gens_capacity);
+    max_nch = std::max<size_t>(max_nch, pl->shape.n_ch);
+  }
+  std::vector<MixStmt> ms(B);
+  std::vector<uint64_t> dyn_off(B + 1), st_off(B + 1);
+  uint64_t n_com = 0, n_pw = 0, n_ch = 0, n_raw = 0, n_abs = 0, n_dyn = 0, n_st = 0;
+  for (uint32_t i = 0; i < B; ++i) {
+    const MixPlan& m = mp[pid[i]];
+    const PrepShape& sh = m.sh;
+    const uint64_t len = proof_offsets[i + 1] - proof_offsets[i];
+    MixStmt& s = ms[i];
+    s.plan = pid[i];
+    s.form = len == 1 + 4ull * sh.proof_words ? MIX_FORM_TWO_PHASE : len + 96 == 1 + 4ull * sh.proof_words ? MIX_FORM_ONE_PHASE : MIX_FORM_BAD_LENGTH;
+    s.proof = proof_offsets[i];
+    s.com = n_com; s.pw = n_pw; s.ch = n_ch; s.raw = n_raw; s.absorb = n_abs; s.dyn = n_dyn; s.st = n_st;
+    dyn_off[i] = n_dyn; st_off[i] = n_st;
+    n_com += 8ull * sh.m; n_pw += sh.proof_words; n_ch += 8ull * sh.n_ch_ext;
+    if (coop) { n_raw += 16ull * sh.n_ch; n_abs += 25ull * m.n_seg; }
+    n_dyn += sh.n_dyn; n_st += sh.n_static;
+  }
+  dyn_off[B] = n_dyn; st_off[B] = n_st;
+  // staging: commitments | proofs | r | table, one pinned block, four copies on the light stream
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t b_com = 4 * n_com, b_pr = proof_offsets[B], b_r = 64 * (size_t)B;
+  const size_t t_plans = 0, t_stmts = up(t_plans + U * sizeof(MixPlan)), t_order = up(t_stmts + B * sizeof(MixStmt)),
+               t_lanes = up(t_order + 4 * (size_t)B), t_doff = up(t_lanes + 4 * lane_order.size()),
+               t_soff = up(t_doff + 8 * ((size_t)B + 1)), t_end = t_soff + 8 * ((size_t)B + 1);
+  const size_t o_pr = up(b_com), o_r = up(o_pr + b_pr), o_tab = up(o_r + b_r);
+  if (c->pinned_in_cap < o_tab + t_end) {
+    if (c->pinned_in) HIP_TRY(c, hipHostFree(c->pinned_in));
+    c->pinned_in = nullptr; c->pinned_in_cap = 0;
+    HIP_TRY(c, hipHostMalloc(&c->pinned_in, o_tab + t_end + 4096, hipHostMallocDefault));
+    c->pinned_in_cap = o_tab + t_end + 4096;
+  }
+  char* h = (char*)c->pinned_in;
+  memcpy(h, commitments, b_com);
+  memcpy(h + o_pr, proofs, b_pr);
+  if (r_bytes) {
+    memcpy(h + o_r, r_bytes, b_r);
+  } else if (!os_random(h + o_r, b_r)) {   // verifier randomness from the OS
+    c->last_error = "getrandom failed";
+    return ZKGPU_EINVAL;
+  }
+  char* tab = h + o_tab;
+  memcpy(tab + t_plans, mp.data(), U * sizeof(MixPlan));
+  memcpy(tab + t_stmts, ms.data(), B * sizeof(MixStmt));
+  memcpy(tab + t_order, order.data(), 4 * (size_t)B);
+  if (!lane_order.empty()) memcpy(tab + t_lanes, lane_order.data(), 4 * lane_order.size());
+  memcpy(tab + t_doff, dyn_off.data(), 8 * ((size_t)B + 1));
+  memcpy(tab + t_soff, st_off.data(), 8 * ((size_t)B + 1));
+  TRY(ensure(c, c->prep_com, std::max<size_t>(b_com, 16)));
+  TRY(ensure(c, c->prep_proofs, std::max<size_t>(b_pr, 16)));
+  TRY(ensure(c, c->prep_r, b_r));
+  TRY(ensure(c, c->mx_tab, t_end));
+  TRY(ensure(c, c->prep_pw, 4 * n_pw));
+  TRY(ensure(c, c->prep_ch, 4 * n_ch));
+  TRY(ensure(c, c->prep_wf, 4 * (size_t)B));
+  TRY(ensure(c, c->prep_dyn_sc, 32 * n_dyn));
+  TRY(ensure(c, c->prep_dyn_pt, 32 * n_dyn));
+  TRY(ensure(c, c->prep_st_sc, 32 * n_st));
+  TRY(ensure(c, c->mx_st_index, 4 * n_st));
+  if (coop) {
+    TRY(ensure(c, c->prep_absorb, std::max<uint64_t>(8 * n_abs, 16)));
+    TRY(ensure(c, c->prep_raw, std::max<uint64_t>(4 * n_raw, 16)));
+  }
+  hipStream_t L = c->stream_l;
+  HIP_TRY(c, hipMemcpyAsync(c->prep_com.p, h, b_com, hipMemcpyHostToDevice, L));
+  HIP_TRY(c, hipMemcpyAsync(c->prep_proofs.p, h + o_pr, b_pr, hipMemcpyHostToDevice, L));
+  HIP_TRY(c, hipMemcpyAsync(c->prep_r.p, h + o_r, b_r, hipMemcpyHostToDevice, L));
+  HIP_TRY(c, hipMemcpyAsync(c->mx_tab.p, tab, t_end, hipMemcpyHostToDevice, L));
+  const char* dt = (const char*)c->mx_tab.p;
+  const MixPlan* d_plans = (const MixPlan*)(dt + t_plans);
+  const MixStmt* d_stmts = (const MixStmt*)(dt + t_stmts);
+  const uint32_t* d_order = (const uint32_t*)(dt + t_order);
+  const uint32_t* d_com = (const uint32_t*)c->prep_com.p;
+  const uint32_t* d_r = (const uint32_t*)c->prep_r.p;
+  uint32_t* d_pw = (uint32_t*)c->prep_pw.p;
+  uint32_t* d_ch = (uint32_t*)c->prep_ch.p;
+  uint32_t* d_wf = (uint32_t*)c->prep_wf.p;
+  {
+    Launch l(c, "k_mx_proof_unpack", L);
+    hipLaunchKernelGGL(k_mx_proof_unpack, dim3(B), dim3(256), 0, L, d_plans, d_stmts, d_order, (const uint8_t*)c->prep_proofs.p,
+                       d_pw, d_wf);
+  }
+  if (coop) {
+    {
+      Launch l(c, "k_mx_tape_gather", L);
+      hipLaunchKernelGGL(k_mx_tape_gather, dim3(B), dim3(256), 0, L, d_plans, d_stmts, d_order, d_com, (const uint32_t*)d_pw,
+                         (uint2*)c->prep_absorb.p);
+    }
+    {
+      Launch l(c, "k_mx_transcript_coop", L);
+      hipLaunchKernelGGL(k_mx_transcript_coop, dim3(B), dim3(64), 0, L, d_plans, d_stmts, d_order, (const uint2*)c->prep_absorb.p,
+                         (uint32_t*)c->prep_raw.p);
+    }
+    {
+      Launch l(c, "k_mx_challenges", L);
+      hipLaunchKernelGGL(k_mx_challenges, dim3(B), dim3(128), max_nch * 32, L, d_plans, d_stmts, d_order,
+                         (const uint32_t*)c->prep_raw.p, (const uint32_t*)d_pw, d_r, d_ch, d_wf);
+    }
+  } else {
+    Launch l(c, "k_mx_transcript", L);
+    hipLaunchKernelGGL(k_mx_transcript, dim3((unsigned)(lane_order.size() / 64)), dim3(64), 0, L, d_plans, d_stmts,
+                       (const uint32_t*)(dt + t_lanes), d_com, (const uint32_t*)d_pw, d_r, d_ch, d_wf);
+  }
+  {
+    // (the attribute is the same for every call: LDS of a CU, the bound plan_finish_inner holds every plan to)
+    HIP_TRY(c, hipFuncSetAttribute((const void*)k_mx_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    for (int k = 0; k < 2; ++k) {
+      const uint32_t n_k = class_start[k + 1] - class_start[k];
+      if (n_k == 0) continue;
+      Launch l(c, "k_mx_prepare", L);
+      hipLaunchKernelGGL(k_mx_prepare, dim3(n_k), dim3(256), class_lds[k], L, d_plans, d_stmts, d_order + class_start[k],
+                         (const uint32_t*)d_ch, (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->prep_st_sc.p, (uint32_t*)c->mx_st_index.p);
+    }
+  }
+  {
+    Launch l(c, "k_mx_gather_dyn_points", L);
+    hipLaunchKernelGGL(k_mx_gather_dyn_points, dim3(B), dim3(256), 0, L, d_plans, d_stmts, d_order, d_com, (const uint32_t*)d_pw,
+                       (uint32_t*)c->prep_dyn_pt.p);
+  }
+  HIP_TRY(c, hipGetLastError());
+  Job job;
+  job.d_dyn_scalars = (const uint32_t*)c->prep_dyn_sc.p;
+  job.d_dyn_points = (const uint32_t*)c->prep_dyn_pt.p;
+  job.d_dyn_offsets = (const uint64_t*)(dt + t_doff);
+  job.n_dyn = n_dyn;
+  job.d_st_scalars = (const uint32_t*)c->prep_st_sc.p;
+  job.d_st_index = (const uint32_t*)c->mx_st_index.p;
+  job.d_st_offsets = (const uint64_t*)(dt + t_soff);
+  job.n_static = n_st;
+  job.d_static_rows = ps->rows;
+  job.n_msm = B;
+  job.d_wellformed = d_wf;                  // folded into the accept bitmap on the device
+  // (the pipeline's first launch follows the preparation on the light stream; its other streams wait for that)
+  if (pipe_eligible(c, job, ps)) return pipe_enqueue(c, job, ps, nullptr);
+  // general shapes (no generator tables, forced window width): synchronous, as cloak_verify_gpu_enqueue
+  HIP_TRY(c, hipStreamSynchronize(L));
+  std::vector<uint8_t> bm((batch + 7) / 8, 0);
+  const int rc = ps->table ? batch_device_tables(c, job, ps, bm.data()) : batch_device(c, job, bm.data());
+  park_sync_result(c, rc, bm.data(), batch);
+  return ZKGPU_OK;
+}
+}  // namespace
+
+int zkgpu_r1cs_verify_mixed_submit(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* const* plans, size_t n_plans,
+                                   size_t batch, const uint32_t* plan_index, const uint8_t* commitments, const uint8_t* proofs,
+                                   const uint64_t* proof_offsets, const uint8_t* r_bytes) {
+  if (!c) return ZKGPU_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  return mixed_enqueue(c, ps, plans, n_plans, batch, plan_index, commitments, proofs, proof_offsets, r_bytes);
+}
+
+int zkgpu_r1cs_verify_mixed(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* const* plans, size_t n_plans, size_t batch,
+                            const uint32_t* plan_index, const uint8_t* commitments, const uint8_t* proofs,
+                            const uint64_t* proof_offsets, const uint8_t* r_bytes, uint8_t* accept_bitmap) {
+  if (!c || (!accept_bitmap && batch)) return ZKGPU_EINVAL;
+  if (accept_bitmap) memset(accept_bitmap, 0, (batch + 7) / 8);
+  uint8_t none = 0;
+  if (!accept_bitmap) accept_bitmap = &none;       // (batch 0: nothing is written)
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  TRY(mixed_enqueue(c, ps, plans, n_plans, batch, plan_index, commitments, proofs, proof_offsets, r_bytes));
+  const int rc = pipe_wait(c, accept_bitmap);
+  if (rc != ZKGPU_OK) memset(accept_bitmap, 0, (batch + 7) / 8);
+  return rc;
+}

@@ -198,6 +198,8 @@ def load_library():
     lib.zkgpu_r1cs_verify_submit.argtypes = [vp, vp, vp, sz, u8p, u8p, sz, u8p]
     lib.zkgpu_r1cs_verify_submit_dev.argtypes = [vp, vp, vp, sz, vp, vp, sz, vp]
     lib.zkgpu_r1cs_verify_batch.argtypes = [vp, vp, vp, sz, sz, u8p, u8p, sz, u8p, u8p, C.c_int]
+    lib.zkgpu_r1cs_verify_mixed.argtypes = [vp, vp, C.POINTER(vp), sz, sz, C.POINTER(C.c_uint32), u8p, u8p, u64p, u8p, u8p]
+    lib.zkgpu_r1cs_verify_mixed_submit.argtypes = [vp, vp, C.POINTER(vp), sz, sz, C.POINTER(C.c_uint32), u8p, u8p, u64p, u8p]
     lib.zkgpu_r1cs_prove_batch.argtypes = [vp, vp, vp, C.POINTER(C.c_uint32), sz, sz, u8p, u8p, u8p, sz, u8p, C.c_int, u8p, u8p, sz,
                                            C.POINTER(sz)]
     lib.zkgpu_runtime_hint.argtypes = [C.c_char_p, sz]

@@ -442,6 +442,79 @@ class R1csVerifier:
             self.h = C.c_void_p()
 
 
+class MixedR1csVerifier:
+    """zkgpu_r1cs_verify_mixed: statements of DIFFERENT constraint systems in one device call -- upstream's batch
+    verification over a list of verifiers, each with its own constraint system.  `plans`: per plan an R1csVerifier (kept
+    referenced here, so that its plan outlives this object's calls) or an (n_in, n_out) cloak shape (the plan is made here
+    and owned by this object); statement i is checked against plans[plan_index[i]].  Every statement's commitments are
+    checked against its plan's m x 32 bytes (the library reads exactly that much)."""
+
+    def __init__(self, ctx: Context, bp_gens: BulletproofGens, plans):
+        self.ctx, self.bp_gens = ctx, bp_gens
+        self._owned, self._verifiers = [], []
+        handles, self.m = [], []
+        for p in plans:
+            if isinstance(p, R1csVerifier):
+                if not p.h:
+                    raise ValueError("R1csVerifier already closed")
+                self._verifiers.append(p)
+                handles.append(p.h.value)
+                self.m.append(p.desc.m)
+            elif isinstance(p, tuple) and len(p) == 2:
+                h = C.c_void_p()
+                ctx._check(ctx.lib.zkgpu_cloak_plan_create(ctx.h, p[0], p[1], bp_gens.gens_capacity, C.byref(h)))
+                self._owned.append(h)
+                handles.append(h.value)
+                self.m.append(2 * (p[0] + p[1]))                  # (quantity, flavor) per value
+            else:
+                raise TypeError("a plan is an R1csVerifier or an (n_in, n_out) cloak shape")
+        self.n_plans = len(handles)
+        self.handles = handles                                    # (what zkgpu_r1cs_verify_batch_gpu would take per plan)
+        self._plans = (C.c_void_p * max(self.n_plans, 1))(*handles)
+
+    def _args(self, plan_index: Sequence[int], commitments: Sequence[bytes], proofs: Sequence[bytes], r_bytes: Optional[bytes]):
+        if any(v.h.value is None for v in self._verifiers) or self._plans is None:
+            raise ValueError("a plan of this verifier has been closed")
+        batch = len(plan_index)
+        if len(commitments) != batch or len(proofs) != batch or (r_bytes is not None and len(r_bytes) != 64 * batch):
+            raise ValueError("one commitment string and one proof per statement; r: 64 bytes per statement")
+        for i, (p, c) in enumerate(zip(plan_index, commitments)):
+            if not 0 <= p < self.n_plans:
+                raise ValueError("statement %d: plan index %d out of range (%d plans)" % (i, p, self.n_plans))
+            if len(c) != 32 * self.m[p]:
+                raise ValueError("statement %d: %d bytes of commitments, its plan takes %d (32 per commitment)" % (i, len(c), 32 * self.m[p]))
+        offs = [0]
+        for p in proofs:
+            offs.append(offs[-1] + len(p))
+        return (batch, (C.c_uint32 * max(batch, 1))(*plan_index), b"".join(commitments), b"".join(proofs),
+                (C.c_uint64 * (batch + 1))(*offs), r_bytes)
+
+    def verify(self, plan_index: Sequence[int], commitments: Sequence[bytes], proofs: Sequence[bytes],
+               r_bytes: Optional[bytes] = None) -> bytes:
+        """-> the accept bitmap, in the order of the statements given"""
+        batch, idx, com, pr, offs, r = self._args(plan_index, commitments, proofs, r_bytes)
+        bm = C.create_string_buffer(max((batch + 7) // 8, 1))
+        self.ctx._check(self.ctx.lib.zkgpu_r1cs_verify_mixed(self.ctx.h, self.bp_gens.points.h, self._plans, self.n_plans, batch,
+                                                             idx, com, pr, offs, r, bm))
+        return bm.raw[: (batch + 7) // 8]
+
+    def submit(self, plan_index: Sequence[int], commitments: Sequence[bytes], proofs: Sequence[bytes],
+               r_bytes: Optional[bytes] = None) -> None:
+        """zkgpu_r1cs_verify_mixed_submit: queued, the inputs free again on return; `wait` collects the bitmap"""
+        batch, idx, com, pr, offs, r = self._args(plan_index, commitments, proofs, r_bytes)
+        self.ctx._check(self.ctx.lib.zkgpu_r1cs_verify_mixed_submit(self.ctx.h, self.bp_gens.points.h, self._plans, self.n_plans,
+                                                                    batch, idx, com, pr, offs, r))
+        self.ctx._pending_batch = batch
+
+    def wait(self) -> bytes:
+        return self.ctx.verify_wait()
+
+    def close(self) -> None:
+        for h in self._owned:
+            self.ctx.lib.zkgpu_cloak_plan_destroy(h)
+        self._owned, self._verifiers, self._plans = [], [], None
+
+
 class Verifier:
     """Batch verifier; `verify_cloak_txs` returns one Optional[VMError] per transaction
     (None = Ok), the shape of `txs.iter().map(|tx| tx.verify(bp_gens))`."""
