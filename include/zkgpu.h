@@ -203,7 +203,15 @@ int zkgpu_cloak_verify_batch(zkgpu_ctx *ctx, const zkgpu_pointset *ps, size_t ge
  * one (version byte 0, A_I2 A_O2 S2 left out: 13 + 2k elements -- what upstream's R1CSProof::to_bytes writes for a
  * statement without a second phase; read as the identity for the three points).  A version byte that disagrees with the
  * length rejects that proof.  Blocks of mixed shapes (zkgpu_verifier_*) may mix the two forms freely.
- * Verdicts are identical to zkgpu_cloak_verify_batch. */
+ * Verdicts are identical to zkgpu_cloak_verify_batch.
+ * Sizes: every shape up to 64 inputs and 64 outputs (padded n 8192, k = 13) over enough generators.  A plan whose
+ * per-statement preparation needs more than a CU's 160 KiB of LDS (12 x 12, 1 x 16 and larger; described programs past
+ * about a thousand multipliers) is prepared across several workgroups from an HBM workspace sized per call; the bits are
+ * the same (its workspace is capped at 512 MiB per call: larger batches are prepared in slices).  ZKGPU_EINVAL from
+ * zkgpu_cloak_plan_create / zkgpu_r1cs_plan_create means only: padded n above gens_capacity, more than 16 IPA rounds, more
+ * than 64 inputs / outputs, more than 65536 constraints (the host-prepared zkgpu_r1cs_verify_batch serves those), or a
+ * malformed description.
+ * zkgpu_cloak_plan_info: multipliers, padded n, constraints, terms, proof_len of any plan, large or not. */
 typedef struct zkgpu_cloak_plan zkgpu_cloak_plan;
 int zkgpu_cloak_plan_create(zkgpu_ctx *ctx, uint32_t n_in, uint32_t n_out, size_t gens_capacity,
                             zkgpu_cloak_plan **out);

@@ -84,6 +84,8 @@ fn bits(bitmap: &[u8], n: usize) -> Vec<bool> {
 
 /// One cloak statement as the VM leaves it: `commitments` = 64 bytes per value (quantity, flavor), the `n_in` inputs
 /// first; `proof` = `R1CSProof::to_bytes()`.
+/// Every shape up to 64 inputs and 64 outputs (padded n 8192) is verified on the device, given enough generators; shapes
+/// whose preparation exceeds a CU's LDS (12 x 12, 1 x 16 and larger) take a multi-workgroup path with the same verdicts.
 #[derive(Clone, Copy)]
 pub struct CloakStatement<'a> {
     pub n_in: u32,

@@ -761,4 +761,22 @@ k_mx_gather_dyn_points(const MixPlan* __restrict__ plans, const MixStmt* __restr
   }
 }
 
+// large_prep.hpp's kernels over the statements of a mixed call whose plans exceed a CU's LDS: launch statement b is
+// order[b]; they write the generator index too, and no recoded form (k_small_tables makes it in mixed calls)
+struct LpMixed {
+  const MixPlan* plans;
+  const MixStmt* stmts;
+  const uint32_t* order;
+  const uint32_t* ch;
+  uint32_t* dyn_scalars;
+  uint32_t* static_scalars;
+  uint32_t* static_index;
+  __device__ LpStmt at(uint32_t b) const {
+    const MixStmt& stm = stmts[order[b]];
+    const MixPlan& pln = plans[stm.plan];
+    return {pln.sh, pln.tgt_off, pln.term_info, pln.prod_qm, pln.prod_coef, ch + stm.ch, dyn_scalars + stm.dyn * 8, nullptr,
+            static_scalars + stm.st * 8, static_index + stm.st, pln.h_base};
+  }
+};
+
 }  // namespace zk

@@ -1046,3 +1046,5 @@ k_group_scalars(const uint32_t* __restrict__ st_scalars /*[B][n_static][8]*/, ui
 }
 
 }  // namespace zk
+
+#include "large_prep.hpp"   // statements past a CU's LDS

@@ -318,7 +318,8 @@ uint64_t cloak_msm_terms(uint32_t n_in, uint32_t n_out) {
 }
 
 // plan of a shape, created on first use.  *rc = ZKGPU_OK and nullptr: a shape the generator set can NEVER serve (more
-// multipliers than generators, no values, more than 64 inputs / outputs) -- the reference rejects exactly those
+// multipliers than generators, no values, more than 64 inputs / outputs; a plan past a CU's LDS is served, by
+// large_prep.hpp, so EINVAL means nothing else) -- the reference rejects exactly those
 // transactions (InvalidGeneratorsLength / a VM error) and so does the caller, one by one; that answer is cached.
 // *rc != ZKGPU_OK: the plan could not be made THIS time (out of device memory, a HIP error): nothing is cached, and the
 // caller fails its block or ticket with that error -- a transient fault must not turn into "the proof is invalid".

@@ -143,7 +143,7 @@ struct zkgpu_ctx {
   std::vector<zkgpu_ctx*> pv_slices;    // helper contexts (one stream each) on which the slices 1.. of a prover call run (run_sliced)
   std::vector<uint32_t> pv_plan_host;   // the tables pv_plan holds (compared before uploading again)
   size_t pv_lay_batch = 0;              // batch size the scaffolding in pv_lay was built for (0: none)
-  Buffer prep_absorb, prep_raw, mx_tab, mx_st_index;    // cooperative transcript: absorbed words per segment, raw challenge bytes | zkgpu_r1cs_verify_mixed: per-call tables, generator index
+  Buffer prep_absorb, prep_raw, mx_tab, mx_st_index, prep_large;    // cooperative transcript: absorbed words per segment, raw challenge bytes | zkgpu_r1cs_verify_mixed: per-call tables, generator index | large_prep.hpp's workspace
   int locate_mode = 0;             // failed groups: 0 automatic, 1 always re-check every transaction, 2 always locate the culprit
   int transcript_mode = 0;         // 0 automatic, 1 one lane per transaction, 2 one wavefront per transaction
   int forced_parts = 0;
@@ -851,7 +851,7 @@ struct PrepLaunch {
   const uint32_t *d_seg_info = nullptr, *d_seg_const = nullptr;   // cooperative transcript (n_seg = 0: not available)
   const uint16_t* d_seg_map = nullptr;
   uint32_t n_seg = 0;
-  size_t lds_bytes;
+  size_t lds_bytes; bool large;   // past a CU's LDS: large_prep.hpp instead of k_prepare
   const uint32_t* d_com;
   const uint8_t* d_proofs;
   const uint32_t* d_r;
@@ -1001,11 +1001,11 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   if (prep) {
     hipStream_t H3 = H3s;
     HIP_TRY(c, hipStreamWaitEvent(H3, c->ev_t, 0));
-    Launch l(c, "k_prepare", H3);
+    if (prep->large) { TRY(lp_prepare_homo(c, H3, prep->sh, prep->d_tgt_off, prep->d_term_q, prep->d_term_mono, prep->d_term_coef, (uint32_t)B)); } else { Launch l(c, "k_prepare", H3);
     hipLaunchKernelGGL(k_prepare, dim3((unsigned)B), dim3(256), prep->lds_bytes, H3, prep->sh, prep->d_mono_chal,
                        prep->d_mono_pow, prep->d_tgt_off, prep->d_term_q, (const uint2*)prep->d_term_mono, prep->d_term_coef,
                        (const uint32_t*)c->prep_ch.p, prep->d_com, (const uint32_t*)c->prep_pw.p,
-                       (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p);
+                       (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p); }
   }
   HIP_TRY(c, hipEventRecord(c->ev_p, prep ? H3s : L));
   HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_p, 0));
@@ -2667,7 +2667,7 @@ struct zkgpu_cloak_plan {
   uint64_t *d_dyn_off = nullptr, *d_st_off = nullptr;
   uint32_t* d_st_index = nullptr;
   std::vector<void*> retired;
-  size_t lds_bytes = 0;
+  size_t lds_bytes = 0; bool large = false;   // k_prepare's state exceeds a CU's LDS: prepared by large_prep.hpp
 };
 
 namespace {
@@ -2689,7 +2689,7 @@ bool desc_from_c(zkgpu_ctx* c, const zkgpu_r1cs_desc* d, R1csDesc& desc);
 // reference answers with InvalidGeneratorsLength); anything else (ZKGPU_ENOMEM, ZKGPU_EHIP) is transient.
 int plan_finish_inner(zkgpu_ctx* c, zkgpu_cloak_plan* p, size_t gens_capacity) {
   const CloakPlan& h = p->host;
-  if (h.pn > gens_capacity || h.k > 16) { c->last_error = "statement needs more generators than the set holds"; return ZKGPU_EINVAL; }
+  if (h.pn > gens_capacity || h.k > 16) { c->last_error = "statement needs more generators than the set holds"; return ZKGPU_EINVAL; } if (h.n_cons > LP_MAX_CONS) { c->last_error = "statement has more than 65536 constraints (the device preparation's z power tables)"; return ZKGPU_EINVAL; }
   PrepShape& s = p->shape;
   s.m = h.m; s.n1 = h.n1; s.n = h.n; s.pn = h.pn; s.k = h.k; s.n_cons = h.n_cons;
   s.n_chal2 = (uint32_t)h.chal_names.size();
@@ -2730,7 +2730,7 @@ int plan_finish_inner(zkgpu_ctx* c, zkgpu_cloak_plan* p, size_t gens_capacity) {
   }
   s = best;
   p->lds_bytes = best_bytes;
-  if (p->lds_bytes > 160 * 1024) { c->last_error = "plan does not fit the 160 KiB LDS of a CU"; return ZKGPU_EINVAL; }
+  p->large = p->lds_bytes > PREP_LDS_MAX || lp_forced();     // past a CU's LDS: the multi-workgroup path of large_prep.hpp
   // STROBE state after Transcript::new("ZkVM.r1cs") + r1cs_domain_sep()
   Transcript tr(h.label.c_str());
   tr.append_message("dom-sep", (const uint8_t*)"r1cs v1", 7);
@@ -2759,7 +2759,7 @@ int plan_finish_inner(zkgpu_ctx* c, zkgpu_cloak_plan* p, size_t gens_capacity) {
     TRY(plan_upload(c, &p->d_term_mono, qm));             //             prod_qm
     TRY(plan_upload(c, &p->d_term_coef, h.prod_coef));    //             prod_coef
   }
-  HIP_TRY(c, hipFuncSetAttribute((const void*)k_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
+  if (!p->large) HIP_TRY(c, hipFuncSetAttribute((const void*)k_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
   return ZKGPU_OK;
 }
 
@@ -2980,7 +2980,7 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
   const PrepShape& sh = plan->shape;
   const uint32_t B = (uint32_t)batch;
   TRY(ensure(c, c->prep_pw, (size_t)B * sh.proof_words * 4));
-  TRY(ensure(c, c->prep_ch, (size_t)B * sh.n_ch_ext * 32));
+  TRY(ensure(c, c->prep_ch, (size_t)B * sh.n_ch_ext * 32)); if (plan->large) TRY(ensure(c, c->prep_large, lp_ws_bytes(lp_layout(sh).slots, B)));
   TRY(ensure(c, c->prep_wf, (size_t)B * 4));
   TRY(ensure(c, c->prep_dyn_sc, (size_t)B * sh.n_dyn * 32));
   TRY(ensure(c, c->prep_dyn_pt, (size_t)B * sh.n_dyn * 32));
@@ -3037,7 +3037,7 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
     pl.sh = sh;
     pl.d_init = plan->d_init; pl.d_mono_chal = plan->d_mono_chal; pl.d_mono_pow = plan->d_mono_pow;
     pl.d_tgt_off = plan->d_tgt_off; pl.d_term_q = plan->d_term_q; pl.d_term_mono = plan->d_term_mono;
-    pl.d_term_coef = plan->d_term_coef; pl.d_tape = plan->d_tape; pl.n_ops = plan->n_ops; pl.lds_bytes = plan->lds_bytes;
+    pl.d_term_coef = plan->d_term_coef; pl.d_tape = plan->d_tape; pl.n_ops = plan->n_ops; pl.lds_bytes = plan->lds_bytes; pl.large = plan->large;
     pl.d_seg_info = plan->d_seg_info; pl.d_seg_const = plan->d_seg_const; pl.d_seg_map = plan->d_seg_map; pl.n_seg = plan->n_seg;
     pl.d_com = d_com; pl.d_proofs = d_proofs; pl.d_r = d_r; pl.proof_len = proof_len;
     return pipe_enqueue(c, job, ps, &pl);
@@ -3062,12 +3062,12 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
                        (const uint32_t*)plan->d_mono_pow, 0u);
   }
   {
-    Launch l(c, "k_prepare");
-    hipLaunchKernelGGL(k_prepare, dim3(B), dim3(256), plan->lds_bytes, s, sh, (const uint32_t*)plan->d_mono_chal,
+    if (plan->large) TRY(lp_prepare_homo(c, s, sh, plan->d_tgt_off, plan->d_term_q, plan->d_term_mono, plan->d_term_coef, B)); Launch l(c, plan->large ? "k_gather_dyn_points" : "k_prepare");
+    if (!plan->large) { hipLaunchKernelGGL(k_prepare, dim3(B), dim3(256), plan->lds_bytes, s, sh, (const uint32_t*)plan->d_mono_chal,
                        (const uint32_t*)plan->d_mono_pow, (const uint32_t*)plan->d_tgt_off, (const uint32_t*)plan->d_term_q,
                        (const uint2*)plan->d_term_mono, (const uint32_t*)plan->d_term_coef, (const uint32_t*)c->prep_ch.p,
                        d_com, (const uint32_t*)c->prep_pw.p, (uint32_t*)c->prep_dyn_sc.p,
-                       (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p);
+                       (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p); }
     hipLaunchKernelGGL(k_gather_dyn_points, dim3(blocks_for((uint64_t)B * sh.n_dyn * 8, 256)), dim3(256), 0, s, sh, d_com,
                        (const uint32_t*)c->prep_pw.p, B, (uint32_t*)c->prep_dyn_pt.p);
   }
@@ -3449,6 +3449,44 @@ int zkgpu_set_window_bits(zkgpu_ctx* c, int w) {
 
 #include "mixed_kernels.hpp"
 
+// ---- statements past a CU's LDS (large_prep.hpp): the four launches, for a batch of one plan and for the large plans of a
+// mixed call.  ws_slots: the workspace slots of one statement (lp_layout of the largest plan among them)
+namespace {
+template <class Src>
+void lp_launch_all(zkgpu_ctx* c, hipStream_t s, const Src& src, uint32_t n_stmt, uint32_t max_targets, uint32_t max_pn, uint32_t ws_slots) {
+  uint32_t* ws = (uint32_t*)c->prep_large.p;
+  {
+    Launch l(c, "k_lp_head", s);
+    hipLaunchKernelGGL(k_lp_head<Src>, dim3(n_stmt), dim3(256), 0, s, src, ws, ws_slots);
+  }
+  {
+    Launch l(c, "k_lp_flatten", s);
+    hipLaunchKernelGGL(k_lp_flatten<Src>, dim3(n_stmt, lp_chunks(max_targets)), dim3(256), 0, s, src, ws, ws_slots);
+  }
+  {
+    Launch l(c, "k_lp_gens", s);
+    hipLaunchKernelGGL(k_lp_gens<Src>, dim3(n_stmt, lp_chunks(max_pn)), dim3(256), 0, s, src, ws, ws_slots);
+  }
+  {
+    Launch l(c, "k_lp_tail", s);
+    hipLaunchKernelGGL(k_lp_tail<Src>, dim3(n_stmt), dim3(64), 0, s, src, ws, ws_slots);
+  }
+}
+}  // namespace
+
+int lp_prepare_homo(zkgpu_ctx* c, hipStream_t s, const PrepShape& sh, const uint32_t* tgt_off, const uint32_t* term_info,
+                    const uint32_t* prod_qm, const uint32_t* prod_coef, uint32_t batch) {
+  const uint32_t slots = lp_layout(sh).slots, slice = lp_slice(slots);
+  if (c->prep_large.cap < lp_ws_bytes(slots, batch)) { c->last_error = "large-plan workspace not reserved"; return ZKGPU_EINVAL; }
+  for (uint32_t b0 = 0; b0 < batch; b0 += slice) {     // slices of the workspace, one after the other on the stream
+    const LpHomo src = {sh, tgt_off, term_info, (const uint2*)prod_qm, prod_coef, (const uint32_t*)c->prep_ch.p,
+                        (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p, b0};
+    lp_launch_all(c, s, src, std::min(slice, batch - b0), sh.n_targets, sh.pn, slots);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return ZKGPU_OK;
+}
+
 // ---- statements of several plans in one call (mixed_kernels.hpp) ----------------------------------------------------
 // zkgpu_r1cs_verify_mixed*: statement i is checked against plans[plan_index[i]].  The host lays out a per-call table
 // (one MixPlan per distinct plan, one MixStmt per statement) and one CSR of multiscalar-multiplication rows whose lengths
@@ -3497,23 +3535,33 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
   // LDS classes of k_mx_prepare: plans that leave room for two or more workgroups per CU, and those that take one alone.
   // Statements are ordered by (class, plan); k_mx_prepare runs once per class present, each launch with its own class's
   // largest LDS, so that one large program in a call does not cut every small statement to one workgroup per CU.
+  // Class 2: plans past a CU's LDS, prepared by large_prep.hpp's four launches, however many such plans the call holds.
   std::vector<uint32_t> count(U, 0), order(B), cls(U), by_class(U);
-  for (uint32_t u = 0; u < U; ++u) { cls[u] = uniq[u]->lds_bytes > MIX_LDS_SMALL ? 1u : 0u; by_class[u] = u; }
+  for (uint32_t u = 0; u < U; ++u) { cls[u] = uniq[u]->large ? 2u : uniq[u]->lds_bytes > MIX_LDS_SMALL ? 1u : 0u; by_class[u] = u; }
   std::stable_sort(by_class.begin(), by_class.end(), [&](uint32_t a, uint32_t b) { return cls[a] < cls[b]; });
   for (uint32_t i = 0; i < B; ++i) ++count[pid[i]];
-  uint32_t class_start[3] = {0, 0, B};
+  uint32_t class_start[4] = {0, 0, 0, B};
   size_t class_lds[2] = {0, 0};
+  uint32_t lp_targets = 0, lp_pn = 0, lp_slots = 0;      // the large plans' widest grids and workspace per statement
   {
     std::vector<uint32_t> at(U, 0);
     uint32_t run = 0;
     for (uint32_t u : by_class) {
       at[u] = run;
-      if (cls[u] == 0) class_start[1] = run + count[u];
       run += count[u];
-      class_lds[cls[u]] = std::max(class_lds[cls[u]], uniq[u]->lds_bytes);
+      for (uint32_t k = cls[u] + 1; k < 3; ++k) class_start[k] = run;
+      if (cls[u] < 2) {
+        class_lds[cls[u]] = std::max(class_lds[cls[u]], uniq[u]->lds_bytes);
+      } else {
+        const PrepShape& sh = uniq[u]->shape;
+        lp_targets = std::max(lp_targets, sh.n_targets);
+        lp_pn = std::max(lp_pn, sh.pn);
+        lp_slots = std::max(lp_slots, lp_layout(sh).slots);
+      }
     }
     for (uint32_t i = 0; i < B; ++i) order[at[pid[i]]++] = i;
   }
+  const uint32_t n_large = B - class_start[2];
   bool coop = c->transcript_mode == 2 || (c->transcript_mode == 0 && batch <= COOP_TRANSCRIPT_MAX);
   for (zkgpu_cloak_plan* pl : uniq) coop &= pl->n_seg != 0 && pl->shape.n_ch <= 0xffffu;
   std::vector<uint32_t> lane_order;
@@ -3598,6 +3646,7 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
   TRY(ensure(c, c->prep_dyn_pt, 32 * n_dyn));
   TRY(ensure(c, c->prep_st_sc, 32 * n_st));
   TRY(ensure(c, c->mx_st_index, 4 * n_st));
+  if (n_large) TRY(ensure(c, c->prep_large, lp_ws_bytes(lp_slots, n_large)));
   if (coop) {
     TRY(ensure(c, c->prep_absorb, std::max<uint64_t>(8 * n_abs, 16)));
     TRY(ensure(c, c->prep_raw, std::max<uint64_t>(4 * n_raw, 16)));
@@ -3652,6 +3701,11 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
       hipLaunchKernelGGL(k_mx_prepare, dim3(n_k), dim3(256), class_lds[k], L, d_plans, d_stmts, d_order + class_start[k],
                          (const uint32_t*)d_ch, (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->prep_st_sc.p, (uint32_t*)c->mx_st_index.p);
     }
+  }
+  for (uint32_t b0 = 0; b0 < n_large; b0 += lp_slice(lp_slots)) {      // slices of the workspace, one after the other
+    const LpMixed src = {d_plans, d_stmts, d_order + class_start[2] + b0, (const uint32_t*)d_ch, (uint32_t*)c->prep_dyn_sc.p,
+                         (uint32_t*)c->prep_st_sc.p, (uint32_t*)c->mx_st_index.p};
+    lp_launch_all(c, L, src, std::min(lp_slice(lp_slots), n_large - b0), lp_targets, lp_pn, lp_slots);
   }
   {
     Launch l(c, "k_mx_gather_dyn_points", L);
