@@ -62,7 +62,12 @@ zkgpu_ctx *zkgpu_verifier_lane(zkgpu_verifier *v, int i);
 /* the arithmetic layers on their own, one lane per element (a, b, out: n x 32 bytes).  op 0 field product, 1 square,
  * 2 inverse, 3 a + b - b + a, 4 x^((p-5)/8)  (GF(2^255-19): 32 little-endian bytes, canonical out); 10 product mod l
  * (canonical Montgomery form), 11 the same in the lazy limb form, 12 a lazy chain (a-b)(a+b) + 16ab - b, 13 / 14 / 16 inverse
- * mod l (a^(l-2) canonical / Euclid / a^(l-2) lazy), 15 a + b - a  (scalars: canonical words out, inputs reduced mod l) */
+ * mod l (a^(l-2) canonical / Euclid / a^(l-2) lazy), 15 a + b - a  (scalars: canonical words out, inputs reduced mod l).
+ * Ops 20 .. 28 take the field layer's RAW limb vectors instead (a, b: n x 40 bytes, 10 little-endian u32 limbs taken as they
+ * are -- non-canonical and loose vectors included, within the op's documented limb bounds; out: n x 80 bytes): 20 r = a,
+ * 21 fe_canon(a), 22 fe_carry(a), 23 fe_mul(a, b), 24 fe_sq(a), 25 fe_add(a, b), 26 fe_sub(a, b), 27 fe_sub_c(a, b),
+ * 28 fe_sub4_loose(a, b); per element 20 words: r's 10 limbs as the op left them, fe_to_words(r) (8 words),
+ * fe_is_negative(r) | fe_is_zero(r) << 1 | fe_eq(r, b) << 2, 0. */
 int zkgpu_debug_arith(zkgpu_ctx *ctx, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t n);
 /* the cross-lane primitives of the cooperative Keccak on given inputs (in: 3 x 64 words a, b, gather byte addresses; out:
  * 8 x 64 words: row_ror:8(a), row_shr:1(a), row_shl:1(a), permlane16_swap(a, b) -> (a', b'), permlane32_swap(a, b) ->
@@ -77,7 +82,9 @@ int zkgpu_debug_coop_selftest(zkgpu_ctx *ctx, const uint32_t *in, uint32_t *out,
  *        (layout[3]: A_I1 A_O1 S1 A_I2 A_O2 S2 | V | T_1 T_3..T_6 | L | R): canonical 32-byte scalars of
  *        the verification equation MULTIPLIED THROUGH by c' = rho * y^(padded_n - 1) * prod u_j^2 (the
  *        device evaluates the equation in this inversion-free form).
-  * ("prover_slices": 4 bytes, the slices the last prover call on the context ran in.)
+  * ("prover_slices": 4 bytes, the slices the last prover call on the context ran in.  "decode_routes": 4 x u64, which DECODE
+  * ran since the context was created -- launches of the one-kernel k_decompress, the points they decoded, then the same for the
+  * split k_decompress_pre -> k_pow22523 -> k_decompress_post of 131072 points and more; both profile as "k_decompress".)
  * Returns bytes copied.  zkgpu_cloak_plan_layout fills layout[0..7] = slots per transaction, challenge
  * slots proper, second-phase challenges, dynamic terms, static terms, k, m, monomials. */
 long long zkgpu_debug_read(zkgpu_ctx *ctx, const char *what, void *out, size_t bytes);

@@ -95,8 +95,9 @@ ZK_HD void ge_double(ge& r, const ge& p) {
   fe_add(t, p.X, p.Y);
   fe_sq(t, t);
   // Only what becomes the SECOND operand of a product (F, -(A+B)) is carried: fe_mul multiplies its second operand by 19 and
-  // needs it below 2^27.7; its first operand may be as loose as 1.25 * 2^28 (a column then stays below 2^61.5).  E and G are
-  // first operands only (round 5: three carry passes fewer per doubling; the same form as quad.hpp's quad_double).
+  // needs it below 2^27.7; its first operand may be an fe_sub4_loose output, even limbs < 2^28 + 2^26 + 2^18 (a column then
+  // stays below 2^61.3; field.hpp).  E and G are first operands only (round 5: three carry passes fewer per doubling; the
+  // same form as quad.hpp's quad_double).
   fe_add(H, A, B);            // loose: A + B < 2^27
   fe_sub4_loose(E, t, H);     // E = (X+Y)^2 - A - B + 4p, not carried
   fe_sub(G, B, A);            // G = B - A + 2p, not carried

@@ -16,8 +16,12 @@
 //
 // Limb bounds ("tight"): even limbs < 2^26 + 2^18, odd limbs < 2^25 + 2^18.
 // fe_mul / fe_sq accept "loose" inputs: even < 2^27.7, odd < 2^26.7, i.e. one
-// fe_add or fe_sub of tight values.  Everything returns tight values except
-// fe_add / fe_sub (loose) -- use fe_carry() when chaining them.
+// fe_add or fe_sub of tight values.  fe_mul's FIRST operand may also be an
+// fe_sub4_loose output (even < 2^28 + 2^26 + 2^18, odd < 2^27 + 2^25 + 2^18)
+// when its second is tight: a column then stays below 2^61.3.  fe_sq never
+// takes one (38 times an odd limb would pass 32 bits).  Everything returns
+// tight values except fe_add / fe_sub / fe_sub4_loose -- use fe_carry() when
+// chaining them.  (tests/test_gpu_arith.py holds every op at these bounds.)
 #pragma once
 #include <stdint.h>
 
@@ -84,8 +88,9 @@ ZK_HD void fe_sub_c(fe& h, const fe& f, const fe& g) {
   fe_carry(h);
 }
 
-// h = f - g + 4p, NOT carried: for a value that is only ever the FIRST operand of a product.  f tight, g < 2^27 (a sum of two
-// tight values): limbs < 2^26 + 2^28 (even) / 2^25 + 2^27 (odd), never negative.
+// h = f - g + 4p, NOT carried: for a value that is only ever the FIRST operand of a product.  f tight, g at most a sum of two
+// tight values (even < 2^27 + 2^19, odd < 2^26 + 2^19): limbs < 2^28 + 2^26 + 2^18 (even) / 2^27 + 2^25 + 2^18 (odd), never
+// negative.
 ZK_HD void fe_sub4_loose(fe& h, const fe& f, const fe& g) {
   h.v[0] = f.v[0] + 4 * (M26 - 18) - g.v[0];
   ZK_UNROLL for (int i = 1; i < 10; ++i) h.v[i] = f.v[i] + 4 * ((i & 1) ? M25 : M26) - g.v[i];

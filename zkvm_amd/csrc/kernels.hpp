@@ -164,6 +164,16 @@ k_decompress(const uint32_t* __restrict__ pts, uint32_t* __restrict__ rows, uint
   }
 }
 
+// Which DECODE a context ran (zkgpu_debug_read "decode_routes"): both forms profile as "k_decompress".
+// n[0] launches of the one-kernel k_decompress and n[1] the points they decoded; n[2] / n[3] the same for the split form.
+struct DecodeRoutes {
+  uint64_t n[4] = {0, 0, 0, 0};
+  void note(bool split, uint64_t points) {
+    n[split ? 2 : 0] += 1;
+    n[split ? 3 : 1] += points;
+  }
+};
+
 // ---- split decompression (large point counts) ----------------------------------
 // DECODE is one 250-squaring chain wrapped in a dozen multiplications.  Fused, the chain
 // shares its registers with everything live around it and the kernel runs one wave per

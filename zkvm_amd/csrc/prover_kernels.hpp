@@ -212,4 +212,35 @@ k_debug_arith(uint32_t op, const uint32_t* __restrict__ a, const uint32_t* __res
   for (int q = 0; q < 8; ++q) out[8 * i + q] = wo[q];
 }
 
+// ---- test hook: the field layer on raw limb vectors (zkgpu_debug_arith ops 20 .. 28), one lane per element ------
+// a, b: 10 limbs each, taken as they are (non-canonical and loose vectors included: the op's limb contract is the
+// caller's to respect).  op: 0 r = a  1 fe_canon  2 fe_carry  3 fe_mul  4 fe_sq  5 fe_add  6 fe_sub  7 fe_sub_c
+// 8 fe_sub4_loose.  out, 20 words per element: r's limbs as the op left them, fe_to_words(r), then
+// fe_is_negative(r) | fe_is_zero(r) << 1 | fe_eq(r, b) << 2, then 0.
+__global__ void __launch_bounds__(64)
+k_debug_fe_raw(uint32_t op, const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, uint32_t* __restrict__ out, uint32_t n) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fe x, y, r;
+  for (int k = 0; k < 10; ++k) { x.v[k] = a[10 * i + k]; y.v[k] = b[10 * i + k]; }
+  switch (op) {
+    case 0: r = x; break;
+    case 1: fe_canon(r, x); break;
+    case 2: r = x; fe_carry(r); break;
+    case 3: fe_mul(r, x, y); break;
+    case 4: fe_sq(r, x); break;
+    case 5: fe_add(r, x, y); break;
+    case 6: fe_sub(r, x, y); break;
+    case 7: fe_sub_c(r, x, y); break;
+    default: fe_sub4_loose(r, x, y); break;
+  }
+  uint32_t w[8];
+  fe_to_words(w, r);
+  uint32_t* o = out + 20 * (uint64_t)i;
+  for (int k = 0; k < 10; ++k) o[k] = r.v[k];
+  for (int k = 0; k < 8; ++k) o[10 + k] = w[k];
+  o[18] = (fe_is_negative(r) ? 1u : 0u) | (fe_is_zero(r) ? 2u : 0u) | (fe_eq(r, y) ? 4u : 0u);
+  o[19] = 0;
+}
+
 }  // namespace zk

@@ -45,8 +45,8 @@ __device__ __forceinline__ void fe_select2(fe& out, bool pick, const fe& a, cons
 
 // p <- 2p, all four lanes of the quad hold (and receive) the same point.  r = lane & 3.
 // Between the two stages only what becomes a SECOND operand of a product (F, -(A+B)) is carried; E and G are first operands
-// only (X3 = E F, Y3 = G H', Z3 = G F, T3 = E H'), and stay as the sums they are.  Bounds: first operand < 1.25 * 2^28 (even
-// limbs) / 2^27 (odd), second tight: a column of fe_mul is at most 5 * 19 * 2^54.4 + 5 * 19 * 2^53.4 < 2^61.5 (r05: three
+// only (X3 = E F, Y3 = G H', Z3 = G F, T3 = E H'), and stay as the sums they are.  Bounds: first operand < 2^28 + 2^26 + 2^18
+// (even limbs) / 2^27 + 2^25 + 2^18 (odd; field.hpp fe_sub4_loose), second tight: a column of fe_mul stays below 2^61.3 (r05: three
 // carry passes and forty conditional moves fewer per doubling than the form that carried E, G and A+B and chose among four).
 __device__ __forceinline__ void quad_double(ge& p, int r) {
   fe in, xy, v;

@@ -159,8 +159,8 @@ struct zkgpu_ctx {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   std::vector<std::pair<int, int>> ev_used;   // (prof index, pool index)
   size_t ev_next = 0;
-  int forced_w = 0;
-  int last_w = 0;
+  int forced_w = 0, last_w = 0;
+  DecodeRoutes decode_routes;   // DECODE launches and points by form (kernels.hpp; zkgpu_debug_read "decode_routes")
   uint64_t last_adds = 0;
 };
 
@@ -433,7 +433,7 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
       HIP_TRY(c, hipStreamWaitEvent(sd, c->ev_fork, 0));
     }
     {
-      Launch l(c, "k_decompress", sd);
+      Launch l(c, "k_decompress", sd); c->decode_routes.note(true, job.n_dyn);
       hipLaunchKernelGGL(k_decompress_pre, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, sd, job.d_dyn_points,
                          (uint32_t*)c->dec_scratch.p, job.n_dyn);
       hipLaunchKernelGGL(k_pow22523, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, sd, (uint32_t*)c->dec_scratch.p,
@@ -444,7 +444,7 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
     }
     if (decompress_aside) HIP_TRY(c, hipEventRecord(c->ev_join, sd));
   } else if (job.n_dyn) {
-    Launch l(c, "k_decompress");
+    Launch l(c, "k_decompress"); c->decode_routes.note(false, job.n_dyn);
     hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, s, job.d_dyn_points,
                        (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, job.n_msm,
                        (uint32_t*)c->msm_fail.p, bad_index, (uint8_t*)nullptr);
@@ -640,7 +640,7 @@ int batch_device_enqueue(zkgpu_ctx* c, const Job& job, bool values) {
                          (uint32_t*)nullptr, (uint32_t)B);
     }
     {
-      Launch l(c, "k_decompress", s);
+      Launch l(c, "k_decompress", s); c->decode_routes.note(false, job.n_dyn);
       hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, s, job.d_dyn_points,
                          (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, (uint32_t)B,
                          (uint32_t*)c->msm_fail.p, (unsigned long long*)((char*)c->status.p + 8), (uint8_t*)nullptr);
@@ -777,7 +777,7 @@ int batch_device_tables_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_points
       TRY(ensure(c, c->msm_fail, (size_t)B * 4));
       HIP_TRY(c, hipMemsetAsync(c->msm_fail.p, 0, (size_t)B * 4, s));
       {
-        Launch l(c, "k_decompress");
+        Launch l(c, "k_decompress"); c->decode_routes.note(false, job.n_dyn);
         hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, s, job.d_dyn_points,
                            (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, (uint32_t)B,
                            (uint32_t*)c->msm_fail.p, (unsigned long long*)((char*)c->status.p + 8), (uint8_t*)nullptr);
@@ -1047,7 +1047,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
     TRY(small_accumulate_launch(c, job, H1));       // points and tables were done beside the transcript
   } else {
     {
-      Launch l(c, "k_decompress", H1);
+      Launch l(c, "k_decompress", H1); c->decode_routes.note(false, job.n_dyn);
       hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, H1, job.d_dyn_points,
                          (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, (uint32_t)B, (uint32_t*)c->msm_fail.p,
                          (unsigned long long*)((char*)c->status.p + 8), (uint8_t*)nullptr);
@@ -1592,7 +1592,7 @@ int zkgpu_pointset_create(zkgpu_ctx* c, const uint8_t* points, size_t n, zkgpu_p
   HIP_TRY(c, hipMemsetAsync(c->status.p, 0xff, 16, c->stream));
   unsigned long long* bad_index = (unsigned long long*)((char*)c->status.p + 8);
   if (n) {
-    Launch l(c, "k_decompress");
+    Launch l(c, "k_decompress"); c->decode_routes.note(false, n);
     hipLaunchKernelGGL(k_decompress, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream,
                        (const uint32_t*)c->in_points.p, rows, (uint64_t)n, (const uint64_t*)nullptr, 1u,
                        (uint32_t*)nullptr, bad_index, (uint8_t*)nullptr);
@@ -1704,7 +1704,7 @@ size_t zkgpu_pointset_table_bytes(const zkgpu_pointset* ps) {
 // Test hook: the intermediate buffers of the last device-side preparation on this context
 // ("challenges": n_ch_ext x 32 B per transaction, Montgomery form; "static_scalars", "dyn_scalars",
 // "dyn_points": canonical 32-byte values).  Copies min(bytes, size) bytes; returns the bytes copied or < 0.
-long long zkgpu_debug_read(zkgpu_ctx* c, const char* what, void* out, size_t bytes) {
+static long long debug_read_buffers(zkgpu_ctx* c, const char* what, void* out, size_t bytes) {
   if (!c || !what || !out) return ZKGPU_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   DeviceGuard g(c->device);
@@ -1791,7 +1791,7 @@ int zkgpu_debug_coop_selftest(zkgpu_ctx* c, const uint32_t* in, uint32_t* out, u
 }
 
 // Test hook: one arithmetic operation of the field / scalar layers on n elements (prover_kernels.hpp, k_debug_arith)
-int zkgpu_debug_arith(zkgpu_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n) {
+static int debug_arith_words(zkgpu_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n) {
   if (!c || !a || !b || !out || n == 0 || n >= (1u << 24)) return ZKGPU_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   DeviceGuard g(c->device);
@@ -2550,7 +2550,7 @@ int zkgpu_decode_check(zkgpu_ctx* c, const uint8_t* points, size_t n, uint8_t* o
   TRY(upload(c, c->in_points, points, n * 32));
   TRY(ensure(c, c->ok_bytes, n));
   {
-    Launch l(c, "k_decompress");
+    Launch l(c, "k_decompress"); c->decode_routes.note(false, n);
     hipLaunchKernelGGL(k_decompress, dim3(blocks_for(n, 256)), dim3(256), 0, c->stream,
                        (const uint32_t*)c->in_points.p, (uint32_t*)nullptr, (uint64_t)n, (const uint64_t*)nullptr,
                        1u, (uint32_t*)nullptr, (unsigned long long*)nullptr, (uint8_t*)c->ok_bytes.p);
@@ -3758,4 +3758,32 @@ int zkgpu_r1cs_verify_mixed(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_
   const int rc = pipe_wait(c, accept_bitmap);
   if (rc != ZKGPU_OK) memset(accept_bitmap, 0, (batch + 7) / 8);
   return rc;
+}
+
+// Test hook zkgpu_debug_read: the context's DECODE counters, or an intermediate buffer (debug_read_buffers)
+long long zkgpu_debug_read(zkgpu_ctx* c, const char* what, void* out, size_t bytes) {
+  if (!c || !what || !out) return ZKGPU_EINVAL;
+  if (strcmp(what, "decode_routes") != 0) return debug_read_buffers(c, what, out, bytes);
+  if (bytes < sizeof(c->decode_routes.n)) return ZKGPU_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  memcpy(out, c->decode_routes.n, sizeof(c->decode_routes.n));
+  return (long long)sizeof(c->decode_routes.n);
+}
+
+// Test hook zkgpu_debug_arith: ops 20 .. 28 run the field layer on raw 10-limb vectors (prover_kernels.hpp, k_debug_fe_raw);
+// every other op goes to debug_arith_words
+int zkgpu_debug_arith(zkgpu_ctx* c, int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n) {
+  if (op < 20 || op > 28) return debug_arith_words(c, op, a, b, out, n);
+  if (!c || !a || !b || !out || n == 0 || n >= (1u << 24)) return ZKGPU_EINVAL;
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  TRY(upload(c, c->in_scalars, a, 40 * n));
+  TRY(upload(c, c->in_points, b, 40 * n));
+  TRY(ensure(c, c->values, 80 * n));
+  hipLaunchKernelGGL(k_debug_fe_raw, dim3(blocks_for(n, 64)), dim3(64), 0, c->stream, (uint32_t)(op - 20),
+                     (const uint32_t*)c->in_scalars.p, (const uint32_t*)c->in_points.p, (uint32_t*)c->values.p, (uint32_t)n);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(out, c->values.p, 80 * n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return ZKGPU_OK;
 }

@@ -15,8 +15,9 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import struct
 import weakref
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -339,6 +340,22 @@ class Context:
         out = C.create_string_buffer(32 * n)
         self._check(self.lib.zkgpu_debug_arith(self.h, op, a, b, out, n))
         return out.raw
+
+    def debug_fe_raw(self, op: int, a: Sequence[Sequence[int]], b: Sequence[Sequence[int]]) -> List[List[int]]:
+        """zkgpu_debug_arith op 20 + op: one field-layer operation on raw 10-limb vectors -> per element 20 words (r's limbs,
+        fe_to_words(r), predicate flags, 0)"""
+        n = len(a)
+        assert 0 <= op <= 8 and len(b) == n > 0 and all(len(x) == 10 for x in a) and all(len(y) == 10 for y in b)
+        ia = struct.pack("<%dI" % (10 * n), *[v for x in a for v in x])
+        ib = struct.pack("<%dI" % (10 * n), *[v for y in b for v in y])
+        out = C.create_string_buffer(80 * n)
+        self._check(self.lib.zkgpu_debug_arith(self.h, 20 + op, ia, ib, out, n))
+        w = struct.unpack("<%dI" % (20 * n), out.raw)
+        return [list(w[20 * i: 20 * i + 20]) for i in range(n)]
+
+    def decode_routes(self) -> Tuple[int, int, int, int]:
+        """zkgpu_debug_read "decode_routes" -> (one-kernel DECODE launches, their points, split DECODE launches, their points)"""
+        return struct.unpack("<4Q", self.debug_read("decode_routes", 32))
 
     def set_prover_mode(self, mode: int) -> None:
         """zkgpu_set_prover_mode: 0 the whole proof on the device, 1 host threads in lockstep, 16 + S: on the device in S slices."""
