@@ -21,7 +21,7 @@ bitmap (copied to the host).
                         are all-gathered over RCCL behind the C ABI (zkgpu_comm_allgather_bitmap);
                         every rank checks the bitmap of the WHOLE batch.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W] [--config 4] [--dump-outputs DIR]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--config 4] [--dump-outputs DIR] [--full]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
                 --master-port P bench.py --gpus N --steps K --warmup W [--config 4]
 Both forms work for N > 1: started WITHOUT a launcher (WORLD_SIZE unset) `--gpus N` makes this process spawn N fresh
@@ -30,13 +30,16 @@ if any rank did.  One process per GPU; shards are independent (weak scaling); th
 the all-gather of the accept bitmaps (ncclAllGather behind zkgpu_comm_allgather_bitmap -- the ONLY RCCL communicator of
 a rank; barriers, the timing reduction and the id broadcast run over gloo on the host).
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (the dominant kernel of the step -- by
-summed solo kernel time -- against the HBM roofline the north-star names, the whole step against
-it, and the integer-ALU figure that actually binds), "setup" (one-time costs that `value` does not
-contain: table build, table bytes), "cpu_baseline" (the CPU oracle's full verifier -- a port of the
-reference's algorithm; the reference itself is not mounted -- on this box's host cores), and in
-config 2 "msm_boundary", "per_tx_checks", "host_memory", "prover", "msm_2p20" (BASELINE configs[2],
-checked against tests/golden/msm_2p20.json).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, writes --dump-outputs
+and prints the headline with "setup" (one-time costs that `value` does not contain: table build,
+table bytes); nothing else runs.  With --full the line also carries what takes runs of its own:
+"roofline" (the dominant kernel of the step -- by summed solo kernel time -- against the HBM roofline
+the north-star names, the whole step against it, and the integer-ALU figure that actually binds),
+the per-kernel times, "cpu_baseline" (the CPU oracle's full verifier -- a port of the reference's
+algorithm; the reference itself is not mounted -- on the host's cores), and in config 2
+"latency_one_batch", "value_by_steps", "steady_state", "msm_boundary", "per_tx_checks",
+"host_memory", "tx_verify", "prover", "msm_2p20" (BASELINE configs[2], checked against
+tests/golden/msm_2p20.json).
 """
 from __future__ import annotations
 
@@ -869,7 +872,9 @@ def run_config2(args, W):
     # Every step is a batch of its own (workload_2x2): distinct proofs order, distinct corruptions, distinct verifier
     # randomness.  The ring is as long as the longest run of this process, so no batch is ever submitted twice while
     # anything that met it could still sit in a cache: 1.35 MB per step in HBM.
-    steady_steps = 0 if (args.lean or args.solo or args.no_steady or world > 1) else 200
+    # (side_legs: the --full measurements beyond the solo pass and the roofline)
+    side_legs = args.full and not args.lean
+    steady_steps = 0 if (not side_legs or args.solo or args.no_steady or world > 1) else 200
     lanes_planned = args.inflight if args.tickets > 0 else 1
     n_sets = max(args.steps + max(args.warmup, 1, lanes_planned * (args.merge // batch)), steady_steps, 2 * args.merge // batch + 2, 24)
     sets = []
@@ -881,7 +886,7 @@ def run_config2(args, W):
         S.bits, S.want = expected, bitmap_of(expected)
         S.txs, S.r_bytes = (txs, r_bytes) if sidx == 0 else (None, None)
         # the same step in HOST memory for the host_memory leg (the first 64 steps: 1.4 MB each)
-        S.host = (b"".join(t[2] for t in txs), b"".join(t[3] for t in txs), r_bytes) if sidx < 64 and rank == 0 else None
+        S.host = (b"".join(t[2] for t in txs), b"".join(t[3] for t in txs), r_bytes) if sidx < 64 and rank == 0 and side_legs else None
         sets.append(S)
     txs, r_bytes = sets[0].txs, sets[0].r_bytes
     n_in, n_out = txs[0][0], txs[0][1]
@@ -1110,20 +1115,6 @@ def run_config2(args, W):
     if rank == 0:
         # the last timed step's accept bitmap, one 0 / 1 per transaction of this rank's batch
         dump_outputs(args, {"accept": bits_of(bm, batch)})
-        if not inflight_events and world == 1:
-            for c in prof_ctxs:
-                c.profile_reset()
-                c.profile(True)
-            timed(args.steps, base=0, gather=False)                # the same steps once more, untimed, with events around every launch
-            for c in prof_ctxs:
-                c.profile(False)
-        prof = profile_lanes(prof_ctxs)
-        in_flight_ms = {k: v[1] / v[0] for k, v in prof.items() if v[0]}
-        solo, launches = solo_pass()
-        ms_per_step = elapsed / args.steps * 1e3
-        alg_step = algorithmic_bytes(lib, [(n_in, n_out)] * batch)
-        alg_dev = alg_step * (dev_batch // batch)                 # per device batch (the unit the kernels are launched for)
-        ms_per_dev_batch = ms_per_step * (dev_batch // batch)
         line = common_line(args, W, batch * world * args.steps / elapsed, elapsed,
                            "synthetic: 1024 distinct real R1CS proofs of the 2-in/2-out cloak statement (committed fixture, oracle "
                            "prover); every step is a batch of its own -- the fixture rotated, its own ~1.5% corruptions, its own "
@@ -1147,16 +1138,31 @@ def run_config2(args, W):
                             "hw_queues_set_by": ("caller" if _HWQ_PRESET else "nobody: the HIP runtime had started before bench.py could export the hint (runtime default)"
                                                  if "GPU_MAX_HW_QUEUES" not in os.environ else "bench.py on zkgpu_runtime_hint's advice, before the HIP runtime started"),
                             "parallelism": "tx-sharded x%d, RCCL all-gather of accept bitmaps" % world})
-        line["roofline"] = roofline_object(solo, launches, in_flight_ms, alg_dev, dev_batch, ms_per_dev_batch, table_bytes,
-                                           "algorithmic bytes per launch = %d B per transaction (64 B x %d proof-specific terms + 32 B x "
-                                           "%d generator scalars) x the %d transactions a launch processes (%d batches of %d merged by the "
-                                           "verifier); `step` figures are per device batch" % (alg_step // batch, n_dyn, n_static, dev_batch, dev_batch // batch, batch))
         line["setup"] = {"table_build_ms": round(table_s * 1e3, 1), "table_bytes": table_bytes,
                          "note": "one-time per generator set (generators + fixed-base tables, zkgpu_pointset_build_tables); not in `value`"}
-        line["kernel_ms_in_flight"] = {k: round(x, 4) for k, x in sorted(in_flight_ms.items())}
-        line["kernel_ms_solo"] = {k: round(x, 4) for k, x in sorted(solo.items())}
         line["host_submit_ms_per_step"] = round(submit_ms, 4)
-        if bv is not None and not args.lean:
+        if args.full:
+            if not inflight_events and world == 1:
+                for c in prof_ctxs:
+                    c.profile_reset()
+                    c.profile(True)
+                timed(args.steps, base=0, gather=False)            # the same steps once more, untimed, with events around every launch
+                for c in prof_ctxs:
+                    c.profile(False)
+            prof = profile_lanes(prof_ctxs)
+            in_flight_ms = {k: v[1] / v[0] for k, v in prof.items() if v[0]}
+            solo, launches = solo_pass()
+            ms_per_step = elapsed / args.steps * 1e3
+            alg_step = algorithmic_bytes(lib, [(n_in, n_out)] * batch)
+            alg_dev = alg_step * (dev_batch // batch)             # per device batch (the unit the kernels are launched for)
+            ms_per_dev_batch = ms_per_step * (dev_batch // batch)
+            line["roofline"] = roofline_object(solo, launches, in_flight_ms, alg_dev, dev_batch, ms_per_dev_batch, table_bytes,
+                                               "algorithmic bytes per launch = %d B per transaction (64 B x %d proof-specific terms + 32 B x "
+                                               "%d generator scalars) x the %d transactions a launch processes (%d batches of %d merged by the "
+                                               "verifier); `step` figures are per device batch" % (alg_step // batch, n_dyn, n_static, dev_batch, dev_batch // batch, batch))
+            line["kernel_ms_in_flight"] = {k: round(x, 4) for k, x in sorted(in_flight_ms.items())}
+            line["kernel_ms_solo"] = {k: round(x, 4) for k, x in sorted(solo.items())}
+        if bv is not None and side_legs:
             # ONE batch of 1024 with nothing else in flight (configs[1] read literally): submit, wait, repeat
             lat = []
             for k in range(12):
@@ -1172,7 +1178,7 @@ def run_config2(args, W):
                                          "tx_per_s": round(batch / lat[len(lat) // 2], 1),
                                          "note": "one %d-transaction batch, nothing else in flight: zkgpu_verifier_submit_dev + "
                                                  "zkgpu_verifier_wait, 12 distinct batches" % batch}
-        if bv is not None and not args.lean and world == 1:
+        if bv is not None and side_legs and world == 1:
             # `value` against the step count (it used to peak where --steps was a multiple of merge / 1024):
             # the same timed arrangement -- one submit_many of everything, then the waits -- for other run lengths, best of 3
             by_steps = {}
@@ -1199,7 +1205,7 @@ def run_config2(args, W):
                                     "steps": steady_steps, "tickets_in_flight": 64,
                                     "note": "same verifier, same merge target, 200 distinct steps with up to 64 tickets in flight"}
         host_tickets = None
-        if bv is not None and not args.lean:
+        if bv is not None and side_legs:
             # tickets from host memory: the timed arrangement again (same --steps, same tickets in flight, same merge target),
             # every step's bytes handed over from host memory; then 200 steps of it
             run_tickets_host(max(bv.lanes() * rep, n_warm), base=32)                    # staging areas are made here
@@ -1212,7 +1218,7 @@ def run_config2(args, W):
                 run_tickets_host(steady_steps, base=0, depth=64)
                 dt = time.perf_counter() - t1
                 host_tickets["steady_tx_per_s"] = round(batch * steady_steps / dt, 1)
-        if not args.lean:
+        if side_legs:
             line["hbm_copy"] = hbm_copy_leg(ctx)
             line["cpu2"] = ("omitted: BASELINE.md's second CPU line (libsodium naive sum of crypto_scalarmult_ristretto255) needs "
                             "libsodium on the GPU box; it exists only in the build container (/opt/conda/lib), where the golden vectors "
@@ -1487,31 +1493,10 @@ def run_config4(args, W):
     if rank == 0:
         # the last timed step's accept bitmap of the WHOLE batch (what every rank receives), one 0 / 1 per transaction
         dump_outputs(args, {"accept": bits_of(whole, total)})
-        ms_per_step = elapsed / args.steps * 1e3
         counts = {}
         for s in shapes:
             counts["%dx%d" % s] = counts.get("%dx%d" % s, 0) + 1
         shard_terms = [sum(sum(shape_terms(lib, *s)) for s in shapes[a:b]) for a, b in parts]
-        alg_step = algorithmic_bytes(lib, shapes[lo:hi])
-        # per-kernel durations: a second verifier with ONE lane, every kernel alone on the chip
-        solo_v = BlockVerifier(ctx, gens, batches_in_flight=1, chunk=args.chunk)
-        lane0 = solo_v.lane(0)
-        lane0.set_group_size(args.group)
-        sblock = solo_v.block(mine, r_bytes[64 * lo: 64 * hi])
-        solo_v.verify_block(sblock)
-        lane0.profile_reset()
-        lane0.set_serial(True)
-        lane0.profile(True)
-        reps = 2
-        for _ in range(reps):
-            assert solo_v.verify_block(sblock) == bitmap_of(expected[lo:hi])
-        lane0.profile(False)
-        lane0.set_serial(False)
-        prof = lane0.profile_read()
-        solo = {k: v[1] / v[0] for k, v in prof.items() if v[0]}
-        launches = {k: v[0] / reps for k, v in prof.items() if v[0]}
-        sblock.close()
-        solo_v.close()
         line = common_line(args, W, total * args.steps / elapsed, elapsed,
                            "synthetic: 160 real R1CS proofs (32 of each shape, committed fixture, oracle prover) drawn with a fixed "
                            "seed, every transaction under its own verifier randomness; 1 in 61 corrupted (six kinds, every shape)",
@@ -1527,15 +1512,36 @@ def run_config4(args, W):
                             "control_plane": "gloo (host)" if world > 1 else None, "bringup": W.bringup,
                             "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "0")),
                             "parallelism": "tx-sharded x%d" % world})
-        line["roofline"] = roofline_object(solo, launches, {}, alg_step, hi - lo, ms_per_step, table_bytes,
-                                           "rank 0's shard: %d transactions, %d algorithmic bytes (64 B per proof-specific term + 32 B "
-                                           "per generator scalar, per shape); the committed counter tables were collected on uniform "
-                                           "2-in/2-out launches and are not applied to mixed shapes (traffic / VALU fields null)"
-                                           % (hi - lo, alg_step), counters=False)
         line["setup"] = {"table_build_ms": round(table_s * 1e3, 1), "table_bytes": table_bytes,
                          "note": "one table set for every shape up to 4x4 (512 + 512 generators); not in `value`"}
-        line["kernel_ms_solo"] = {k: round(x, 4) for k, x in sorted(solo.items())}
-        if not args.lean:
+        if args.full:
+            # per-kernel durations: a second verifier with ONE lane, every kernel alone on the chip
+            solo_v = BlockVerifier(ctx, gens, batches_in_flight=1, chunk=args.chunk)
+            lane0 = solo_v.lane(0)
+            lane0.set_group_size(args.group)
+            sblock = solo_v.block(mine, r_bytes[64 * lo: 64 * hi])
+            solo_v.verify_block(sblock)
+            lane0.profile_reset()
+            lane0.set_serial(True)
+            lane0.profile(True)
+            reps = 2
+            for _ in range(reps):
+                assert solo_v.verify_block(sblock) == bitmap_of(expected[lo:hi])
+            lane0.profile(False)
+            lane0.set_serial(False)
+            prof = lane0.profile_read()
+            solo = {k: v[1] / v[0] for k, v in prof.items() if v[0]}
+            launches = {k: v[0] / reps for k, v in prof.items() if v[0]}
+            sblock.close()
+            solo_v.close()
+            alg_step = algorithmic_bytes(lib, shapes[lo:hi])
+            line["roofline"] = roofline_object(solo, launches, {}, alg_step, hi - lo, elapsed / args.steps * 1e3, table_bytes,
+                                               "rank 0's shard: %d transactions, %d algorithmic bytes (64 B per proof-specific term + 32 B "
+                                               "per generator scalar, per shape); the committed counter tables were collected on uniform "
+                                               "2-in/2-out launches and are not applied to mixed shapes (traffic / VALU fields null)"
+                                               % (hi - lo, alg_step), counters=False)
+            line["kernel_ms_solo"] = {k: round(x, 4) for k, x in sorted(solo.items())}
+        if args.full and not args.lean:
             # the same shard handed over in HOST memory (grouping, PCIe copies, python marshalling included)
             t0 = time.perf_counter()
             hb = bv.verify(mine, r_bytes[64 * lo: 64 * hi])
@@ -1584,12 +1590,15 @@ def main():
     ap.add_argument("--horner-mode", type=int, default=0, choices=(0, 1, 2), help="zkgpu_set_horner_mode")
     ap.add_argument("--transcript-mode", type=int, default=0, choices=(0, 1, 2),
                     help="zkgpu_set_transcript_mode: 0 automatic, 1 one lane per transaction, 2 one wavefront per transaction")
-    ap.add_argument("--lean", action="store_true", help="the timed steps and the solo pass only (what tools/profile_bench.sh profiles)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's steps, also measure what takes runs of its own: the per-kernel times and the roofline, the "
+                         "CPU baseline and (config 2) the side legs -- latency, steady state, host memory, table widths, prover, MSM")
+    ap.add_argument("--lean", action="store_true", help="with --full: of those, the per-kernel times and the roofline only (what tools/profile_bench.sh profiles)")
     ap.add_argument("--solo", action="store_true", help="config 2: only serial steps, every kernel alone on the chip (for rocprofv3 --stats)")
-    ap.add_argument("--no-steady", action="store_true", help="config 2: skip the 200-step steady-state leg")
-    ap.add_argument("--no-sweep", action="store_true", help="config 2: skip the generator-table width sweep")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-msm", action="store_true", help="skip the prover and 2^20 MSM legs")
+    ap.add_argument("--no-steady", action="store_true", help="config 2 with --full: skip the 200-step steady-state leg")
+    ap.add_argument("--no-sweep", action="store_true", help="config 2 with --full: skip the generator-table width sweep")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-msm", action="store_true", help="config 2 with --full: skip the transaction, prover and 2^20 MSM legs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the accept bitmap of the last timed step as DIR/accept.npy (float32, one 0 / 1 per "
                          "transaction; config 2: rank 0's batch, config 4: the whole batch)")

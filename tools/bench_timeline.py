@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Kernel timeline of the LAST burst of device batches in a rocprofv3 --kernel-trace CSV of `bench.py --lean` (the solo pass runs
+"""Kernel timeline of the LAST burst of device batches in a rocprofv3 --kernel-trace CSV of `bench.py --full --lean` (the solo pass runs
 last: pass --skip-solo to cut the serial launches at the end off by their signature -- k_small_accumulate launches that do not
 overlap anything).  usage: bench_timeline.py <kernel_trace.csv> [window_ms=8]
 Prints the kernels of the timed region's device batches: start (ms), duration, end, queue, name, grid."""
@@ -10,7 +10,7 @@ for r in csv.DictReader(open(sys.argv[1])):
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), n, r.get("Queue_Id", "?"), r.get("Grid_Size_X", "?")))
 rows.sort()
 win = float(sys.argv[2]) if len(sys.argv) > 2 else 8.0
-# `bench.py --lean --steps 20 --warmup 5` merges tickets into device batches: 5 (priming, one per lane) + 1 (the warm-up's five
+# `bench.py --full --lean --steps 20 --warmup 5` merges tickets into device batches: 5 (priming, one per lane) + 1 (the warm-up's five
 # tickets) + 2 (THE TIMED STEPS) + 2 (the same steps again with events) -- one k_merge_inputs launch each; the solo pass has none
 merges = [i for i, r in enumerate(rows) if r[2] == "k_merge_inputs"]
 if len(merges) < 8:

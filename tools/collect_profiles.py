@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Turn the raw output of tools/profile_bench.sh <tag> (under gpurun_out/) into the committed summaries:
+"""Turn the raw output of tools/profile_bench.sh <tag> <output directory> into the committed summaries:
   profiles/<tag>_bench_kernel_stats.csv            rocprofv3 --stats table of the timed bench (batches in flight)
   profiles/<tag>_bench_kernel_trace_summary.txt    per-kernel durations of the last dispatches (= timed steps)
   profiles/<tag>_solo_kernel_stats.csv             rocprofv3 --stats table of `bench.py --solo` (each kernel alone on the chip)
@@ -9,7 +9,7 @@
   profiles/<tag>_pmc_<PASS>.txt, <tag>_pmcmsm_<PASS>.txt   per kernel and counter: dispatches, last value, mean
   profiles/pmc_traffic.json                        HBM bytes per launch = 2 x FETCH_SIZE + WRITE_SIZE (KiB -> B)
   profiles/pmc_valu.json                           SQ_INSTS_VALU (wave instructions) per launch
-usage: python tools/collect_profiles.py <tag>"""
+usage: python tools/collect_profiles.py <tag> <the output directory profile_bench.sh wrote>"""
 import collections, csv, glob as _glob, json, os, shutil, subprocess, sys
 
 
@@ -22,8 +22,8 @@ class glob:     # gpurun MERGES what a call wrote into gpurun_out/: a directory 
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
+go = os.path.abspath(sys.argv[2])
 out = os.path.join(ROOT, "profiles")
-go = os.path.join(ROOT, "gpurun_out")
 
 
 def short(name):

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Per-kernel means of the counters collected by tools/pmc_breakdown.sh <tag> -> profiles/<tag>_pmc_breakdown.txt"""
+"""Per-kernel means of the counters collected by tools/pmc_breakdown.sh <tag> <output directory> -> profiles/<tag>_pmc_breakdown.txt
+usage: python tools/pmc_breakdown.py <tag> <that output directory>"""
 import collections, csv, glob, os, sys
-tag = sys.argv[1]
+tag, raw = sys.argv[1], sys.argv[2]
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tot = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.defaultdict(collections.Counter)
-for f in glob.glob(os.path.join(root, "gpurun_out", "pmcx_%s_*" % tag, "*", "*counter_collection.csv")):
+for f in glob.glob(os.path.join(raw, "pmcx_%s_*" % tag, "*", "*counter_collection.csv")):
     for row in csv.DictReader(open(f)):
         k = row["Kernel_Name"].split("(")[0].replace("zk::", "").replace("void ", "").split("<")[0]
         tot[k][row["Counter_Name"]] += float(row["Counter_Value"]); n[k][row["Counter_Name"]] += 1
