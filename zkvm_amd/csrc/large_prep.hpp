@@ -18,8 +18,8 @@
 // static_scalars; static_index in mixed calls), all multiplied through by c'; the lazy limb form and its bounds are
 // those of sc_dev.hpp / k_prepare, operation for operation.
 //
-// A source (LpHomo here, LpMixed in mixed_kernels.hpp) maps a launch's statement b to its plan and its input / output
-// rows; the workspace of launch statement b starts at b * ws_slots slots.
+// A source (LpHomo here, LpMixed in mixed_kernels.hpp) maps a launch's statement b to its view (PrepStmt: its plan and its
+// input / output rows; dr or sx nullptr: not written); the workspace of launch statement b starts at b * ws_slots slots.
 #pragma once
 
 namespace zk {
@@ -64,21 +64,6 @@ __host__ inline size_t lp_ws_bytes(uint32_t slots, uint32_t batch) {
   return (size_t)n * slots * SCL_WORDS * 4;
 }
 
-// one statement of a launch: its plan and where its rows are
-struct LpStmt {
-  PrepShape sh;                 // (a copy: its fields become scalar registers)
-  const uint32_t* tgt_off;
-  const uint32_t* term_info;
-  const uint2* prod_qm;
-  const uint32_t* prod_coef;
-  const uint32_t* ch;           // its challenge slots (canonical Montgomery words)
-  uint32_t* ds;                 // dynamic scalars
-  uint32_t* dr;                 // their recoded form (nullptr: not written)
-  uint32_t* ss;                 // static scalars
-  uint32_t* sx;                 // generator index of the static terms (nullptr: not written)
-  uint32_t h_base;
-};
-
 // a homogeneous batch: one plan, launch statement b at row first + b
 struct LpHomo {
   PrepShape sh;
@@ -91,10 +76,14 @@ struct LpHomo {
   uint32_t* dyn_recoded;
   uint32_t* static_scalars;
   uint32_t first;
-  __device__ LpStmt at(uint32_t b_) const {
+  __device__ PrepStmt at(uint32_t b_) const {
     const uint32_t b = first + b_;
-    return {sh, tgt_off, term_info, prod_qm, prod_coef, ch + (uint64_t)b * sh.n_ch_ext * 8, dyn_scalars + (uint64_t)b * sh.n_dyn * 8,
-            dyn_recoded + (uint64_t)b * sh.n_dyn * 8, static_scalars + (uint64_t)b * sh.n_static * 8, nullptr, 0};
+    PrepStmt st = {sh, nullptr, nullptr, tgt_off, term_info, prod_qm, prod_coef};
+    st.ch = ch + (uint64_t)b * sh.n_ch_ext * 8;
+    st.ds = dyn_scalars + (uint64_t)b * sh.n_dyn * 8;
+    st.dr = dyn_recoded + (uint64_t)b * sh.n_dyn * 8;
+    st.ss = static_scalars + (uint64_t)b * sh.n_static * 8;
+    return st;
   }
 };
 
@@ -110,8 +99,8 @@ __device__ __forceinline__ scl lp_packed_mul(const uint32_t* pa, const uint32_t*
 template <class Src>
 __global__ void __launch_bounds__(256)
 k_lp_head(Src src, uint32_t* __restrict__ ws_all, uint32_t ws_slots) {
-  const LpStmt st = src.at(blockIdx.x);
-  const PrepShape& sh = st.sh;
+  const PrepStmt st = src.at(blockIdx.x);
+  const PrepShape sh = st.sh;                   // (a copy: its fields become scalar registers)
   constexpr uint32_t SW = SCL_WORDS;
   const LpLayout ly = lp_layout(sh);
   uint32_t* ws = ws_all + (uint64_t)blockIdx.x * ws_slots * SW;
@@ -201,8 +190,8 @@ k_lp_head(Src src, uint32_t* __restrict__ ws_all, uint32_t ws_slots) {
 template <class Src>
 __global__ void __launch_bounds__(256)
 k_lp_flatten(Src src, uint32_t* __restrict__ ws_all, uint32_t ws_slots) {
-  const LpStmt st = src.at(blockIdx.x);
-  const PrepShape& sh = st.sh;
+  const PrepStmt st = src.at(blockIdx.x);
+  const PrepShape sh = st.sh;                   // (a copy: its fields become scalar registers)
   const uint32_t g0 = blockIdx.y * LP_CHUNK;
   if (g0 >= sh.n_targets) return;
   const uint32_t g1 = min(g0 + LP_CHUNK, sh.n_targets);
@@ -270,8 +259,8 @@ k_lp_flatten(Src src, uint32_t* __restrict__ ws_all, uint32_t ws_slots) {
 template <class Src>
 __global__ void __launch_bounds__(256)
 k_lp_gens(Src src, uint32_t* __restrict__ ws_all, uint32_t ws_slots) {
-  const LpStmt st = src.at(blockIdx.x);
-  const PrepShape& sh = st.sh;
+  const PrepStmt st = src.at(blockIdx.x);
+  const PrepShape sh = st.sh;                   // (a copy: its fields become scalar registers)
   const uint32_t i0 = blockIdx.y * LP_CHUNK;
   if (i0 >= sh.pn) return;
   constexpr uint32_t SW = SCL_WORDS;
@@ -332,8 +321,8 @@ k_lp_gens(Src src, uint32_t* __restrict__ ws_all, uint32_t ws_slots) {
 template <class Src>
 __global__ void __launch_bounds__(64)
 k_lp_tail(Src src, uint32_t* __restrict__ ws_all, uint32_t ws_slots) {
-  const LpStmt st = src.at(blockIdx.x);
-  const PrepShape& sh = st.sh;
+  const PrepStmt st = src.at(blockIdx.x);
+  const PrepShape sh = st.sh;                   // (a copy: its fields become scalar registers)
   constexpr uint32_t SW = SCL_WORDS;
   const LpLayout ly = lp_layout(sh);
   uint32_t* ws = ws_all + (uint64_t)blockIdx.x * ws_slots * SW;

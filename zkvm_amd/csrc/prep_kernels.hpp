@@ -64,6 +64,11 @@ __device__ inline scm scm_pow_u32(const scm& base, uint32_t e) {
 // ---- k_proof_unpack -------------------------------------------------------------------
 // compact != 0: the one-phase wire format (version byte 0; A_I2, A_O2, S2 left out, proof_stride = 1 + 4 (proof_words - 24)):
 // the identity -- 32 zero bytes -- stands in for the three points, as upstream's R1CSProof::from_bytes has it
+__device__ __forceinline__ uint32_t proof_word(const uint8_t* p /*version byte*/, uint32_t j, uint32_t compact) {
+  if (compact && j >= 24 && j < 48) return 0;
+  const uint8_t* b = p + 1 + 4 * (uint64_t)((compact && j >= 48) ? j - 24 : j);
+  return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+}
 __global__ void __launch_bounds__(256)
 k_proof_unpack(const uint8_t* __restrict__ proofs, uint64_t proof_stride, uint32_t* __restrict__ pw,
                uint32_t proof_words, uint32_t batch, uint32_t* __restrict__ wellformed, uint32_t compact) {
@@ -71,14 +76,25 @@ k_proof_unpack(const uint8_t* __restrict__ proofs, uint64_t proof_stride, uint32
   if (g >= (uint64_t)batch * proof_words) return;
   const uint32_t tx = (uint32_t)(g / proof_words), j = (uint32_t)(g % proof_words);
   const uint8_t* p = proofs + (uint64_t)tx * proof_stride;
-  uint32_t v = 0;
-  if (!compact || j < 24 || j >= 48) {
-    const uint8_t* b = p + 1 + 4 * (uint64_t)((compact && j >= 48) ? j - 24 : j);
-    v = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
-  }
-  pw[g] = v;
+  pw[g] = proof_word(p, j, compact);
   if (j == 0 && p[0] != (compact ? 0 : 1)) atomicAnd(&wellformed[tx], 0u);   // version byte and length must agree
 }
+
+// One statement as the per-statement stages see it: its plan and where its rows are, made by each kernel from its arguments
+// (per-plan kernels: statement tx of a batch of one plan) or from a call's table (mixed_kernels.hpp, large_prep.hpp)
+struct PrepStmt {
+  const PrepShape& sh;                                         // (k_prepare indexes its arrays: a reference, not a copy in scratch)
+  const uint32_t *mono_chal = nullptr, *mono_pow = nullptr;    // the plan's arrays
+  const uint32_t *tgt_off = nullptr, *term_info = nullptr;
+  const uint2* prod_qm = nullptr;
+  const uint32_t* prod_coef = nullptr;
+  const uint32_t *com = nullptr, *pw = nullptr;                // inputs: commitments [m][8], proof words [proof_words],
+  const uint32_t *rbytes = nullptr, *raw = nullptr;            // r bytes [16], raw challenge bytes [n_ch][16],
+  const uint32_t* ch = nullptr;                                // challenge slots [n_ch_ext][8]
+  uint32_t *ds = nullptr, *dr = nullptr;                       // outputs: dynamic scalars, their recoded form (per-plan calls),
+  uint32_t *ss = nullptr, *sx = nullptr;                       // static scalars, generator index of the static terms (mixed calls)
+  uint32_t h_base = 0;                                         // index of H_0 in the point set (mixed calls)
+};
 
 // ---- k_transcript -----------------------------------------------------------------------
 __device__ __forceinline__ bool words_are_zero(const uint32_t* w) {
@@ -88,30 +104,14 @@ __device__ __forceinline__ bool words_are_zero(const uint32_t* w) {
   return acc == 0;
 }
 
-// One lane per transaction runs the shape's tape (transcript_tape.hpp).  LDS per lane, word-
-// interleaved over the 64 lanes of the block: the 50 words of STROBE state.
-// init: the STROBE state after Transcript::new("ZkVM.r1cs") + r1cs_domain_sep (same for every tx).
-//
-// No inversion anywhere: the verification equation is used multiplied through by
-// c = y^(pn-1) prod_j u_j^2, which turns every y^-i, 1/u_j and u_j^-2 into a product of positive
-// powers (k_prepare); "sum == identity" is unchanged by a non-zero factor, and a zero y or u_j
-// (where the reference's inversion has no answer either) rejects the proof.
-__global__ void __launch_bounds__(64)
-k_transcript(PrepShape sh, const uint32_t* __restrict__ init_state /*50 words*/, const uint4* __restrict__ tape,
-             uint32_t n_ops, const uint32_t* __restrict__ com /*[B][m][8]*/,
-             const uint32_t* __restrict__ pw /*[B][proof_words]*/, const uint32_t* __restrict__ rbytes /*[B][16]*/,
-             uint32_t batch, uint32_t* __restrict__ ch /*[B][n_ch_ext][8]*/, uint32_t* __restrict__ wellformed,
-             const uint32_t* __restrict__ mono_chal, const uint32_t* __restrict__ mono_pow, uint32_t grouped) {
-  __shared__ uint32_t lds[50 * 64];
-  const uint32_t lane = threadIdx.x;
-  const uint32_t tx_raw = blockIdx.x * 64 + lane;
-  const bool live = tx_raw < batch;
-  const uint32_t tx = live ? tx_raw : batch - 1;
-  uint32_t* st = lds + lane;                    // word w of this lane: st[w * 64]
+// One lane's statement ps: writes its challenge slots to out and returns its well-formedness.  st: the lane's 50 state words,
+// st[w * 64]; tape, n_ops, init_state: the plan's tape.  grouped = 0: rho = 1.
+__device__ __forceinline__ bool transcript_stmt(const PrepStmt& ps, uint32_t* out, uint32_t* st, const uint32_t* init_state,
+                                                const uint4* tape, uint32_t n_ops, uint32_t grouped) {
+  const PrepShape& sh = ps.sh;
+  const uint32_t *mono_chal = ps.mono_chal, *mono_pow = ps.mono_pow;
   for (int i = 0; i < 50; ++i) st[i * 64] = init_state[i];
-  const uint32_t* c = com + (uint64_t)tx * sh.m * 8;
-  const uint32_t* p = pw + (uint64_t)tx * sh.proof_words;
-  uint32_t* out = ch + (uint64_t)tx * sh.n_ch_ext * 8;
+  const uint32_t *c = ps.com, *p = ps.pw;
 #pragma unroll 1
   for (uint32_t i = 0; i < n_ops; ++i) {
     const uint4 op = tape[i];
@@ -163,7 +163,7 @@ k_transcript(PrepShape sh, const uint32_t* __restrict__ init_state /*50 words*/,
     // r combines the two halves of this proof's equation; rho = r^2 weighs the whole equation inside a
     // group of transactions checked by one multiscalar multiplication (coefficients r^2, r^3 of a
     // transaction's two halves: a polynomial identity in independent r's, Schwartz-Zippel as for r alone)
-    const scm rr = scm_from_wide(rbytes + (uint64_t)tx * 16);
+    const scm rr = scm_from_wide(ps.rbytes);
     st_scm(out + 7 * 8, rr);
     scm rho = grouped ? scm_sq(rr) : scm_one();
     uint32_t any = 0;
@@ -226,7 +226,7 @@ k_transcript(PrepShape sh, const uint32_t* __restrict__ init_state /*50 words*/,
       run = scm_mul(run, sq);
     }
   }
-  if (live && !ok) atomicAnd(&wellformed[tx], 0u);
+  return ok;
 }
 
 // ---- the cooperative transcript: k_tape_gather + k_transcript_coop + k_challenges ------------------
@@ -288,19 +288,13 @@ k_coop_selftest(const uint32_t* __restrict__ in /*[3][64]: a, b, addr*/, uint32_
   }
 }
 
-__global__ void __launch_bounds__(256)
-k_tape_gather(PrepShape sh, uint32_t n_seg, const uint32_t* __restrict__ seg_const /*[n_seg][50]*/,
-              const uint16_t* __restrict__ seg_map /*[n_seg][200]*/, const uint32_t* __restrict__ com,
-              const uint32_t* __restrict__ pw, uint32_t batch, uint2* __restrict__ absorb /*[B][n_seg][25]*/) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t per_tx = n_seg * 25;
-  if (g >= (uint64_t)batch * per_tx) return;
-  const uint32_t tx = (uint32_t)(g / per_tx), rem = (uint32_t)(g % per_tx), seg = rem / 25, q = rem % 25;
+// state word q (a u64) of segment seg of statement ps: the segment's constants ^ the commitment / proof bytes it absorbs
+__device__ __forceinline__ uint2 tape_gather_word(const PrepStmt& ps, const uint32_t* seg_const /*[n_seg][50]*/,
+                                                  const uint16_t* seg_map /*[n_seg][200]*/, uint32_t seg, uint32_t q) {
   const uint4 mp4 = *reinterpret_cast<const uint4*>(seg_map + (uint64_t)seg * 200 + 8 * q);
   const uint32_t mp[4] = {mp4.x, mp4.y, mp4.z, mp4.w};
-  const uint32_t* c = com + (uint64_t)tx * sh.m * 8;
-  const uint32_t* p = pw + (uint64_t)tx * sh.proof_words;
-  const uint32_t n_com_bytes = 32 * sh.m;
+  const uint32_t *c = ps.com, *p = ps.pw;
+  const uint32_t n_com_bytes = 32 * ps.sh.m;
   uint32_t lo = seg_const[seg * 50 + 2 * q], hi = seg_const[seg * 50 + 2 * q + 1];
 #pragma unroll
   for (int b = 0; b < 8; ++b) {
@@ -312,19 +306,29 @@ k_tape_gather(PrepShape sh, uint32_t n_seg, const uint32_t* __restrict__ seg_con
       if (b < 4) lo ^= byte << (8 * b); else hi ^= byte << (8 * (b - 4));
     }
   }
-  absorb[g] = make_uint2(lo, hi);
+  return make_uint2(lo, hi);
+}
+__global__ void __launch_bounds__(256)
+k_tape_gather(PrepShape sh, uint32_t n_seg, const uint32_t* __restrict__ seg_const /*[n_seg][50]*/,
+              const uint16_t* __restrict__ seg_map /*[n_seg][200]*/, const uint32_t* __restrict__ com,
+              const uint32_t* __restrict__ pw, uint32_t batch, uint2* __restrict__ absorb /*[B][n_seg][25]*/) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t per_tx = n_seg * 25;
+  if (g >= (uint64_t)batch * per_tx) return;
+  const uint32_t tx = (uint32_t)(g / per_tx), rem = (uint32_t)(g % per_tx), seg = rem / 25, q = rem % 25;
+  PrepStmt ps = {sh};
+  ps.com = com + (uint64_t)tx * sh.m * 8;
+  ps.pw = pw + (uint64_t)tx * sh.proof_words;
+  absorb[g] = tape_gather_word(ps, seg_const, seg_map, seg, q);
 }
 
-__global__ void __launch_bounds__(64)
-k_transcript_coop(uint32_t n_seg, const uint32_t* __restrict__ seg_info, const uint32_t* __restrict__ init_state /*50 words*/,
-                  const uint2* __restrict__ absorb /*[B][n_seg][25]*/, uint32_t batch, uint32_t n_ch,
-                  uint32_t* __restrict__ raw /*[B][n_ch][16]*/) {
-  const uint32_t tx = blockIdx.x, lane = threadIdx.x;
-  if (tx >= batch) return;
-  const coop::KcLane k = coop::kc_lane(lane);
+// the replay of one statement by one wavefront: ab, its absorbed words [n_seg][25] -> raw, its challenge bytes [n_ch][16]
+__device__ __forceinline__ void transcript_coop_stmt(uint32_t n_seg, const uint32_t* seg_info, const uint32_t* init_state,
+                                                     const uint2* ab, uint32_t* raw) {
+  const coop::KcLane k = coop::kc_lane(threadIdx.x);
   const coop::KeccakCoop<DevKcTraits>::Consts c = {k.live, k.rot_swap, k.rot_t, k.src[0], k.src[1], k.src[2], k.iota};
   uint32_t lo = k.live ? init_state[2 * k.q] : 0, hi = k.live ? init_state[2 * k.q + 1] : 0;
-  const uint2* ab = absorb + (uint64_t)tx * n_seg * 25 + k.q;
+  ab += k.q;
   const bool first8 = k.live && k.q < 8;           // state bytes 0..63: what a challenge squeezes
   uint2 nxt = k.live ? ab[0] : make_uint2(0, 0);
 #pragma unroll 1
@@ -335,7 +339,7 @@ k_transcript_coop(uint32_t n_seg, const uint32_t* __restrict__ seg_info, const u
     const uint32_t slot = info & 0xffffu;
     if (slot) {
       if (k.primary && k.q < 8) {
-        uint32_t* o = raw + ((uint64_t)tx * n_ch + (slot - 1)) * 16 + 2 * k.q;
+        uint32_t* o = raw + (uint64_t)(slot - 1) * 16 + 2 * k.q;
         o[0] = lo; o[1] = hi;
       }
       if (first8) { lo = 0; hi = 0; }
@@ -346,17 +350,13 @@ k_transcript_coop(uint32_t n_seg, const uint32_t* __restrict__ seg_info, const u
 }
 
 // blockDim = 128: wavefront 0 reduces the challenges and runs the power chains, wavefront 1 the
-// well-formedness checks and the products of the inner-product challenges.
-__global__ void __launch_bounds__(128)
-k_challenges(PrepShape sh, const uint32_t* __restrict__ raw /*[B][n_ch][16]*/, const uint32_t* __restrict__ pw,
-             const uint32_t* __restrict__ rbytes, uint32_t batch, uint32_t* __restrict__ ch /*[B][n_ch_ext][8]*/,
-             uint32_t* __restrict__ wellformed, const uint32_t* __restrict__ mono_chal, const uint32_t* __restrict__ mono_pow,
-             uint32_t grouped) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];     // n_ch slots of 8 words
-  const uint32_t tx = blockIdx.x, t = threadIdx.x, nt = blockDim.x;
-  if (tx >= batch) return;
-  const uint32_t* p = pw + (uint64_t)tx * sh.proof_words;
-  uint32_t* out = ch + (uint64_t)tx * sh.n_ch_ext * 8;
+// well-formedness checks and the products of the inner-product challenges.  Statement ps: its challenge slots to out, its
+// well-formedness flag at wf; lds: n_ch slots of 8 words.  grouped = 0: rho = 1.
+__device__ __forceinline__ void challenges_stmt(const PrepStmt& ps, uint32_t* out, uint32_t* lds, uint32_t* wf, uint32_t grouped) {
+  const PrepShape& sh = ps.sh;
+  const uint32_t *mono_chal = ps.mono_chal, *mono_pow = ps.mono_pow;
+  const uint32_t t = threadIdx.x, nt = blockDim.x;
+  const uint32_t* p = ps.pw;
   const uint32_t n2 = sh.n_chal2, k = sh.k;
   // phase 1: every slot is the reduction of 64 little-endian bytes (8-word sources padded with zeros)
   for (uint32_t s = t; s < sh.n_ch; s += nt) {
@@ -366,8 +366,8 @@ k_challenges(PrepShape sh, const uint32_t* __restrict__ raw /*[B][n_ch][16]*/, c
     const bool is_chal = s < 5 || (s >= (uint32_t)CH_FIXED && s < CH_FIXED + n2 + k);
     const uint32_t* src = nullptr;
     int words = 0;
-    if (is_chal) { src = raw + ((uint64_t)tx * sh.n_ch + s) * 16; words = 16; }
-    else if (s == 7 || s == 13) { src = rbytes + (uint64_t)tx * 16; words = 16; }
+    if (is_chal) { src = ps.raw + (uint64_t)s * 16; words = 16; }
+    else if (s == 7 || s == 13) { src = ps.rbytes; words = 16; }
     else if (s >= 8 && s <= 12) { src = s <= 10 ? p + 88 + 8 * (s - 8) : p + 112 + 16 * k + 8 * (s - 11); words = 8; }
 #pragma unroll
     for (int q = 0; q < 16; ++q) if (q < words) w[q] = src[q];
@@ -467,7 +467,59 @@ k_challenges(PrepShape sh, const uint32_t* __restrict__ raw /*[B][n_ch][16]*/, c
     st_scm(out + 5 * 8, p1);
     st_scm(out + 6 * 8, scm_sq(p1));
   }
-  if (!__all(ok) && lane == 0) atomicAnd(&wellformed[tx], 0u);
+  if (!__all(ok) && lane == 0) atomicAnd(wf, 0u);
+}
+
+// ---- the per-plan kernels of the one-lane and cooperative transcripts: statement tx of the batch ----------------
+// One lane per transaction runs the shape's tape (transcript_tape.hpp).  LDS per lane, word-
+// interleaved over the 64 lanes of the block: the 50 words of STROBE state.
+// init: the STROBE state after Transcript::new("ZkVM.r1cs") + r1cs_domain_sep (same for every tx).
+//
+// No inversion anywhere: the verification equation is used multiplied through by
+// c = y^(pn-1) prod_j u_j^2, which turns every y^-i, 1/u_j and u_j^-2 into a product of positive
+// powers (k_prepare); "sum == identity" is unchanged by a non-zero factor, and a zero y or u_j
+// (where the reference's inversion has no answer either) rejects the proof.
+__global__ void __launch_bounds__(64)
+k_transcript(PrepShape sh, const uint32_t* __restrict__ init_state /*50 words*/, const uint4* __restrict__ tape,
+             uint32_t n_ops, const uint32_t* __restrict__ com /*[B][m][8]*/,
+             const uint32_t* __restrict__ pw /*[B][proof_words]*/, const uint32_t* __restrict__ rbytes /*[B][16]*/,
+             uint32_t batch, uint32_t* __restrict__ ch /*[B][n_ch_ext][8]*/, uint32_t* __restrict__ wellformed,
+             const uint32_t* __restrict__ mono_chal, const uint32_t* __restrict__ mono_pow, uint32_t grouped) {
+  __shared__ uint32_t lds[50 * 64];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t tx_raw = blockIdx.x * 64 + lane;
+  const bool live = tx_raw < batch;
+  const uint32_t tx = live ? tx_raw : batch - 1;
+  PrepStmt ps = {sh, mono_chal, mono_pow};
+  ps.com = com + (uint64_t)tx * sh.m * 8;
+  ps.pw = pw + (uint64_t)tx * sh.proof_words;
+  ps.rbytes = rbytes + (uint64_t)tx * 16;
+  const bool ok = transcript_stmt(ps, ch + (uint64_t)tx * sh.n_ch_ext * 8, lds + lane, init_state, tape, n_ops, grouped);
+  if (live && !ok) atomicAnd(&wellformed[tx], 0u);
+}
+
+__global__ void __launch_bounds__(64)
+k_transcript_coop(uint32_t n_seg, const uint32_t* __restrict__ seg_info, const uint32_t* __restrict__ init_state /*50 words*/,
+                  const uint2* __restrict__ absorb /*[B][n_seg][25]*/, uint32_t batch, uint32_t n_ch,
+                  uint32_t* __restrict__ raw /*[B][n_ch][16]*/) {
+  const uint32_t tx = blockIdx.x;
+  if (tx >= batch) return;
+  transcript_coop_stmt(n_seg, seg_info, init_state, absorb + (uint64_t)tx * n_seg * 25, raw + (uint64_t)tx * n_ch * 16);
+}
+
+__global__ void __launch_bounds__(128)
+k_challenges(PrepShape sh, const uint32_t* __restrict__ raw /*[B][n_ch][16]*/, const uint32_t* __restrict__ pw,
+             const uint32_t* __restrict__ rbytes, uint32_t batch, uint32_t* __restrict__ ch /*[B][n_ch_ext][8]*/,
+             uint32_t* __restrict__ wellformed, const uint32_t* __restrict__ mono_chal, const uint32_t* __restrict__ mono_pow,
+             uint32_t grouped) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];     // n_ch slots of 8 words
+  const uint32_t tx = blockIdx.x;
+  if (tx >= batch) return;
+  PrepStmt ps = {sh, mono_chal, mono_pow};
+  ps.pw = pw + (uint64_t)tx * sh.proof_words;
+  ps.rbytes = rbytes + (uint64_t)tx * 16;
+  ps.raw = raw + (uint64_t)tx * sh.n_ch * 16;
+  challenges_stmt(ps, ch + (uint64_t)tx * sh.n_ch_ext * 8, lds, &wellformed[tx], grouped);
 }
 
 // ---- k_prepare ------------------------------------------------------------------------------
@@ -572,23 +624,26 @@ __device__ __forceinline__ scl wave_sum_scl(scl part) {
 }
 
 // Per-section clocks (build variant -DZK_PREP_STAMPS only: tools/prep_stamps.py): thread 0 and thread 255 of the workgroups
-// 4096 .. 4351 (the middle of a 10 240-transaction launch) note s_memtime where a section ends; read back through zkgpu_debug_read("prep_stamps").
+// 4096 .. 4351 (the middle of a 10 240-transaction launch) of k_prepare note s_memtime where a section ends; read back through
+// zkgpu_debug_read("prep_stamps").
 #ifdef ZK_PREP_STAMPS
 constexpr int PREP_STAMP_SLOTS = 16;
 __device__ unsigned long long g_prep_stamps[256 * 2 * PREP_STAMP_SLOTS];
-#define PREP_STAMP(i) do { if ((blockIdx.x >> 8) == 16 && (t == 0 || t == 255)) \
+#define PREP_STAMP(i) do { if (!MIXED && (blockIdx.x >> 8) == 16 && (t == 0 || t == 255)) \
   g_prep_stamps[((blockIdx.x & 255) * 2 + (t ? 1 : 0)) * PREP_STAMP_SLOTS + (i)] = __builtin_readcyclecounter(); } while (0)
 #else
 #define PREP_STAMP(i) do { } while (0)
 #endif
 
-__global__ void __launch_bounds__(256, 4)
-k_prepare(PrepShape sh, const uint32_t* __restrict__ mono_chal, const uint32_t* __restrict__ mono_pow,
-          const uint32_t* __restrict__ tgt_off, const uint32_t* __restrict__ term_info,
-          const uint2* __restrict__ prod_qm, const uint32_t* __restrict__ prod_coef,
-          const uint32_t* __restrict__ ch, const uint32_t* __restrict__ com, const uint32_t* __restrict__ pw,
-          uint32_t* __restrict__ dyn_scalars, uint32_t* __restrict__ dyn_recoded, uint32_t* __restrict__ static_scalars) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+// Statement ps in one workgroup of 256; lds: prepare_lds_bytes(ps.sh).  MIXED (k_mx_prepare): the generator index of the
+// static terms is written instead of the recoded dynamic scalars (k_small_tables recodes them in mixed calls), and no clocks.
+template <bool MIXED>
+__device__ __forceinline__ void prepare_stmt(const PrepStmt& ps, uint32_t* lds) {
+  const PrepShape& sh = ps.sh;
+  const uint32_t* tgt_off = ps.tgt_off;
+  const uint32_t* term_info = ps.term_info;
+  const uint2* prod_qm = ps.prod_qm;
+  const uint32_t* prod_coef = ps.prod_coef;
   constexpr uint32_t SW = SCL_WORDS;
   uint32_t* chs = lds;
   uint32_t* sym = chs + sh.n_ch * SW;
@@ -610,12 +665,12 @@ k_prepare(PrepShape sh, const uint32_t* __restrict__ mono_chal, const uint32_t* 
   uint32_t* zhi = tv + 16 * SW;                  // z^(16 h)
   uint32_t* yip = zpow;                          // region A, second life: two packed tables (8 words per entry)
   uint32_t* sv = yip + sh.pn * 8;
-  const uint32_t tx = blockIdx.x, t = threadIdx.x, nt = blockDim.x;
+  const uint32_t t = threadIdx.x, nt = blockDim.x;
   PREP_STAMP(0);
 
   // the transaction's slots (canonical Montgomery words) -> limb form
   for (uint32_t i = t; i < sh.n_ch_ext; i += nt) {
-    const uint4* src = reinterpret_cast<const uint4*>(ch + ((uint64_t)tx * sh.n_ch_ext + i) * 8);
+    const uint4* src = reinterpret_cast<const uint4*>(ps.ch + (uint64_t)i * 8);
     const uint4 a = src[0], b = src[1];
     const uint32_t w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     st_scl(chs + i * SW, scl_from_words(w));
@@ -803,9 +858,11 @@ k_prepare(PrepShape sh, const uint32_t* __restrict__ mono_chal, const uint32_t* 
     __syncthreads();
   }
   PREP_STAMP(5);                                  // dsum, c'
-  uint32_t* ds = dyn_scalars + (uint64_t)tx * sh.n_dyn * 8;
-  uint32_t* dr = dyn_recoded + (uint64_t)tx * sh.n_dyn * 8;
-  uint32_t* ss = static_scalars + (uint64_t)tx * sh.n_static * 8;
+  uint32_t* ds = ps.ds;
+  uint32_t* dr = ps.dr;
+  uint32_t* ss = ps.ss;
+  uint32_t* sx = ps.sx;
+  if (MIXED && t == 0) { sx[0] = 0; sx[1] = 1; }
   // ---- proof-point scalars, B and B_blinding: the last wavefront, BEFORE its share of the generator scalars, so that
   // this short serial tail runs beside the other wavefronts' generator loop instead of after it.  Every lane does the
   // same two rounds v = a * b with operands of its own, read from LDS where they are needed (a lane that needs fewer
@@ -884,7 +941,7 @@ k_prepare(PrepShape sh, const uint32_t* __restrict__ mono_chal, const uint32_t* 
         for (int q = 0; q < 8; ++q) {
           ds[j * 8 + q] = o[q];
           const uint64_t vv = (uint64_t)o[q] + 0x88888888u + carry;
-          dr[j * 8 + q] = (uint32_t)vv;
+          if (!MIXED) dr[j * 8 + q] = (uint32_t)vv;
           carry = (uint32_t)(vv >> 32);
         }
       } else if (pos == 0 || pos == 4) {
@@ -934,22 +991,32 @@ k_prepare(PrepShape sh, const uint32_t* __restrict__ mono_chal, const uint32_t* 
       uint4* oh = reinterpret_cast<uint4*>(ss + (2 + sh.pn + i) * 8);
       og[0] = make_uint4(gw[0], gw[1], gw[2], gw[3]); og[1] = make_uint4(gw[4], gw[5], gw[6], gw[7]);
       oh[0] = make_uint4(hw[0], hw[1], hw[2], hw[3]); oh[1] = make_uint4(hw[4], hw[5], hw[6], hw[7]);
+      if (MIXED) { sx[2 + i] = 2 + i; sx[2 + sh.pn + i] = ps.h_base + i; }
     }
   }
   PREP_STAMP(7);                                  // generator scalars
 }
 
-// the proof-specific points of every transaction in the order of the MSM's dynamic terms
-// [A_I1 A_O1 S1 A_I2 A_O2 S2 | V.. | T_1 T_3 T_4 T_5 T_6 | L.. | R..]: needs the proof bytes only, so the
+__global__ void __launch_bounds__(256, 4)
+k_prepare(PrepShape sh, const uint32_t* __restrict__ mono_chal, const uint32_t* __restrict__ mono_pow,
+          const uint32_t* __restrict__ tgt_off, const uint32_t* __restrict__ term_info,
+          const uint2* __restrict__ prod_qm, const uint32_t* __restrict__ prod_coef,
+          const uint32_t* __restrict__ ch, const uint32_t* __restrict__ com, const uint32_t* __restrict__ pw,
+          uint32_t* __restrict__ dyn_scalars, uint32_t* __restrict__ dyn_recoded, uint32_t* __restrict__ static_scalars) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const uint32_t tx = blockIdx.x;
+  PrepStmt ps = {sh, mono_chal, mono_pow, tgt_off, term_info, prod_qm, prod_coef};
+  ps.ch = ch + (uint64_t)tx * (sh.n_ch_ext * 8);
+  ps.ds = dyn_scalars + (uint64_t)tx * sh.n_dyn * 8;
+  ps.dr = dyn_recoded + (uint64_t)tx * sh.n_dyn * 8;
+  ps.ss = static_scalars + (uint64_t)tx * sh.n_static * 8;
+  prepare_stmt<false>(ps, lds);
+}
+
+// the proof-specific point j of a statement (commitments c, proof words p) in the order of the MSM's dynamic terms
+// [A_I1 A_O1 S1 A_I2 A_O2 S2 | V.. | T_1 T_3 T_4 T_5 T_6 | L.. | R..]: the gathers need the proof bytes only, so the
 // decompression and the per-point tables run while the transcript is still being replayed
-__global__ void __launch_bounds__(256)
-k_gather_dyn_points(PrepShape sh, const uint32_t* __restrict__ com, const uint32_t* __restrict__ pw, uint32_t batch,
-                    uint32_t* __restrict__ dyn_points) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (uint64_t)batch * sh.n_dyn * 8) return;
-  const uint32_t q = (uint32_t)(g & 7), j = (uint32_t)((g >> 3) % sh.n_dyn), tx = (uint32_t)((g >> 3) / sh.n_dyn);
-  const uint32_t* p = pw + (uint64_t)tx * sh.proof_words;
-  const uint32_t* c = com + (uint64_t)tx * sh.m * 8;
+__device__ __forceinline__ const uint32_t* dyn_point(const PrepShape& sh, const uint32_t* c, const uint32_t* p, uint32_t j) {
   const uint32_t* src;
   if (j < 6) src = p + 8 * j;
   else if (j < 6 + sh.m) src = c + 8 * (j - 6);
@@ -958,7 +1025,18 @@ k_gather_dyn_points(PrepShape sh, const uint32_t* __restrict__ com, const uint32
     const uint32_t r = j - 11 - sh.m;
     src = p + 112 + (r < sh.k ? 16 * r : 16 * (r - sh.k) + 8);
   }
-  dyn_points[g] = src[q];
+  return src;
+}
+
+__global__ void __launch_bounds__(256)
+k_gather_dyn_points(PrepShape sh, const uint32_t* __restrict__ com, const uint32_t* __restrict__ pw, uint32_t batch,
+                    uint32_t* __restrict__ dyn_points) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (uint64_t)batch * sh.n_dyn * 8) return;
+  const uint32_t q = (uint32_t)(g & 7), j = (uint32_t)((g >> 3) % sh.n_dyn), tx = (uint32_t)((g >> 3) / sh.n_dyn);
+  const uint32_t* p = pw + (uint64_t)tx * sh.proof_words;
+  const uint32_t* c = com + (uint64_t)tx * sh.m * 8;
+  dyn_points[g] = dyn_point(sh, c, p, j)[q];
 }
 
 // The same gather fused with the RFC 9496 DECODE and the per-point tables of the small-MSM path
@@ -976,14 +1054,7 @@ k_points_tables(PrepShape sh, const uint32_t* __restrict__ com, const uint32_t* 
   const uint32_t j = (uint32_t)(g % sh.n_dyn), tx = (uint32_t)(g / sh.n_dyn);
   const uint32_t* p = pw + (uint64_t)tx * sh.proof_words;
   const uint32_t* c = com + (uint64_t)tx * sh.m * 8;
-  const uint32_t* src;
-  if (j < 6) src = p + 8 * j;
-  else if (j < 6 + sh.m) src = c + 8 * (j - 6);
-  else if (j < 11 + sh.m) src = p + 8 * (6 + (j - 6 - sh.m));
-  else {
-    const uint32_t r = j - 11 - sh.m;
-    src = p + 112 + (r < sh.k ? 16 * r : 16 * (r - sh.k) + 8);
-  }
+  const uint32_t* src = dyn_point(sh, c, p, j);
   uint32_t w[8];
 #pragma unroll
   for (int q = 0; q < 8; ++q) w[q] = src[q];
