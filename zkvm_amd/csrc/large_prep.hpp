@@ -434,5 +434,4 @@ inline bool lp_forced() {
 }  // namespace zk
 
 // the four launches for a batch of one plan (zkgpu.hip, beside the mixed calls' launches of the same kernels)
-int lp_prepare_homo(zkgpu_ctx* c, hipStream_t s, const zk::PrepShape& sh, const uint32_t* tgt_off, const uint32_t* term_info,
-                    const uint32_t* prod_qm, const uint32_t* prod_coef, uint32_t batch);
+int lp_prepare_homo(zkgpu_ctx* c, hipStream_t s, const zk::PrepPlan& plan, uint32_t batch);

@@ -2,7 +2,7 @@
 // DIFFERENT constraint systems (zkgpu_r1cs_verify_mixed): the per-statement stages of prep_kernels.hpp, run on a view
 // (PrepStmt) made from a per-call table instead of from a by-value PrepShape, so that one launch per stage serves every plan.
 //
-//   MixPlan   one per distinct plan of the call: its PrepShape and the device addresses of its replay arrays
+//   PrepPlan  (prep_kernels.hpp) one per distinct plan of the call, copied from the plan as it stands
 //   MixStmt   one per statement, in the CALLER's order: its plan, proof wire form, and where its inputs, its
 //             challenge slots and its rows of the multiscalar multiplication live (rows have the statement's own
 //             lengths: 11 + m + 2k dynamic and 2 + 2 pn static terms)
@@ -16,24 +16,6 @@
 #include "prep_kernels.hpp"
 
 namespace zk {
-
-struct MixPlan {
-  PrepShape sh;
-  const uint32_t* init;        // STROBE state after Transcript::new(label) + the r1cs domain separator (50 words)
-  const uint4* tape;
-  const uint32_t* seg_info;    // cooperative transcript (n_seg = 0: not available for this plan)
-  const uint32_t* seg_const;
-  const uint16_t* seg_map;
-  const uint32_t* mono_chal;
-  const uint32_t* mono_pow;
-  const uint32_t* tgt_off;
-  const uint32_t* term_info;
-  const uint2* prod_qm;
-  const uint32_t* prod_coef;
-  uint32_t n_ops, n_seg;
-  uint32_t h_base;             // index of H_0 in the point set: 2 + the plan's generator capacity
-  uint32_t pad;
-};
 
 // k_mx_prepare's LDS classes: a plan needing more than this takes a CU's 160 KiB LDS alone (one workgroup per CU)
 constexpr size_t MIX_LDS_SMALL = 80 * 1024;
@@ -49,7 +31,7 @@ struct MixStmt {
 };
 
 // a statement's view without its rows: its plan's shape and arrays
-__device__ __forceinline__ PrepStmt mix_view(const MixPlan& pln) {
+__device__ __forceinline__ PrepStmt mix_view(const PrepPlan& pln) {
   PrepStmt ps = {pln.sh, pln.mono_chal, pln.mono_pow, pln.tgt_off, pln.term_info, pln.prod_qm, pln.prod_coef};
   ps.h_base = pln.h_base;
   return ps;
@@ -57,7 +39,7 @@ __device__ __forceinline__ PrepStmt mix_view(const MixPlan& pln) {
 
 // ---- k_mx_proof_unpack: one workgroup per statement; sets the statement's well-formedness flag (first writer)
 __global__ void __launch_bounds__(256)
-k_mx_proof_unpack(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
+k_mx_proof_unpack(const PrepPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
                   const uint8_t* __restrict__ proofs, uint32_t* __restrict__ pw, uint32_t* __restrict__ wellformed) {
   const uint32_t stmt = order[blockIdx.x];
   const MixStmt& stm = stmts[stmt];
@@ -72,7 +54,7 @@ k_mx_proof_unpack(const MixPlan* __restrict__ plans, const MixStmt* __restrict__
 
 // ---- k_mx_transcript: k_transcript with one plan per wavefront (lane_order)
 __global__ void __launch_bounds__(64)
-k_mx_transcript(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ lane_order,
+k_mx_transcript(const PrepPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ lane_order,
                 const uint32_t* __restrict__ com, const uint32_t* __restrict__ pw, const uint32_t* __restrict__ rbytes,
                 uint32_t* __restrict__ ch, uint32_t* __restrict__ wellformed) {
   __shared__ uint32_t lds[50 * 64];
@@ -82,7 +64,7 @@ k_mx_transcript(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ s
   const bool live = mine != ~0u;
   const uint32_t stmt = live ? mine : first;                // padding lanes replay their wavefront's first statement
   const MixStmt& stm = stmts[stmt];
-  const MixPlan& pln = plans[stmts[first].plan];            // the wavefront's plan, the lane's own rows
+  const PrepPlan& pln = plans[stmts[first].plan];           // the wavefront's plan, the lane's own rows
   PrepStmt ps = mix_view(pln);
   ps.com = com + stm.com;
   ps.pw = pw + stm.pw;
@@ -94,10 +76,10 @@ k_mx_transcript(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ s
 // ---- the cooperative transcript: k_mx_tape_gather + k_mx_transcript_coop + k_mx_challenges --------------------------
 // k_mx_tape_gather: one workgroup per statement, its n_seg x 25 absorbed words
 __global__ void __launch_bounds__(256)
-k_mx_tape_gather(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
+k_mx_tape_gather(const PrepPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
                  const uint32_t* __restrict__ com, const uint32_t* __restrict__ pw, uint2* __restrict__ absorb) {
   const MixStmt& stm = stmts[order[blockIdx.x]];
-  const MixPlan& pln = plans[stm.plan];
+  const PrepPlan& pln = plans[stm.plan];
   PrepStmt ps = mix_view(pln);
   ps.com = com + stm.com;
   ps.pw = pw + stm.pw;
@@ -107,16 +89,16 @@ k_mx_tape_gather(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ 
 
 // k_mx_transcript_coop: one wavefront per statement
 __global__ void __launch_bounds__(64)
-k_mx_transcript_coop(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
+k_mx_transcript_coop(const PrepPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
                      const uint2* __restrict__ absorb, uint32_t* __restrict__ raw) {
   const MixStmt& stm = stmts[order[blockIdx.x]];
-  const MixPlan& pln = plans[stm.plan];
+  const PrepPlan& pln = plans[stm.plan];
   transcript_coop_stmt(pln.n_seg, pln.seg_info, pln.init, absorb + stm.absorb, raw + stm.raw);
 }
 
 // k_mx_challenges: k_challenges per statement (blockDim = 128; dynamic LDS: the largest n_ch of the call x 32 bytes)
 __global__ void __launch_bounds__(128)
-k_mx_challenges(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
+k_mx_challenges(const PrepPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
                 const uint32_t* __restrict__ raw, const uint32_t* __restrict__ pw, const uint32_t* __restrict__ rbytes,
                 uint32_t* __restrict__ ch, uint32_t* __restrict__ wellformed) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];     // n_ch slots of 8 words
@@ -133,7 +115,7 @@ k_mx_challenges(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ s
 // that exceed a CU's LDS, large_prep.hpp's.  They write the generator index too, and no recoded form (k_small_tables makes
 // it in mixed calls)
 struct LpMixed {
-  const MixPlan* plans;
+  const PrepPlan* plans;
   const MixStmt* stmts;
   const uint32_t* order;
   const uint32_t* ch;
@@ -154,7 +136,7 @@ struct LpMixed {
 // ---- k_mx_prepare: k_prepare per statement (dynamic LDS: the largest plan of the call).  Also writes the generator index
 // of the statement's static terms: B, B_blinding, G_0..G_{pn-1}, H_0..H_{pn-1}
 __global__ void __launch_bounds__(256, 4)
-k_mx_prepare(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
+k_mx_prepare(const PrepPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
              const uint32_t* __restrict__ ch, uint32_t* __restrict__ dyn_scalars, uint32_t* __restrict__ static_scalars,
              uint32_t* __restrict__ static_index) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -165,7 +147,7 @@ k_mx_prepare(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ stmt
 // ---- k_mx_gather_dyn_points: one workgroup per statement, its proof-specific points in the order of its dynamic terms
 // (compressed; decoded by the MSM's k_decompress)
 __global__ void __launch_bounds__(256)
-k_mx_gather_dyn_points(const MixPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
+k_mx_gather_dyn_points(const PrepPlan* __restrict__ plans, const MixStmt* __restrict__ stmts, const uint32_t* __restrict__ order,
                        const uint32_t* __restrict__ com, const uint32_t* __restrict__ pw, uint32_t* __restrict__ dyn_points) {
   const MixStmt& stm = stmts[order[blockIdx.x]];
   const PrepShape& sh = plans[stm.plan].sh;

@@ -96,6 +96,28 @@ struct PrepStmt {
   uint32_t h_base = 0;                                         // index of H_0 in the point set (mixed calls)
 };
 
+// One plan as the device reads it: its shape and the device addresses of its replay arrays.  A plan fills one at creation
+// (zkgpu.hip, plan_finish_inner) and frees its arrays through it; a per-plan call hands its members to the kernels one
+// by one, a mixed call copies it into its table as it stands (mixed_kernels.hpp: the k_mx_* kernels index an array of it,
+// so its layout is theirs).
+struct PrepPlan {
+  PrepShape sh;
+  const uint32_t* init;        // STROBE state after Transcript::new(label) + the r1cs domain separator (50 words)
+  const uint4* tape;           // transcript_tape.hpp, one uint4 per operation
+  const uint32_t* seg_info;    // cooperative transcript (n_seg = 0: not available for this plan)
+  const uint32_t* seg_const;
+  const uint16_t* seg_map;
+  const uint32_t* mono_chal;
+  const uint32_t* mono_pow;
+  const uint32_t* tgt_off;
+  const uint32_t* term_info;
+  const uint2* prod_qm;
+  const uint32_t* prod_coef;
+  uint32_t n_ops, n_seg;
+  uint32_t h_base;             // index of H_0 in the point set: 2 + the plan's generator capacity
+  uint32_t pad;
+};
+
 // ---- k_transcript -----------------------------------------------------------------------
 __device__ __forceinline__ bool words_are_zero(const uint32_t* w) {
   uint32_t acc = 0;

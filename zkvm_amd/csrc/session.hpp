@@ -522,7 +522,7 @@ int txblock_stage_host(zkgpu_verifier* v, size_t batch, const TxSource* src, con
         int prc = ZKGPU_OK;
         g.plan = verifier_plan(v, g.n_in, g.n_out, &prc, err);
         if (prc != ZKGPU_OK) return prc;
-        if (g.plan && !proof_len_fits(g.plan->shape, g.proof_len)) g.plan = nullptr;   // wrong length for the statement
+        if (g.plan && !proof_len_fits(g.plan->dev.sh, g.proof_len)) g.plan = nullptr;   // wrong length for the statement
         g.com_off = g.proof_off = g.r_off = 0;
         it = where.emplace(key, b->groups.size()).first;
         b->groups.push_back(std::move(g));
@@ -940,10 +940,10 @@ int ticket_dispatch(zkgpu_verifier* v, bool force) {       // v->mu held
       for (zkgpu_request* r : pick)
         if (r->ready && r->ready != seen) { seen = r->ready; if (hipStreamWaitEvent(L->stream_l, r->ready, 0) != hipSuccess && rc == ZKGPU_OK) { L->last_error = "hipStreamWaitEvent (block copy)"; rc = ZKGPU_EHIP; } }
     }
-    if (rc == ZKGPU_OK && plan && proof_len_fits(plan->shape, head->proof_len) && pick.size() > 1) {
+    if (rc == ZKGPU_OK && plan && proof_len_fits(plan->dev.sh, head->proof_len) && pick.size() > 1) {
       std::lock_guard<std::recursive_mutex> lk(L->mu);
       DeviceGuard g(L->device);
-      const size_t wcom = (size_t)plan->shape.m * 32;
+      const size_t wcom = (size_t)plan->dev.sh.m * 32;
       rc = ensure(L, L->coal_com, total * wcom);
       if (rc == ZKGPU_OK) rc = ensure(L, L->coal_proofs, total * head->proof_len + 16);   // (k_merge_inputs writes whole words)
       if (rc == ZKGPU_OK) rc = ensure(L, L->coal_r, total * 64);
@@ -1150,11 +1150,11 @@ int host_submit_one(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, size_t bat
   std::string plan_err;
   zkgpu_cloak_plan* plan = verifier_plan(v, n_in, n_out, &rc, &plan_err);
   if (rc != ZKGPU_OK) v->last_error = plan_err;
-  if (rc != ZKGPU_OK || !plan || !proof_len_fits(plan->shape, proof_len)) {   // no plan THIS time: the ticket fails with rc; a shape or
+  if (rc != ZKGPU_OK || !plan || !proof_len_fits(plan->dev.sh, proof_len)) {   // no plan THIS time: the ticket fails with rc; a shape or
     r->state = 2; r->rc = rc; r->bits.assign((batch + 7) / 8, 0);             // length the reference rejects: every proof is Err
     return ZKGPU_OK;
   }
-  const size_t wcom = (size_t)plan->shape.m * 32;
+  const size_t wcom = (size_t)plan->dev.sh.m * 32;
   zkgpu_host_batch* F = nullptr;
   for (auto& f : v->forming)
     if (f->n_in == n_in && f->n_out == n_out && f->proof_len == proof_len && f->total < std::min(f->cap_tx, v->merge_target) && f->total + batch <= f->cap_tx) F = f.get();
@@ -1250,8 +1250,8 @@ int zkgpu_verifier_reserve(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, siz
   if (rc != ZKGPU_OK) { v->last_error = err; return rc; }
   if (!plan) return ZKGPU_OK;
   while (!v->busy.empty()) ticket_collect(v, v->busy.front());       // (the lanes must be idle: their workspaces are about to move)
-  const size_t proof_len = 1 + 4 * (size_t)plan->shape.proof_words;
-  const size_t wcom = (size_t)plan->shape.m * 32;
+  const size_t proof_len = 1 + 4 * (size_t)plan->dev.sh.proof_words;
+  const size_t wcom = (size_t)plan->dev.sh.m * 32;
   for (zkgpu_ctx* L : v->lanes) {
     rc = cloak_reserve(L, v->ps, plan, transactions, proof_len);
     if (rc == ZKGPU_OK) {

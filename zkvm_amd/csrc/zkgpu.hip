@@ -351,6 +351,15 @@ inline uint64_t longest_row(const uint64_t* offsets, size_t batch) {
   return m;
 }
 
+// a job's proof points decoded by the one-kernel form into c->dyn_rows; a point that does not decode marks its row in msm_fail
+void decompress_launch(zkgpu_ctx* c, const Job& job, hipStream_t s) {
+  Launch l(c, "k_decompress", s);
+  c->decode_routes.note(false, job.n_dyn);
+  hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, s, job.d_dyn_points,
+                     (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, job.n_msm, (uint32_t*)c->msm_fail.p,
+                     (unsigned long long*)((char*)c->status.p + 8), (uint8_t*)nullptr);
+}
+
 // Runs decompress .. window sums.  On return (stream not yet synchronised):
 //   c->window_sums / c->window_flags hold n_msm * n_windows extended points
 //   c->msm_fail[m] != 0 when MSM m had an undecodable point
@@ -444,10 +453,7 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
     }
     if (decompress_aside) HIP_TRY(c, hipEventRecord(c->ev_join, sd));
   } else if (job.n_dyn) {
-    Launch l(c, "k_decompress"); c->decode_routes.note(false, job.n_dyn);
-    hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, s, job.d_dyn_points,
-                       (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, job.n_msm,
-                       (uint32_t*)c->msm_fail.p, bad_index, (uint8_t*)nullptr);
+    decompress_launch(c, job, s);
   }
   uint32_t* class_count = (uint32_t*)c->class_count.p;
   uint32_t* class_cursor = class_count + SIZE_CLASSES;
@@ -639,12 +645,7 @@ int batch_device_enqueue(zkgpu_ctx* c, const Job& job, bool values) {
       hipLaunchKernelGGL(k_batch_init, dim3(blocks_for(B, 256)), dim3(256), 0, s, (uint32_t*)c->status.p, (uint32_t*)c->msm_fail.p,
                          (uint32_t*)nullptr, (uint32_t)B);
     }
-    {
-      Launch l(c, "k_decompress", s); c->decode_routes.note(false, job.n_dyn);
-      hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, s, job.d_dyn_points,
-                         (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, (uint32_t)B,
-                         (uint32_t*)c->msm_fail.p, (unsigned long long*)((char*)c->status.p + 8), (uint8_t*)nullptr);
-    }
+    decompress_launch(c, job, s);
     TRY(small_msm_launch(c, job, s));
   } else {
     TRY(run_to_windows(c, job, jd));
@@ -776,12 +777,7 @@ int batch_device_tables_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_points
       TRY(ensure(c, c->window_flags, (size_t)B * 64 * 4));
       TRY(ensure(c, c->msm_fail, (size_t)B * 4));
       HIP_TRY(c, hipMemsetAsync(c->msm_fail.p, 0, (size_t)B * 4, s));
-      {
-        Launch l(c, "k_decompress"); c->decode_routes.note(false, job.n_dyn);
-        hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, s, job.d_dyn_points,
-                           (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, (uint32_t)B,
-                           (uint32_t*)c->msm_fail.p, (unsigned long long*)((char*)c->status.p + 8), (uint8_t*)nullptr);
-      }
+      decompress_launch(c, job, s);
       TRY(small_msm_launch(c, job, s));
     } else {
       TRY(run_to_windows(c, dj, jd, /*reset_status=*/false));
@@ -843,14 +839,9 @@ int batch_device_tables(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, 
 // while each batch's latency-bound kernels sit on its context's own light stream and run beside
 // them.  (Letting whole batches share the chip on equal terms instead makes them finish together,
 // start their transcripts together, and leave the chip idle for the length of a transcript.)
+// a whole-proof batch of one plan: the plan as the device reads it (prep_kernels.hpp) + this call's inputs
 struct PrepLaunch {
-  PrepShape sh;
-  const uint32_t *d_init, *d_mono_chal, *d_mono_pow, *d_tgt_off, *d_term_q, *d_term_mono, *d_term_coef;
-  const uint32_t* d_tape;
-  uint32_t n_ops;
-  const uint32_t *d_seg_info = nullptr, *d_seg_const = nullptr;   // cooperative transcript (n_seg = 0: not available)
-  const uint16_t* d_seg_map = nullptr;
-  uint32_t n_seg = 0;
+  PrepPlan plan;
   size_t lds_bytes; bool large;   // past a CU's LDS: large_prep.hpp instead of k_prepare
   const uint32_t* d_com;
   const uint8_t* d_proofs;
@@ -861,6 +852,32 @@ struct PrepLaunch {
 // proof bytes of a statement shape: the two-phase wire format, or the one-phase one (three points fewer)
 inline bool proof_len_fits(const PrepShape& sh, size_t len) { return len == 1 + 4ull * sh.proof_words || len + 96 == 1 + 4ull * sh.proof_words; }
 inline uint32_t proof_is_compact(const PrepShape& sh, size_t len) { return len + 96 == 1 + 4ull * sh.proof_words ? 1u : 0u; }
+
+// The transcript with one wavefront per statement while that still leaves the chip room (the cooperative form costs ~9x the
+// wave-instructions of the one-lane form, and buys latency only); beyond that, one lane per statement.  (A caller ANDs in
+// that each of its plans has the cooperative form: n_seg != 0.)
+bool coop_transcript(const zkgpu_ctx* c, size_t batch) {
+  return c->transcript_mode == 2 || (c->transcript_mode == 0 && batch <= COOP_TRANSCRIPT_MAX);
+}
+
+// k_prepare on stream s, or for a plan past a CU's LDS the launches of large_prep.hpp.  with_points (the synchronous path):
+// k_gather_dyn_points follows, inside k_prepare's profile entry, or for a large plan inside one of its own name.
+int prepare_launch(zkgpu_ctx* c, hipStream_t s, const PrepLaunch& pl, uint32_t B, bool with_points) {
+  const PrepPlan& d = pl.plan;
+  if (pl.large) TRY(lp_prepare_homo(c, s, d, B));
+  if (pl.large && !with_points) return ZKGPU_OK;
+  Launch l(c, pl.large ? "k_gather_dyn_points" : "k_prepare", s);
+  if (!pl.large) {
+    hipLaunchKernelGGL(k_prepare, dim3(B), dim3(256), pl.lds_bytes, s, d.sh, d.mono_chal, d.mono_pow, d.tgt_off, d.term_info,
+                       d.prod_qm, d.prod_coef, (const uint32_t*)c->prep_ch.p, pl.d_com, (const uint32_t*)c->prep_pw.p,
+                       (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p);
+  }
+  if (with_points) {
+    hipLaunchKernelGGL(k_gather_dyn_points, dim3(blocks_for((uint64_t)B * d.sh.n_dyn * 8, 256)), dim3(256), 0, s, d.sh, pl.d_com,
+                       (const uint32_t*)c->prep_pw.p, B, (uint32_t*)c->prep_dyn_pt.p);
+  }
+  return ZKGPU_OK;
+}
 
 bool pipe_eligible(const zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps) {
   return ps && ps->table && job.n_static && job.n_dyn && !c->forced_w && job.n_dyn <= 128ull * job.n_msm;
@@ -889,7 +906,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   // group checks (k_group_combine): only for whole proofs (the weights come from k_transcript)
   const uint32_t group = (prep && c->group_size > 1) ? (uint32_t)std::min<size_t>(c->group_size, B) : 1;
   const uint32_t n_groups = (uint32_t)((B + group - 1) / group);
-  const uint32_t ns = prep ? prep->sh.n_static : 0;
+  const uint32_t ns = prep ? prep->plan.sh.n_static : 0;
   // locating the culprit of a failed group saves work (one multiscalar multiplication instead of `group`) at the
   // price of two more dependent stages: worth it once the batch is large enough for the work to matter.  Mode 3 forms the
   // locating sums of ALL groups beside the group sums (twice the rows in the same multiplication), so that a failed group's
@@ -942,7 +959,8 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
                        (uint32_t*)c->msm_fail.p, prep ? (uint32_t*)c->prep_wf.p : (uint32_t*)nullptr, (uint32_t)B);
   }
   if (prep) {
-    const PrepShape& sh = prep->sh;
+    const PrepPlan& d = prep->plan;
+    const PrepShape& sh = d.sh;
     {
       Launch l(c, "k_proof_unpack", L);
       hipLaunchKernelGGL(k_proof_unpack, dim3(blocks_for((uint64_t)B * sh.proof_words, 256)), dim3(256), 0, L,
@@ -950,32 +968,29 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
                          (uint32_t)B, (uint32_t*)c->prep_wf.p, proof_is_compact(sh, prep->proof_len));
     }
     HIP_TRY(c, hipEventRecord(c->ev_u, L));
-    // one wavefront per transaction while that still leaves the chip room (the cooperative form costs ~9x the
-    // wave-instructions of the one-lane form, and buys latency only); beyond that, one lane per transaction
-    const bool coop = prep->n_seg && (c->transcript_mode == 2 || (c->transcript_mode == 0 && B <= COOP_TRANSCRIPT_MAX));
-    if (coop) {
+    if (d.n_seg && coop_transcript(c, B)) {
       {
         Launch l(c, "k_tape_gather", L);
-        hipLaunchKernelGGL(k_tape_gather, dim3(blocks_for((uint64_t)B * prep->n_seg * 25, 256)), dim3(256), 0, L, sh, prep->n_seg,
-                           prep->d_seg_const, prep->d_seg_map, prep->d_com, (const uint32_t*)c->prep_pw.p, (uint32_t)B,
+        hipLaunchKernelGGL(k_tape_gather, dim3(blocks_for((uint64_t)B * d.n_seg * 25, 256)), dim3(256), 0, L, sh, d.n_seg,
+                           d.seg_const, d.seg_map, prep->d_com, (const uint32_t*)c->prep_pw.p, (uint32_t)B,
                            (uint2*)c->prep_absorb.p);
       }
       {
         Launch l(c, "k_transcript_coop", L);
-        hipLaunchKernelGGL(k_transcript_coop, dim3((unsigned)B), dim3(64), 0, L, prep->n_seg, prep->d_seg_info, prep->d_init,
+        hipLaunchKernelGGL(k_transcript_coop, dim3((unsigned)B), dim3(64), 0, L, d.n_seg, d.seg_info, d.init,
                            (const uint2*)c->prep_absorb.p, (uint32_t)B, sh.n_ch, (uint32_t*)c->prep_raw.p);
       }
       {
         Launch l(c, "k_challenges", L);
         hipLaunchKernelGGL(k_challenges, dim3((unsigned)B), dim3(128), (size_t)sh.n_ch * 32, L, sh, (const uint32_t*)c->prep_raw.p,
                            (const uint32_t*)c->prep_pw.p, prep->d_r, (uint32_t)B, (uint32_t*)c->prep_ch.p,
-                           (uint32_t*)c->prep_wf.p, prep->d_mono_chal, prep->d_mono_pow, group > 1 ? 1u : 0u);
+                           (uint32_t*)c->prep_wf.p, d.mono_chal, d.mono_pow, group > 1 ? 1u : 0u);
       }
     } else {
       Launch l(c, "k_transcript", L);
-      hipLaunchKernelGGL(k_transcript, dim3(blocks_for(B, 64)), dim3(64), 0, L, sh, prep->d_init,
-                         (const uint4*)prep->d_tape, prep->n_ops, prep->d_com, (const uint32_t*)c->prep_pw.p, prep->d_r, (uint32_t)B, (uint32_t*)c->prep_ch.p,
-                         (uint32_t*)c->prep_wf.p, prep->d_mono_chal, prep->d_mono_pow, group > 1 ? 1u : 0u);
+      hipLaunchKernelGGL(k_transcript, dim3(blocks_for(B, 64)), dim3(64), 0, L, sh, d.init, d.tape, d.n_ops, prep->d_com,
+                         (const uint32_t*)c->prep_pw.p, prep->d_r, (uint32_t)B, (uint32_t*)c->prep_ch.p,
+                         (uint32_t*)c->prep_wf.p, d.mono_chal, d.mono_pow, group > 1 ? 1u : 0u);
     }
   }
   HIP_TRY(c, hipEventRecord(c->ev_t, L));
@@ -986,7 +1001,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
     // stream while the transcript is replayed.  Queued AFTER the transcript: k_points_tables takes every register of the chip
     // (255 per lane, two wavefronts per SIMD), and a light kernel queued behind it waits for one of its wavefronts to retire
     // -- ~0.6 ms (measured: the next batch's 30 us merge copy took 0.59 ms there, profiles/archive/r04an_timeline.txt)
-    const PrepShape& sh = prep->sh;
+    const PrepShape& sh = prep->plan.sh;
     HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_u, 0));
     {
       Launch l(c, "k_points_tables", H1);
@@ -999,13 +1014,8 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   if (phase == zkgpu_ctx::ENQ_MID) { HIP_TRY(c, hipGetLastError()); return ZKGPU_OK; }
   c->awaiting_back = false;
   if (prep) {
-    hipStream_t H3 = H3s;
-    HIP_TRY(c, hipStreamWaitEvent(H3, c->ev_t, 0));
-    if (prep->large) { TRY(lp_prepare_homo(c, H3, prep->sh, prep->d_tgt_off, prep->d_term_q, prep->d_term_mono, prep->d_term_coef, (uint32_t)B)); } else { Launch l(c, "k_prepare", H3);
-    hipLaunchKernelGGL(k_prepare, dim3((unsigned)B), dim3(256), prep->lds_bytes, H3, prep->sh, prep->d_mono_chal,
-                       prep->d_mono_pow, prep->d_tgt_off, prep->d_term_q, (const uint2*)prep->d_term_mono, prep->d_term_coef,
-                       (const uint32_t*)c->prep_ch.p, prep->d_com, (const uint32_t*)c->prep_pw.p,
-                       (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p); }
+    HIP_TRY(c, hipStreamWaitEvent(H3s, c->ev_t, 0));
+    TRY(prepare_launch(c, H3s, *prep, (uint32_t)B, /*with_points=*/false));
   }
   HIP_TRY(c, hipEventRecord(c->ev_p, prep ? H3s : L));
   HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_p, 0));
@@ -1046,12 +1056,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   if (prep) {
     TRY(small_accumulate_launch(c, job, H1));       // points and tables were done beside the transcript
   } else {
-    {
-      Launch l(c, "k_decompress", H1); c->decode_routes.note(false, job.n_dyn);
-      hipLaunchKernelGGL(k_decompress, dim3(blocks_for(job.n_dyn, 256)), dim3(256), 0, H1, job.d_dyn_points,
-                         (uint32_t*)c->dyn_rows.p, job.n_dyn, job.d_dyn_offsets, (uint32_t)B, (uint32_t*)c->msm_fail.p,
-                         (unsigned long long*)((char*)c->status.p + 8), (uint8_t*)nullptr);
-    }
+    decompress_launch(c, job, H1);
     TRY(small_msm_launch(c, job, H1));
   }
   HIP_TRY(c, hipEventRecord(c->ev_sm, H1));
@@ -1198,6 +1203,14 @@ void park_sync_result(zkgpu_ctx* c, int rc, const uint8_t* bitmap, size_t batch)
   c->pending_batch = batch;
 }
 
+// a job of a shape the pipeline does not cover: run here and now, its result parked for zkgpu_verify_wait
+int run_sync_and_park(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps) {
+  std::vector<uint8_t> bm(((size_t)job.n_msm + 7) / 8, 0);
+  const int rc = (ps->table && job.n_static) ? batch_device_tables(c, job, ps, bm.data()) : batch_device(c, job, bm.data());
+  park_sync_result(c, rc, bm.data(), job.n_msm);
+  return ZKGPU_OK;
+}
+
 int pipe_wait(zkgpu_ctx* c, uint8_t* accept_bitmap) {
   if (!c->pending) return ZKGPU_EINVAL;
   const size_t nbytes = (c->pending_batch + 7) / 8;
@@ -1244,6 +1257,34 @@ int pipe_wait(zkgpu_ctx* c, uint8_t* accept_bitmap) {
 int upload(zkgpu_ctx* c, Buffer& b, const void* src, size_t bytes, hipStream_t stream = nullptr) {
   TRY(ensure(c, b, std::max<size_t>(bytes, 16)));
   if (bytes) HIP_TRY(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, stream ? stream : c->stream));
+  return ZKGPU_OK;
+}
+
+// Spans of host memory -> one pinned block (at 256-byte-aligned offsets) -> their device buffers, the copies queued on the
+// context's light stream (no host wait: the caller's memory is free again when this returns, the copies overlap the batches
+// in flight).  src nullptr: the span is verifier randomness, drawn from the OS.
+struct StageSpan { const void* src; size_t bytes; Buffer* dst; };
+template <size_t N>
+int stage_inputs(zkgpu_ctx* c, const StageSpan (&sp)[N]) {
+  size_t off[N], end = 0;
+  for (size_t i = 0; i < N; ++i) { off[i] = (end + 255) & ~(size_t)255; end = off[i] + sp[i].bytes; }
+  if (c->pinned_in_cap < end) {
+    if (c->pinned_in) HIP_TRY(c, hipHostFree(c->pinned_in));
+    c->pinned_in = nullptr; c->pinned_in_cap = 0;
+    HIP_TRY(c, hipHostMalloc(&c->pinned_in, end + 4096, hipHostMallocDefault));
+    c->pinned_in_cap = end + 4096;
+  }
+  char* h = (char*)c->pinned_in;
+  for (size_t i = 0; i < N; ++i) {
+    if (sp[i].src) {
+      memcpy(h + off[i], sp[i].src, sp[i].bytes);
+    } else if (!os_random(h + off[i], sp[i].bytes)) {
+      c->last_error = "getrandom failed";
+      return ZKGPU_EINVAL;
+    }
+  }
+  for (size_t i = 0; i < N; ++i) TRY(ensure(c, *sp[i].dst, std::max<size_t>(sp[i].bytes, 16)));
+  for (size_t i = 0; i < N; ++i) HIP_TRY(c, hipMemcpyAsync(sp[i].dst->p, h + off[i], sp[i].bytes, hipMemcpyHostToDevice, c->stream_l));
   return ZKGPU_OK;
 }
 
@@ -2650,15 +2691,8 @@ struct zkgpu_cloak_plan {
   int device = 0;
   std::mutex mu;       // guards the per-batch-size scaffolding below
   CloakPlan host;
-  PrepShape shape;
   size_t gens_capacity;
-  uint32_t *d_init = nullptr, *d_mono_chal = nullptr, *d_mono_pow = nullptr, *d_tgt_off = nullptr, *d_term_q = nullptr,
-           *d_term_mono = nullptr, *d_term_coef = nullptr;
-  uint32_t* d_tape = nullptr;     // transcript_tape.hpp, four words per operation
-  uint32_t n_ops = 0;
-  uint32_t *d_seg_info = nullptr, *d_seg_const = nullptr;   // the tape regrouped for k_transcript_coop
-  uint16_t* d_seg_map = nullptr;
-  uint32_t n_seg = 0;
+  PrepPlan dev = {};   // the plan as the device reads it (prep_kernels.hpp): its shape and its arrays, which the plan owns
   // CSR scaffolding of a uniform batch (offsets, generator index template) for the largest batch seen so
   // far; a prefix of it serves every smaller batch.  It only grows: a larger one is built beside the old
   // one, which batches in flight on other contexts may still be reading and which is therefore kept
@@ -2689,8 +2723,11 @@ bool desc_from_c(zkgpu_ctx* c, const zkgpu_r1cs_desc* d, R1csDesc& desc);
 // reference answers with InvalidGeneratorsLength); anything else (ZKGPU_ENOMEM, ZKGPU_EHIP) is transient.
 int plan_finish_inner(zkgpu_ctx* c, zkgpu_cloak_plan* p, size_t gens_capacity) {
   const CloakPlan& h = p->host;
-  if (h.pn > gens_capacity || h.k > 16) { c->last_error = "statement needs more generators than the set holds"; return ZKGPU_EINVAL; } if (h.n_cons > LP_MAX_CONS) { c->last_error = "statement has more than 65536 constraints (the device preparation's z power tables)"; return ZKGPU_EINVAL; }
-  PrepShape& s = p->shape;
+  if (h.pn > gens_capacity || h.k > 16) { c->last_error = "statement needs more generators than the set holds"; return ZKGPU_EINVAL; }
+  if (h.n_cons > LP_MAX_CONS) { c->last_error = "statement has more than 65536 constraints (the device preparation's z power tables)"; return ZKGPU_EINVAL; }
+  PrepPlan& d = p->dev;
+  PrepShape& s = d.sh;
+  d.h_base = (uint32_t)(2 + gens_capacity);
   s.m = h.m; s.n1 = h.n1; s.n = h.n; s.pn = h.pn; s.k = h.k; s.n_cons = h.n_cons;
   s.n_chal2 = (uint32_t)h.chal_names.size();
   s.n_mono = (uint32_t)h.mono_chal.size();
@@ -2736,28 +2773,28 @@ int plan_finish_inner(zkgpu_ctx* c, zkgpu_cloak_plan* p, size_t gens_capacity) {
   tr.append_message("dom-sep", (const uint8_t*)"r1cs v1", 7);
   std::vector<uint32_t> init(52);
   tr.export_state(init.data());
-  TRY(plan_upload(c, &p->d_init, init));
+  TRY(plan_upload(c, &d.init, init));
   {
     const std::vector<uint32_t> tape = build_r1cs_verifier_tape(init[50], init[51], s.m, h.chal_names, s.k, s.pn, CH_FIXED);
-    p->n_ops = (uint32_t)(tape.size() / 4);
-    TRY(plan_upload(c, &p->d_tape, tape));
+    d.n_ops = (uint32_t)(tape.size() / 4);
+    TRY(plan_upload(c, &d.tape, tape));
     const CoopSegments segs = build_coop_segments(tape, s.m);
     if (segs.n_seg() && s.n_ch <= 0xffffu) {
-      p->n_seg = segs.n_seg();
-      TRY(plan_upload(c, &p->d_seg_info, segs.info));
-      TRY(plan_upload(c, &p->d_seg_const, segs.consts));
-      TRY(plan_upload(c, &p->d_seg_map, segs.map));
+      d.n_seg = segs.n_seg();
+      TRY(plan_upload(c, &d.seg_info, segs.info));
+      TRY(plan_upload(c, &d.seg_const, segs.consts));
+      TRY(plan_upload(c, &d.seg_map, segs.map));
     }
   }
-  TRY(plan_upload(c, &p->d_mono_chal, h.mono_chal));
-  TRY(plan_upload(c, &p->d_mono_pow, h.mono_pow));
-  TRY(plan_upload(c, &p->d_tgt_off, h.tgt_off));
+  TRY(plan_upload(c, &d.mono_chal, h.mono_chal));
+  TRY(plan_upload(c, &d.mono_pow, h.mono_pow));
+  TRY(plan_upload(c, &d.tgt_off, h.tgt_off));
   {
     std::vector<uint32_t> qm(2 * h.prod_q.size());
     for (size_t i = 0; i < h.prod_q.size(); ++i) { qm[2 * i] = h.prod_q[i]; qm[2 * i + 1] = h.prod_mono[i]; }
-    TRY(plan_upload(c, &p->d_term_q, h.term_info));       // k_prepare's term_info
-    TRY(plan_upload(c, &p->d_term_mono, qm));             //             prod_qm
-    TRY(plan_upload(c, &p->d_term_coef, h.prod_coef));    //             prod_coef
+    TRY(plan_upload(c, &d.term_info, h.term_info));
+    TRY(plan_upload(c, &d.prod_qm, qm));
+    TRY(plan_upload(c, &d.prod_coef, h.prod_coef));
   }
   if (!p->large) HIP_TRY(c, hipFuncSetAttribute((const void*)k_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
   return ZKGPU_OK;
@@ -2837,9 +2874,10 @@ void zkgpu_r1cs_plan_destroy(zkgpu_cloak_plan* p) { zkgpu_cloak_plan_destroy(p);
 void zkgpu_cloak_plan_destroy(zkgpu_cloak_plan* p) {
   if (!p) return;
   DeviceGuard g(p->ctx->device);
-  void* ptrs[] = {p->d_seg_info, p->d_seg_const, p->d_seg_map, p->d_tape, p->d_init, p->d_mono_chal, p->d_mono_pow, p->d_tgt_off, p->d_term_q, p->d_term_mono,
-                  p->d_term_coef, p->d_dyn_off, p->d_st_off, p->d_st_index};
-  for (void* q : ptrs) if (q) (void)hipFree(q);
+  const PrepPlan& d = p->dev;
+  const void* ptrs[] = {d.seg_info, d.seg_const, d.seg_map, d.tape, d.init, d.mono_chal, d.mono_pow, d.tgt_off, d.term_info, d.prod_qm,
+                        d.prod_coef, p->d_dyn_off, p->d_st_off, p->d_st_index};
+  for (const void* q : ptrs) if (q) (void)hipFree(const_cast<void*>(q));
   for (void* q : p->retired) (void)hipFree(q);
   delete p;
 }
@@ -2860,7 +2898,7 @@ int zkgpu_cloak_plan_info(const zkgpu_cloak_plan* p, uint32_t* multipliers, uint
 // [3] dynamic terms, [4] static terms, [5] k, [6] commitments m, [7] monomials.
 int zkgpu_cloak_plan_layout(const zkgpu_cloak_plan* p, uint32_t out[8]) {
   if (!p || !out) return ZKGPU_EINVAL;
-  const PrepShape& s = p->shape;
+  const PrepShape& s = p->dev.sh;
   out[0] = s.n_ch_ext; out[1] = s.n_ch; out[2] = s.n_chal2; out[3] = s.n_dyn; out[4] = s.n_static; out[5] = s.k;
   out[6] = s.m; out[7] = s.n_mono;
   return ZKGPU_OK;
@@ -2878,38 +2916,6 @@ int cloak_verify_gpu_body(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_pl
                           uint8_t* accept_bitmap);
 }  // namespace
 
-namespace {
-// host buffers -> pinned staging -> device, queued on the context's light stream (no host wait: the
-// caller's buffers are free again when this returns, the copies overlap the batches in flight)
-int stage_inputs(zkgpu_ctx* c, const PrepShape& sh, size_t batch, const uint8_t* commitments, const uint8_t* proofs,
-                 size_t proof_len, const uint8_t* r_bytes) {
-  const size_t n_com = batch * sh.m * 32, n_pr = batch * proof_len, n_r = batch * 64;
-  const size_t o_pr = (n_com + 255) & ~(size_t)255, o_r = (o_pr + n_pr + 255) & ~(size_t)255;
-  if (c->pinned_in_cap < o_r + n_r) {
-    if (c->pinned_in) HIP_TRY(c, hipHostFree(c->pinned_in));
-    c->pinned_in = nullptr; c->pinned_in_cap = 0;
-    HIP_TRY(c, hipHostMalloc(&c->pinned_in, o_r + n_r + 4096, hipHostMallocDefault));
-    c->pinned_in_cap = o_r + n_r + 4096;
-  }
-  char* h = (char*)c->pinned_in;
-  memcpy(h, commitments, n_com);
-  memcpy(h + o_pr, proofs, n_pr);
-  if (r_bytes) {
-    memcpy(h + o_r, r_bytes, n_r);
-  } else if (!os_random(h + o_r, n_r)) {   // verifier randomness from the OS
-    c->last_error = "getrandom failed";
-    return ZKGPU_EINVAL;
-  }
-  TRY(ensure(c, c->prep_com, std::max<size_t>(n_com, 16)));
-  TRY(ensure(c, c->prep_proofs, std::max<size_t>(n_pr, 16)));
-  TRY(ensure(c, c->prep_r, std::max<size_t>(n_r, 16)));
-  HIP_TRY(c, hipMemcpyAsync(c->prep_com.p, h, n_com, hipMemcpyHostToDevice, c->stream_l));
-  HIP_TRY(c, hipMemcpyAsync(c->prep_proofs.p, h + o_pr, n_pr, hipMemcpyHostToDevice, c->stream_l));
-  HIP_TRY(c, hipMemcpyAsync(c->prep_r.p, h + o_r, n_r, hipMemcpyHostToDevice, c->stream_l));
-  return ZKGPU_OK;
-}
-}  // namespace
-
 // Asynchronous form of zkgpu_cloak_verify_batch_gpu (inputs in host memory; they may be reused as
 // soon as this returns); zkgpu_verify_wait collects the bitmap.
 int zkgpu_cloak_verify_submit(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
@@ -2917,7 +2923,7 @@ int zkgpu_cloak_verify_submit(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloa
                               const uint8_t* r_bytes) {
   if (!c || !ps || !plan || plan->device != c->device || ps->ctx->device != c->device) return ZKGPU_EINVAL;
   if (batch == 0 || !commitments || !proofs || batch >= (1ull << 24)) return ZKGPU_EINVAL;
-  const PrepShape& sh = plan->shape;
+  const PrepShape& sh = plan->dev.sh;
   {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (c->pending) return ZKGPU_EINVAL;
@@ -2927,7 +2933,9 @@ int zkgpu_cloak_verify_submit(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloa
       return ZKGPU_OK;
     }
     DeviceGuard g(c->device);
-    TRY(stage_inputs(c, sh, batch, commitments, proofs, proof_len, r_bytes));
+    const StageSpan in[] = {{commitments, batch * sh.m * 32, &c->prep_com}, {proofs, batch * proof_len, &c->prep_proofs},
+                            {r_bytes, batch * 64, &c->prep_r}};
+    TRY(stage_inputs(c, in));
   }
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   DeviceGuard g(c->device);
@@ -2958,7 +2966,7 @@ int zkgpu_cloak_verify_batch_gpu_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, zkg
   memset(accept_bitmap, 0, (batch + 7) / 8);
   if (batch == 0) return ZKGPU_OK;
   if (!d_commitments || !d_proofs || !d_r || batch >= (1ull << 24)) return ZKGPU_EINVAL;
-  if (!proof_len_fits(plan->shape, proof_len)) return ZKGPU_OK;
+  if (!proof_len_fits(plan->dev.sh, proof_len)) return ZKGPU_OK;
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   DeviceGuard g(c->device);
   return cloak_verify_gpu_body(c, ps, plan, batch, (const uint32_t*)d_commitments, (const uint8_t*)d_proofs,
@@ -2977,16 +2985,17 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
     c->dep_event = nullptr;
     HIP_TRY(c, hipStreamWaitEvent(c->stream_l, ev, 0));
   }
-  const PrepShape& sh = plan->shape;
+  const PrepShape& sh = plan->dev.sh;
   const uint32_t B = (uint32_t)batch;
   TRY(ensure(c, c->prep_pw, (size_t)B * sh.proof_words * 4));
-  TRY(ensure(c, c->prep_ch, (size_t)B * sh.n_ch_ext * 32)); if (plan->large) TRY(ensure(c, c->prep_large, lp_ws_bytes(lp_layout(sh).slots, B)));
+  TRY(ensure(c, c->prep_ch, (size_t)B * sh.n_ch_ext * 32));
+  if (plan->large) TRY(ensure(c, c->prep_large, lp_ws_bytes(lp_layout(sh).slots, B)));
   TRY(ensure(c, c->prep_wf, (size_t)B * 4));
   TRY(ensure(c, c->prep_dyn_sc, (size_t)B * sh.n_dyn * 32));
   TRY(ensure(c, c->prep_dyn_pt, (size_t)B * sh.n_dyn * 32));
   TRY(ensure(c, c->prep_st_sc, (size_t)B * sh.n_static * 32));
-  if (plan->n_seg && (c->transcript_mode == 2 || (c->transcript_mode == 0 && batch <= COOP_TRANSCRIPT_MAX))) {
-    TRY(ensure(c, c->prep_absorb, (size_t)B * plan->n_seg * 25 * 8));
+  if (plan->dev.n_seg && coop_transcript(c, batch)) {
+    TRY(ensure(c, c->prep_absorb, (size_t)B * plan->dev.n_seg * 25 * 8));
     TRY(ensure(c, c->prep_raw, (size_t)B * sh.n_ch * 64));
   }
   const uint64_t *d_dyn_off, *d_st_off;
@@ -3032,16 +3041,8 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
   job.d_static_rows = ps->rows;
   job.n_msm = B;
   job.d_wellformed = (const uint32_t*)c->prep_wf.p;   // folded into the accept bitmap on the device
-  if (pipe_eligible(c, job, ps)) {
-    PrepLaunch pl;
-    pl.sh = sh;
-    pl.d_init = plan->d_init; pl.d_mono_chal = plan->d_mono_chal; pl.d_mono_pow = plan->d_mono_pow;
-    pl.d_tgt_off = plan->d_tgt_off; pl.d_term_q = plan->d_term_q; pl.d_term_mono = plan->d_term_mono;
-    pl.d_term_coef = plan->d_term_coef; pl.d_tape = plan->d_tape; pl.n_ops = plan->n_ops; pl.lds_bytes = plan->lds_bytes; pl.large = plan->large;
-    pl.d_seg_info = plan->d_seg_info; pl.d_seg_const = plan->d_seg_const; pl.d_seg_map = plan->d_seg_map; pl.n_seg = plan->n_seg;
-    pl.d_com = d_com; pl.d_proofs = d_proofs; pl.d_r = d_r; pl.proof_len = proof_len;
-    return pipe_enqueue(c, job, ps, &pl);
-  }
+  const PrepLaunch pl = {plan->dev, plan->lds_bytes, plan->large, d_com, d_proofs, d_r, proof_len};
+  if (pipe_eligible(c, job, ps)) return pipe_enqueue(c, job, ps, &pl);
   // general shapes (no generator tables, forced window width, many proof points): one stream, synchronous
   hipStream_t s = c->stream;
   TRY(ensure(c, c->recoded, std::max<uint64_t>(job.n_dyn, 1) * 32));
@@ -3056,26 +3057,13 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
   }
   {
     Launch l(c, "k_transcript");
-    hipLaunchKernelGGL(k_transcript, dim3(blocks_for(B, 64)), dim3(64), 0, s, sh, (const uint32_t*)plan->d_init,
-                       (const uint4*)plan->d_tape, plan->n_ops, d_com, (const uint32_t*)c->prep_pw.p,
-                       d_r, B, (uint32_t*)c->prep_ch.p, (uint32_t*)c->prep_wf.p, (const uint32_t*)plan->d_mono_chal,
-                       (const uint32_t*)plan->d_mono_pow, 0u);
+    hipLaunchKernelGGL(k_transcript, dim3(blocks_for(B, 64)), dim3(64), 0, s, sh, pl.plan.init, pl.plan.tape, pl.plan.n_ops, d_com,
+                       (const uint32_t*)c->prep_pw.p, d_r, B, (uint32_t*)c->prep_ch.p, (uint32_t*)c->prep_wf.p,
+                       pl.plan.mono_chal, pl.plan.mono_pow, 0u);
   }
-  {
-    if (plan->large) TRY(lp_prepare_homo(c, s, sh, plan->d_tgt_off, plan->d_term_q, plan->d_term_mono, plan->d_term_coef, B)); Launch l(c, plan->large ? "k_gather_dyn_points" : "k_prepare");
-    if (!plan->large) { hipLaunchKernelGGL(k_prepare, dim3(B), dim3(256), plan->lds_bytes, s, sh, (const uint32_t*)plan->d_mono_chal,
-                       (const uint32_t*)plan->d_mono_pow, (const uint32_t*)plan->d_tgt_off, (const uint32_t*)plan->d_term_q,
-                       (const uint2*)plan->d_term_mono, (const uint32_t*)plan->d_term_coef, (const uint32_t*)c->prep_ch.p,
-                       d_com, (const uint32_t*)c->prep_pw.p, (uint32_t*)c->prep_dyn_sc.p,
-                       (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p); }
-    hipLaunchKernelGGL(k_gather_dyn_points, dim3(blocks_for((uint64_t)B * sh.n_dyn * 8, 256)), dim3(256), 0, s, sh, d_com,
-                       (const uint32_t*)c->prep_pw.p, B, (uint32_t*)c->prep_dyn_pt.p);
-  }
+  TRY(prepare_launch(c, s, pl, B, /*with_points=*/true));
   HIP_TRY(c, hipGetLastError());
-  std::vector<uint8_t> bm((batch + 7) / 8, 0);
-  int rc = ps->table ? batch_device_tables(c, job, ps, bm.data()) : batch_device(c, job, bm.data());
-  park_sync_result(c, rc, bm.data(), batch);
-  return ZKGPU_OK;
+  return run_sync_and_park(c, job, ps);
 }
 
 int cloak_verify_gpu_body(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
@@ -3098,7 +3086,7 @@ int zkgpu_cloak_verify_submit_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_
   {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (c->pending) return ZKGPU_EINVAL;
-    if (!proof_len_fits(plan->shape, proof_len)) {     // wrong length for this statement: every proof is Err
+    if (!proof_len_fits(plan->dev.sh, proof_len)) {     // wrong length for this statement: every proof is Err
       std::vector<uint8_t> z((batch + 7) / 8, 0);
       c->dep_event = nullptr;
       park_sync_result(c, ZKGPU_OK, z.data(), batch);
@@ -3149,10 +3137,7 @@ int zkgpu_verify_batch_ps_submit_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, siz
   job.d_static_rows = ps->rows;
   job.n_msm = (uint32_t)batch;
   if (pipe_eligible(c, job, ps)) return pipe_enqueue(c, job, ps, nullptr);
-  std::vector<uint8_t> bm((batch + 7) / 8, 0);
-  int rc = (ps->table && n_static) ? batch_device_tables(c, job, ps, bm.data()) : batch_device(c, job, bm.data());
-  park_sync_result(c, rc, bm.data(), batch);
-  return ZKGPU_OK;
+  return run_sync_and_park(c, job, ps);
 }
 
 int zkgpu_verify_wait(zkgpu_ctx* c, uint8_t* accept_bitmap) {
@@ -3474,12 +3459,12 @@ void lp_launch_all(zkgpu_ctx* c, hipStream_t s, const Src& src, uint32_t n_stmt,
 }
 }  // namespace
 
-int lp_prepare_homo(zkgpu_ctx* c, hipStream_t s, const PrepShape& sh, const uint32_t* tgt_off, const uint32_t* term_info,
-                    const uint32_t* prod_qm, const uint32_t* prod_coef, uint32_t batch) {
+int lp_prepare_homo(zkgpu_ctx* c, hipStream_t s, const PrepPlan& plan, uint32_t batch) {
+  const PrepShape& sh = plan.sh;
   const uint32_t slots = lp_layout(sh).slots, slice = lp_slice(slots);
   if (c->prep_large.cap < lp_ws_bytes(slots, batch)) { c->last_error = "large-plan workspace not reserved"; return ZKGPU_EINVAL; }
   for (uint32_t b0 = 0; b0 < batch; b0 += slice) {     // slices of the workspace, one after the other on the stream
-    const LpHomo src = {sh, tgt_off, term_info, (const uint2*)prod_qm, prod_coef, (const uint32_t*)c->prep_ch.p,
+    const LpHomo src = {sh, plan.tgt_off, plan.term_info, plan.prod_qm, plan.prod_coef, (const uint32_t*)c->prep_ch.p,
                         (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->recoded.p, (uint32_t*)c->prep_st_sc.p, b0};
     lp_launch_all(c, s, src, std::min(slice, batch - b0), sh.n_targets, sh.pn, slots);
   }
@@ -3489,7 +3474,7 @@ int lp_prepare_homo(zkgpu_ctx* c, hipStream_t s, const PrepShape& sh, const uint
 
 // ---- statements of several plans in one call (mixed_kernels.hpp) ----------------------------------------------------
 // zkgpu_r1cs_verify_mixed*: statement i is checked against plans[plan_index[i]].  The host lays out a per-call table
-// (one MixPlan per distinct plan, one MixStmt per statement) and one CSR of multiscalar-multiplication rows whose lengths
+// (one PrepPlan per distinct plan, one MixStmt per statement) and one CSR of multiscalar-multiplication rows whose lengths
 // are the statements' own; the preparation is one launch per stage whatever the number of plans, and the rows go
 // through the same multiscalar-multiplication pipeline as zkgpu_verify_batch_ps_submit_dev.  Statements are checked
 // alone (no group checks): bit i is what a batch of that statement alone would give.
@@ -3553,7 +3538,7 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
       if (cls[u] < 2) {
         class_lds[cls[u]] = std::max(class_lds[cls[u]], uniq[u]->lds_bytes);
       } else {
-        const PrepShape& sh = uniq[u]->shape;
+        const PrepShape& sh = uniq[u]->dev.sh;
         lp_targets = std::max(lp_targets, sh.n_targets);
         lp_pn = std::max(lp_pn, sh.pn);
         lp_slots = std::max(lp_slots, lp_layout(sh).slots);
@@ -3562,8 +3547,8 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     for (uint32_t i = 0; i < B; ++i) order[at[pid[i]]++] = i;
   }
   const uint32_t n_large = B - class_start[2];
-  bool coop = c->transcript_mode == 2 || (c->transcript_mode == 0 && batch <= COOP_TRANSCRIPT_MAX);
-  for (zkgpu_cloak_plan* pl : uniq) coop &= pl->n_seg != 0 && pl->shape.n_ch <= 0xffffu;
+  bool coop = coop_transcript(c, batch);
+  for (zkgpu_cloak_plan* pl : uniq) coop &= pl->dev.n_seg != 0 && pl->dev.sh.n_ch <= 0xffffu;
   std::vector<uint32_t> lane_order;
   if (!coop) {                           // each plan's run padded to whole wavefronts
     lane_order.reserve(B + 64 * U);
@@ -3573,26 +3558,23 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
         while (lane_order.size() % 64) lane_order.push_back(~0u);
     }
   }
-  // the table
-  std::vector<MixPlan> mp(U);
+  // the table, laid out as the device reads it: plans | statements | order | lane order | row offsets (dynamic, static)
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t t_plans = 0, t_stmts = up(t_plans + U * sizeof(PrepPlan)), t_order = up(t_stmts + B * sizeof(MixStmt)),
+               t_lanes = up(t_order + 4 * (size_t)B), t_doff = up(t_lanes + 4 * lane_order.size()),
+               t_soff = up(t_doff + 8 * ((size_t)B + 1)), t_end = t_soff + 8 * ((size_t)B + 1);
+  std::vector<char> tab(t_end);
+  PrepPlan* mp = (PrepPlan*)(tab.data() + t_plans);
   size_t max_nch = 0;
   for (uint32_t u = 0; u < U; ++u) {
-    const zkgpu_cloak_plan* pl = uniq[u];
-    MixPlan& m = mp[u];
-    memset(&m, 0, sizeof m);
-    m.sh = pl->shape;
-    m.init = pl->d_init; m.tape = (const uint4*)pl->d_tape; m.n_ops = pl->n_ops;
-    m.seg_info = pl->d_seg_info; m.seg_const = pl->d_seg_const; m.seg_map = pl->d_seg_map; m.n_seg = pl->n_seg;
-    m.mono_chal = pl->d_mono_chal; m.mono_pow = pl->d_mono_pow; m.tgt_off = pl->d_tgt_off; m.term_info = pl->d_term_q;
-    m.prod_qm = (const uint2*)pl->d_term_mono; m.prod_coef = pl->d_term_coef;
-    m.h_base = (uint32_t)(2 + pl->gens_capacity);
-    max_nch = std::max<size_t>(max_nch, pl->shape.n_ch);
+    mp[u] = uniq[u]->dev;
+    max_nch = std::max<size_t>(max_nch, mp[u].sh.n_ch);
   }
-  std::vector<MixStmt> ms(B);
-  std::vector<uint64_t> dyn_off(B + 1), st_off(B + 1);
+  MixStmt* ms = (MixStmt*)(tab.data() + t_stmts);
+  uint64_t *dyn_off = (uint64_t*)(tab.data() + t_doff), *st_off = (uint64_t*)(tab.data() + t_soff);
   uint64_t n_com = 0, n_pw = 0, n_ch = 0, n_raw = 0, n_abs = 0, n_dyn = 0, n_st = 0;
   for (uint32_t i = 0; i < B; ++i) {
-    const MixPlan& m = mp[pid[i]];
+    const PrepPlan& m = mp[pid[i]];
     const PrepShape& sh = m.sh;
     const uint64_t len = proof_offsets[i + 1] - proof_offsets[i];
     MixStmt& s = ms[i];
@@ -3606,39 +3588,8 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     n_dyn += sh.n_dyn; n_st += sh.n_static;
   }
   dyn_off[B] = n_dyn; st_off[B] = n_st;
-  // staging: commitments | proofs | r | table, one pinned block, four copies on the light stream
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t b_com = 4 * n_com, b_pr = proof_offsets[B], b_r = 64 * (size_t)B;
-  const size_t t_plans = 0, t_stmts = up(t_plans + U * sizeof(MixPlan)), t_order = up(t_stmts + B * sizeof(MixStmt)),
-               t_lanes = up(t_order + 4 * (size_t)B), t_doff = up(t_lanes + 4 * lane_order.size()),
-               t_soff = up(t_doff + 8 * ((size_t)B + 1)), t_end = t_soff + 8 * ((size_t)B + 1);
-  const size_t o_pr = up(b_com), o_r = up(o_pr + b_pr), o_tab = up(o_r + b_r);
-  if (c->pinned_in_cap < o_tab + t_end) {
-    if (c->pinned_in) HIP_TRY(c, hipHostFree(c->pinned_in));
-    c->pinned_in = nullptr; c->pinned_in_cap = 0;
-    HIP_TRY(c, hipHostMalloc(&c->pinned_in, o_tab + t_end + 4096, hipHostMallocDefault));
-    c->pinned_in_cap = o_tab + t_end + 4096;
-  }
-  char* h = (char*)c->pinned_in;
-  memcpy(h, commitments, b_com);
-  memcpy(h + o_pr, proofs, b_pr);
-  if (r_bytes) {
-    memcpy(h + o_r, r_bytes, b_r);
-  } else if (!os_random(h + o_r, b_r)) {   // verifier randomness from the OS
-    c->last_error = "getrandom failed";
-    return ZKGPU_EINVAL;
-  }
-  char* tab = h + o_tab;
-  memcpy(tab + t_plans, mp.data(), U * sizeof(MixPlan));
-  memcpy(tab + t_stmts, ms.data(), B * sizeof(MixStmt));
-  memcpy(tab + t_order, order.data(), 4 * (size_t)B);
-  if (!lane_order.empty()) memcpy(tab + t_lanes, lane_order.data(), 4 * lane_order.size());
-  memcpy(tab + t_doff, dyn_off.data(), 8 * ((size_t)B + 1));
-  memcpy(tab + t_soff, st_off.data(), 8 * ((size_t)B + 1));
-  TRY(ensure(c, c->prep_com, std::max<size_t>(b_com, 16)));
-  TRY(ensure(c, c->prep_proofs, std::max<size_t>(b_pr, 16)));
-  TRY(ensure(c, c->prep_r, b_r));
-  TRY(ensure(c, c->mx_tab, t_end));
+  memcpy(tab.data() + t_order, order.data(), 4 * (size_t)B);
+  if (!lane_order.empty()) memcpy(tab.data() + t_lanes, lane_order.data(), 4 * lane_order.size());
   TRY(ensure(c, c->prep_pw, 4 * n_pw));
   TRY(ensure(c, c->prep_ch, 4 * n_ch));
   TRY(ensure(c, c->prep_wf, 4 * (size_t)B));
@@ -3651,13 +3602,12 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     TRY(ensure(c, c->prep_absorb, std::max<uint64_t>(8 * n_abs, 16)));
     TRY(ensure(c, c->prep_raw, std::max<uint64_t>(4 * n_raw, 16)));
   }
+  const StageSpan in[] = {{commitments, (size_t)(4 * n_com), &c->prep_com}, {proofs, (size_t)proof_offsets[B], &c->prep_proofs},
+                          {r_bytes, 64 * (size_t)B, &c->prep_r}, {tab.data(), t_end, &c->mx_tab}};
+  TRY(stage_inputs(c, in));
   hipStream_t L = c->stream_l;
-  HIP_TRY(c, hipMemcpyAsync(c->prep_com.p, h, b_com, hipMemcpyHostToDevice, L));
-  HIP_TRY(c, hipMemcpyAsync(c->prep_proofs.p, h + o_pr, b_pr, hipMemcpyHostToDevice, L));
-  HIP_TRY(c, hipMemcpyAsync(c->prep_r.p, h + o_r, b_r, hipMemcpyHostToDevice, L));
-  HIP_TRY(c, hipMemcpyAsync(c->mx_tab.p, tab, t_end, hipMemcpyHostToDevice, L));
   const char* dt = (const char*)c->mx_tab.p;
-  const MixPlan* d_plans = (const MixPlan*)(dt + t_plans);
+  const PrepPlan* d_plans = (const PrepPlan*)(dt + t_plans);
   const MixStmt* d_stmts = (const MixStmt*)(dt + t_stmts);
   const uint32_t* d_order = (const uint32_t*)(dt + t_order);
   const uint32_t* d_com = (const uint32_t*)c->prep_com.p;
@@ -3729,10 +3679,7 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
   if (pipe_eligible(c, job, ps)) return pipe_enqueue(c, job, ps, nullptr);
   // general shapes (no generator tables, forced window width): synchronous, as cloak_verify_gpu_enqueue
   HIP_TRY(c, hipStreamSynchronize(L));
-  std::vector<uint8_t> bm((batch + 7) / 8, 0);
-  const int rc = ps->table ? batch_device_tables(c, job, ps, bm.data()) : batch_device(c, job, bm.data());
-  park_sync_result(c, rc, bm.data(), batch);
-  return ZKGPU_OK;
+  return run_sync_and_park(c, job, ps);
 }
 }  // namespace
 
