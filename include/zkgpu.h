@@ -283,9 +283,17 @@ int zkgpu_r1cs_verify_batch(zkgpu_ctx *ctx, const zkgpu_pointset *ps, const zkgp
  * the bitmap zeroed, before any device work: a plan index out of range, a NULL plan, a plan that needs more generators
  * than ps holds, decreasing offsets or a first offset other than 0.  batch = 0 is OK (accept_bitmap may then be NULL).
  * The preparation is one launch per stage whatever the number of plans (the scalar preparation once per LDS class present:
- * plans that leave room for two or more workgroups per CU, and those that do not), and the multiscalar multiplications
- * cover each statement's own rows; statements are
- * checked alone (no group checks).  *_submit: as zkgpu_cloak_verify_submit (host buffers free on return), collected by
+ * plans that leave room for two or more workgroups per CU, and those that do not).
+ * Group checks: generators depend on their index alone, so statements whose plans have the same padded n and generator
+ * capacity share their generator terms whatever their constraints.  Such statements are checked in groups of up to 16
+ * (zkgpu_set_group_size; 1 = every statement alone, the launch sequence of a call without groups): the group's equations
+ * are added under independent weights rho = r^2 (r from r_bytes; 1 where r = 0), its generator scalars collapse into one
+ * row, each statement keeps its own proof-point row.  Statements known bad beforehand (malformed proof, undecodable point)
+ * are left out of their group; every member of a group that fails is re-checked alone on the device, so a bit differs
+ * from the statement-alone verdict only where a sum of non-zero equations vanishes under random weights (probability
+ * ~2^-250 per group).  A remainder of one statement, and a statement that shares its key with no other, is checked alone.
+ * The launch sequence depends on the call only (LDS classes present, whether a group exists, the transcript form), never
+ * on an earlier batch.  *_submit: as zkgpu_cloak_verify_submit (host buffers free on return), collected by
  * zkgpu_verify_wait. */
 int zkgpu_r1cs_verify_mixed(zkgpu_ctx *ctx, const zkgpu_pointset *ps, zkgpu_r1cs_plan *const *plans, size_t n_plans,
                             size_t batch, const uint32_t *plan_index, const uint8_t *commitments,

@@ -2,9 +2,11 @@
 """Statements of 8 different constraint systems verified in ONE zkgpu_r1cs_verify_mixed call, against the same statements
 sent as one zkgpu_r1cs_verify_batch_gpu call per plan (wall time of the synchronous calls, inputs in host memory for both).
 
-    python tools/mixed_bench.py [--batches 1024,8192] [--reps 5] [--once N]
+    python tools/mixed_bench.py [--batches 1024,8192] [--reps 5] [--once N] [--group N]
 
 --once N: a single mixed call of N statements (for a kernel trace of one call).
+--group N: group size of the mixed call (default: the library's 16; 1: every statement alone); the counters of
+zkgpu_debug_read "mixed_groups" are printed with each result.
 --per-plan-group 1: the per-plan calls check every statement alone, as the mixed call does (default: groups of 16).
 Plans: range(8), range(64), shuffle(5), the 1032-constraint program, two random systems with challenges, cloak 2x2 and
 3x2; statements are dealt round-robin over the plans (64 distinct valid proofs per plan, repeated)."""
@@ -96,6 +98,8 @@ def main():
     ap.add_argument("--lds-case", type=int, default=0,
                     help="N range(8) statements alone, then the same with one 1032-constraint statement added: the cost of "
                          "the large plan's LDS to the small statements (k_mx_prepare time from the profiling hook)")
+    ap.add_argument("--group", type=int, default=0,
+                    help="group size of the mixed call (0: the library's default of 16; 1: every statement checked alone)")
     ap.add_argument("--per-plan-group", type=int, default=0,
                     help="group size of the per-plan calls (0: the library's default; 1: every statement checked alone, as "
                          "the mixed call does)")
@@ -108,6 +112,14 @@ def main():
     mv = MixedR1csVerifier(ctx, gens, plans)
     handles = mv.handles
     P = len(plans)
+    mixed_group = a.group or 16
+
+    def mixed_call(idx, coms, proofs, r):
+        ctx.set_group_size(mixed_group)
+        try:
+            return mv.verify(idx, coms, proofs, r)
+        finally:
+            ctx.set_group_size(16)
     if a.lds_case:
         n = a.lds_case
         small = [pool[0][i % len(pool[0])] for i in range(n)]
@@ -129,13 +141,15 @@ def main():
         coms, proofs = [s[0] for s in st], [s[1] for s in st]
         r = hashlib.shake_256(b"mixed bench r %d" % batch).digest(64 * batch)
         if a.once:
-            bm = mv.verify(idx, coms, proofs, r)
-            print(json.dumps({"once": batch, "accepted": sum(bin(b).count("1") for b in bm)}))
+            bm = mixed_call(idx, coms, proofs, r)
+            print(json.dumps({"once": batch, "group": mixed_group, "accepted": sum(bin(b).count("1") for b in bm),
+                              "mixed_groups": list(ctx.mixed_group_stats())}))
             continue
         groups = [[i for i in range(batch) if idx[i] == p] for p in range(P)]
-        bm = mv.verify(idx, coms, proofs, r)
+        bm = mixed_call(idx, coms, proofs, r)
         assert sum(bin(b).count("1") for b in bm) == batch, "every statement is valid"
-        t_mixed = timed(lambda: mv.verify(idx, coms, proofs, r), a.reps)
+        t_mixed = timed(lambda: mixed_call(idx, coms, proofs, r), a.reps)
+        stats = list(ctx.mixed_group_stats())
         if a.per_plan_group:
             ctx.set_group_size(a.per_plan_group)
         t_plan = []
@@ -145,7 +159,8 @@ def main():
             gc, gp = [coms[i] for i in g], [proofs[i] for i in g]
             t_plan.append(timed(lambda: per_plan_call(ctx, gens, handles[p], gc, gp, rp), a.reps))
         ctx.set_group_size(16)
-        print(json.dumps({"batch": batch, "plans": P, "per_plan_group": a.per_plan_group or 16, "mixed_ms": round(1e3 * t_mixed, 3),
+        print(json.dumps({"batch": batch, "plans": P, "group": mixed_group, "mixed_groups": stats,
+                          "per_plan_group": a.per_plan_group or 16, "mixed_ms": round(1e3 * t_mixed, 3),
                           "per_plan_sum_ms": round(1e3 * sum(t_plan), 3),
                           "per_plan_ms": {names[p]: round(1e3 * t_plan[p], 3) for p in range(P)},
                           "mixed_stmts_per_s": round(batch / t_mixed), "per_plan_stmts_per_s": round(batch / sum(t_plan)),

@@ -123,10 +123,10 @@ struct zkgpu_ctx {
   Buffer grp_sc, grp_digits, grp_partials, grp_ok, row_map;
   Buffer grp_ws, grp_wf, grp_dyn;             // window sums of the groups, their flags, the groups' proof-point sums
   Buffer grp_fail, grp_fail_sum, rechk_pts;   // failed groups: list | located candidate, their sums S1; sums of the re-checked transactions
-  // the batch in flight, kept for the (never expected) ungrouped re-run when a located transaction does not explain its group
-  struct LastBatch { bool valid = false, has_prep = false; const zkgpu_pointset* ps = nullptr; std::vector<uint8_t> job, prep; } last;
+  // the batch in flight, kept for the (never expected) ungrouped re-run when a located transaction does not explain its group; mixed: a zkgpu_r1cs_verify_mixed call, with its groups of two or more and the statements in them
+  struct LastBatch { bool valid = false, has_prep = false; const zkgpu_pointset* ps = nullptr; std::vector<uint8_t> job, prep; bool mixed = false; uint64_t mx_groups = 0, mx_stmts = 0; } last;
   bool force_unresolved = false;   // test hook: take that re-run path
-  uint64_t regroup_fallbacks = 0;
+  uint64_t regroup_fallbacks = 0, mx_stats[4] = {0, 0, 0, 0};   // | zkgpu_debug_read "mixed_groups": the mixed call finished last
   int group_size = 16;             // transactions per group check (1 = every transaction on its own)
   bool serial = false;             // measurement aid: the whole DAG of a batch on one stream
   int horner_mode = 0;             // 0 automatic, 1 one chain per transaction, 2 one per group (+ the failed groups' transactions)
@@ -143,7 +143,7 @@ struct zkgpu_ctx {
   std::vector<zkgpu_ctx*> pv_slices;    // helper contexts (one stream each) on which the slices 1.. of a prover call run (run_sliced)
   std::vector<uint32_t> pv_plan_host;   // the tables pv_plan holds (compared before uploading again)
   size_t pv_lay_batch = 0;              // batch size the scaffolding in pv_lay was built for (0: none)
-  Buffer prep_absorb, prep_raw, mx_tab, mx_st_index, prep_large;    // cooperative transcript: absorbed words per segment, raw challenge bytes | zkgpu_r1cs_verify_mixed: per-call tables, generator index | large_prep.hpp's workspace
+  Buffer prep_absorb, prep_raw, mx_tab, mx_st_index, prep_large, mx_grp_index;    // cooperative transcript: absorbed words per segment, raw challenge bytes | zkgpu_r1cs_verify_mixed: per-call tables, generator index | large_prep.hpp's workspace
   int locate_mode = 0;             // failed groups: 0 automatic, 1 always re-check every transaction, 2 always locate the culprit
   int transcript_mode = 0;         // 0 automatic, 1 one lane per transaction, 2 one wavefront per transaction
   int forced_parts = 0;
@@ -890,7 +890,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
     memcpy(jb.data(), &job, sizeof(Job));
     if (prep) memcpy(pb.data(), prep, sizeof(PrepLaunch));
     c->last.job.swap(jb); c->last.prep.swap(pb);
-    c->last.ps = ps; c->last.has_prep = prep != nullptr; c->last.valid = true;
+    c->last.ps = ps; c->last.has_prep = prep != nullptr; c->last.valid = true; c->last.mixed = false;
   }
   const size_t B = job.n_msm;
   const size_t nbytes = (B + 7) / 8;
@@ -1226,12 +1226,12 @@ int pipe_wait(zkgpu_ctx* c, uint8_t* accept_bitmap) {
   const char* h = (const char*)c->pinned;
   uint32_t st;
   memcpy(&st, h + nbytes, 4);
-  if (c->group_size > 1) {             // failed groups steer the next batches' Horner arrangement (pipe_enqueue)
-    uint32_t n_fail;
-    memcpy(&n_fail, h + nbytes + 36, 4);
-    (c->parent ? c->parent : c)->last_failed_groups.store(n_fail);
-  }
-  if ((st & 4u) && c->last.valid && c->group_size > 1) {
+  uint32_t tail[2];                    // statements re-checked alone, failed groups (status words 8 and 9)
+  memcpy(tail, h + nbytes + 32, 8);
+  const bool mixed = c->last.mixed;    // a mixed call keeps counters of its own and stays out of what steers the next batches' Horner arrangement (pipe_enqueue)
+  if (mixed) { const uint64_t n[4] = {c->last.mx_groups, c->last.mx_stmts, tail[1], tail[0]}; memcpy(c->mx_stats, n, sizeof n); c->last.mixed = false; }
+  else if (c->group_size > 1) (c->parent ? c->parent : c)->last_failed_groups.store(tail[1]);
+  if (!mixed && (st & 4u) && c->last.valid && c->group_size > 1) {
     // a located transaction did not account for its group's sum (probability ~2^-248, or the test hook): verdicts
     // must not rest on it -- run the same batch again with every transaction checked on its own
     Job job;
@@ -3476,9 +3476,125 @@ int lp_prepare_homo(zkgpu_ctx* c, hipStream_t s, const PrepPlan& plan, uint32_t 
 // zkgpu_r1cs_verify_mixed*: statement i is checked against plans[plan_index[i]].  The host lays out a per-call table
 // (one PrepPlan per distinct plan, one MixStmt per statement) and one CSR of multiscalar-multiplication rows whose lengths
 // are the statements' own; the preparation is one launch per stage whatever the number of plans, and the rows go
-// through the same multiscalar-multiplication pipeline as zkgpu_verify_batch_ps_submit_dev.  Statements are checked
-// alone (no group checks): bit i is what a batch of that statement alone would give.
+// through the same multiscalar-multiplication pipeline as zkgpu_verify_batch_ps_submit_dev.
+//
+// Group checks (mixed_kernels.hpp, "group checks"): a statement's generator KEY is (padded n, generator capacity) of its
+// plan; the statements of one key, in the order (class, plan), are cut into checks of up to c->group_size members (a
+// remainder of one is a check of one), whatever their constraint systems.  When some check has two or more members the call
+// takes the launch sequence of mixed_group_tail; otherwise (group_size 1, one statement, no two statements of one key, a
+// point set without tables) every statement is checked alone by pipe_enqueue as before.  The sequence depends on the call
+// alone -- LDS classes present, whether such a check exists, the transcript form -- never on an earlier batch: one Horner
+// chain per statement always (the members' own sums are what a failed check's re-check needs), and the re-check launch
+// sized for every check failing.
 namespace {
+struct MixGroupTable {
+  uint32_t n_checks = 0, n_grouped = 0;      // checks of the call; statements in checks of two or more members
+  uint64_t n_rows = 0;                       // static terms over the checks' rows
+  const MixStmt* d_stmts = nullptr;
+  const MixGroup* d_groups = nullptr;
+  const uint32_t* d_members = nullptr;
+  const uint64_t* d_row_offsets = nullptr;
+  uint32_t max_ns = 0;
+};
+
+// Workspace of a grouped mixed call (before its first launch)
+int mixed_group_reserve(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const MixGroupTable& gt, int* Pg_out) {
+  const size_t B = job.n_msm;
+  const int W = ps->tbl_W;
+  const int Pg = (int)std::max<uint64_t>(1, std::min<uint64_t>(32, (65536 + (uint64_t)gt.n_checks * W - 1) / ((uint64_t)gt.n_checks * W)));
+  *Pg_out = Pg;
+  TRY(ensure(c, c->grp_digits, gt.n_rows * W * 2));
+  TRY(ensure(c, c->mx_grp_index, gt.n_rows * 4));
+  TRY(ensure(c, c->grp_partials, (size_t)gt.n_checks * W * Pg * EXT_WORDS * 4));
+  TRY(ensure(c, c->row_map, B * 4));
+  TRY(ensure(c, c->accept, B));
+  TRY(ensure(c, c->accept2, B));
+  TRY(ensure(c, c->bitmap, (B + 7) / 8));
+  TRY(ensure_pinned(c, (B + 7) / 8 + 64));
+  TRY(ensure(c, c->status, 64));
+  TRY(ensure(c, c->digits, std::max<uint64_t>(job.n_static, 1) * W * 2));
+  TRY(ensure(c, c->st_partials, (size_t)gt.n_grouped * TAIL_THREADS * EXT_WORDS * 4));
+  TRY(ensure(c, c->dynsum, B * EXT_WORDS * 4));
+  TRY(ensure(c, c->dyn_rows, std::max<uint64_t>(job.n_dyn, 1) * NIELS_WORDS * 4));
+  TRY(ensure(c, c->window_sums, B * 64 * EXT_WORDS * 4));
+  TRY(ensure(c, c->window_flags, B * 64 * 4));
+  TRY(ensure(c, c->msm_fail, B * 4));
+  TRY(ensure(c, c->small_tbl, std::max<uint64_t>(job.n_dyn, 1) * SMALL_TBL * EXT_WORDS * 4));
+  TRY(ensure(c, c->recoded, std::max<uint64_t>(job.n_dyn, 1) * 32));
+  c->last_w = 4;
+  return ZKGPU_OK;
+}
+
+// The rows of a grouped mixed call.  The light stream has run the preparation (c->ev_p is recorded behind it) and H1 the
+// decoding of the proof points (c->ev_dig: msm_fail is final):
+//     H2: k_mx_group_scalars -> k_static_accumulate (one row per check)
+//     H1: k_small_tables -> k_small_accumulate (every statement's own dynamic row)
+//     L:  k_msm_finish_quad (one chain per statement) -> k_mx_group_combine -> k_recheck_fused -> k_pack_bitmap
+int mixed_group_tail(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const MixGroupTable& gt, int Pg) {
+  const size_t B = job.n_msm, nbytes = (B + 7) / 8;
+  hipStream_t L = c->stream_l, H1 = c->serial ? L : c->stream, H2 = c->serial ? L : c->stream2;
+  const int W = ps->tbl_W;
+  uint32_t* n_recheck = (uint32_t*)((char*)c->status.p + 32);
+  uint32_t* n_fail = (uint32_t*)((char*)c->status.p + 36);
+  HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_p, 0));
+  HIP_TRY(c, hipStreamWaitEvent(H2, c->ev_p, 0));
+  HIP_TRY(c, hipStreamWaitEvent(H2, c->ev_dig, 0));
+  {
+    Launch l(c, "k_mx_group_scalars", H2);
+    hipLaunchKernelGGL(k_mx_group_scalars, dim3(gt.n_checks, blocks_for(gt.max_ns, 256)), dim3(256), 0, H2, gt.d_stmts, gt.d_groups,
+                       gt.d_members, job.d_st_scalars, job.d_st_index, (const uint32_t*)c->msm_fail.p, job.d_wellformed, gt.n_rows,
+                       (int16_t*)c->grp_digits.p, (uint32_t*)c->mx_grp_index.p, ps->tbl_w, W);
+  }
+  {
+    Launch l(c, "k_static_accumulate", H2);
+    hipLaunchKernelGGL(k_static_accumulate<false>, dim3(blocks_for((uint64_t)gt.n_checks * W * Pg, 256)), dim3(256), 0, H2,
+                       (const int16_t*)c->grp_digits.p, gt.d_row_offsets, (const uint32_t*)c->mx_grp_index.p,
+                       (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, W, Pg, gt.n_checks, gt.n_rows,
+                       (uint32_t*)c->grp_partials.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 1u);
+  }
+  HIP_TRY(c, hipEventRecord(c->ev_sa, H2));
+  TRY(small_msm_launch(c, job, H1));
+  HIP_TRY(c, hipEventRecord(c->ev_sm, H1));
+  HIP_TRY(c, hipStreamWaitEvent(L, c->ev_sm, 0));
+  {
+    Launch l(c, "k_msm_finish_quad", L);
+    hipLaunchKernelGGL(k_msm_finish_quad, dim3(blocks_for(4 * B, 256)), dim3(256), 0, L, (const uint32_t*)c->window_sums.p,
+                       (const uint32_t*)c->window_flags.p, (const uint32_t*)c->msm_fail.p, (uint8_t*)c->accept.p, (uint32_t*)nullptr,
+                       (uint32_t*)c->dynsum.p, (uint32_t)B, 4, 64, (const uint32_t*)nullptr, 0u);
+  }
+  HIP_TRY(c, hipStreamWaitEvent(L, c->ev_sa, 0));
+  {
+    Launch l(c, "k_mx_group_combine", L);
+    hipLaunchKernelGGL(k_mx_group_combine, dim3(gt.n_checks), dim3(256), 0, L, (const uint32_t*)c->grp_partials.p, (uint32_t)(W * Pg),
+                       (const uint32_t*)c->dynsum.p, (const uint32_t*)c->msm_fail.p, job.d_wellformed, gt.d_stmts, gt.d_groups,
+                       gt.d_members, job.d_st_scalars, job.n_static, (uint8_t*)c->accept2.p, n_fail, (uint32_t*)c->row_map.p,
+                       n_recheck, (int16_t*)c->digits.p, ps->tbl_w, W);
+  }
+  {
+    Launch l(c, "k_recheck_fused", L);     // sized for every check failing; workgroups past the device-side count leave at once
+    hipLaunchKernelGGL(k_recheck_fused, dim3(gt.n_grouped), dim3(TAIL_THREADS), 0, L, (const int16_t*)c->digits.p, job.d_st_offsets,
+                       job.d_st_index, (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, W, (uint64_t)job.n_static,
+                       (uint32_t*)c->st_partials.p, (const uint32_t*)c->dynsum.p, (const uint8_t*)c->accept.p,
+                       (const uint32_t*)c->row_map.p, (const uint32_t*)n_recheck, (uint8_t*)c->accept2.p, (uint32_t*)nullptr);
+  }
+  {
+    Launch l(c, "k_pack_bitmap", L);
+    hipLaunchKernelGGL(k_pack_bitmap, dim3(blocks_for(nbytes, 256)), dim3(256), 0, L, (const uint8_t*)c->accept2.p,
+                       job.d_wellformed, (uint8_t*)c->bitmap.p, (uint32_t)B);
+  }
+  HIP_TRY(c, hipGetLastError());
+  char* h = (char*)c->pinned;
+  HIP_TRY(c, hipMemcpyAsync(h, c->bitmap.p, nbytes, hipMemcpyDeviceToHost, L));
+  HIP_TRY(c, hipMemcpyAsync(h + nbytes, c->status.p, 48, hipMemcpyDeviceToHost, L));
+  HIP_TRY(c, hipEventRecord(c->ev_done, L));
+  c->pending = true;
+  c->pending_batch = B;
+  c->sync_result_valid = false;
+  c->last.valid = false;               // (nothing of this call is ever re-run by zkgpu_verify_wait)
+  c->last.mixed = false;
+  return ZKGPU_OK;
+}
+
 int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* const* plans, size_t n_plans, size_t batch,
                   const uint32_t* plan_index, const uint8_t* commitments, const uint8_t* proofs, const uint64_t* proof_offsets,
                   const uint8_t* r_bytes) {
@@ -3488,7 +3604,7 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
   if (!ps || ps->ctx->device != c->device) { c->last_error = "mixed verification: no point set, or one of another device"; return ZKGPU_EINVAL; }
   if (batch >= (1ull << 24)) { c->last_error = "mixed verification: batch of 2^24 statements or more"; return ZKGPU_EINVAL; }
   if (c->pending) { c->last_error = "a submitted batch is still waiting for zkgpu_verify_wait"; return ZKGPU_EINVAL; }
-  if (batch == 0) { park_sync_result(c, ZKGPU_OK, nullptr, 0); return ZKGPU_OK; }
+  if (batch == 0) { park_sync_result(c, ZKGPU_OK, nullptr, 0); memset(c->mx_stats, 0, sizeof c->mx_stats); return ZKGPU_OK; }
   if (!plans || n_plans == 0 || !plan_index || !commitments || !proofs || !proof_offsets) {
     c->last_error = "mixed verification: null plan list, plan index, commitments, proofs or offsets";
     return ZKGPU_EINVAL;
@@ -3558,12 +3674,58 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
         while (lane_order.size() % 64) lane_order.push_back(~0u);
     }
   }
-  // the table, laid out as the device reads it: plans | statements | order | lane order | row offsets (dynamic, static)
+  // the checks: statements in (class, plan) order, stably by generator key, each key's run cut into checks of group_size
+  uint64_t n_dyn_all = 0, n_st_all = 0;
+  for (uint32_t u = 0; u < U; ++u) { n_dyn_all += (uint64_t)count[u] * uniq[u]->dev.sh.n_dyn; n_st_all += (uint64_t)count[u] * uniq[u]->dev.sh.n_static; }
+  const bool piped = ps->table && n_st_all && n_dyn_all && !c->forced_w && n_dyn_all <= 128ull * B;      // (pipe_eligible of the job below)
+  std::vector<MixGroup> checks;
+  std::vector<uint32_t> members;
+  MixGroupTable gt;
+  if (piped && c->group_size > 1 && B > 1) {
+    std::vector<std::pair<uint32_t, uint32_t>> keys;      // (padded n, index of H_0)
+    std::vector<uint32_t> key_of(U);
+    for (uint32_t u : by_class) {
+      const std::pair<uint32_t, uint32_t> k(uniq[u]->dev.sh.pn, uniq[u]->dev.h_base);
+      size_t at = std::find(keys.begin(), keys.end(), k) - keys.begin();
+      if (at == keys.size()) keys.push_back(k);
+      key_of[u] = (uint32_t)at;
+    }
+    members = order;
+    std::stable_sort(members.begin(), members.end(), [&](uint32_t a, uint32_t b) { return key_of[pid[a]] < key_of[pid[b]]; });
+    const uint32_t gs = (uint32_t)c->group_size;
+    for (uint32_t i = 0; i < B;) {
+      const uint32_t key = key_of[pid[members[i]]];
+      uint32_t n = 1;
+      while (n < gs && i + n < B && key_of[pid[members[i + n]]] == key) ++n;
+      const uint32_t ns = uniq[pid[members[i]]]->dev.sh.n_static;
+      checks.push_back(MixGroup{i, n, ns, 0, gt.n_rows});
+      gt.n_rows += ns;
+      gt.max_ns = std::max(gt.max_ns, ns);
+      if (n >= 2) gt.n_grouped += n;
+      i += n;
+    }
+    if (gt.n_grouped == 0) { checks.clear(); members.clear(); gt = MixGroupTable{}; }
+    gt.n_checks = (uint32_t)checks.size();
+  }
+  const bool grouped = gt.n_checks != 0;
+  uint64_t n_groups2 = 0;
+  for (const MixGroup& g : checks) n_groups2 += g.count >= 2;
+  // the table, laid out as the device reads it: plans | statements | order | lane order | row offsets (dynamic, static) |
+  // checks | their members | row offsets of the checks
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t t_plans = 0, t_stmts = up(t_plans + U * sizeof(PrepPlan)), t_order = up(t_stmts + B * sizeof(MixStmt)),
                t_lanes = up(t_order + 4 * (size_t)B), t_doff = up(t_lanes + 4 * lane_order.size()),
-               t_soff = up(t_doff + 8 * ((size_t)B + 1)), t_end = t_soff + 8 * ((size_t)B + 1);
+               t_soff = up(t_doff + 8 * ((size_t)B + 1)), t_grp = up(t_soff + 8 * ((size_t)B + 1)),
+               t_mem = up(t_grp + checks.size() * sizeof(MixGroup)), t_goff = up(t_mem + 4 * members.size()),
+               t_end = t_goff + (grouped ? 8 * (checks.size() + 1) : 0);
   std::vector<char> tab(t_end);
+  if (grouped) {
+    memcpy(tab.data() + t_grp, checks.data(), checks.size() * sizeof(MixGroup));
+    memcpy(tab.data() + t_mem, members.data(), 4 * members.size());
+    uint64_t* goff = (uint64_t*)(tab.data() + t_goff);
+    for (size_t g = 0; g < checks.size(); ++g) goff[g] = checks[g].st;
+    goff[checks.size()] = gt.n_rows;
+  }
   PrepPlan* mp = (PrepPlan*)(tab.data() + t_plans);
   size_t max_nch = 0;
   for (uint32_t u = 0; u < U; ++u) {
@@ -3607,6 +3769,29 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
   TRY(stage_inputs(c, in));
   hipStream_t L = c->stream_l;
   const char* dt = (const char*)c->mx_tab.p;
+  Job job;
+  job.d_dyn_scalars = (const uint32_t*)c->prep_dyn_sc.p;
+  job.d_dyn_points = (const uint32_t*)c->prep_dyn_pt.p;
+  job.d_dyn_offsets = (const uint64_t*)(dt + t_doff);
+  job.n_dyn = n_dyn;
+  job.d_st_scalars = (const uint32_t*)c->prep_st_sc.p;
+  job.d_st_index = (const uint32_t*)c->mx_st_index.p;
+  job.d_st_offsets = (const uint64_t*)(dt + t_soff);
+  job.n_static = n_st;
+  job.d_static_rows = ps->rows;
+  job.n_msm = B;
+  job.d_wellformed = (const uint32_t*)c->prep_wf.p;      // folded into the accept bitmap on the device
+  int Pg = 1;
+  if (grouped) {
+    gt.d_stmts = (const MixStmt*)(dt + t_stmts);
+    gt.d_groups = (const MixGroup*)(dt + t_grp);
+    gt.d_members = (const uint32_t*)(dt + t_mem);
+    gt.d_row_offsets = (const uint64_t*)(dt + t_goff);
+    TRY(mixed_group_reserve(c, job, ps, gt, &Pg));
+    Launch l(c, "k_batch_init", L);
+    hipLaunchKernelGGL(k_batch_init, dim3(blocks_for(B, 256)), dim3(256), 0, L, (uint32_t*)c->status.p, (uint32_t*)c->msm_fail.p,
+                       (uint32_t*)nullptr, B);
+  }
   const PrepPlan* d_plans = (const PrepPlan*)(dt + t_plans);
   const MixStmt* d_stmts = (const MixStmt*)(dt + t_stmts);
   const uint32_t* d_order = (const uint32_t*)(dt + t_order);
@@ -3619,6 +3804,15 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     Launch l(c, "k_mx_proof_unpack", L);
     hipLaunchKernelGGL(k_mx_proof_unpack, dim3(B), dim3(256), 0, L, d_plans, d_stmts, d_order, (const uint8_t*)c->prep_proofs.p,
                        d_pw, d_wf);
+  }
+  auto gather_points = [&]() {
+    Launch l(c, "k_mx_gather_dyn_points", L);
+    hipLaunchKernelGGL(k_mx_gather_dyn_points, dim3(B), dim3(256), 0, L, d_plans, d_stmts, d_order, d_com, (const uint32_t*)d_pw,
+                       (uint32_t*)c->prep_dyn_pt.p);
+  };
+  if (grouped) {                      // the proof points need the proof bytes only: they are decoded beside the transcript
+    gather_points();
+    HIP_TRY(c, hipEventRecord(c->ev_u, L));
   }
   if (coop) {
     {
@@ -3634,12 +3828,18 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     {
       Launch l(c, "k_mx_challenges", L);
       hipLaunchKernelGGL(k_mx_challenges, dim3(B), dim3(128), max_nch * 32, L, d_plans, d_stmts, d_order,
-                         (const uint32_t*)c->prep_raw.p, (const uint32_t*)d_pw, d_r, d_ch, d_wf);
+                         (const uint32_t*)c->prep_raw.p, (const uint32_t*)d_pw, d_r, d_ch, d_wf, grouped ? 1u : 0u);
     }
   } else {
     Launch l(c, "k_mx_transcript", L);
     hipLaunchKernelGGL(k_mx_transcript, dim3((unsigned)(lane_order.size() / 64)), dim3(64), 0, L, d_plans, d_stmts,
-                       (const uint32_t*)(dt + t_lanes), d_com, (const uint32_t*)d_pw, d_r, d_ch, d_wf);
+                       (const uint32_t*)(dt + t_lanes), d_com, (const uint32_t*)d_pw, d_r, d_ch, d_wf, grouped ? 1u : 0u);
+  }
+  if (grouped) {                      // (queued behind the transcript's launches, as the homogeneous pipeline queues k_points_tables)
+    hipStream_t H1 = c->serial ? L : c->stream;
+    HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_u, 0));
+    decompress_launch(c, job, H1);
+    HIP_TRY(c, hipEventRecord(c->ev_dig, H1));      // msm_fail is final: the checks leave such statements out
   }
   {
     // (the attribute is the same for every call: LDS of a CU, the bound plan_finish_inner holds every plan to)
@@ -3657,29 +3857,26 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
                          (uint32_t*)c->prep_st_sc.p, (uint32_t*)c->mx_st_index.p};
     lp_launch_all(c, L, src, std::min(lp_slice(lp_slots), n_large - b0), lp_targets, lp_pn, lp_slots);
   }
-  {
-    Launch l(c, "k_mx_gather_dyn_points", L);
-    hipLaunchKernelGGL(k_mx_gather_dyn_points, dim3(B), dim3(256), 0, L, d_plans, d_stmts, d_order, d_com, (const uint32_t*)d_pw,
-                       (uint32_t*)c->prep_dyn_pt.p);
+  if (grouped) {
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_p, L));
+    TRY(mixed_group_tail(c, job, ps, gt, Pg));
+    c->last.mixed = true; c->last.mx_groups = n_groups2; c->last.mx_stmts = gt.n_grouped;       // (counted when the call is waited for)
+    return ZKGPU_OK;
   }
+  gather_points();
   HIP_TRY(c, hipGetLastError());
-  Job job;
-  job.d_dyn_scalars = (const uint32_t*)c->prep_dyn_sc.p;
-  job.d_dyn_points = (const uint32_t*)c->prep_dyn_pt.p;
-  job.d_dyn_offsets = (const uint64_t*)(dt + t_doff);
-  job.n_dyn = n_dyn;
-  job.d_st_scalars = (const uint32_t*)c->prep_st_sc.p;
-  job.d_st_index = (const uint32_t*)c->mx_st_index.p;
-  job.d_st_offsets = (const uint64_t*)(dt + t_soff);
-  job.n_static = n_st;
-  job.d_static_rows = ps->rows;
-  job.n_msm = B;
-  job.d_wellformed = d_wf;                  // folded into the accept bitmap on the device
   // (the pipeline's first launch follows the preparation on the light stream; its other streams wait for that)
-  if (pipe_eligible(c, job, ps)) return pipe_enqueue(c, job, ps, nullptr);
+  if (piped) {
+    TRY(pipe_enqueue(c, job, ps, nullptr));
+    c->last.mixed = true; c->last.mx_groups = c->last.mx_stmts = 0;
+    return ZKGPU_OK;
+  }
   // general shapes (no generator tables, forced window width): synchronous, as cloak_verify_gpu_enqueue
   HIP_TRY(c, hipStreamSynchronize(L));
-  return run_sync_and_park(c, job, ps);
+  TRY(run_sync_and_park(c, job, ps));
+  memset(c->mx_stats, 0, sizeof c->mx_stats);        // (the call has run: no groups on this route)
+  return ZKGPU_OK;
 }
 }  // namespace
 
@@ -3710,6 +3907,12 @@ int zkgpu_r1cs_verify_mixed(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_
 // Test hook zkgpu_debug_read: the context's DECODE counters, or an intermediate buffer (debug_read_buffers)
 long long zkgpu_debug_read(zkgpu_ctx* c, const char* what, void* out, size_t bytes) {
   if (!c || !what || !out) return ZKGPU_EINVAL;
+  if (strcmp(what, "mixed_groups") == 0) {     // the mixed call finished last on this context: checks of two or more members,
+    if (bytes < sizeof(c->mx_stats)) return ZKGPU_EINVAL;      // statements in them, such checks that failed, statements re-checked alone
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    memcpy(out, c->mx_stats, sizeof(c->mx_stats));
+    return (long long)sizeof(c->mx_stats);
+  }
   if (strcmp(what, "decode_routes") != 0) return debug_read_buffers(c, what, out, bytes);
   if (bytes < sizeof(c->decode_routes.n)) return ZKGPU_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(c->mu);

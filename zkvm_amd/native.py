@@ -357,6 +357,11 @@ class Context:
         """zkgpu_debug_read "decode_routes" -> (one-kernel DECODE launches, their points, split DECODE launches, their points)"""
         return struct.unpack("<4Q", self.debug_read("decode_routes", 32))
 
+    def mixed_group_stats(self) -> Tuple[int, int, int, int]:
+        """zkgpu_debug_read "mixed_groups": the mixed call finished last on this context -> (groups of two or more
+        statements, statements in them, groups that failed, statements re-checked alone because their group failed)"""
+        return struct.unpack("<4Q", self.debug_read("mixed_groups", 32))
+
     def set_prover_mode(self, mode: int) -> None:
         """zkgpu_set_prover_mode: 0 the whole proof on the device, 1 host threads in lockstep, 16 + S: on the device in S slices."""
         self._check(self.lib.zkgpu_set_prover_mode(self.h, mode))
