@@ -540,8 +540,30 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * (its loops on the library's worker pool, `host_threads` wide) and the calling thread, which only talks to the device.
  * The verifier keeps what the VM leaves per transaction (700 bytes) between calls, for at most
  * zkgpu_verifier_set_tx_statements_kept transactions (default 131 072, i.e. 90 MB; what a longer call needs beyond
- * that is allocated for the call). */
+ * that is allocated for the call).
+ * WHY a transaction was rejected (upstream's Tx::verify returns Result<VerifiedTx, VMError>): format
+ * ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS reads the same bytes, launches the same checks and gives the same accept bitmap
+ * as ZKGPU_TXFORMAT_RECOLLECTED_V1; only the status bytes differ.  0 still stands beside a set bit and nowhere else, 2
+ * still means outside the subset; a rejected transaction reads ONE of the codes 16 .. 21 below -- the LOWEST that applies,
+ * which is the order upstream would meet the faults in (decoding and the VM, then r1cs::Verifier::verify, then the
+ * deferred signature check) -- whatever the size of the call, its chunks, the device's group checks or the round
+ * zkgpu_tx_verify_submit merged it into.  The proof codes come from the device: the flags that tell a malformed proof,
+ * an undecodable point and a failed equation apart are read there once the batch's bitmap is final, and travel back
+ * beside it.  (One exception to "lowest": a signature scalar s that is not canonical is found by the VM on the host,
+ * before any proof is looked at, and reads 21.)  Fail-closed: on any error every transaction inside the subset reads
+ * ZKGPU_TXSTATUS_REJECTED -- never a reason, never 0 -- and the bitmap is zero.  With format 1 nothing changes.
+ * The mapping to upstream's VMError variants is a recollection like the format itself. */
 #define ZKGPU_TXFORMAT_RECOLLECTED_V1 1
+#define ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS 2   /* same wire format as ..._V1; status bytes carry a reason */
+#define ZKGPU_TXSTATUS_ACCEPTED 0
+#define ZKGPU_TXSTATUS_REJECTED 1                 /* rejected, reason not available (V1 format, or any error path) */
+#define ZKGPU_TXSTATUS_OUTSIDE_SUBSET 2
+#define ZKGPU_TXSTATUS_TX_INVALID 16              /* the transaction itself: wire format, time bounds, program / VM error (host) */
+#define ZKGPU_TXSTATUS_PROOF_FORMAT 17            /* R1CSProof malformed: length, version byte, non-canonical scalar, forbidden identity */
+#define ZKGPU_TXSTATUS_PROOF_POINT 18             /* a commitment or proof point is not a ristretto255 encoding */
+#define ZKGPU_TXSTATUS_PROOF_EQUATION 19          /* well-formed, every point decodes, verification equation fails */
+#define ZKGPU_TXSTATUS_KEY 20                     /* a verification key the signature must cover does not decode */
+#define ZKGPU_TXSTATUS_SIGNATURE 21               /* R undecodable, s non-canonical, or s B != R + c X */
 int zkgpu_verifier_set_tx_format(zkgpu_verifier *v, int format);
 int zkgpu_verifier_set_tx_chunk(zkgpu_verifier *v, size_t transactions);
 int zkgpu_verifier_set_tx_statements_kept(zkgpu_verifier *v, size_t transactions);

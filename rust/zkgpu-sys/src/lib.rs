@@ -22,6 +22,16 @@ pub const ZKGPU_HINT_APPLY: c_int = 0;
 pub const ZKGPU_HINT_PRESENT: c_int = 1;
 pub const ZKGPU_HINT_LATE: c_int = 2;
 pub const ZKGPU_TXFORMAT_RECOLLECTED_V1: c_int = 1;
+pub const ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS: c_int = 2;
+pub const ZKGPU_TXSTATUS_ACCEPTED: c_int = 0;
+pub const ZKGPU_TXSTATUS_REJECTED: c_int = 1;
+pub const ZKGPU_TXSTATUS_OUTSIDE_SUBSET: c_int = 2;
+pub const ZKGPU_TXSTATUS_TX_INVALID: c_int = 16;
+pub const ZKGPU_TXSTATUS_PROOF_FORMAT: c_int = 17;
+pub const ZKGPU_TXSTATUS_PROOF_POINT: c_int = 18;
+pub const ZKGPU_TXSTATUS_PROOF_EQUATION: c_int = 19;
+pub const ZKGPU_TXSTATUS_KEY: c_int = 20;
+pub const ZKGPU_TXSTATUS_SIGNATURE: c_int = 21;
 pub const ZKGPU_COMM_ID_BYTES: usize = 128;
 
 #[repr(C)]

@@ -99,10 +99,58 @@ pub struct CloakStatement<'a> {
 pub enum TxVerdict {
     /// transaction ID, signature and cloak proof hold
     Accepted,
-    /// the reference's `Err`
+    /// the reference's `Err`, reason not known: the plain format, or any error path
     Rejected,
+    /// the reference's `Err` and which check failed (`enable_recollected_tx_format_with_reasons`)
+    RejectedBecause(TxReject),
     /// the transaction uses more of the VM than the payment subset: run it through `Tx::verify` on the CPU
     OutsideSubset,
+}
+
+/// Why a transaction was rejected: the status byte of the transaction calls under `ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS`,
+/// the LOWEST code that applies -- the order upstream's `Tx::verify` would meet the faults in.  The mapping to `VMError`
+/// is a recollection: `TxInvalid` ~ `FormatError` and the VM's own variants, the three `Proof*` ~
+/// `InvalidR1CSProof`, `Key` ~ `InvalidPoint`, `Signature` ~ the musig error of the deferred signature check.
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub enum TxReject {
+    /// the transaction itself: wire format, time bounds, a program or VM error
+    TxInvalid,
+    /// `R1CSProof` malformed: length, version byte, a scalar that is not canonical, an identity upstream forbids
+    ProofFormat,
+    /// a commitment or proof point is not a ristretto255 encoding
+    ProofPoint,
+    /// well-formed, every point decodes, the verification equation fails
+    ProofEquation,
+    /// a verification key the signature must cover does not decode
+    Key,
+    /// R does not decode, s is not canonical, or s B != R + c X
+    Signature,
+}
+
+impl TxReject {
+    /// the status byte (`ZKGPU_TXSTATUS_*`) -> the reason; `None` for 0, 1, 2 and bytes this version does not know
+    pub fn from_status(status: u8) -> Option<TxReject> {
+        match status as c_int {
+            sys::ZKGPU_TXSTATUS_TX_INVALID => Some(TxReject::TxInvalid),
+            sys::ZKGPU_TXSTATUS_PROOF_FORMAT => Some(TxReject::ProofFormat),
+            sys::ZKGPU_TXSTATUS_PROOF_POINT => Some(TxReject::ProofPoint),
+            sys::ZKGPU_TXSTATUS_PROOF_EQUATION => Some(TxReject::ProofEquation),
+            sys::ZKGPU_TXSTATUS_KEY => Some(TxReject::Key),
+            sys::ZKGPU_TXSTATUS_SIGNATURE => Some(TxReject::Signature),
+            _ => None,
+        }
+    }
+}
+
+/// one status byte and its accept bit -> the verdict (a status of "accepted" without its bit cannot happen; it would be a
+/// rejection)
+fn tx_verdict(status: u8, bit: u8) -> TxVerdict {
+    match (status as c_int, bit) {
+        (sys::ZKGPU_TXSTATUS_ACCEPTED, 1) => TxVerdict::Accepted,
+        (sys::ZKGPU_TXSTATUS_OUTSIDE_SUBSET, _) => TxVerdict::OutsideSubset,
+        (sys::ZKGPU_TXSTATUS_REJECTED, _) | (sys::ZKGPU_TXSTATUS_ACCEPTED, _) => TxVerdict::Rejected,
+        _ => TxReject::from_status(status).map_or(TxVerdict::Rejected, TxVerdict::RejectedBecause),
+    }
 }
 
 /// A batch queued with `submit`; redeemed exactly once with `wait`.
@@ -290,6 +338,13 @@ impl GpuVerifier {
         check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, sys::ZKGPU_TXFORMAT_RECOLLECTED_V1) }, self.err())
     }
 
+    /// The same format, and every rejected transaction says why: `verify_txs` and `wait_txs` then return
+    /// `TxVerdict::RejectedBecause(TxReject)` instead of `Rejected` (which remains what an error path leaves).  Same bytes
+    /// read, same accept / reject decisions.
+    pub fn enable_recollected_tx_format_with_reasons(&self) -> Result<(), Error> {
+        check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS) }, self.err())
+    }
+
     /// Drop-in for `txs.iter().map(|tx| tx.verify(bp_gens))` on `Tx::encode()` bytes (payment subset): VM, transaction
     /// ID, MuSig / Schnorr signature and cloak proof.  `host_threads`: 0 = the CPUs the process may keep busy.
     pub fn verify_txs(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<TxVerdict>, Error> {
@@ -312,13 +367,7 @@ impl GpuVerifier {
             },
             self.err(),
         )?;
-        Ok((0..n)
-            .map(|i| match (status[i], (bitmap[i / 8] >> (i % 8)) & 1) {
-                (0, 1) => TxVerdict::Accepted,
-                (2, _) => TxVerdict::OutsideSubset,
-                _ => TxVerdict::Rejected, // (status 0 without its accept bit cannot happen; it would be a rejection)
-            })
-            .collect())
+        Ok((0..n).map(|i| tx_verdict(status[i], (bitmap[i / 8] >> (i % 8)) & 1)).collect())
     }
 
     /// `verify_txs` in two halves, callable from many threads at once (upstream's `Tx::verify` is pure and `&self`): the
@@ -353,13 +402,7 @@ impl GpuVerifier {
         let rc = unsafe { sys::zkgpu_tx_verify_wait(self.v, call.id, bitmap.as_mut_ptr(), status.as_mut_ptr()) };
         call.waited = true; // (whatever it returned, the library is done with the call's bytes)
         check(rc, self.err())?;
-        Ok((0..n)
-            .map(|i| match (status[i], (bitmap[i / 8] >> (i % 8)) & 1) {
-                (0, 1) => TxVerdict::Accepted,
-                (2, _) => TxVerdict::OutsideSubset,
-                _ => TxVerdict::Rejected,
-            })
-            .collect())
+        Ok((0..n).map(|i| tx_verdict(status[i], (bitmap[i / 8] >> (i % 8)) & 1)).collect())
     }
 
     /// Transactions per merged device batch (default 4096; the MI355X bench uses 10 240).

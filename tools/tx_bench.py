@@ -1,5 +1,5 @@
 """zkgpu_tx_verify_batch on the committed 1024 transactions (per-stage times with ZKGPU_PROVER_TIMING=1).
-usage: tx_bench.py [copies of the fixture per call] [block chunk] [tx chunk]"""
+usage: tx_bench.py [copies of the fixture per call] [block chunk] [tx chunk]   (TX_BENCH_FORMAT=2: the format with reason codes)"""
 import os as _os; _os.environ.setdefault("ZKGPU_TEST_HOOKS", "1")   # the profile / mode hooks (include/zkgpu_hooks.h) are not exports
 import ctypes as C
 import os, sys, time
@@ -15,7 +15,7 @@ ctx = Context(0)
 gens = BulletproofGens(ctx, 256, table_bits=16)
 chunk = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 bv = BlockVerifier(ctx, gens, chunk=chunk)
-bv.set_tx_format(bv.TXFORMAT_RECOLLECTED_V1)
+bv.set_tx_format(int(os.environ.get("TX_BENCH_FORMAT", bv.TXFORMAT_RECOLLECTED_V1)))     # TX_BENCH_FORMAT=2: status bytes with reasons
 if len(sys.argv) > 3:
     bv.set_tx_chunk(int(sys.argv[3]))
 HT = int(sys.argv[4]) if len(sys.argv) > 4 else 0

@@ -949,7 +949,7 @@ class HostTxDevice : public TxDevice {
     return 0;
   }
   bool keys_done(int slot) override { return keys_[slot].done; }
-  int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values) override {
+  int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values, uint8_t*) override {     // (a device without reasons: `why` is ignored)
     Stage& s = keys_[slot];
     if (!s.th.joinable()) { err_ = "nothing to collect in this key slot"; return -1; }
     s.th.join();
@@ -991,7 +991,7 @@ class HostTxDevice : public TxDevice {
     return 0;
   }
   bool proofs_done(void* handle) override { return ((Proofs*)handle)->done; }
-  int proofs_finish(void* handle, uint8_t* accept_bits) override {
+  int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t*) override {
     Proofs* p = (Proofs*)handle;
     if (p->th.joinable()) p->th.join();
     const bool fail = failing();
@@ -1034,7 +1034,7 @@ class HostTxDevice : public TxDevice {
     return 0;
   }
   bool sigs_done(int slot) override { return sigs_[slot].done; }
-  int sigs_collect(int slot, uint8_t* bits) override {
+  int sigs_collect(int slot, uint8_t* bits, uint8_t*) override {
     Stage& s = sigs_[slot];
     if (!s.th.joinable()) { err_ = "nothing to collect in this signature slot"; return -1; }
     s.th.join();

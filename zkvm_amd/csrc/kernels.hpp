@@ -2057,3 +2057,5 @@ k_pack_bitmap_groups(const uint8_t* __restrict__ accept, const uint32_t* __restr
 }
 
 }  // namespace zk
+
+#include "tx_reason_kernels.hpp"   // (reason bytes of a format-2 transaction call: queued for nothing else)

@@ -34,6 +34,8 @@ struct zkgpu_request {                 // one submitted batch (zkgpu_verifier_su
   size_t group = 0, off = 0;
   hipEvent_t ready = nullptr;
   std::vector<uint8_t> bits;
+  bool reasons = false;                // a batch of a format-2 transaction call: it also wants to know WHY (tx_reason_kernels.hpp)
+  std::vector<uint8_t> why;            // ... one ZKGPU_TXSTATUS_* byte per statement, beside `bits`
 };
 
 // Tickets from HOST memory (zkgpu_verifier_submit): a device batch is FORMED in pinned host memory -- every ticket's
@@ -89,11 +91,14 @@ struct zkgpu_verifier {
     std::vector<zkgpu_request*> reqs;                   // those batches (the run owns them until they are collected)
     int rc = 0;
     uint64_t id = 0;
+    bool reasons = false;                               // the block of a format-2 transaction call: reason bytes gathered beside the bits
+    std::vector<uint8_t> why;                           // by position in the block; a group no plan serves keeps PROOF_FORMAT
   };
   std::map<uint64_t, std::unique_ptr<BlockRun>> block_runs;
   uint64_t next_run = 1;
   int lanes_requested = 0, lanes_dropped = 0;           // lanes whose light stream shared a hardware queue with an earlier lane's were not kept
-  int tx_format = 0;                                    // zkgpu_verifier_set_tx_format: 0 = no serialized-transaction format enabled
+  int tx_format = 0;                                    // zkgpu_verifier_set_tx_format: 0 = no serialized-transaction format enabled;
+                                                        // 1 and 2 read the same bytes, 2 writes a reason into the status bytes
   // zkgpu_tx_verify_batch: two contexts of their own for the key and the signature stages (each a pair of streams beside
   // the lanes'), and a ring of staging areas (pinned host + device, grow-only) for the cloak statements of the chunks in
   // flight -- nothing on that path allocates or frees device memory once the sizes have been seen (hipFree synchronises)
@@ -674,13 +679,15 @@ namespace {
 // target says (a block somebody is about to wait for); otherwise the requests wait -- for requests of the same shape from
 // the next blocks, until the merge target is reached -- and block_finish forces them out.
 // nullptr: out of host memory while queueing (nothing of the block is left queued; v->last_error says so).
-zkgpu_verifier::BlockRun* block_start(zkgpu_verifier* v, const zkgpu_txblock* b, bool now) {
+zkgpu_verifier::BlockRun* block_start(zkgpu_verifier* v, const zkgpu_txblock* b, bool now, bool reasons = false) {
   zkgpu_verifier::BlockRun* run = nullptr;
   try {
     std::unique_ptr<zkgpu_verifier::BlockRun> owned(new zkgpu_verifier::BlockRun());
     run = owned.get();
     run->b = b;
     run->bits.assign((b->batch + 7) / 8, 0);
+    run->reasons = reasons;
+    if (reasons) run->why.assign(b->batch, (uint8_t)ZKGPU_TXSTATUS_PROOF_FORMAT);   // (what a shape or proof length no plan serves reads)
     run->id = v->next_run++;
     v->block_runs[run->id] = std::move(owned);
     for (size_t gi = 0; gi < b->groups.size(); ++gi) {
@@ -695,7 +702,7 @@ zkgpu_verifier::BlockRun* block_start(zkgpu_verifier* v, const zkgpu_txblock* b,
         r->d_com = b->dev + g.com_off + off * wcom;
         r->d_proofs = b->dev + g.proof_off + off * g.proof_len;
         r->d_r = b->dev + g.r_off + off * 64;
-        r->run = run; r->group = gi; r->off = off; r->ready = b->ready;
+        r->run = run; r->group = gi; r->off = off; r->ready = b->ready; r->reasons = reasons;
         run->reqs.reserve(run->reqs.size() + 1);
         v->queue.push_back(r.get());
         run->reqs.push_back(r.release());                 // (cannot throw: reserved)
@@ -728,7 +735,7 @@ bool block_done(zkgpu_verifier* v, zkgpu_verifier::BlockRun* run) {
 }
 
 // waits for the block's batches (always all of them: nothing of the run is left queued or on a lane after an error); v->mu held
-int block_finish(zkgpu_verifier* v, zkgpu_verifier::BlockRun* run, uint8_t* accept_bitmap) {
+int block_finish(zkgpu_verifier* v, zkgpu_verifier::BlockRun* run, uint8_t* accept_bitmap, uint8_t* why = nullptr) {
   while (run->pending) {
     zkgpu_request* r = run->reqs.back();                // (collected requests leave the list: see ticket_collect)
     if (r->state == 0) (void)ticket_dispatch(v, true);  // everything that is queued goes out, merged by shape across blocks
@@ -737,6 +744,9 @@ int block_finish(zkgpu_verifier* v, zkgpu_verifier::BlockRun* run, uint8_t* acce
   const int rc = run->rc;
   const size_t nbytes = (run->b->batch + 7) / 8;
   if (rc == ZKGPU_OK) memcpy(accept_bitmap, run->bits.data(), nbytes); else memset(accept_bitmap, 0, nbytes);
+  if (why) {                                             // (an error is never a reason: the caller then reads "rejected" alone)
+    if (rc == ZKGPU_OK && run->reasons) memcpy(why, run->why.data(), run->b->batch); else memset(why, ZKGPU_TXSTATUS_REJECTED, run->b->batch);
+  }
   v->block_runs.erase(run->id);
   return rc;
 }
@@ -748,6 +758,8 @@ void block_request_done(zkgpu_verifier* v, zkgpu_request* r) {
     const auto& idx = run->b->groups[r->group].idx;
     for (size_t j = 0; j < r->batch; ++j)
       if ((r->bits[j / 8] >> (j % 8)) & 1) { const uint32_t i = idx[r->off + j]; run->bits[i / 8] |= (uint8_t)(1u << (i % 8)); }
+    if (run->reasons && r->why.size() == r->batch)
+      for (size_t j = 0; j < r->batch; ++j) run->why[idx[r->off + j]] = r->why[j];
   } else if (run->rc == ZKGPU_OK) {
     run->rc = r->rc;
   }
@@ -815,6 +827,68 @@ int zkgpu_verifier_verify(zkgpu_verifier* v, size_t batch, const uint32_t* n_in,
 // has no counterpart.)  The inputs must stay valid until the ticket has been waited for.
 namespace {
 
+// ---- reason bytes (tx_reason_kernels.hpp) ---------------------------------------------------------------------------------
+// Queued behind a whole-proof batch's bitmap fold on the same stream, by pipe_enqueue, when the context was asked for them
+// (zkgpu_ctx::want_reasons: set by ticket_dispatch for a device batch that holds a format-2 transaction call's statements):
+// one launch and one copy to the pinned result buffer, behind the bitmap's -- the event the collector waits for covers both.
+static_assert(TXR_ACCEPTED == ZKGPU_TXSTATUS_ACCEPTED && TXR_REJECTED == ZKGPU_TXSTATUS_REJECTED && TXR_TX_INVALID == ZKGPU_TXSTATUS_TX_INVALID &&
+              TXR_PROOF_FORMAT == ZKGPU_TXSTATUS_PROOF_FORMAT && TXR_PROOF_POINT == ZKGPU_TXSTATUS_PROOF_POINT &&
+              TXR_PROOF_EQUATION == ZKGPU_TXSTATUS_PROOF_EQUATION && TXR_KEY == ZKGPU_TXSTATUS_KEY && TXR_SIGNATURE == ZKGPU_TXSTATUS_SIGNATURE,
+              "tx_reason_kernels.hpp restates the status codes of zkgpu.h");
+
+int tx_reasons_launch(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, hipStream_t st) {
+  TRY(ensure(c, c->tx_reason, B));
+  {
+    Launch l(c, "k_tx_reason_proofs", st);
+    hipLaunchKernelGGL(k_tx_reason_proofs, dim3(blocks_for(B, 256)), dim3(256), 0, st, d_wellformed, (const uint32_t*)c->msm_fail.p,
+                       (const uint8_t*)c->bitmap.p, (uint32_t)B, (uint8_t*)c->tx_reason.p);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return ZKGPU_OK;
+}
+
+int tx_reasons_enqueue(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, hipStream_t st, char* h_out) {
+  c->reasons_src = 0;
+  TRY(tx_reasons_launch(c, d_wellformed, B, st));
+  HIP_TRY(c, hipMemcpyAsync(h_out, c->tx_reason.p, B, hipMemcpyDeviceToHost, st));
+  c->reasons_src = 1;
+  return ZKGPU_OK;
+}
+
+// a batch the pipeline does not cover has just run synchronously and its bitmap is parked (rc: what that gave): the flags
+// it left are final, and so the reasons are read here and now and parked beside the bitmap
+int tx_reasons_parked(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, int rc) {
+  c->reasons_src = 0;
+  if (rc != ZKGPU_OK || !c->want_reasons || !c->sync_result_valid || c->sync_rc != ZKGPU_OK) return rc;
+  auto fetch = [&]() -> int {
+    TRY(tx_reasons_launch(c, d_wellformed, B, c->stream));
+    c->sync_reasons.assign(B, (uint8_t)ZKGPU_TXSTATUS_REJECTED);
+    HIP_TRY(c, hipMemcpyAsync(c->sync_reasons.data(), c->tx_reason.p, B, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return ZKGPU_OK;
+  };
+  const int frc = fetch();
+  if (frc != ZKGPU_OK) { c->pending = false; c->sync_result_valid = false; return frc; }     // (nothing is parked: the submit failed)
+  c->reasons_src = 2;
+  return ZKGPU_OK;
+}
+
+// the reason bytes of the batch zkgpu_verify_wait has just collected on this context (bitmap: what it gave); the context
+// forgets that it was asked.  A batch that never reached the device (a proof length no plan serves: every bit is zero)
+// reads PROOF_FORMAT; a byte that disagrees with its bit is never handed on: "rejected" alone.
+void tx_reasons_take(zkgpu_ctx* c, size_t B, const uint8_t* bitmap, uint8_t* out) {
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  const int src = c->reasons_src;
+  c->reasons_src = 0; c->want_reasons = false;
+  if (src == 1) memcpy(out, (const char*)c->pinned + (B + 7) / 8 + 64, B);
+  else if (src == 2 && c->sync_reasons.size() == B) memcpy(out, c->sync_reasons.data(), B);
+  else memset(out, ZKGPU_TXSTATUS_PROOF_FORMAT, B);
+  for (size_t i = 0; i < B; ++i) {
+    const bool bit = (bitmap[i / 8] >> (i % 8)) & 1;
+    if (bit != (out[i] == ZKGPU_TXSTATUS_ACCEPTED)) out[i] = bit ? ZKGPU_TXSTATUS_ACCEPTED : ZKGPU_TXSTATUS_REJECTED;
+  }
+}
+
 void ticket_collect(zkgpu_verifier* v, int lane) {       // v->mu held
   std::vector<zkgpu_request*> members;
   members.swap(v->running[(size_t)lane]);
@@ -825,6 +899,10 @@ void ticket_collect(zkgpu_verifier* v, int lane) {       // v->mu held
   std::vector<uint8_t> big((total + 7) / 8, 0);
   const int rc = zkgpu_verify_wait(v->lanes[(size_t)lane], big.data());
   if (rc != ZKGPU_OK) v->last_error = zkgpu_last_error(v->lanes[(size_t)lane]);
+  std::vector<uint8_t> big_why;                          // (only for a device batch that holds statements of a format-2 transaction call)
+  for (auto* r : members) if (r->reasons) { big_why.assign(total, (uint8_t)ZKGPU_TXSTATUS_REJECTED); break; }
+  if (!big_why.empty() && rc == ZKGPU_OK) tx_reasons_take(v->lanes[(size_t)lane], total, big.data(), big_why.data());
+  { zkgpu_ctx* L = v->lanes[(size_t)lane]; std::lock_guard<std::recursive_mutex> lk(L->mu); L->want_reasons = false; L->reasons_src = 0; }
   if ((size_t)lane < v->lane_stage.size() && v->lane_stage[(size_t)lane] >= 0) {      // a batch formed from host memory: its twin is free
     v->host_stages[(size_t)v->lane_stage[(size_t)lane]].taken = false;
     v->lane_stage[(size_t)lane] = -1;
@@ -836,6 +914,7 @@ void ticket_collect(zkgpu_verifier* v, int lane) {       // v->mu held
         const size_t b = r->bit_off + i;
         if ((big[b / 8] >> (b % 8)) & 1) r->bits[i / 8] |= (uint8_t)(1u << (i % 8));
       }
+    if (r->reasons) r->why.assign(big_why.begin() + (long)r->bit_off, big_why.begin() + (long)(r->bit_off + r->batch));
     r->rc = rc;
     r->state = 2;
     if (r->run) block_request_done(v, r);                // (a block's batch: its verdicts go to the block's run)
@@ -867,7 +946,7 @@ int ticket_dispatch(zkgpu_verifier* v, bool force) {       // v->mu held
         { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_BACK; }
         rc = zkgpu_cloak_verify_submit_dev(L, v->ps, f.plan, f.total, f.com, f.proofs, f.proof_len, f.r);
       }
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; L->awaiting_back = false; }
+      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; L->awaiting_back = false; if (rc != ZKGPU_OK) L->want_reasons = false; }
       if (rc != ZKGPU_OK) {
         // the back half could not be queued (a launch failed): what the front half queued is waited for, and the batch's
         // requests fail with the error -- nothing is left in flight on the lane
@@ -986,9 +1065,11 @@ int ticket_dispatch(zkgpu_verifier* v, bool force) {       // v->mu held
     }
     bool front_only = false;
     if (rc == ZKGPU_OK && plan) {
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_FRONT; L->awaiting_back = false; }
+      bool why = false;                                   // statements of a format-2 transaction call among them: the batch also says why
+      for (zkgpu_request* r : pick) why = why || r->reasons;
+      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_FRONT; L->awaiting_back = false; L->want_reasons = why; L->reasons_src = 0; }
       rc = zkgpu_cloak_verify_submit_dev(L, v->ps, plan, total, p_com, p_proofs, head->proof_len, p_r);
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; front_only = rc == ZKGPU_OK && L->awaiting_back; }
+      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; front_only = rc == ZKGPU_OK && L->awaiting_back; if (rc != ZKGPU_OK) L->want_reasons = false; }
       if (front_only) fronts.push_back(Front{lane, plan, total, head->proof_len, p_com, p_proofs, p_r});
     }
     size_t off = 0;
@@ -1532,7 +1613,7 @@ int zkgpu_verifier_verify_sharded(zkgpu_verifier* v, zkgpu_comm* cm, size_t batc
 // (the verdicts stay with their tickets / runs) -- a synchronous call on a context with a batch in flight would
 // overwrite that batch's status words and pinned result buffer (and is refused by the context: refuse_if_pending).
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
-  if (!v || (format != 0 && format != ZKGPU_TXFORMAT_RECOLLECTED_V1)) return ZKGPU_EINVAL;
+  if (!v || (format != 0 && format != ZKGPU_TXFORMAT_RECOLLECTED_V1 && format != ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS)) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> lk(v->mu);
   v->tx_format = format;
   return ZKGPU_OK;
@@ -1568,6 +1649,50 @@ int split_collect(zkgpu_ctx* c, uint8_t* bitmap, uint8_t* values) {
   DeviceGuard g(c->device);
   c->pending = false;
   return batch_collect(c, bitmap, values);
+}
+
+// Reason bytes of a key or signature stage (tx_reason_kernels.hpp: k_tx_reason_stage), in two halves like the stage itself.
+// They lie behind everything else the stage copies to the context's pinned result buffer -- bitmap | 64 status bytes | the
+// values of a key stage -- so the buffer is brought to size BEFORE the stage is queued (it never shrinks, and the context is
+// idle then); the kernel and its copy are queued behind the stage's own on the same stream, and the one wait of
+// batch_collect covers them.
+size_t stage_reasons_offset(size_t batch, bool values) { return (batch + 7) / 8 + 64 + (values ? 32 * batch : 0); }
+int stage_reasons_reserve(zkgpu_ctx* c, size_t batch, bool values) {
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  TRY(refuse_if_pending(c));
+  DeviceGuard g(c->device);
+  return ensure_pinned(c, stage_reasons_offset(batch, values) + batch);
+}
+int stage_reasons_enqueue(zkgpu_ctx* c, uint8_t code_when_clear) {
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  const size_t B = c->split.batch;
+  if (c->split.kind == 0 || B == 0) return ZKGPU_OK;
+  auto queue = [&]() -> int {
+    TRY(ensure(c, c->tx_reason, B));
+    {
+      Launch l(c, "k_tx_reason_stage", c->split.stream);
+      hipLaunchKernelGGL(k_tx_reason_stage, dim3(blocks_for(B, 256)), dim3(256), 0, c->split.stream, (const uint8_t*)c->bitmap.p, (uint32_t)B,
+                         (uint32_t)code_when_clear, (uint8_t*)c->tx_reason.p);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync((char*)c->pinned + stage_reasons_offset(B, c->split.values), c->tx_reason.p, B, hipMemcpyDeviceToHost, c->split.stream));
+    return ZKGPU_OK;
+  };
+  const int rc = queue();
+  if (rc != ZKGPU_OK) { c->split = zkgpu_ctx::SplitOp{}; c->pending = false; }     // (the failed call has drained the device: the stage is not in flight any more)
+  return rc;
+}
+// split_collect, and the stage's reason bytes with it (why may be NULL)
+int split_collect_why(zkgpu_ctx* c, uint8_t* bitmap, uint8_t* values, uint8_t* why) {
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  const size_t B = c->split.batch;
+  const bool vals = c->split.values;
+  const int rc = split_collect(c, bitmap, values);
+  if (!why) return rc;
+  if (rc != ZKGPU_OK) { memset(why, ZKGPU_TXSTATUS_REJECTED, B); return rc; }
+  if (B) memcpy(why, (const char*)c->pinned + stage_reasons_offset(B, vals), B);
+  return rc;
 }
 
 // has everything queued by the last *_enqueue on this context run?  (never blocks)
@@ -1635,13 +1760,19 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
  public:
   // slot_base / arena_base: which of the verifier's stage contexts and staging areas this call uses (a call alone: slots 0
   // and 1, areas 0 .. RING - 1; two rounds in flight: one slot and one set of areas each)
-  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0) : v_(v), sb_(slot_base), ab_(arena_base) {}
+  // reasons: a format-2 call -- every stage also brings back one reason byte per row (tx_reason_kernels.hpp)
+  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false) : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons) {}
+  bool reasons() const override { return reasons_; }
   const uint8_t* basepoint() override { return v_->basepoint; }
   int keys_enqueue(int slot, const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t rows) override {
-    return seen(msm_values_enqueue(keys(slot), scalars, points, offsets, rows), keys(slot));
+    if (reasons_) { const int rc = seen(stage_reasons_reserve(keys(slot), rows, true), keys(slot)); if (rc != ZKGPU_OK) return rc; }
+    const int rc = seen(msm_values_enqueue(keys(slot), scalars, points, offsets, rows), keys(slot));
+    return (rc == ZKGPU_OK && reasons_) ? seen(stage_reasons_enqueue(keys(slot), ZKGPU_TXSTATUS_KEY), keys(slot)) : rc;
   }
   bool keys_done(int slot) override { return split_done(keys(slot)); }
-  int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values) override { return seen(split_collect(keys(slot), ok_bits, values), keys(slot)); }
+  int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values, uint8_t* why) override {
+    return seen(split_collect_why(keys(slot), ok_bits, values, reasons_ ? why : nullptr), keys(slot));
+  }
   // (staging thread: touches the plans -- plans_mu -- the given arena and nothing else of the verifier)
   int proofs_stage(size_t ring_slot, size_t n, const zk::zkvm::TxProofSource* src, int host_threads, void** handle, std::string* err) override {
     zkgpu_txblock* blk = nullptr;
@@ -1661,7 +1792,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     // the one-wavefront-per-transaction transcript, or cut in two, does not shorten the tail of the call)
     const size_t saved_chunk = v_->chunk;
     v_->chunk = std::max<size_t>(saved_chunk, 4096);
-    st->run = block_start(v_, st->blk, true);
+    st->run = block_start(v_, st->blk, true, reasons_);
     v_->chunk = saved_chunk;
     if (!st->run) { err_ = v_->last_error; return ZKGPU_ENOMEM; }
     if (st->run->rc != ZKGPU_OK) { err_ = v_->last_error; return st->run->rc; }     // (proofs_finish still collects what was queued)
@@ -1672,10 +1803,10 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     if (!st->run) return true;
     return block_done(v_, st->run);
   }
-  int proofs_finish(void* handle, uint8_t* accept_bits) override {
+  int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t* why) override {
     Staged* st = (Staged*)handle;
     int rc = ZKGPU_OK;
-    if (st->run) { rc = block_finish(v_, st->run, accept_bits); if (rc != ZKGPU_OK) err_ = v_->last_error; }
+    if (st->run) { rc = block_finish(v_, st->run, accept_bits, reasons_ ? why : nullptr); if (rc != ZKGPU_OK) err_ = v_->last_error; }
     proofs_release(handle);
     return rc;
   }
@@ -1690,11 +1821,15 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     sidx_[slot].assign(rows, 0);
     soff_[slot].resize(rows + 1);
     for (size_t q = 0; q <= rows; ++q) soff_[slot][q] = q;
-    return seen(verify_ps_enqueue(sigs(slot), v_->ps, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, sidx_[slot].data(),
-                                  soff_[slot].data()), sigs(slot));
+    if (reasons_) { const int rc = seen(stage_reasons_reserve(sigs(slot), rows, false), sigs(slot)); if (rc != ZKGPU_OK) return rc; }
+    const int rc = seen(verify_ps_enqueue(sigs(slot), v_->ps, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, sidx_[slot].data(),
+                                          soff_[slot].data()), sigs(slot));
+    return (rc == ZKGPU_OK && reasons_) ? seen(stage_reasons_enqueue(sigs(slot), ZKGPU_TXSTATUS_SIGNATURE), sigs(slot)) : rc;
   }
   bool sigs_done(int slot) override { return split_done(sigs(slot)); }
-  int sigs_collect(int slot, uint8_t* bits) override { return seen(split_collect(sigs(slot), bits, nullptr), sigs(slot)); }
+  int sigs_collect(int slot, uint8_t* bits, uint8_t* why) override {
+    return seen(split_collect_why(sigs(slot), bits, nullptr, reasons_ ? why : nullptr), sigs(slot));
+  }
   std::string last_error() override { return err_; }
 
  private:
@@ -1705,6 +1840,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   zkgpu_verifier* v_;
   const int sb_;
   const size_t ab_;
+  const bool reasons_;
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];
   std::string err_;
@@ -1773,12 +1909,14 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   if (!txs || !tx_offsets || batch >= (1ull << 31)) return ZKGPU_EINVAL;
   for (size_t i = 0; i < batch; ++i) if (tx_offsets[i + 1] < tx_offsets[i]) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> vlk(v->mu);
-  if (v->tx_format != ZKGPU_TXFORMAT_RECOLLECTED_V1) {            // no format enabled: nothing is inside the subset
+  if (v->tx_format == 0) {                                        // no format enabled: nothing is inside the subset
     if (status) memset(status, TX_UNSUPPORTED, batch);
     return ZKGPU_OK;
   }
   TRY(tx_call_prepare(v));
-  GpuTxDevice dev(v);
+  // (format 2 reads the same bytes and gives the same bits; what differs is what the status bytes say -- with no status
+  // array there is nothing to say, and the call is the format-1 call)
+  GpuTxDevice dev(v, 0, 0, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS && status != nullptr);
   int rc;
   try {
     TxCall call(dev, v->tx_statements, v->tx_statements_kept, batch, txs, tx_offsets, host_threads, v->tx_chunk, accept_bitmap, status);
@@ -1790,7 +1928,7 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   }
   if (rc != ZKGPU_OK) {                                          // both outputs read "nothing accepted"
     memset(accept_bitmap, 0, (batch + 7) / 8);
-    if (status) for (size_t i = 0; i < batch; ++i) if (status[i] == TX_OK) status[i] = TX_INVALID;
+    if (status) for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;     // (never a reason, never 0)
   }
   return rc;
 }
@@ -1907,13 +2045,13 @@ void tx_engine_main(zkgpu_verifier* v) {
       for (auto* p : r.calls) { r.pieces.push_back({p->txs, p->offsets, p->batch}); threads = std::max(threads, p->host_threads); }
       r.bits.assign((r.total + 7) / 8 + 1, 0);
       r.status.assign(r.total, TX_INVALID);
-      if (v->tx_format != ZKGPU_TXFORMAT_RECOLLECTED_V1) {
+      if (v->tx_format == 0) {
         std::fill(r.status.begin(), r.status.end(), (uint8_t)TX_UNSUPPORTED);       // no format enabled: nothing is inside the subset
       } else {
         r.rc = tx_call_prepare(v, !active[0] && !active[1]);
         if (r.rc == ZKGPU_OK) {
           try {
-            r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING));
+            r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS));
             r.call.reset(new TxCall(*r.dev, set ? v->tx_statements_b : v->tx_statements, v->tx_statements_kept, r.pieces, threads, v->tx_chunk,
                                     r.bits.data(), r.status.data(), 1));
             r.call->set_on_news([&] { { std::lock_guard<std::mutex> nl(news_mu); news = true; } news_cv.notify_one(); });

@@ -20,6 +20,11 @@
 //   the CALLING thread: everything that talks to the device, never waiting for one thing while another could be queued:
 //     key stages (two slots, alternating), proofs (a ring of RING staging areas), signature stages (two slots).
 // accept = the VM accepted & the keys decode & the signature holds & the proof verifies; fail-closed in both outputs.
+//
+// A device that brings back REASONS (TxDevice::reasons(): the verifier's format 2) hands every stage's rows one byte each
+// beside the bit; verdicts() then writes, beside every clear bit, the LOWEST code that applies to the transaction -- the
+// order upstream would meet the faults in: decoding and the VM (16, host), r1cs::Verifier::verify (17 .. 19), the keys the
+// signature covers (20), the deferred signature check (21).  The bits are formed exactly as without reasons.
 #pragma once
 #include "host_pool.hpp"
 #include "zkvm_tx.hpp"
@@ -28,6 +33,7 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -49,34 +55,38 @@ class TxDevice {
   // aggregated keys: rows of (a_i, X_i) -> per row the encoding of sum a_i X_i (values) and "every key decodes" (ok bits)
   virtual int keys_enqueue(int slot, const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t rows) = 0;
   virtual bool keys_done(int slot) = 0;                                     // never blocks
-  virtual int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values) = 0;
+  // why (here and below; may be NULL, and is ignored by a device without reasons): one reason byte per row, 0 beside a set bit
+  virtual int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values, uint8_t* why) = 0;
   // cloak proofs of one chunk.  proofs_stage runs on the STAGING thread (host work: grouping by shape, gathering into the
   // ring slot's staging area); start / finish / release on the calling thread.  A handle that was staged is released
   // exactly once -- by proofs_finish, or by proofs_release if it was never started.
   virtual int proofs_stage(size_t ring_slot, size_t n, const TxProofSource* src, int host_threads, void** handle, std::string* err) = 0;
   virtual int proofs_start(size_t ring_slot, void* handle) = 0;
   virtual bool proofs_done(void* handle) = 0;                               // never blocks: would proofs_finish return at once?
-  virtual int proofs_finish(void* handle, uint8_t* accept_bits) = 0;
+  virtual int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t* why) = 0;
   virtual void proofs_release(void* handle) = 0;
   // signature equations: per row dynamic terms (scalars, points) + one term on the basepoint's table -> "is the identity"
   virtual int sigs_enqueue(int slot, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points, const uint64_t* dyn_offsets,
                            const uint8_t* base_scalars) = 0;
   virtual bool sigs_done(int slot) = 0;                                     // never blocks
-  virtual int sigs_collect(int slot, uint8_t* bits) = 0;
+  virtual int sigs_collect(int slot, uint8_t* bits, uint8_t* why) = 0;
   virtual std::string last_error() = 0;
+  virtual bool reasons() const { return false; }                            // does every stage bring back reason bytes?
 };
 
 class TxCall {
  public:
   static constexpr size_t RING = 6;                      // staging areas for the proofs of chunks in flight
   enum : int { OK = 0, ENOMEM_ = -4 };                   // (ZKGPU_OK / ZKGPU_ENOMEM: this header does not see zkgpu.h)
+  // status bytes of a call with reasons (ZKGPU_TXSTATUS_*, restated for the same reason; session.hpp asserts them)
+  enum : uint8_t { WHY_NONE = 1, WHY_TX_INVALID = 16, WHY_PROOF_FIRST = 17, WHY_KEY = 20, WHY_SIGNATURE = 21 };
 
   // store: what the VM leaves per transaction, kept by the caller between calls (fresh memory costs a page fault per 4 KB);
   // at most `kept` entries of it are used, the rest of a longer call lives in the call.
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(batch), threads_(host_threads), accept_(accept_bitmap),
-        status_(status), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        status_(status), reasons_(dev.reasons() && status != nullptr), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.resize(batch); len_.resize(batch);
     for (size_t i = 0; i < batch; ++i) { ptr_[i] = txs + tx_offsets[i]; len_[i] = (size_t)(tx_offsets[i + 1] - tx_offsets[i]); }
     plan(chunk_override, kept);
@@ -87,7 +97,7 @@ class TxCall {
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
-        timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        reasons_(dev.reasons() && status != nullptr), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
     for (const Piece& pc : pieces)
       for (size_t i = 0; i < pc.batch; ++i) { ptr_.push_back(pc.txs + pc.tx_offsets[i]); len_.push_back((size_t)(pc.tx_offsets[i + 1] - pc.tx_offsets[i])); }
@@ -184,21 +194,21 @@ class TxCall {
     std::vector<size_t> live;                            // positions in the chunk the VM accepted
     void* handle = nullptr;                              // its staged proofs
     bool started = false;
-    std::vector<uint8_t> pbits;
+    std::vector<uint8_t> pbits, pwhy;                    // the proofs' verdicts by position in `live`; with reasons, why
     int stage_rc = 0;
     std::string stage_err;
   };
   struct Segment {                                       // the key stage of one chunk
     size_t g_lo = 0, g_hi = 0;                           // live transactions of the call (positions in live_all_)
     std::vector<uint64_t> koff;                          // rows (a_i, X_i) per live transaction
-    std::vector<uint8_t> ksc, kpt, kok;
+    std::vector<uint8_t> ksc, kpt, kok, kwhy;
     bool pending = false;
   };
   struct SigStage {                                      // the signature equations of a run of chunks
     size_t first = 0, last = 0;                          // chunks [first, last)
     std::vector<size_t> keyed;                           // global live indices of the transactions whose keys all decode
     std::vector<uint64_t> soff;
-    std::vector<uint8_t> ssc, spt, sst, bits;
+    std::vector<uint8_t> ssc, spt, sst, bits, why;
     bool pending = false;
   };
   struct Span { size_t first, last; };
@@ -276,12 +286,14 @@ class TxCall {
       if (t.status == TX_OK) { k.live.push_back(i); live_all_.push_back(k.lo + i); }
     }
     k.pbits.assign((k.live.size() + 7) / 8 + 1, 0);
+    if (reasons_) k.pwhy.assign(k.live.size(), (uint8_t)WHY_NONE);
     sg.g_hi = live_all_.size();
   }
   void key_rows_out(size_t ci, Segment& sg) {           // rows (a_i, X_i) of the chunk's aggregated keys -> the calling thread
     const double t0 = now();
     const size_t nl = sg.g_hi - sg.g_lo;
     sg.kok.assign((nl + 7) / 8 + 1, 0);
+    if (reasons_) sg.kwhy.assign(nl, (uint8_t)WHY_NONE);
     sg.koff.assign(nl + 1, 0);
     for (size_t j = 0; j < nl; ++j) sg.koff[j + 1] = sg.koff[j] + statement(live_all_[sg.g_lo + j]).sig_scalars.size() / 32 - 2;
     sg.ksc.resize(32 * sg.koff.back()); sg.kpt.resize(32 * sg.koff.back());
@@ -325,6 +337,7 @@ class TxCall {
     for (size_t g = g_lo; g < g_hi; ++g) if (key_ok_[g]) sg.keyed.push_back(g);
     const size_t ns = sg.keyed.size();
     sg.bits.assign((ns + 7) / 8 + 1, 0);
+    if (reasons_) sg.why.assign(ns, (uint8_t)WHY_NONE);
     if (ns == 0) return;
     sg.soff.assign(ns + 1, 0);
     for (size_t q = 0; q < ns; ++q) sg.soff[q + 1] = sg.soff[q] + statement(live_all_[sg.keyed[q]]).sig_scalars.size() / 32 - 1;
@@ -417,7 +430,7 @@ class TxCall {
     if (!sg.pending) return;
     sg.pending = false;
     const double t0 = now();
-    const int rc = dev_.keys_collect((int)(s % n_slots_), sg.kok.data(), agg_.data() + 32 * sg.g_lo);
+    const int rc = dev_.keys_collect((int)(s % n_slots_), sg.kok.data(), agg_.data() + 32 * sg.g_lo, reasons_ ? sg.kwhy.data() : nullptr);
     if (rc != OK) note(rc, dev_.last_error());
     t_wait_ += now() - t0;
     for (size_t j = 0; j < sg.g_hi - sg.g_lo; ++j) key_ok_[sg.g_lo + j] = (sg.kok[j / 8] >> (j % 8)) & 1;
@@ -428,7 +441,7 @@ class TxCall {
     if (!sg.pending) return;
     sg.pending = false;
     const double t0 = now();
-    const int rc = dev_.sigs_collect((int)(s % n_slots_), sg.bits.data());
+    const int rc = dev_.sigs_collect((int)(s % n_slots_), sg.bits.data(), reasons_ ? sg.why.data() : nullptr);
     if (rc != OK) note(rc, dev_.last_error());
     t_wait_ += now() - t0;
     mark("signatures collected, stage", s);
@@ -437,7 +450,7 @@ class TxCall {
     if (k.handle) {
       if (k.started) {
         const double t0 = now();
-        const int rc = dev_.proofs_finish(k.handle, k.pbits.data());
+        const int rc = dev_.proofs_finish(k.handle, k.pbits.data(), reasons_ ? k.pwhy.data() : nullptr);
         if (rc != OK) note(rc, dev_.last_error());
         t_wait_ += now() - t0;
         mark("proofs collected, chunk at", k.lo);
@@ -553,6 +566,31 @@ class TxCall {
         if (status_) status_[i] = TX_OK;
       }
     }
+    if (reasons_) reasons_out();
+  }
+  // what the host itself rejected: the transaction (16) -- except the one check of the SIGNATURE the VM makes on the host, a
+  // scalar s that is not canonical, which is the signature's reason (the text is zkvm_tx.hpp's, which keeps one status for both)
+  static uint8_t host_reason(const TxStatement& t) {
+    return strcmp(t.why, "signature scalar not canonical") == 0 ? (uint8_t)WHY_SIGNATURE : (uint8_t)WHY_TX_INVALID;
+  }
+  // Beside every clear bit of a transaction inside the subset, the lowest code that applies; 0 stays where verdicts() wrote it,
+  // beside a set bit, and nowhere else.  A transaction no stage gave a reason for (cannot happen) reads "rejected" alone.
+  void reasons_out() {
+    for (size_t i = 0; i < batch_; ++i)
+      if (statement(i).status == TX_INVALID) status_[i] = host_reason(statement(i));
+    std::vector<uint8_t> sig_why(live_all_.size(), 0);
+    for (const auto& sg : sig_stages_)
+      for (size_t q = 0; q < sg->keyed.size(); ++q) sig_why[sg->keyed[q]] = sg->why[q];
+    for (size_t s = 0; s < seg_.size(); ++s) {
+      const Chunk& k = *chunks_[s];
+      const Segment& sg = seg_[s];
+      for (size_t j = 0; j < k.live.size(); ++j) {
+        const size_t i = k.lo + k.live[j];
+        if ((accept_[i / 8] >> (i % 8)) & 1) continue;
+        const uint8_t p = k.pwhy[j], ky = j < sg.kwhy.size() ? sg.kwhy[j] : (uint8_t)WHY_NONE, sv = sig_why[k.g0 + j];
+        status_[i] = p >= WHY_PROOF_FIRST && p < WHY_KEY ? p : ky == WHY_KEY ? ky : sv == WHY_SIGNATURE ? sv : (uint8_t)WHY_NONE;
+      }
+    }
   }
   void report() const {
     if (!timing_) return;
@@ -573,6 +611,7 @@ class TxCall {
   const int threads_;
   uint8_t* const accept_;
   uint8_t* const status_;
+  const bool reasons_;                                   // the device brings back reason bytes, and there is a status array to write them to
   const bool timing_;
   const double t00_;
   const size_t n_slots_;                                 // key / signature stages in flight at once (2; 1 when two calls share the stage contexts)

@@ -109,9 +109,9 @@ struct zkgpu_ctx {
   enum { ENQ_ALL = 0, ENQ_FRONT = 1, ENQ_MID = 2, ENQ_BACK = 3 };
   int enqueue_phase = ENQ_ALL;
   bool awaiting_back = false;      // an ENQ_FRONT call really queued a front half (shapes outside the pipeline run whole, at once)
-  std::vector<uint8_t> sync_result; // result of a submit that had to run synchronously
-  bool sync_result_valid = false;
-  int sync_rc = 0;
+  std::vector<uint8_t> sync_result, sync_reasons; // result of a submit that had to run synchronously | its reason bytes (tx_reasons_parked)
+  bool sync_result_valid = false, want_reasons = false;   // | the whole-proof batches of this context also say WHY (tx_reason_kernels.hpp)
+  int sync_rc = 0, reasons_src = 0;   // | where the reason bytes of the batch in flight are: 0 nowhere, 1 pinned result buffer, 2 sync_reasons
   std::recursive_mutex mu;
   std::string last_error;
   // workspace (grown on demand, never shrunk; no allocation in steady state)
@@ -133,7 +133,7 @@ struct zkgpu_ctx {
   std::atomic<uint32_t> last_failed_groups{0};   // root context: failed groups in the batch finished last (any fork)
   hipEvent_t ev_dig = nullptr, ev_u = nullptr;
   Buffer prep_com, prep_proofs, prep_r, prep_pw, prep_ch, prep_wf, prep_dyn_sc, prep_dyn_pt, prep_st_sc;
-  Buffer coal_com, coal_proofs, coal_r;  // merged inputs of the batches a zkgpu_verifier runs as one (session.hpp, tickets)
+  Buffer coal_com, coal_proofs, coal_r, tx_reason;  // merged inputs of the batches a zkgpu_verifier runs as one (session.hpp, tickets) | reason bytes
   Buffer ipa_lv, ipa_rv, ipa_cg, ipa_ch, ipa_w, ipa_u;   // prover: the inner-product argument's vectors (ipa_kernels.hpp)
   // the device prover (prover_kernels.hpp): constant tables, per-proof state, inputs, the rows of the phases' multiscalar
   // multiplications with their offsets / generator indices, the points coming back, the proofs
@@ -618,7 +618,7 @@ int msm_device(zkgpu_ctx* c, const void* d_scalars, const void* d_points, size_t
 // ---- batch ------------------------------------------------------------------------
 // values != nullptr: "value mode" -- write the 32-byte encoding of every MSM to
 // values[32 * i] (host) and make bit i mean "all points of MSM i decoded".
-int small_msm_launch(zkgpu_ctx* c, const Job& job, hipStream_t st);
+int small_msm_launch(zkgpu_ctx* c, const Job& job, hipStream_t st); int tx_reasons_enqueue(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, hipStream_t st, char* h_out); int tx_reasons_parked(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, int rc);   // (session.hpp)
 
 int batch_device_enqueue(zkgpu_ctx* c, const Job& job, bool values) {
   const size_t B = job.n_msm;
@@ -938,7 +938,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   TRY(ensure(c, c->accept, B));
   TRY(ensure(c, c->accept2, B));
   TRY(ensure(c, c->bitmap, nbytes));
-  TRY(ensure_pinned(c, nbytes + 64));
+  TRY(ensure_pinned(c, nbytes + 64 + (c->want_reasons ? B : 0)));
   TRY(ensure(c, c->status, 64));
   TRY(ensure(c, c->digits, std::max<uint64_t>(job.n_static, 1) * W * 2));
   TRY(ensure(c, c->st_partials, std::max<uint64_t>(n_lanes, group > 1 ? (uint64_t)B * std::max(W * Pf, TAIL_THREADS) : 0) * EXT_WORDS * 4));
@@ -1187,7 +1187,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   char* h = (char*)c->pinned;
   HIP_TRY(c, hipMemcpyAsync(h, c->bitmap.p, nbytes, hipMemcpyDeviceToHost, L));
   HIP_TRY(c, hipMemcpyAsync(h + nbytes, c->status.p, 48, hipMemcpyDeviceToHost, L));
-  HIP_TRY(c, hipEventRecord(c->ev_done, L));
+  if (c->want_reasons) TRY(tx_reasons_enqueue(c, job.d_wellformed, B, L, h + nbytes + 64)); HIP_TRY(c, hipEventRecord(c->ev_done, L));
   c->pending = true;
   c->pending_batch = B;
   c->sync_result_valid = false;
@@ -1533,7 +1533,7 @@ void zkgpu_destroy(zkgpu_ctx* c) {
                     &c->digits, &c->st_partials, &c->dynsum, &c->accept2, &c->bin_order, &c->class_count, &c->part_hist, &c->part_entries, &c->part_lo, &c->dec_scratch, &c->heavy, &c->small_tbl, &c->recoded, &c->grp_sc, &c->grp_digits, &c->grp_partials, &c->grp_ok, &c->row_map, &c->grp_fail, &c->grp_fail_sum, &c->rechk_pts, &c->grp_ws, &c->grp_wf, &c->grp_dyn, &c->pv_plan, &c->pv_state, &c->pv_in, &c->pv_rows0, &c->pv_rows1, &c->pv_rows2, &c->pv_rows3, &c->pv_lay, &c->pv_pts, &c->pv_com, &c->pv_ab, &c->pv_proofs, &c->prep_com, &c->prep_proofs, &c->prep_r,
                     &c->prep_pw, &c->prep_ch, &c->prep_wf, &c->prep_dyn_sc, &c->prep_dyn_pt, &c->prep_st_sc,
                     &c->prep_absorb, &c->prep_raw, &c->ipa_lv, &c->ipa_rv, &c->ipa_cg, &c->ipa_ch, &c->ipa_w, &c->ipa_u,
-                    &c->coal_com, &c->coal_proofs, &c->coal_r, &c->mx_tab, &c->mx_st_index};
+                    &c->coal_com, &c->coal_proofs, &c->coal_r, &c->mx_tab, &c->mx_st_index, &c->tx_reason};
   for (Buffer* b : bufs) if (b->p) (void)hipFree(b->p);
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->pinned_in) (void)hipHostFree(c->pinned_in);
@@ -3063,7 +3063,7 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
   }
   TRY(prepare_launch(c, s, pl, B, /*with_points=*/true));
   HIP_TRY(c, hipGetLastError());
-  return run_sync_and_park(c, job, ps);
+  return tx_reasons_parked(c, job.d_wellformed, B, run_sync_and_park(c, job, ps));
 }
 
 int cloak_verify_gpu_body(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,

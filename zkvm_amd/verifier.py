@@ -28,7 +28,43 @@ class VMError(Exception):
 
 
 class InvalidR1CSProof(VMError):
-    pass
+    """VMError::InvalidR1CSProof.  `reason`: the status byte of a transaction call with reasons (TXSTATUS_PROOF_FORMAT,
+    _PROOF_POINT or _PROOF_EQUATION: upstream has the one variant for the three), None where no reason is known."""
+    reason: Optional[int] = None
+
+
+class TxFormatError(VMError):
+    """The transaction itself was rejected before any proof or signature was looked at (TXSTATUS_TX_INVALID): wire format,
+    time bounds, a program or VM error -- upstream's VMError::FormatError and the VM's own variants, which this path keeps
+    as one code."""
+    reason: Optional[int] = None
+
+
+class InvalidSignature(VMError):
+    """The deferred signature check failed (TXSTATUS_KEY: a key the signature must cover does not decode; TXSTATUS_SIGNATURE:
+    R, s or the equation) -- upstream's VMError::InvalidPoint / the musig error of Signature::verify, as recalled."""
+    reason: Optional[int] = None
+
+
+def tx_errors(status) -> List[Optional[VMError]]:
+    """status bytes of verify_txs / wait_txs -> per transaction None (accepted) or the VMError upstream's Tx::verify would
+    return, as recalled (INTEGRATION.md): TxFormatError (16), InvalidR1CSProof (17, 18, 19), InvalidSignature (20, 21), each
+    with the code as `.reason`; a plain VMError for "rejected, no reason known" (1), for a transaction outside the subset
+    (2: not an error of the transaction -- the caller's own VM decides) and for a byte this version does not know."""
+    texts = {1: "rejected (no reason available)", 2: "outside the subset this library verifies: ask your own VM",
+             16: "the transaction is malformed or its program failed in the VM", 17: "R1CS proof is malformed",
+             18: "a commitment or proof point is not a ristretto255 encoding", 19: "R1CS proof did not verify",
+             20: "a verification key does not decode", 21: "the transaction signature did not verify"}
+    kinds = {16: TxFormatError, 17: InvalidR1CSProof, 18: InvalidR1CSProof, 19: InvalidR1CSProof, 20: InvalidSignature, 21: InvalidSignature}
+    out: List[Optional[VMError]] = []
+    for b in bytes(status):
+        if b == 0:
+            out.append(None)
+            continue
+        e = kinds.get(b, VMError)(texts.get(b, "unknown status byte %d" % b))
+        e.reason = b
+        out.append(e)
+    return out
 
 
 @dataclass
@@ -282,11 +318,25 @@ class BlockVerifier:
         return bm.raw[: (n + 7) // 8]
 
     TXFORMAT_RECOLLECTED_V1 = 1
+    TXFORMAT_RECOLLECTED_V1_REASONS = 2    # the same bytes and the same bitmap; the status bytes say WHY (tx_errors)
+    # status bytes (include/zkgpu.h: ZKGPU_TXSTATUS_*); 16 .. 21 only with TXFORMAT_RECOLLECTED_V1_REASONS, lowest code first
+    TXSTATUS_ACCEPTED = 0
+    TXSTATUS_REJECTED = 1                  # rejected, no reason known (format 1, or any error)
+    TXSTATUS_OUTSIDE_SUBSET = 2
+    TXSTATUS_TX_INVALID = 16
+    TXSTATUS_PROOF_FORMAT = 17
+    TXSTATUS_PROOF_POINT = 18
+    TXSTATUS_PROOF_EQUATION = 19
+    TXSTATUS_KEY = 20
+    TXSTATUS_SIGNATURE = 21
+
+    tx_errors = staticmethod(lambda status: tx_errors(status))    # (the module's helper, where the constants are)
 
     def set_tx_format(self, fmt: int) -> None:
         """zkgpu_verifier_set_tx_format: the serialized-transaction format zkgpu_tx_verify_batch reads.  0 (the default):
         none -- every transaction is reported as outside the subset; TXFORMAT_RECOLLECTED_V1: the payment subset of
-        DESIGN.md sec 4.5, an UNPINNED recollection of the ZkVM wire format (opt-in for exactly that reason)."""
+        DESIGN.md sec 4.5, an UNPINNED recollection of the ZkVM wire format (opt-in for exactly that reason);
+        TXFORMAT_RECOLLECTED_V1_REASONS: the same, with a reason code in the status byte of every rejected transaction."""
         self._check(self.lib.zkgpu_verifier_set_tx_format(self.h, fmt))
 
     def set_tx_chunk(self, transactions: int) -> None:
@@ -299,11 +349,14 @@ class BlockVerifier:
 
     def verify_txs(self, txs: Sequence[bytes], host_threads: int = 0):
         """zkgpu_tx_verify_batch: serialized ZkVM transactions (payment subset) -> (accept bitmap, status bytes:
-        0 accepted, 1 rejected, 2 outside the subset).  Inert until set_tx_format names a format."""
+        0 accepted, 1 rejected, 2 outside the subset).  Inert until set_tx_format names a format.  With
+        TXFORMAT_RECOLLECTED_V1_REASONS the bitmap is the same and a rejected transaction reads one of TXSTATUS_TX_INVALID ..
+        TXSTATUS_SIGNATURE instead of 1 (the lowest code that applies; 1 for every transaction after an error): tx_errors(status)
+        turns the bytes into upstream's error variants."""
         return self.verify_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads)
 
     def verify_txs_packed(self, blob: bytes, lengths, host_threads: int = 0):
-        """the same over one buffer of concatenated transactions and their lengths"""
+        """the same over one buffer of concatenated transactions and their lengths (same status bytes, reasons included)"""
         batch = len(lengths)
         offs = np.zeros(batch + 1, dtype=np.uint64)
         np.cumsum(lengths if isinstance(lengths, np.ndarray) and lengths.dtype == np.uint64 else np.asarray(lengths, dtype=np.uint64), out=offs[1:])
@@ -331,7 +384,8 @@ class BlockVerifier:
         return self.submit_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads)
 
     def wait_txs(self, call_id: int):
-        """zkgpu_tx_verify_wait -> (accept bitmap, status bytes) of that call"""
+        """zkgpu_tx_verify_wait -> (accept bitmap, status bytes) of that call; the status bytes are those verify_txs gives for
+        the same transactions -- with TXFORMAT_RECOLLECTED_V1_REASONS the same reason codes, whatever round the call was merged into"""
         _, _, batch = self.__dict__["_tx_calls"][call_id]
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
         st = C.create_string_buffer(max(batch, 1))
