@@ -278,6 +278,47 @@ def test_verdict_parity_under_corruption(ctx, gens, oracle, suite):
     assert stats == (len(groups), sum(len(g) for g in groups), len(failed), sum(len(set(g) - left_out) for g in failed))
 
 
+def _planner_counts(ctx, gens, handles, idx, proofs, gs):
+    """what the host's planner (csrc/mixed_plan.hpp through libzkhost's zkhost_mixed_plan, the hook tests/test_mixed_plan.py
+    drives) makes of this call -> (checks of two or more members, statements in them).  The plans' rows and keys are what
+    zkgpu_cloak_plan_info / _layout give; LDS class and transcript form, which they do not give, order the statements inside
+    a key and leave the counts alone"""
+    import os
+    import zkvm_amd
+    host = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(zkvm_amd.__file__)), "lib", "libzkhost.so"))
+    host.zkhost_mixed_plan.restype = C.c_longlong
+    rows = []
+    for h in handles:
+        lay = (C.c_uint32 * 8)()
+        assert ctx.lib.zkgpu_cloak_plan_layout(C.c_void_p(h), lay) == 0
+        # id | proof_words m n_ch n_ch_ext n_seg n_dyn n_static pn h_base n_targets | lds_bytes large lp_slots
+        rows += [h, (16 + 2 * lay[5]) * 8, lay[6], lay[1], lay[0], 1, lay[3], lay[4], _padded_n(ctx, h), 2 + gens.gens_capacity, 0, 0, 0, 0]
+    offs = [0]
+    for p in proofs:
+        offs.append(offs[-1] + len(p))
+    summary, uniq, err = (C.c_uint64 * 35)(), (C.c_uint32 * len(handles))(), C.create_string_buffer(128)
+    size = host.zkhost_mixed_plan((C.c_uint64 * len(rows))(*rows), C.c_size_t(len(handles)), (C.c_uint32 * len(idx))(*idx),
+                                  (C.c_uint64 * len(offs))(*offs), C.c_size_t(len(idx)), 1, C.c_uint32(gs), 1, C.c_size_t(256), None,
+                                  C.c_size_t(0), summary, uniq, err, C.c_size_t(128))
+    assert size > 0, err.value
+    return summary[23], summary[20]
+
+
+def test_the_call_runs_the_planner_the_cpu_tests_drive(ctx, gens, suite):
+    """5 statements over 3 plans of 2 generator keys (range(8) and the random system: padded n = 8; range(64)), group_size 2:
+    the counters of the call are those of zkhost_mixed_plan for the same call -- 2 checks of two, 4 statements in them, none
+    failed, none re-checked -- and the bitmap is the per-plan calls'"""
+    mv, pool, pn = suite
+    idx, coms, proofs, _ = _take(pool, [(RANGE8, 2), (RANGE64, 2), (SYSTEM_A, 1)], random.Random(12))
+    n = len(idx)
+    r = hashlib.shake_256(b"groups planner").digest(64 * n)
+    predicted = _planner_counts(ctx, gens, mv.handles, idx, proofs, 2)
+    assert predicted == (2, 4) == _formed(idx, pn, 2)
+    got, stats = _run(ctx, mv, 2, idx, coms, proofs, r)
+    assert stats == predicted + (0, 0)
+    assert got == _per_plan(ctx, gens, mv.handles, idx, coms, proofs, r) == [1] * n
+
+
 def _profiled(ctx, fn):
     ctx.profile(True)
     ctx.profile_reset()

@@ -768,6 +768,40 @@ extern "C" size_t zkhost_ticket_cut(const uint64_t* sizes, size_t n, uint64_t ta
   return cut.size();
 }
 
+// the plan of one zkgpu_r1cs_verify_mixed call (mixed_plan.hpp).  infos: n_infos rows of MIXHOOK_INFO values in the order of
+// MixPlanInfo's fields; plan_record_bytes stands for sizeof(PrepPlan) (the plans section stays zero).  -> the table's bytes
+// (copied to `table` when they fit `cap`), or -1 with the argument error's text in `err`.  summary[MIXHOOK_SUMMARY]:
+// distinct plans | class_start[4] | class_lds[2] | lp_targets lp_pn lp_slots | coop | max_nch | n_com n_pw n_ch n_raw n_abs
+// n_dyn n_st | n_checks n_grouped n_rows max_ns, checks of two or more | lane-order entries | t_plans .. t_end (10);
+// uniq[n_infos]: the distinct plans as indices into infos
+#include "mixed_plan.hpp"
+constexpr int MIXHOOK_INFO = 14, MIXHOOK_SUMMARY = 35;
+extern "C" long long zkhost_mixed_plan(const uint64_t* infos, size_t n_infos, const uint32_t* plan_index, const uint64_t* proof_offsets,
+                                       size_t batch, int coop_wanted, uint32_t group_size, int may_group, size_t plan_record_bytes,
+                                       uint8_t* table, size_t cap, uint64_t* summary, uint32_t* uniq, char* err, size_t err_cap) {
+  std::vector<MixPlanInfo> in(n_infos);
+  for (size_t p = 0; p < n_infos; ++p) {
+    const uint64_t* f = infos + MIXHOOK_INFO * p;
+    in[p] = MixPlanInfo{f[0], (uint32_t)f[1], (uint32_t)f[2], (uint32_t)f[3], (uint32_t)f[4], (uint32_t)f[5], (uint32_t)f[6], (uint32_t)f[7],
+                        (uint32_t)f[8], (uint32_t)f[9], (uint32_t)f[10], (size_t)f[11], f[12] != 0, (uint32_t)f[13]};
+  }
+  const MixCallPlan mp = plan_mixed_call(in.data(), n_infos, plan_index, proof_offsets, batch,
+                                         MixPlanOptions{coop_wanted != 0, group_size, may_group != 0}, plan_record_bytes);
+  if (mp.error) {
+    if (err_cap) { std::strncpy(err, mp.error, err_cap - 1); err[err_cap - 1] = 0; }
+    return -1;
+  }
+  const uint64_t sum[MIXHOOK_SUMMARY] = {
+      mp.uniq.size(), mp.class_start[0], mp.class_start[1], mp.class_start[2], mp.class_start[3], mp.class_lds[0], mp.class_lds[1],
+      mp.lp_targets, mp.lp_pn, mp.lp_slots, mp.coop, mp.max_nch, mp.n_com, mp.n_pw, mp.n_ch, mp.n_raw, mp.n_abs, mp.n_dyn, mp.n_st,
+      mp.n_checks, mp.n_grouped, mp.n_rows, mp.max_ns, mp.n_pairs, mp.n_lanes,
+      mp.t_plans, mp.t_stmts, mp.t_order, mp.t_lanes, mp.t_doff, mp.t_soff, mp.t_grp, mp.t_mem, mp.t_goff, mp.t_end};
+  std::memcpy(summary, sum, sizeof sum);
+  std::copy(mp.uniq.begin(), mp.uniq.end(), uniq);
+  if (mp.t_end <= cap) std::memcpy(table, mp.tab.data(), mp.t_end);
+  return (long long)mp.t_end;
+}
+
 #include "comm_frame.hpp"
 extern "C" size_t zkhost_comm_slot_bytes(const uint64_t* cuts, int world) { return commframe::slot_bytes(cuts, world); }
 extern "C" void zkhost_comm_pack(uint8_t* out, size_t slot, const uint64_t* cuts, int rank, const uint8_t* local_bitmap, int local_status) {

@@ -15,21 +15,9 @@
 // members, see "group checks" below) makes the transcript stages put rho = r^2 into every statement's scalars.
 #pragma once
 #include "prep_kernels.hpp"
+#include "mixed_plan.hpp"     // MixStmt, MixGroup, MIX_FORM_*: the table as the host lays it out
 
 namespace zk {
-
-// k_mx_prepare's LDS classes: a plan needing more than this takes a CU's 160 KiB LDS alone (one workgroup per CU)
-constexpr size_t MIX_LDS_SMALL = 80 * 1024;
-
-constexpr uint32_t MIX_FORM_TWO_PHASE = 0, MIX_FORM_ONE_PHASE = 1, MIX_FORM_BAD_LENGTH = 2;
-
-struct MixStmt {
-  uint32_t plan, form;         // form: MIX_FORM_*; a proof of the wrong length is never read
-  uint64_t proof;              // first byte of the proof
-  uint64_t com, pw, ch, raw;   // first word of its commitments, proof words, challenge slots, raw challenge bytes
-  uint64_t absorb;             // first entry of its absorbed words (cooperative transcript)
-  uint64_t dyn, st;            // first dynamic / static term of its row
-};
 
 // a statement's view without its rows: its plan's shape and arrays
 __device__ __forceinline__ PrepStmt mix_view(const PrepPlan& pln) {
@@ -159,16 +147,11 @@ k_mx_gather_dyn_points(const PrepPlan* __restrict__ plans, const MixStmt* __rest
 // ---- group checks of a mixed call ------------------------------------------------------------------------------------
 // Generators depend on their index alone: statements whose plans have the same padded multiplier count and the same
 // generator capacity have the same static index list [B, B_blinding, G_0.., H_0..], whatever their constraints.  The host
-// cuts the statements of each such key into CHECKS of up to group_size members (MixGroup; a statement checked alone is a
+// cuts the statements of each such key into CHECKS of up to group_size members (MixGroup, mixed_plan.hpp; a statement checked alone is a
 // check of one member).  The equations of a check's members are added under the weights rho = r^2 the transcript put into
 // their scalars: the members' generator scalars collapse into ONE static row per check (k_mx_group_scalars ->
 // k_static_accumulate over the checks' rows), the members' own dynamic sums are added to it (k_mx_group_combine).  A check
 // of two or more members that fails queues its members for k_recheck_fused, each alone on its own static row.
-struct MixGroup {
-  uint32_t first, count;       // its members: members[first .. first + count), statements in the caller's numbering
-  uint32_t ns, pad;            // static terms of its row: 2 + 2 pn of its key
-  uint64_t st;                 // first static term of its row among the checks' rows
-};
 
 // lane (check, j): sum over the members (those not known bad already: their rows are left out) of static scalar j, its
 // digits as k_static_digits writes them, and the generator index of term j (the first member's: the key's)

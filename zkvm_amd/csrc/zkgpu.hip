@@ -42,6 +42,7 @@
 #include "zkvm_tx.hpp"
 #include "host_pool.hpp"
 #include "ticket_cut.hpp"
+#include "mixed_plan.hpp"
 
 using namespace zk;
 
@@ -850,8 +851,8 @@ struct PrepLaunch {
 };
 
 // proof bytes of a statement shape: the two-phase wire format, or the one-phase one (three points fewer)
-inline bool proof_len_fits(const PrepShape& sh, size_t len) { return len == 1 + 4ull * sh.proof_words || len + 96 == 1 + 4ull * sh.proof_words; }
-inline uint32_t proof_is_compact(const PrepShape& sh, size_t len) { return len + 96 == 1 + 4ull * sh.proof_words ? 1u : 0u; }
+inline bool proof_len_fits(const PrepShape& sh, size_t len) { return proof_form(sh.proof_words, len) != MIX_FORM_BAD_LENGTH; }
+inline uint32_t proof_is_compact(const PrepShape& sh, size_t len) { return proof_form(sh.proof_words, len) == MIX_FORM_ONE_PHASE ? 1u : 0u; }
 
 // The transcript with one wavefront per statement while that still leaves the chip room (the cooperative form costs ~9x the
 // wave-instructions of the one-lane form, and buys latency only); beyond that, one lane per statement.  (A caller ANDs in
@@ -879,8 +880,10 @@ int prepare_launch(zkgpu_ctx* c, hipStream_t s, const PrepLaunch& pl, uint32_t B
   return ZKGPU_OK;
 }
 
-bool pipe_eligible(const zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps) {
-  return ps && ps->table && job.n_static && job.n_dyn && !c->forced_w && job.n_dyn <= 128ull * job.n_msm;
+// The pipeline takes a point set with generator tables at their own window width (pipe_tables) and rows it has room for
+bool pipe_tables(const zkgpu_ctx* c, const zkgpu_pointset* ps) { return ps && ps->table && !c->forced_w; }
+bool pipe_eligible(const zkgpu_ctx* c, const zkgpu_pointset* ps, uint64_t n_msm, uint64_t n_dyn, uint64_t n_static) {
+  return pipe_tables(c, ps) && pipe_rows_fit(n_msm, n_dyn, n_static);
 }
 
 int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const PrepLaunch* prep) {
@@ -3042,7 +3045,7 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
   job.n_msm = B;
   job.d_wellformed = (const uint32_t*)c->prep_wf.p;   // folded into the accept bitmap on the device
   const PrepLaunch pl = {plan->dev, plan->lds_bytes, plan->large, d_com, d_proofs, d_r, proof_len};
-  if (pipe_eligible(c, job, ps)) return pipe_enqueue(c, job, ps, &pl);
+  if (pipe_eligible(c, ps, job.n_msm, job.n_dyn, job.n_static)) return pipe_enqueue(c, job, ps, &pl);
   // general shapes (no generator tables, forced window width, many proof points): one stream, synchronous
   hipStream_t s = c->stream;
   TRY(ensure(c, c->recoded, std::max<uint64_t>(job.n_dyn, 1) * 32));
@@ -3136,7 +3139,7 @@ int zkgpu_verify_batch_ps_submit_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, siz
   job.n_static = n_static;
   job.d_static_rows = ps->rows;
   job.n_msm = (uint32_t)batch;
-  if (pipe_eligible(c, job, ps)) return pipe_enqueue(c, job, ps, nullptr);
+  if (pipe_eligible(c, ps, job.n_msm, job.n_dyn, job.n_static)) return pipe_enqueue(c, job, ps, nullptr);
   return run_sync_and_park(c, job, ps);
 }
 
@@ -3609,192 +3612,64 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     c->last_error = "mixed verification: null plan list, plan index, commitments, proofs or offsets";
     return ZKGPU_EINVAL;
   }
+  std::vector<MixPlanInfo> infos(n_plans);
   for (size_t p = 0; p < n_plans; ++p) {
     const zkgpu_cloak_plan* pl = plans[p];
     if (!pl || pl->device != c->device) { c->last_error = "mixed verification: null plan, or a plan of another device"; return ZKGPU_EINVAL; }
     if (ps->n < 2 + 2 * pl->gens_capacity) { c->last_error = "mixed verification: a plan needs more generators than the set holds"; return ZKGPU_EINVAL; }
+    const PrepShape& sh = pl->dev.sh;
+    infos[p] = MixPlanInfo{(uint64_t)(uintptr_t)pl, sh.proof_words, sh.m, sh.n_ch, sh.n_ch_ext, pl->dev.n_seg, sh.n_dyn, sh.n_static, sh.pn,
+                           pl->dev.h_base, sh.n_targets, pl->lds_bytes, pl->large, lp_layout(sh).slots};
   }
   if (proof_offsets[0] != 0) { c->last_error = "mixed verification: proof_offsets[0] must be 0"; return ZKGPU_EINVAL; }
-  for (size_t i = 0; i < batch; ++i) {
-    if (plan_index[i] >= n_plans) { c->last_error = "mixed verification: plan index out of range"; return ZKGPU_EINVAL; }
-    if (proof_offsets[i + 1] < proof_offsets[i]) { c->last_error = "mixed verification: proof offsets decrease"; return ZKGPU_EINVAL; }
-  }
-  const uint32_t B = (uint32_t)batch;
-  // distinct plans (by handle) and the statements sorted by plan
-  std::vector<zkgpu_cloak_plan*> uniq;
-  std::vector<uint32_t> pid_of(n_plans, ~0u), pid(B);
-  for (uint32_t i = 0; i < B; ++i) {
-    uint32_t& slot = pid_of[plan_index[i]];
-    if (slot == ~0u) {
-      zkgpu_cloak_plan* pl = plans[plan_index[i]];
-      for (uint32_t u = 0; u < uniq.size() && slot == ~0u; ++u) if (uniq[u] == pl) slot = u;
-      if (slot == ~0u) { slot = (uint32_t)uniq.size(); uniq.push_back(pl); }
-    }
-    pid[i] = slot;
-  }
-  const uint32_t U = (uint32_t)uniq.size();
-  // LDS classes of k_mx_prepare: plans that leave room for two or more workgroups per CU, and those that take one alone.
-  // Statements are ordered by (class, plan); k_mx_prepare runs once per class present, each launch with its own class's
-  // largest LDS, so that one large program in a call does not cut every small statement to one workgroup per CU.
-  // Class 2: plans past a CU's LDS, prepared by large_prep.hpp's four launches, however many such plans the call holds.
-  std::vector<uint32_t> count(U, 0), order(B), cls(U), by_class(U);
-  for (uint32_t u = 0; u < U; ++u) { cls[u] = uniq[u]->large ? 2u : uniq[u]->lds_bytes > MIX_LDS_SMALL ? 1u : 0u; by_class[u] = u; }
-  std::stable_sort(by_class.begin(), by_class.end(), [&](uint32_t a, uint32_t b) { return cls[a] < cls[b]; });
-  for (uint32_t i = 0; i < B; ++i) ++count[pid[i]];
-  uint32_t class_start[4] = {0, 0, 0, B};
-  size_t class_lds[2] = {0, 0};
-  uint32_t lp_targets = 0, lp_pn = 0, lp_slots = 0;      // the large plans' widest grids and workspace per statement
-  {
-    std::vector<uint32_t> at(U, 0);
-    uint32_t run = 0;
-    for (uint32_t u : by_class) {
-      at[u] = run;
-      run += count[u];
-      for (uint32_t k = cls[u] + 1; k < 3; ++k) class_start[k] = run;
-      if (cls[u] < 2) {
-        class_lds[cls[u]] = std::max(class_lds[cls[u]], uniq[u]->lds_bytes);
-      } else {
-        const PrepShape& sh = uniq[u]->dev.sh;
-        lp_targets = std::max(lp_targets, sh.n_targets);
-        lp_pn = std::max(lp_pn, sh.pn);
-        lp_slots = std::max(lp_slots, lp_layout(sh).slots);
-      }
-    }
-    for (uint32_t i = 0; i < B; ++i) order[at[pid[i]]++] = i;
-  }
-  const uint32_t n_large = B - class_start[2];
-  bool coop = coop_transcript(c, batch);
-  for (zkgpu_cloak_plan* pl : uniq) coop &= pl->dev.n_seg != 0 && pl->dev.sh.n_ch <= 0xffffu;
-  std::vector<uint32_t> lane_order;
-  if (!coop) {                           // each plan's run padded to whole wavefronts
-    lane_order.reserve(B + 64 * U);
-    for (uint32_t i = 0; i < B; ++i) {
-      lane_order.push_back(order[i]);
-      if (i + 1 == B || pid[order[i + 1]] != pid[order[i]])
-        while (lane_order.size() % 64) lane_order.push_back(~0u);
-    }
-  }
-  // the checks: statements in (class, plan) order, stably by generator key, each key's run cut into checks of group_size
-  uint64_t n_dyn_all = 0, n_st_all = 0;
-  for (uint32_t u = 0; u < U; ++u) { n_dyn_all += (uint64_t)count[u] * uniq[u]->dev.sh.n_dyn; n_st_all += (uint64_t)count[u] * uniq[u]->dev.sh.n_static; }
-  const bool piped = ps->table && n_st_all && n_dyn_all && !c->forced_w && n_dyn_all <= 128ull * B;      // (pipe_eligible of the job below)
-  std::vector<MixGroup> checks;
-  std::vector<uint32_t> members;
-  MixGroupTable gt;
-  if (piped && c->group_size > 1 && B > 1) {
-    std::vector<std::pair<uint32_t, uint32_t>> keys;      // (padded n, index of H_0)
-    std::vector<uint32_t> key_of(U);
-    for (uint32_t u : by_class) {
-      const std::pair<uint32_t, uint32_t> k(uniq[u]->dev.sh.pn, uniq[u]->dev.h_base);
-      size_t at = std::find(keys.begin(), keys.end(), k) - keys.begin();
-      if (at == keys.size()) keys.push_back(k);
-      key_of[u] = (uint32_t)at;
-    }
-    members = order;
-    std::stable_sort(members.begin(), members.end(), [&](uint32_t a, uint32_t b) { return key_of[pid[a]] < key_of[pid[b]]; });
-    const uint32_t gs = (uint32_t)c->group_size;
-    for (uint32_t i = 0; i < B;) {
-      const uint32_t key = key_of[pid[members[i]]];
-      uint32_t n = 1;
-      while (n < gs && i + n < B && key_of[pid[members[i + n]]] == key) ++n;
-      const uint32_t ns = uniq[pid[members[i]]]->dev.sh.n_static;
-      checks.push_back(MixGroup{i, n, ns, 0, gt.n_rows});
-      gt.n_rows += ns;
-      gt.max_ns = std::max(gt.max_ns, ns);
-      if (n >= 2) gt.n_grouped += n;
-      i += n;
-    }
-    if (gt.n_grouped == 0) { checks.clear(); members.clear(); gt = MixGroupTable{}; }
-    gt.n_checks = (uint32_t)checks.size();
-  }
-  const bool grouped = gt.n_checks != 0;
-  uint64_t n_groups2 = 0;
-  for (const MixGroup& g : checks) n_groups2 += g.count >= 2;
-  // the table, laid out as the device reads it: plans | statements | order | lane order | row offsets (dynamic, static) |
-  // checks | their members | row offsets of the checks
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t t_plans = 0, t_stmts = up(t_plans + U * sizeof(PrepPlan)), t_order = up(t_stmts + B * sizeof(MixStmt)),
-               t_lanes = up(t_order + 4 * (size_t)B), t_doff = up(t_lanes + 4 * lane_order.size()),
-               t_soff = up(t_doff + 8 * ((size_t)B + 1)), t_grp = up(t_soff + 8 * ((size_t)B + 1)),
-               t_mem = up(t_grp + checks.size() * sizeof(MixGroup)), t_goff = up(t_mem + 4 * members.size()),
-               t_end = t_goff + (grouped ? 8 * (checks.size() + 1) : 0);
-  std::vector<char> tab(t_end);
-  if (grouped) {
-    memcpy(tab.data() + t_grp, checks.data(), checks.size() * sizeof(MixGroup));
-    memcpy(tab.data() + t_mem, members.data(), 4 * members.size());
-    uint64_t* goff = (uint64_t*)(tab.data() + t_goff);
-    for (size_t g = 0; g < checks.size(); ++g) goff[g] = checks[g].st;
-    goff[checks.size()] = gt.n_rows;
-  }
-  PrepPlan* mp = (PrepPlan*)(tab.data() + t_plans);
-  size_t max_nch = 0;
-  for (uint32_t u = 0; u < U; ++u) {
-    mp[u] = uniq[u]->dev;
-    max_nch = std::max<size_t>(max_nch, mp[u].sh.n_ch);
-  }
-  MixStmt* ms = (MixStmt*)(tab.data() + t_stmts);
-  uint64_t *dyn_off = (uint64_t*)(tab.data() + t_doff), *st_off = (uint64_t*)(tab.data() + t_soff);
-  uint64_t n_com = 0, n_pw = 0, n_ch = 0, n_raw = 0, n_abs = 0, n_dyn = 0, n_st = 0;
-  for (uint32_t i = 0; i < B; ++i) {
-    const PrepPlan& m = mp[pid[i]];
-    const PrepShape& sh = m.sh;
-    const uint64_t len = proof_offsets[i + 1] - proof_offsets[i];
-    MixStmt& s = ms[i];
-    s.plan = pid[i];
-    s.form = len == 1 + 4ull * sh.proof_words ? MIX_FORM_TWO_PHASE : len + 96 == 1 + 4ull * sh.proof_words ? MIX_FORM_ONE_PHASE : MIX_FORM_BAD_LENGTH;
-    s.proof = proof_offsets[i];
-    s.com = n_com; s.pw = n_pw; s.ch = n_ch; s.raw = n_raw; s.absorb = n_abs; s.dyn = n_dyn; s.st = n_st;
-    dyn_off[i] = n_dyn; st_off[i] = n_st;
-    n_com += 8ull * sh.m; n_pw += sh.proof_words; n_ch += 8ull * sh.n_ch_ext;
-    if (coop) { n_raw += 16ull * sh.n_ch; n_abs += 25ull * m.n_seg; }
-    n_dyn += sh.n_dyn; n_st += sh.n_static;
-  }
-  dyn_off[B] = n_dyn; st_off[B] = n_st;
-  memcpy(tab.data() + t_order, order.data(), 4 * (size_t)B);
-  if (!lane_order.empty()) memcpy(tab.data() + t_lanes, lane_order.data(), 4 * lane_order.size());
-  TRY(ensure(c, c->prep_pw, 4 * n_pw));
-  TRY(ensure(c, c->prep_ch, 4 * n_ch));
+  // the call's plan and its table (mixed_plan.hpp), all but the plans' own records
+  const MixPlanOptions opt = {coop_transcript(c, batch), (uint32_t)c->group_size, pipe_tables(c, ps)};
+  MixCallPlan mp = plan_mixed_call(infos.data(), n_plans, plan_index, proof_offsets, batch, opt, sizeof(PrepPlan));
+  if (mp.error) { c->last_error = mp.error; return ZKGPU_EINVAL; }
+  const uint32_t B = (uint32_t)batch, n_large = B - mp.class_start[2];
+  const bool coop = mp.coop, grouped = mp.n_checks != 0;
+  TRY(ensure(c, c->prep_pw, 4 * mp.n_pw));
+  TRY(ensure(c, c->prep_ch, 4 * mp.n_ch));
   TRY(ensure(c, c->prep_wf, 4 * (size_t)B));
-  TRY(ensure(c, c->prep_dyn_sc, 32 * n_dyn));
-  TRY(ensure(c, c->prep_dyn_pt, 32 * n_dyn));
-  TRY(ensure(c, c->prep_st_sc, 32 * n_st));
-  TRY(ensure(c, c->mx_st_index, 4 * n_st));
-  if (n_large) TRY(ensure(c, c->prep_large, lp_ws_bytes(lp_slots, n_large)));
+  TRY(ensure(c, c->prep_dyn_sc, 32 * mp.n_dyn));
+  TRY(ensure(c, c->prep_dyn_pt, 32 * mp.n_dyn));
+  TRY(ensure(c, c->prep_st_sc, 32 * mp.n_st));
+  TRY(ensure(c, c->mx_st_index, 4 * mp.n_st));
+  if (n_large) TRY(ensure(c, c->prep_large, lp_ws_bytes(mp.lp_slots, n_large)));
   if (coop) {
-    TRY(ensure(c, c->prep_absorb, std::max<uint64_t>(8 * n_abs, 16)));
-    TRY(ensure(c, c->prep_raw, std::max<uint64_t>(4 * n_raw, 16)));
+    TRY(ensure(c, c->prep_absorb, std::max<uint64_t>(8 * mp.n_abs, 16)));
+    TRY(ensure(c, c->prep_raw, std::max<uint64_t>(4 * mp.n_raw, 16)));
   }
-  const StageSpan in[] = {{commitments, (size_t)(4 * n_com), &c->prep_com}, {proofs, (size_t)proof_offsets[B], &c->prep_proofs},
-                          {r_bytes, 64 * (size_t)B, &c->prep_r}, {tab.data(), t_end, &c->mx_tab}};
+  for (size_t u = 0; u < mp.uniq.size(); ++u) ((PrepPlan*)(mp.tab.data() + mp.t_plans))[u] = plans[mp.uniq[u]]->dev;
+  const StageSpan in[] = {{commitments, (size_t)(4 * mp.n_com), &c->prep_com}, {proofs, (size_t)proof_offsets[B], &c->prep_proofs},
+                          {r_bytes, 64 * (size_t)B, &c->prep_r}, {mp.tab.data(), mp.t_end, &c->mx_tab}};
   TRY(stage_inputs(c, in));
   hipStream_t L = c->stream_l;
   const char* dt = (const char*)c->mx_tab.p;
   Job job;
   job.d_dyn_scalars = (const uint32_t*)c->prep_dyn_sc.p;
   job.d_dyn_points = (const uint32_t*)c->prep_dyn_pt.p;
-  job.d_dyn_offsets = (const uint64_t*)(dt + t_doff);
-  job.n_dyn = n_dyn;
+  job.d_dyn_offsets = (const uint64_t*)(dt + mp.t_doff);
+  job.n_dyn = mp.n_dyn;
   job.d_st_scalars = (const uint32_t*)c->prep_st_sc.p;
   job.d_st_index = (const uint32_t*)c->mx_st_index.p;
-  job.d_st_offsets = (const uint64_t*)(dt + t_soff);
-  job.n_static = n_st;
+  job.d_st_offsets = (const uint64_t*)(dt + mp.t_soff);
+  job.n_static = mp.n_st;
   job.d_static_rows = ps->rows;
   job.n_msm = B;
   job.d_wellformed = (const uint32_t*)c->prep_wf.p;      // folded into the accept bitmap on the device
+  const MixGroupTable gt = {mp.n_checks, mp.n_grouped, mp.n_rows, (const MixStmt*)(dt + mp.t_stmts), (const MixGroup*)(dt + mp.t_grp),
+                            (const uint32_t*)(dt + mp.t_mem), (const uint64_t*)(dt + mp.t_goff), mp.max_ns};
   int Pg = 1;
   if (grouped) {
-    gt.d_stmts = (const MixStmt*)(dt + t_stmts);
-    gt.d_groups = (const MixGroup*)(dt + t_grp);
-    gt.d_members = (const uint32_t*)(dt + t_mem);
-    gt.d_row_offsets = (const uint64_t*)(dt + t_goff);
     TRY(mixed_group_reserve(c, job, ps, gt, &Pg));
     Launch l(c, "k_batch_init", L);
     hipLaunchKernelGGL(k_batch_init, dim3(blocks_for(B, 256)), dim3(256), 0, L, (uint32_t*)c->status.p, (uint32_t*)c->msm_fail.p,
                        (uint32_t*)nullptr, B);
   }
-  const PrepPlan* d_plans = (const PrepPlan*)(dt + t_plans);
-  const MixStmt* d_stmts = (const MixStmt*)(dt + t_stmts);
-  const uint32_t* d_order = (const uint32_t*)(dt + t_order);
+  const PrepPlan* d_plans = (const PrepPlan*)(dt + mp.t_plans);
+  const MixStmt* d_stmts = (const MixStmt*)(dt + mp.t_stmts);
+  const uint32_t* d_order = (const uint32_t*)(dt + mp.t_order);
   const uint32_t* d_com = (const uint32_t*)c->prep_com.p;
   const uint32_t* d_r = (const uint32_t*)c->prep_r.p;
   uint32_t* d_pw = (uint32_t*)c->prep_pw.p;
@@ -3827,13 +3702,13 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     }
     {
       Launch l(c, "k_mx_challenges", L);
-      hipLaunchKernelGGL(k_mx_challenges, dim3(B), dim3(128), max_nch * 32, L, d_plans, d_stmts, d_order,
+      hipLaunchKernelGGL(k_mx_challenges, dim3(B), dim3(128), mp.max_nch * 32, L, d_plans, d_stmts, d_order,
                          (const uint32_t*)c->prep_raw.p, (const uint32_t*)d_pw, d_r, d_ch, d_wf, grouped ? 1u : 0u);
     }
   } else {
     Launch l(c, "k_mx_transcript", L);
-    hipLaunchKernelGGL(k_mx_transcript, dim3((unsigned)(lane_order.size() / 64)), dim3(64), 0, L, d_plans, d_stmts,
-                       (const uint32_t*)(dt + t_lanes), d_com, (const uint32_t*)d_pw, d_r, d_ch, d_wf, grouped ? 1u : 0u);
+    hipLaunchKernelGGL(k_mx_transcript, dim3((unsigned)(mp.n_lanes / 64)), dim3(64), 0, L, d_plans, d_stmts,
+                       (const uint32_t*)(dt + mp.t_lanes), d_com, (const uint32_t*)d_pw, d_r, d_ch, d_wf, grouped ? 1u : 0u);
   }
   if (grouped) {                      // (queued behind the transcript's launches, as the homogeneous pipeline queues k_points_tables)
     hipStream_t H1 = c->serial ? L : c->stream;
@@ -3841,33 +3716,31 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     decompress_launch(c, job, H1);
     HIP_TRY(c, hipEventRecord(c->ev_dig, H1));      // msm_fail is final: the checks leave such statements out
   }
-  {
-    // (the attribute is the same for every call: LDS of a CU, the bound plan_finish_inner holds every plan to)
-    HIP_TRY(c, hipFuncSetAttribute((const void*)k_mx_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    for (int k = 0; k < 2; ++k) {
-      const uint32_t n_k = class_start[k + 1] - class_start[k];
-      if (n_k == 0) continue;
-      Launch l(c, "k_mx_prepare", L);
-      hipLaunchKernelGGL(k_mx_prepare, dim3(n_k), dim3(256), class_lds[k], L, d_plans, d_stmts, d_order + class_start[k],
-                         (const uint32_t*)d_ch, (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->prep_st_sc.p, (uint32_t*)c->mx_st_index.p);
-    }
+  // (the attribute is the same for every call: LDS of a CU, the bound plan_finish_inner holds every plan to)
+  HIP_TRY(c, hipFuncSetAttribute((const void*)k_mx_prepare, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  for (int k = 0; k < 2; ++k) {
+    const uint32_t n_k = mp.class_start[k + 1] - mp.class_start[k];
+    if (n_k == 0) continue;
+    Launch l(c, "k_mx_prepare", L);
+    hipLaunchKernelGGL(k_mx_prepare, dim3(n_k), dim3(256), mp.class_lds[k], L, d_plans, d_stmts, d_order + mp.class_start[k],
+                       (const uint32_t*)d_ch, (uint32_t*)c->prep_dyn_sc.p, (uint32_t*)c->prep_st_sc.p, (uint32_t*)c->mx_st_index.p);
   }
-  for (uint32_t b0 = 0; b0 < n_large; b0 += lp_slice(lp_slots)) {      // slices of the workspace, one after the other
-    const LpMixed src = {d_plans, d_stmts, d_order + class_start[2] + b0, (const uint32_t*)d_ch, (uint32_t*)c->prep_dyn_sc.p,
+  for (uint32_t b0 = 0; b0 < n_large; b0 += lp_slice(mp.lp_slots)) {      // slices of the workspace, one after the other
+    const LpMixed src = {d_plans, d_stmts, d_order + mp.class_start[2] + b0, (const uint32_t*)d_ch, (uint32_t*)c->prep_dyn_sc.p,
                          (uint32_t*)c->prep_st_sc.p, (uint32_t*)c->mx_st_index.p};
-    lp_launch_all(c, L, src, std::min(lp_slice(lp_slots), n_large - b0), lp_targets, lp_pn, lp_slots);
+    lp_launch_all(c, L, src, std::min(lp_slice(mp.lp_slots), n_large - b0), mp.lp_targets, mp.lp_pn, mp.lp_slots);
   }
   if (grouped) {
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_p, L));
     TRY(mixed_group_tail(c, job, ps, gt, Pg));
-    c->last.mixed = true; c->last.mx_groups = n_groups2; c->last.mx_stmts = gt.n_grouped;       // (counted when the call is waited for)
+    c->last.mixed = true; c->last.mx_groups = mp.n_pairs; c->last.mx_stmts = gt.n_grouped;       // (counted when the call is waited for)
     return ZKGPU_OK;
   }
   gather_points();
   HIP_TRY(c, hipGetLastError());
   // (the pipeline's first launch follows the preparation on the light stream; its other streams wait for that)
-  if (piped) {
+  if (pipe_eligible(c, ps, B, mp.n_dyn, mp.n_st)) {
     TRY(pipe_enqueue(c, job, ps, nullptr));
     c->last.mixed = true; c->last.mx_groups = c->last.mx_stmts = 0;
     return ZKGPU_OK;
