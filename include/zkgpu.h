@@ -555,6 +555,12 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * The mapping to upstream's VMError variants is a recollection like the format itself. */
 #define ZKGPU_TXFORMAT_RECOLLECTED_V1 1
 #define ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS 2   /* same wire format as ..._V1; status bytes carry a reason */
+/* A FLAG, or-ed to one of the two formats above (alone it is ZKGPU_EINVAL): the contract IDs, the anchor ratchets and the
+ * Merkle tree of the transaction ID -- about fifteen of the twenty Merlin transcripts of a payment -- are computed on the
+ * device (one lane per transaction) instead of on `host_threads` CPUs; the MuSig coefficients and the signature challenge
+ * stay on the host.  Same bytes read, same bitmap, same status bytes.  There is no host fallback: an error of that stage is
+ * an error of the call like any other (fail-closed).  Opt-in: whether it pays depends on the host. */
+#define ZKGPU_TXFORMAT_HASH_ON_DEVICE 256   /* 0x100 (decimal like every constant here: the binding generator reads decimals) */
 #define ZKGPU_TXSTATUS_ACCEPTED 0
 #define ZKGPU_TXSTATUS_REJECTED 1                 /* rejected, reason not available (V1 format, or any error path) */
 #define ZKGPU_TXSTATUS_OUTSIDE_SUBSET 2

@@ -345,6 +345,13 @@ impl GpuVerifier {
         check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS) }, self.err())
     }
 
+    /// Either format with `ZKGPU_TXFORMAT_HASH_ON_DEVICE`: contract IDs, anchors and the transaction ID are hashed on the
+    /// device instead of on the host's threads.  Same verdicts; opt-in (whether it pays depends on the host's CPUs).
+    pub fn enable_recollected_tx_format_hashing_on_device(&self, with_reasons: bool) -> Result<(), Error> {
+        let base = if with_reasons { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS } else { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1 };
+        check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, base | sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE) }, self.err())
+    }
+
     /// Drop-in for `txs.iter().map(|tx| tx.verify(bp_gens))` on `Tx::encode()` bytes (payment subset): VM, transaction
     /// ID, MuSig / Schnorr signature and cloak proof.  `host_threads`: 0 = the CPUs the process may keep busy.
     pub fn verify_txs(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<TxVerdict>, Error> {

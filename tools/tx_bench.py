@@ -1,5 +1,7 @@
 """zkgpu_tx_verify_batch on the committed 1024 transactions (per-stage times with ZKGPU_PROVER_TIMING=1).
-usage: tx_bench.py [copies of the fixture per call] [block chunk] [tx chunk]   (TX_BENCH_FORMAT=2: the format with reason codes)"""
+usage: tx_bench.py [--device-hashing] [--host-threads N] [--in-flight K] [copies of the fixture per call] [block chunk] [tx chunk]
+(TX_BENCH_FORMAT=2: the format with reason codes; --device-hashing: or-ed with ZKGPU_TXFORMAT_HASH_ON_DEVICE; --host-threads N: the
+host_threads of every call, 0 = the CPUs the process may use; --in-flight K: also K calls of that size through submit / wait)"""
 import os as _os; _os.environ.setdefault("ZKGPU_TEST_HOOKS", "1")   # the profile / mode hooks (include/zkgpu_hooks.h) are not exports
 import ctypes as C
 import os, sys, time
@@ -9,16 +11,28 @@ import numpy as np
 from gpu_util import load_tx_fixture
 from zkvm_amd import Context
 from zkvm_amd.verifier import BulletproofGens, BlockVerifier
+DEVICE_HASHING = "--device-hashing" in sys.argv
+if DEVICE_HASHING:
+    sys.argv.remove("--device-hashing")
+def _option(name, default):
+    if name not in sys.argv:
+        return default
+    i = sys.argv.index(name)
+    v = int(sys.argv[i + 1])
+    del sys.argv[i: i + 2]
+    return v
+HOST_THREADS = _option("--host-threads", None)
+IN_FLIGHT = _option("--in-flight", 0)
 rep = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 txs = load_tx_fixture() * rep
 ctx = Context(0)
 gens = BulletproofGens(ctx, 256, table_bits=16)
 chunk = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 bv = BlockVerifier(ctx, gens, chunk=chunk)
-bv.set_tx_format(int(os.environ.get("TX_BENCH_FORMAT", bv.TXFORMAT_RECOLLECTED_V1)))     # TX_BENCH_FORMAT=2: status bytes with reasons
+bv.set_tx_format(int(os.environ.get("TX_BENCH_FORMAT", bv.TXFORMAT_RECOLLECTED_V1)) | (bv.TXFORMAT_HASH_ON_DEVICE if DEVICE_HASHING else 0))
 if len(sys.argv) > 3:
     bv.set_tx_chunk(int(sys.argv[3]))
-HT = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+HT = HOST_THREADS if HOST_THREADS is not None else int(sys.argv[4]) if len(sys.argv) > 4 else 0
 if os.environ.get("TX_BENCH_TRANSCRIPT_MODE"):        # experiment: the lanes' transcript replay (0 automatic, 1 lane, 2 cooperative)
     for i in range(bv.lanes()):
         bv.lane(i).set_transcript_mode(int(os.environ["TX_BENCH_TRANSCRIPT_MODE"]))
@@ -26,7 +40,7 @@ bv.verify_txs(txs[:64])
 blob, lens = b"".join(txs), [len(t) for t in txs]
 for _ in range(4):
     t0 = time.perf_counter()
-    bm, st = bv.verify_txs_packed(blob, lens)
+    bm, st = bv.verify_txs_packed(blob, lens, HT)
     dt = time.perf_counter() - t0
     print("%.2f ms, %.0f tx/s (%d transactions per call)" % (dt * 1e3, len(txs) / dt, len(txs)), file=sys.stderr)
 assert os.environ.get("ZKGPU_TEST_TX_FREE_HASHING") == "1" or not any(st)      # (a -DZK_MEASURE_FREE_HASHING build with that variable set makes every signature fail)
@@ -39,6 +53,17 @@ for _ in range(3):
     rc = bv.lib.zkgpu_tx_verify_batch(bv.h, len(lens), blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), HT, bmb, stb)
     dt = time.perf_counter() - t0
     print("library call alone: %.2f ms, %.0f tx/s (rc %d)" % (dt * 1e3, len(txs) / dt, rc), file=sys.stderr)
+if IN_FLIGHT:
+    for _ in range(5):
+        t0 = time.perf_counter()
+        ids = [bv.submit_txs_packed(blob, lens, HT) for _ in range(IN_FLIGHT)]
+        for i in ids:
+            bv.wait_txs(i)
+        dt = time.perf_counter() - t0
+        print("%d calls in flight: %.2f ms, %.0f tx/s" % (IN_FLIGHT, dt * 1e3, IN_FLIGHT * len(txs) / dt), file=sys.stderr)
+if DEVICE_HASHING:
+    import struct
+    print("transaction IDs from the device so far: %d" % struct.unpack("<Q", ctx.debug_read("tx_hashed_on_device", 8)), file=sys.stderr)
 ctx.profile(True); ctx.profile_reset()
 bm, st = bv.verify_txs(txs)
 ctx.profile(False)

@@ -1168,3 +1168,134 @@ extern "C" int zkhost_txcall_pair_selftest(size_t batch, size_t split, const uin
   for (size_t i = split; i < batch; ++i) { const size_t q = i - split; if ((bits[1][q / 8] >> (q % 8)) & 1) accept_bitmap[i / 8] |= (uint8_t)(1u << (i % 8)); }
   return 0;
 }
+
+// ---- the hash tape of a flagged transaction call (tx_hash_tape.hpp) on the CPU: the VM's structure pass over `count`
+// ---- transactions as ONE chunk, the flattener, the interpreter -- the function k_tx_hash runs per lane -- and, beside it,
+// ---- run_plan over the same plans.  Out: status per transaction; the block's head (16 words; its last, unused word holds
+// ---- the STROBE position at which a contract-ID transcript starts, for the test's model of the rate boundary), its piece
+// ---- records (4 words each, pieces_cap of them at most) and lane table; per
+// ---- transaction its shape on the tape (0xffffffff: not on it) and first slot; the tape's transaction IDs (32 bytes per
+// ---- transaction, zero where not on it); every slot as the tape left it and as run_plan did, and which of them the tape's
+// ---- three protocols write (the others are the host's MuSig slots, which the tape leaves zero).
+// ---- -> transactions on the tape, or -1 a plan the tape cannot hold, -2 the block fails hash_tape_check, -3 an output too small
+#include "tx_hash_tape.hpp"
+extern "C" long long zkhost_tx_hash_tape(const uint8_t* txs, const uint64_t* offs, size_t count, int threads, uint8_t* status,
+                                         uint32_t* head16, uint32_t* pieces, size_t pieces_cap, uint32_t* lanes, size_t lanes_cap, uint32_t* tx_shape, uint64_t* tx_slot0,
+                                         uint8_t* txid, uint8_t* slots_tape, uint8_t* slots_plan, uint8_t* slot_kept, size_t slots_cap) {
+  using namespace zk::zkvm;
+  TxHashTape tape;
+  tape.reset(count);
+  std::vector<TxStatement> st(count);
+  std::atomic<int> bad{0};
+  zk::host_parallel((count + 7) / 8, threads, [&](size_t g) {
+    const uint8_t* p[8]; size_t l[8];
+    const size_t first = 8 * g, n = std::min<size_t>(8, count - first);
+    for (size_t i = 0; i < n; ++i) { p[i] = txs + offs[first + i]; l[i] = (size_t)(offs[first + i + 1] - offs[first + i]); }
+    if (!tx_prepare_many_taped(p, l, &st[first], n, tape, first)) bad = 1;
+  });
+  for (size_t i = 0; i < count; ++i) { status[i] = (uint8_t)st[i].status; tx_shape[i] = TAPE_IDLE; tx_slot0[i] = 0; }
+  std::memset(txid, 0, 32 * count);
+  if (bad) return -1;
+  tape.finish(threads);
+  const HashTapeHead& h = tape.head();
+  if (!hash_tape_check(tape.block(), h.words)) return -2;
+  std::memcpy(head16, &h, 64);
+  if (h.n_lanes > lanes_cap || h.n_slots > slots_cap || h.n_pieces > pieces_cap) return -3;
+  std::memcpy(pieces, tape.block() + h.pieces, 16 * (size_t)h.n_pieces);
+  std::memcpy(lanes, tape.block() + h.lanes, 4 * (size_t)h.n_lanes);
+  std::vector<uint32_t> protos, sl, ids;
+  std::vector<uint8_t> labels;
+  hash_tape_constants(protos, labels);
+  head16[15] = protos[(size_t)P_CONTRACTID * TAPE_PROTO_WORDS + 50];
+  hash_tape_run_host(tape.block(), protos, labels, sl, ids);
+  std::memcpy(slots_tape, sl.data(), 32 * (size_t)h.n_slots);
+  std::memset(slots_plan, 0, 32 * (size_t)h.n_slots);
+  std::memset(slot_kept, 0, h.n_slots);
+  TxPlan P; TxSlots out; TxStatement s2;
+  for (size_t t = 0; t < tape.n_tx(); ++t) {
+    const size_t i = tape.position(t);
+    const uint32_t* rec = tape.block() + h.txs + 4 * t;
+    tx_shape[i] = rec[0]; tx_slot0[i] = rec[2];
+    std::memcpy(txid + 32 * i, &ids[8 * t], 32);
+    P.only = 0xff;
+    tx_structure(txs + offs[i], (size_t)(offs[i + 1] - offs[i]), s2, P, out);
+    if (s2.status != TX_OK || (uint64_t)rec[2] + P.n_slots > h.n_slots) return -2;
+    run_plan(P, slots_plan + 32 * (size_t)rec[2]);
+    for (const HashJob& j : P.jobs) if (tape_keeps(j.proto)) slot_kept[rec[2] + j.out_slot] = 1;
+  }
+  return (long long)tape.n_tx();
+}
+
+// ---- the scheduling of a FLAGGED call (a device that hashes: TxDevice::hashes) on the CPU: the stand-in above, and the
+// ---- tapes of the chunks interpreted by tx_hash_run on a thread of their own after a random delay.  hash_fail_at: the
+// ---- n-th hash_enqueue / hash_collect reports an error (-1: none).  *hashed: transaction IDs the stand-in produced.
+namespace {
+class HostHashingTxDevice : public HostTxDevice {
+ public:
+  HostHashingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int hash_fail_at)
+      : HostTxDevice(txs, offs, batch, proof_ok, seed, -1), hrng_(seed ^ 0x9e3779b9u), hash_fail_at_(hash_fail_at) { hash_tape_constants(protos_, labels_); }
+  ~HostHashingTxDevice() override { for (auto& s : h_) if (s.th.joinable()) s.th.join(); }
+  bool hashes() const override { return true; }
+  TxHashTape* hash_tape(int slot) override { return &h_[slot].tape; }
+  int hash_enqueue(int slot, const TxHashTape& tape) override {
+    HashStage& s = h_[slot];
+    if (s.th.joinable()) { herr_ = "hash slot reused before it was collected"; return -1; }
+    if (&tape != &s.tape || !hash_tape_check(tape.block(), tape.head().words)) { herr_ = "not this slot's tape, or a block that fails its check"; return -1; }
+    if (hash_failing()) { herr_ = "injected fault of the hashing stage"; return -3; }
+    s.done = false;
+    const unsigned us = (unsigned)(hrng_() % 400);
+    s.th = std::thread([this, &s, us] {
+      std::this_thread::sleep_for(std::chrono::microseconds(us));
+      hash_tape_run_host(s.tape.block(), protos_, labels_, s.slots, s.ids);
+      s.done = true;
+    });
+    return 0;
+  }
+  bool hash_done(int slot) override { return h_[slot].done; }
+  int hash_collect(int slot, uint8_t* txids, uint8_t*) override {
+    HashStage& s = h_[slot];
+    if (!s.th.joinable()) { herr_ = "nothing to collect in this hash slot"; return -1; }
+    s.th.join();
+    if (hash_failing()) { herr_ = "injected fault of the hashing stage"; return -3; }
+    std::memcpy(txids, s.ids.data(), 32 * s.tape.n_tx());
+    hashed_ += s.tape.n_tx();
+    return 0;
+  }
+  std::string last_error() override { return herr_.empty() ? HostTxDevice::last_error() : herr_; }
+  uint64_t hashed() const { return hashed_; }
+
+ private:
+  struct HashStage { TxHashTape tape; std::thread th; std::atomic<bool> done{true}; std::vector<uint32_t> slots, ids; };
+  bool hash_failing() { return hash_fail_at_ >= 0 && hops_++ == hash_fail_at_; }
+  HashStage h_[2];
+  std::vector<uint32_t> protos_;
+  std::vector<uint8_t> labels_;
+  std::mt19937 hrng_;
+  const int hash_fail_at_;
+  int hops_ = 0;
+  uint64_t hashed_ = 0;
+  std::string herr_;
+};
+}  // namespace
+
+extern "C" int zkhost_txcall_hashing_selftest(size_t batch, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok, int host_threads,
+                                              size_t chunk, uint32_t delay_seed, int hash_fail_at, int n_slots, uint8_t* accept_bitmap,
+                                              uint8_t* status, size_t* n_chunks, size_t* leaked, uint64_t* hashed) {
+  std::memset(accept_bitmap, 0, (batch + 7) / 8);
+  std::memset(status, TX_INVALID, batch);
+  std::vector<TxStatement> store;
+  HostHashingTxDevice dev(txs, offs, batch, proof_ok, delay_seed, hash_fail_at);
+  int rc;
+  {
+    TxCall call(dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, accept_bitmap, status, n_slots);
+    *n_chunks = call.n_chunks();
+    rc = call.run();
+  }
+  *leaked = dev.leaked();
+  *hashed = dev.hashed();
+  if (rc != 0) {
+    std::memset(accept_bitmap, 0, (batch + 7) / 8);
+    for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;
+  }
+  return rc;
+}

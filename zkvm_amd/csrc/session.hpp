@@ -14,6 +14,7 @@
 #pragma once
 #include "comm_frame.hpp"
 #include "tx_call.hpp"
+#include "tx_hash_kernels.hpp"
 #include "zkvm_tx.hpp"
 
 #include <deque>
@@ -99,6 +100,19 @@ struct zkgpu_verifier {
   int lanes_requested = 0, lanes_dropped = 0;           // lanes whose light stream shared a hardware queue with an earlier lane's were not kept
   int tx_format = 0;                                    // zkgpu_verifier_set_tx_format: 0 = no serialized-transaction format enabled;
                                                         // 1 and 2 read the same bytes, 2 writes a reason into the status bytes
+  bool tx_hash_on_device = false;                       // the format's flag ZKGPU_TXFORMAT_HASH_ON_DEVICE (tx_format keeps the low byte)
+  // its stage, per key / signature slot: a stream of its own (never behind the proofs), the tape's flattener, the tape on its
+  // way up (pinned, device), the slot memory, the IDs on their way down (device, pinned); and, once per verifier, the
+  // protocols' initial transcripts and the label table.  Made at the first flagged call; grow-only.
+  struct TxHashStage {
+    hipStream_t stream = nullptr;
+    zk::zkvm::TxHashTape tape;
+    void *h_in = nullptr, *h_out = nullptr;
+    size_t h_in_cap = 0, h_out_cap = 0, n_tx = 0;
+    Buffer d_tape, d_slots, d_txid;
+  };
+  TxHashStage tx_hash[2];
+  Buffer tx_hash_const;
   // zkgpu_tx_verify_batch: two contexts of their own for the key and the signature stages (each a pair of streams beside
   // the lanes'), and a ring of staging areas (pinned host + device, grow-only) for the cloak statements of the chunks in
   // flight -- nothing on that path allocates or frees device memory once the sizes have been seen (hipFree synchronises)
@@ -370,6 +384,7 @@ int zkgpu_verifier_create(zkgpu_ctx* ctx, const zkgpu_pointset* ps, size_t gens_
   batches_in_flight = std::min(batches_in_flight, 1 + MAX_FORKS);
   zkgpu_verifier* v = new zkgpu_verifier();
   v->root = ctx; v->ps = ps; v->gens_capacity = gens_capacity;
+  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; }
   v->lanes.push_back(ctx);
   v->lanes_requested = batches_in_flight;
   // A lane is worth having only if its light stream -- the latency-bound kernels of its batch: transcript, Horner chains,
@@ -446,6 +461,13 @@ void zkgpu_verifier_destroy(zkgpu_verifier* v) {
     for (auto& a : v->tx_arenas) { if (a.h_pin) (void)hipHostFree(a.h_pin); if (a.dev) (void)hipFree(a.dev); if (a.copied) (void)hipEventDestroy(a.copied); }
     for (auto& hs : v->host_stages) { if (hs.pin) (void)hipHostFree(hs.pin); if (hs.dev) (void)hipFree(hs.dev); if (hs.copied) (void)hipEventDestroy(hs.copied); }
     if (v->copy_stream) (void)hipStreamDestroy(v->copy_stream);
+    for (auto& hs : v->tx_hash) {
+      if (hs.stream) { (void)hipStreamSynchronize(hs.stream); (void)hipStreamDestroy(hs.stream); }
+      if (hs.h_in) (void)hipHostFree(hs.h_in);
+      if (hs.h_out) (void)hipHostFree(hs.h_out);
+      for (Buffer* b : {&hs.d_tape, &hs.d_slots, &hs.d_txid}) if (b->p) (void)hipFree(b->p);
+    }
+    if (v->tx_hash_const.p) (void)hipFree(v->tx_hash_const.p);
   }
   for (auto& kv : v->plans) if (kv.second) zkgpu_cloak_plan_destroy(kv.second);
   delete v;
@@ -1613,9 +1635,11 @@ int zkgpu_verifier_verify_sharded(zkgpu_verifier* v, zkgpu_comm* cm, size_t batc
 // (the verdicts stay with their tickets / runs) -- a synchronous call on a context with a batch in flight would
 // overwrite that batch's status words and pinned result buffer (and is refused by the context: refuse_if_pending).
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
-  if (!v || (format != 0 && format != ZKGPU_TXFORMAT_RECOLLECTED_V1 && format != ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS)) return ZKGPU_EINVAL;
+  const int base = format & ~ZKGPU_TXFORMAT_HASH_ON_DEVICE;          // (the flag goes with a format: alone it names none)
+  if (!v || (format != 0 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS)) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> lk(v->mu);
-  v->tx_format = format;
+  v->tx_format = base;
+  v->tx_hash_on_device = (format & ZKGPU_TXFORMAT_HASH_ON_DEVICE) != 0;
   return ZKGPU_OK;
 }
 
@@ -1755,14 +1779,35 @@ namespace {
 // The device side of a transaction call (tx_call.hpp: TxDevice) on a verifier: key stages on aux_keys[slot], signature
 // stages on aux_sigs[slot] (contexts of their own, each a pair of streams beside the lanes'), cloak proofs as blocks of
 // mixed shapes on the lanes, staged through the verifier's ring of pinned / device areas.  v->mu is held by the call.
-static_assert(zk::zkvm::TxCall::OK == ZKGPU_OK && zk::zkvm::TxCall::ENOMEM_ == ZKGPU_ENOMEM, "tx_call.hpp restates two status codes");
+static_assert(zk::zkvm::TxCall::OK == ZKGPU_OK && zk::zkvm::TxCall::ENOMEM_ == ZKGPU_ENOMEM && zk::zkvm::TxCall::EINVAL_ == ZKGPU_EINVAL, "tx_call.hpp restates three status codes");
 class GpuTxDevice : public zk::zkvm::TxDevice {
  public:
   // slot_base / arena_base: which of the verifier's stage contexts and staging areas this call uses (a call alone: slots 0
   // and 1, areas 0 .. RING - 1; two rounds in flight: one slot and one set of areas each)
   // reasons: a format-2 call -- every stage also brings back one reason byte per row (tx_reason_kernels.hpp)
-  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false) : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons) {}
+  // hashes: the format's flag ZKGPU_TXFORMAT_HASH_ON_DEVICE -- the transaction IDs of every chunk come from k_tx_hash
+  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false, bool hashes = false)
+      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes) {}
   bool reasons() const override { return reasons_; }
+  bool hashes() const override { return hashes_; }
+  zk::zkvm::TxHashTape* hash_tape(int slot) override { return &hash(slot).tape; }
+  // one copy up, one launch, one copy of the IDs down, on the stage's own high-priority stream
+  int hash_enqueue(int slot, const zk::zkvm::TxHashTape& tape) override {
+    const int rc = hash_queue(slot, tape);
+    if (rc != ZKGPU_OK) err_ = std::string("transaction-ID hashing stage: ") + zkgpu_last_error(keys(slot));
+    return rc;
+  }
+  bool hash_done(int slot) override {
+    zkgpu_verifier::TxHashStage& hs = hash(slot);
+    if (!hs.stream || hs.n_tx == 0) return true;
+    DeviceGuard g(v_->root->device);
+    return hipStreamQuery(hs.stream) != hipErrorNotReady;
+  }
+  int hash_collect(int slot, uint8_t* txids, uint8_t*) override {
+    const int rc = hash_wait(slot, txids);
+    if (rc != ZKGPU_OK) err_ = std::string("transaction-ID hashing stage: ") + zkgpu_last_error(keys(slot));
+    return rc;
+  }
   const uint8_t* basepoint() override { return v_->basepoint; }
   int keys_enqueue(int slot, const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t rows) override {
     if (reasons_) { const int rc = seen(stage_reasons_reserve(keys(slot), rows, true), keys(slot)); if (rc != ZKGPU_OK) return rc; }
@@ -1795,7 +1840,18 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     st->run = block_start(v_, st->blk, true, reasons_);
     v_->chunk = saved_chunk;
     if (!st->run) { err_ = v_->last_error; return ZKGPU_ENOMEM; }
-    if (st->run->rc != ZKGPU_OK) { err_ = v_->last_error; return st->run->rc; }     // (proofs_finish still collects what was queued)
+    if (st->run->rc != ZKGPU_OK) {
+      // One device batch of the block could not be queued.  The call releases a chunk that was not started WITHOUT finishing
+      // it, and the block goes with it -- but batches of the block's other shapes may already be on lanes, and their requests
+      // refer to the block through the run: they are collected here, before the error leaves (found by injecting a fault at
+      // every runtime call of a call of four shapes: the next call collected such a request and read the freed block).
+      const int rc = st->run->rc;
+      err_ = v_->last_error;
+      std::vector<uint8_t> none((zkgpu_txblock_size(st->blk) + 7) / 8 + 1, 0);
+      (void)block_finish(v_, st->run, none.data(), nullptr);
+      st->run = nullptr;
+      return rc;
+    }
     return ZKGPU_OK;
   }
   bool proofs_done(void* handle) override {                // have the lanes finished every batch of this block?  (never blocks)
@@ -1834,13 +1890,80 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
 
  private:
   struct Staged { zkgpu_txblock* blk = nullptr; zkgpu_verifier::BlockRun* run = nullptr; };
+  zkgpu_verifier::TxHashStage& hash(int slot) const { return v_->tx_hash[(sb_ + slot) & 1]; }
+  // (errors are kept by the slot's key context, whose runtime-call macros these are)
+  static int pinned_grow(zkgpu_ctx* c, void*& p, size_t& cap, size_t bytes) {
+    if (bytes <= cap) return ZKGPU_OK;
+    if (p) HIP_TRY(c, hipHostFree(p));
+    p = nullptr; cap = 0;
+    HIP_TRY(c, hipHostMalloc(&p, bytes + bytes / 8 + 4096, hipHostMallocDefault));
+    cap = bytes + bytes / 8 + 4096;
+    return ZKGPU_OK;
+  }
+  int hash_queue(int slot, const zk::zkvm::TxHashTape& tape) {
+    using namespace zk::zkvm;
+    zkgpu_ctx* c = keys(slot);
+    zkgpu_verifier::TxHashStage& hs = hash(slot);
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    hs.n_tx = 0;
+    if (!hs.stream) {
+      int least = 0, greatest = 0;
+      HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+      HIP_TRY(c, hipStreamCreateWithPriority(&hs.stream, hipStreamNonBlocking, greatest));
+    }
+    if (!v_->tx_hash_const.p) {                          // once per verifier: the protocols' initial transcripts, the label table
+      std::vector<uint32_t> protos;
+      std::vector<uint8_t> labels;
+      hash_tape_constants(protos, labels);
+      const size_t pb = 4 * protos.size();
+      Buffer made;
+      TRY(ensure(c, made, pb + labels.size()));
+      hipError_t e = hipMemcpy(made.p, protos.data(), pb, hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = hipMemcpy((char*)made.p + pb, labels.data(), labels.size(), hipMemcpyHostToDevice);
+      if (e != hipSuccess) { (void)hipFree(made.p); HIP_TRY(c, e); }
+      v_->tx_hash_const = made;
+    }
+    const HashTapeHead& h = tape.head();
+    const size_t bytes = tape.bytes(), id_bytes = 32 * (size_t)h.n_tx;
+    TRY(pinned_grow(c, hs.h_in, hs.h_in_cap, bytes));
+    TRY(pinned_grow(c, hs.h_out, hs.h_out_cap, id_bytes));
+    TRY(ensure(c, hs.d_tape, bytes));
+    TRY(ensure(c, hs.d_slots, 32 * (size_t)h.n_slots + 32));
+    TRY(ensure(c, hs.d_txid, id_bytes));
+    memcpy(hs.h_in, tape.block(), bytes);
+    HIP_TRY(c, hipMemcpyAsync(hs.d_tape.p, hs.h_in, bytes, hipMemcpyHostToDevice, hs.stream));
+    HashTapeView view{(const uint32_t*)hs.d_tape.p, (const uint32_t*)v_->tx_hash_const.p,
+                      (const uint8_t*)v_->tx_hash_const.p + 4 * (size_t)N_PROTO * TAPE_PROTO_WORDS, (uint32_t*)hs.d_slots.p, (uint32_t*)hs.d_txid.p};
+    {
+      Launch l(c, "k_tx_hash", hs.stream);
+      hipLaunchKernelGGL(zk::k_tx_hash, dim3(h.n_lanes / 64), dim3(64), 0, hs.stream, view, h.n_lanes);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));
+    hs.n_tx = h.n_tx;
+    return ZKGPU_OK;
+  }
+  int hash_wait(int slot, uint8_t* txids) {
+    zkgpu_ctx* c = keys(slot);
+    zkgpu_verifier::TxHashStage& hs = hash(slot);
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    const size_t n = hs.n_tx;
+    hs.n_tx = 0;
+    if (n == 0) return ZKGPU_OK;
+    HIP_TRY(c, hipStreamSynchronize(hs.stream));
+    memcpy(txids, hs.h_out, 32 * n);
+    { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_hashed_on_device += n; }
+    return ZKGPU_OK;
+  }
   int seen(int rc, zkgpu_ctx* where) { if (rc != ZKGPU_OK) err_ = zkgpu_last_error(where); return rc; }
   zkgpu_ctx* keys(int slot) const { return v_->aux_keys[(sb_ + slot) & 1]; }
   zkgpu_ctx* sigs(int slot) const { return v_->aux_sigs[(sb_ + slot) & 1]; }
   zkgpu_verifier* v_;
   const int sb_;
   const size_t ab_;
-  const bool reasons_;
+  const bool reasons_, hashes_;
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];
   std::string err_;
@@ -1916,7 +2039,7 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   TRY(tx_call_prepare(v));
   // (format 2 reads the same bytes and gives the same bits; what differs is what the status bytes say -- with no status
   // array there is nothing to say, and the call is the format-1 call)
-  GpuTxDevice dev(v, 0, 0, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS && status != nullptr);
+  GpuTxDevice dev(v, 0, 0, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS && status != nullptr, v->tx_hash_on_device);
   int rc;
   try {
     TxCall call(dev, v->tx_statements, v->tx_statements_kept, batch, txs, tx_offsets, host_threads, v->tx_chunk, accept_bitmap, status);
@@ -2051,7 +2174,7 @@ void tx_engine_main(zkgpu_verifier* v) {
         r.rc = tx_call_prepare(v, !active[0] && !active[1]);
         if (r.rc == ZKGPU_OK) {
           try {
-            r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS));
+            r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS, v->tx_hash_on_device));
             r.call.reset(new TxCall(*r.dev, set ? v->tx_statements_b : v->tx_statements, v->tx_statements_kept, r.pieces, threads, v->tx_chunk,
                                     r.bits.data(), r.status.data(), 1));
             r.call->set_on_news([&] { { std::lock_guard<std::mutex> nl(news_mu); news = true; } news_cv.notify_one(); });

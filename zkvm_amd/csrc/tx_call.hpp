@@ -25,10 +25,19 @@
 // beside the bit; verdicts() then writes, beside every clear bit, the LOWEST code that applies to the transaction -- the
 // order upstream would meet the faults in: decoding and the VM (16, host), r1cs::Verifier::verify (17 .. 19), the keys the
 // signature covers (20), the deferred signature check (21).  The bits are formed exactly as without reasons.
+//
+// A device that HASHES (TxDevice::hashes(): the format flag ZKGPU_TXFORMAT_HASH_ON_DEVICE) takes the contract IDs, the anchor
+// ratchets and the transaction-ID tree of every chunk off the staging thread: the second pass writes the chunk's plans into a
+// tape (tx_hash_tape.hpp) instead of running them, the calling thread queues the tape (hash_enqueue: one copy up, one launch,
+// one copy of the IDs down) and hands the IDs to the statements when they are back; the signature transcripts of a chunk then
+// wait for its IDs as they wait for its keys.  Two tapes may be in flight (one when two calls share the stage contexts).  There
+// is no host fallback: an error of the stage is an error of the call.
 #pragma once
 #include "host_pool.hpp"
+#include "tx_hash_tape.hpp"
 #include "zkvm_tx.hpp"
 
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -72,12 +81,20 @@ class TxDevice {
   virtual int sigs_collect(int slot, uint8_t* bits, uint8_t* why) = 0;
   virtual std::string last_error() = 0;
   virtual bool reasons() const { return false; }                            // does every stage bring back reason bytes?
+  // transaction IDs on the device.  hashes(): does the device take them?  hash_tape(slot): the flattener of that slot, kept
+  // by the device between calls (the staging thread fills it).  hash_enqueue queues the finished tape; hash_collect waits
+  // and writes 32 bytes per transaction of the tape, in the tape's order.  A device that does not hash is never asked.
+  virtual bool hashes() const { return false; }
+  virtual TxHashTape* hash_tape(int) { return nullptr; }
+  virtual int hash_enqueue(int, const TxHashTape&) { return -1; }
+  virtual bool hash_done(int) { return true; }                              // never blocks
+  virtual int hash_collect(int, uint8_t*, uint8_t*) { return -1; }
 };
 
 class TxCall {
  public:
   static constexpr size_t RING = 6;                      // staging areas for the proofs of chunks in flight
-  enum : int { OK = 0, ENOMEM_ = -4 };                   // (ZKGPU_OK / ZKGPU_ENOMEM: this header does not see zkgpu.h)
+  enum : int { OK = 0, EINVAL_ = -1, ENOMEM_ = -4 };     // (ZKGPU_OK / _EINVAL / _ENOMEM: this header does not see zkgpu.h)
   // status bytes of a call with reasons (ZKGPU_TXSTATUS_*, restated for the same reason; session.hpp asserts them)
   enum : uint8_t { WHY_NONE = 1, WHY_TX_INVALID = 16, WHY_PROOF_FIRST = 17, WHY_KEY = 20, WHY_SIGNATURE = 21 };
 
@@ -86,7 +103,7 @@ class TxCall {
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(batch), threads_(host_threads), accept_(accept_bitmap),
-        status_(status), reasons_(dev.reasons() && status != nullptr), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        status_(status), reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.resize(batch); len_.resize(batch);
     for (size_t i = 0; i < batch; ++i) { ptr_[i] = txs + tx_offsets[i]; len_[i] = (size_t)(tx_offsets[i + 1] - tx_offsets[i]); }
     plan(chunk_override, kept);
@@ -97,7 +114,7 @@ class TxCall {
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
-        reasons_(dev.reasons() && status != nullptr), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
     for (const Piece& pc : pieces)
       for (size_t i = 0; i < pc.batch; ++i) { ptr_.push_back(pc.txs + pc.tx_offsets[i]); len_.push_back((size_t)(pc.tx_offsets[i + 1] - pc.tx_offsets[i])); }
@@ -160,6 +177,7 @@ class TxCall {
     const size_t n_sig = n_sig_made_locked();
     for (size_t s = 0; s < n_sig; ++s) if (sig_stages_[s]->pending && !dev_.sigs_done((int)(s % n_slots_))) return false;
     for (const auto& k : chunks_) if (k->handle && k->started && !dev_.proofs_done(k->handle)) return false;
+    for (size_t c = next_hcollect_; c < next_hash_; ++c) if (hash_pending_[c] && !dev_.hash_done((int)(c % n_slots_))) return false;
     return true;
   }
   int finish() {
@@ -176,6 +194,7 @@ class TxCall {
     }
     // (after an error: nothing is left pending on the device)
     for (size_t s = 0; s < seg_.size(); ++s) keys_collect(s);
+    while (next_hcollect_ < next_hash_) hash_collect(next_hcollect_++);
     for (size_t s = 0; s < n_sig_made_locked(); ++s) sigs_collect(s);
     for (size_t c = 0; c < chunks_.size(); ++c) proofs_collect(*chunks_[c]);
     report();
@@ -250,6 +269,7 @@ class TxCall {
     }
     sig_stages_.reserve(sig_plan_.size());               // the calling thread indexes it while the staging thread appends: it never moves
     staged_.assign(n, 0); arena_free_.assign(n, 0); key_rows_.assign(n, 0); keys_arrived_.assign(n, 0);
+    tape_ready_.assign(n, 0); hash_pending_.assign(n, 0);
     const size_t k8 = kept & ~(size_t)7;                 // (a multiple of eight: see the chunk boundaries)
     if (store_.size() > k8) { store_.resize(k8); store_.shrink_to_fit(); }
     if (store_.size() < std::min(batch_, k8)) store_.resize(std::min(batch_, k8));
@@ -277,6 +297,24 @@ class TxCall {
     });
     std::lock_guard<std::mutex> lk(hm_);
     (only == ALL_PROTOS ? t_vm_ : t_keys_host_) += now() - t0;
+  }
+  // the second pass of a chunk on a device that hashes: the plans into the slot's tape, the MuSig jobs alone on the host
+  void vm_pass_taped(Chunk& k, TxHashTape& tape) {
+    const double t0 = now();
+    const size_t t_lo = k.lo, t_hi = k.lo + k.n;
+    std::atomic<int> bad{0};
+    tape.reset(k.n);
+    host_parallel((t_hi - t_lo + 7) / 8, threads_, [&](size_t g) {
+      const uint8_t* p[8];
+      size_t l[8];
+      const size_t first = t_lo + 8 * g, cnt = std::min<size_t>(8, t_hi - first);
+      for (size_t q = 0; q < cnt; ++q) { p[q] = ptr_[first + q]; l[q] = len_[first + q]; }
+      if (!tx_prepare_many_taped(p, l, &statement(first), cnt, tape, 8 * g)) bad = 1;
+    });
+    tape.finish(threads_);
+    std::lock_guard<std::mutex> lk(hm_);
+    if (bad) tape_failed_ = true;
+    t_vm_ += now() - t0;
   }
   void scan(Chunk& k, Segment& sg) {                    // which transactions the VM accepts
     sg.g_lo = k.g0 = live_all_.size();
@@ -402,19 +440,31 @@ class TxCall {
       for (size_t ci = run.first; ci < run.last; ++ci) {   // second pass, chunk by chunk
         {
           std::unique_lock<std::mutex> lk(hm_);
-          make_sig_stages(lk, ci);
+          make_sig_stages(lk, std::min(ci, ids_upto_));
           if (quit_) return;
+        }
+        if (hashes_) {                                   // the chunk's tape: its slot is free once chunk ci - n_slots has been collected
+          {
+            std::unique_lock<std::mutex> lk(hm_);
+            hcv_.wait(lk, [&] { return quit_ || ids_upto_ + n_slots_ > ci; });
+            if (quit_) return;
+          }
+          vm_pass_taped(*chunks_[ci], *dev_.hash_tape((int)(ci % n_slots_)));
+          std::lock_guard<std::mutex> lk(hm_);
+          tape_ready_[ci] = 1;
+          news();
+          continue;
         }
         vm_pass(*chunks_[ci], ALL_PROTOS);
         std::lock_guard<std::mutex> lk(hm_);
-        hashed_upto_ = ci + 1;
+        hashed_upto_ = ids_upto_ = ci + 1;
       }
     }
     std::unique_lock<std::mutex> lk(hm_);
     for (;;) {
-      make_sig_stages(lk, hashed_upto_);
+      make_sig_stages(lk, ids_upto_);
       if (quit_ || all_sigs_made_) return;
-      hcv_.wait(lk, [&] { return quit_ || keys_back(sig_plan_[sig_next_]); });
+      hcv_.wait(lk, [&] { return quit_ || (keys_back(sig_plan_[sig_next_]) && sig_plan_[sig_next_].last <= ids_upto_); });
     }
   }
   void stop_stager() {
@@ -445,6 +495,23 @@ class TxCall {
     if (rc != OK) note(rc, dev_.last_error());
     t_wait_ += now() - t0;
     mark("signatures collected, stage", s);
+  }
+  // the IDs of chunk c, from the device to the statements; the staging thread is told (ids_upto_)
+  void hash_collect(size_t c) {
+    Chunk& k = *chunks_[c];
+    if (hash_pending_[c]) {
+      hash_pending_[c] = 0;
+      const double t0 = now();
+      const TxHashTape& tape = *dev_.hash_tape((int)(c % n_slots_));
+      hash_ids_.resize(32 * tape.n_tx() + 32);
+      const int rc = dev_.hash_collect((int)(c % n_slots_), hash_ids_.data(), nullptr);
+      if (rc != OK) note(rc, dev_.last_error());
+      else for (size_t t = 0; t < tape.n_tx(); ++t) memcpy(statement(k.lo + tape.position(t)).txid, &hash_ids_[32 * t], 32);
+      t_wait_ += now() - t0;
+      mark("transaction IDs collected, chunk", c);
+    }
+    { std::lock_guard<std::mutex> lk(hm_); ids_upto_ = c + 1; }
+    hcv_.notify_all();
   }
   void proofs_collect(Chunk& k) {
     if (k.handle) {
@@ -485,7 +552,7 @@ class TxCall {
     if (finished_) return false;
     if (rc_ != OK) { finished_ = true; return true; }
     const size_t n_seg = seg_.size(), n_chunks = chunks_.size();
-    bool progress = false, sigs_all, rows = false, st_ready = false, ring_free = true;
+    bool progress = false, sigs_all, rows = false, st_ready = false, ring_free = true, tape_ready = false;
     size_t sig_avail;
     {
       std::lock_guard<std::mutex> lk(hm_);
@@ -494,8 +561,26 @@ class TxCall {
       if (next_key_ < n_seg) rows = key_rows_[next_key_] != 0;
       if (next_stage_ < n_chunks) st_ready = staged_[next_stage_] != 0;
       if (next_stage_ >= RING) ring_free = arena_free_[next_stage_ - RING] != 0;
+      if (hashes_ && next_hash_ < n_chunks) tape_ready = tape_ready_[next_hash_] != 0;
+      if (tape_failed_) note(EINVAL_, "a transaction's hash plan does not fit the device's tape");
     }
-    if (next_kcollect_ == n_seg && next_stage_ == n_chunks && sigs_all && next_sig_ == sig_avail) { finished_ = true; return true; }
+    if (next_kcollect_ == n_seg && next_stage_ == n_chunks && sigs_all && next_sig_ == sig_avail && (!hashes_ || next_hcollect_ == n_chunks)) { finished_ = true; return true; }
+    if (rc_ == OK && tape_ready && next_hcollect_ + n_slots_ > next_hash_) {       // (its slot is free once chunk next_hash - n_slots is collected)
+      const TxHashTape& tape = *dev_.hash_tape((int)(next_hash_ % n_slots_));
+      const double t0 = now();
+      if (tape.n_tx()) {
+        const int rc = dev_.hash_enqueue((int)(next_hash_ % n_slots_), tape);
+        if (rc != OK) note(rc, dev_.last_error()); else hash_pending_[next_hash_] = 1;
+      }
+      t_keys_ += now() - t0;
+      mark("transaction-ID tape queued, chunk", next_hash_);
+      ++next_hash_;
+      progress = true;
+    }
+    if (rc_ == OK && next_hcollect_ < next_hash_ && (!hash_pending_[next_hcollect_] || dev_.hash_done((int)(next_hcollect_ % n_slots_)))) {
+      hash_collect(next_hcollect_++);
+      progress = true;
+    }
     if (rows && next_kcollect_ + n_slots_ > next_key_) {                     // (its slot is free once segment next_key - n_slots is collected)
       Segment& sg = seg_[next_key_];
       mark("key rows ready, segment", next_key_);
@@ -612,6 +697,7 @@ class TxCall {
   uint8_t* const accept_;
   uint8_t* const status_;
   const bool reasons_;                                   // the device brings back reason bytes, and there is a status array to write them to
+  const bool hashes_;                                    // the device hashes the transaction IDs (tapes instead of the host's second-pass hashing)
   const bool timing_;
   const double t00_;
   const size_t n_slots_;                                 // key / signature stages in flight at once (2; 1 when two calls share the stage contexts)
@@ -628,6 +714,11 @@ class TxCall {
   std::mutex hm_;
   std::condition_variable hcv_;
   std::vector<char> staged_, arena_free_, key_rows_, keys_arrived_;
+  // (a device that hashes) tape_ready_[c]: the staging thread has finished chunk c's tape; ids_upto_: chunks whose transaction
+  // IDs are in the statements (without such a device: = hashed_upto_); tape_failed_: a plan the tape cannot hold
+  std::vector<char> tape_ready_;
+  size_t ids_upto_ = 0;
+  bool tape_failed_ = false;
   std::vector<std::unique_ptr<SigStage>> sig_stages_;
   size_t n_sig_stages_ = 0, sig_next_ = 0, hashed_upto_ = 0;
   bool all_sigs_made_ = false, quit_ = false, stager_failed_ = false;
@@ -638,7 +729,9 @@ class TxCall {
   std::vector<uint8_t> agg_, key_ok_;
   std::thread stager_;
   // calling thread only
-  size_t next_key_ = 0, next_kcollect_ = 0, next_stage_ = 0, next_sig_ = 0;
+  size_t next_key_ = 0, next_kcollect_ = 0, next_stage_ = 0, next_sig_ = 0, next_hash_ = 0, next_hcollect_ = 0;
+  std::vector<char> hash_pending_;
+  std::vector<uint8_t> hash_ids_;
   bool finished_ = false;
   int rc_ = OK;
   std::string error_;
