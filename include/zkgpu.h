@@ -561,6 +561,17 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * stay on the host.  Same bytes read, same bitmap, same status bytes.  There is no host fallback: an error of that stage is
  * an error of the call like any other (fail-closed).  Opt-in: whether it pays depends on the host. */
 #define ZKGPU_TXFORMAT_HASH_ON_DEVICE 256   /* 0x100 (decimal like every constant here: the binding generator reads decimals) */
+/* A second FLAG, or-ed to a format TOGETHER WITH ZKGPU_TXFORMAT_HASH_ON_DEVICE (valid values of the call: 0, 1, 2, 0x101,
+ * 0x102, 0x301, 0x302; without the first flag, or alone, it is ZKGPU_EINVAL): the signature's challenge c = H(txid, X, R) is
+ * formed on the device as well, from the transaction ID where the hashing stage left it and the aggregated key where the
+ * key stage left it -- which is why it needs the first flag: an ID uploaded for the purpose would be the round trip it
+ * removes -- and the scalars -c a_i are written into the signature stage's own device buffers.  A chunk's key stage, hashing
+ * stage and signature stage are then ordered by events on the device; the host waits for nothing between them.  Same bytes
+ * read, same accept bitmap, same status bytes for formats 1 and 2, whatever the call size, chunking, host_threads or round
+ * of zkgpu_tx_verify_submit.  No host fallback: an error of the new step is an error of the call, fail-closed exactly as
+ * above (bitmap zero, status 1 for every transaction inside the subset, status 2 left alone).  The MuSig coefficients a_i
+ * stay on the host: they are known from the transaction's own bytes before anything reaches the device.  Opt-in. */
+#define ZKGPU_TXFORMAT_SIGN_ON_DEVICE 512   /* 0x200 */
 #define ZKGPU_TXSTATUS_ACCEPTED 0
 #define ZKGPU_TXSTATUS_REJECTED 1                 /* rejected, reason not available (V1 format, or any error path) */
 #define ZKGPU_TXSTATUS_OUTSIDE_SUBSET 2

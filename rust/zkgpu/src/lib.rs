@@ -352,6 +352,14 @@ impl GpuVerifier {
         check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, base | sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE) }, self.err())
     }
 
+    /// The same with `ZKGPU_TXFORMAT_SIGN_ON_DEVICE` beside it: the signature's challenge is formed on the device as well, from
+    /// the ID and the aggregated key where the device left them.  Same verdicts; opt-in.
+    pub fn enable_recollected_tx_format_signing_on_device(&self, with_reasons: bool) -> Result<(), Error> {
+        let base = if with_reasons { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS } else { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1 };
+        let flags = sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE | sys::ZKGPU_TXFORMAT_SIGN_ON_DEVICE;
+        check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, base | flags) }, self.err())
+    }
+
     /// Drop-in for `txs.iter().map(|tx| tx.verify(bp_gens))` on `Tx::encode()` bytes (payment subset): VM, transaction
     /// ID, MuSig / Schnorr signature and cloak proof.  `host_threads`: 0 = the CPUs the process may keep busy.
     pub fn verify_txs(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<TxVerdict>, Error> {

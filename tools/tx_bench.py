@@ -1,6 +1,7 @@
 """zkgpu_tx_verify_batch on the committed 1024 transactions (per-stage times with ZKGPU_PROVER_TIMING=1).
-usage: tx_bench.py [--device-hashing] [--host-threads N] [--in-flight K] [copies of the fixture per call] [block chunk] [tx chunk]
-(TX_BENCH_FORMAT=2: the format with reason codes; --device-hashing: or-ed with ZKGPU_TXFORMAT_HASH_ON_DEVICE; --host-threads N: the
+usage: tx_bench.py [--device-hashing] [--device-signing] [--host-threads N] [--calls N] [--in-flight K] [copies of the fixture per call] [block chunk] [tx chunk]
+(TX_BENCH_FORMAT=2: the format with reason codes; --device-hashing: or-ed with ZKGPU_TXFORMAT_HASH_ON_DEVICE; --device-signing: with
+that flag and ZKGPU_TXFORMAT_SIGN_ON_DEVICE; --calls N: library calls timed alone (3); --host-threads N: the
 host_threads of every call, 0 = the CPUs the process may use; --in-flight K: also K calls of that size through submit / wait)"""
 import os as _os; _os.environ.setdefault("ZKGPU_TEST_HOOKS", "1")   # the profile / mode hooks (include/zkgpu_hooks.h) are not exports
 import ctypes as C
@@ -11,8 +12,11 @@ import numpy as np
 from gpu_util import load_tx_fixture
 from zkvm_amd import Context
 from zkvm_amd.verifier import BulletproofGens, BlockVerifier
-DEVICE_HASHING = "--device-hashing" in sys.argv
-if DEVICE_HASHING:
+DEVICE_SIGNING = "--device-signing" in sys.argv
+if DEVICE_SIGNING:
+    sys.argv.remove("--device-signing")
+DEVICE_HASHING = "--device-hashing" in sys.argv or DEVICE_SIGNING
+if "--device-hashing" in sys.argv:
     sys.argv.remove("--device-hashing")
 def _option(name, default):
     if name not in sys.argv:
@@ -23,13 +27,15 @@ def _option(name, default):
     return v
 HOST_THREADS = _option("--host-threads", None)
 IN_FLIGHT = _option("--in-flight", 0)
+CALLS = _option("--calls", 3)
 rep = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 txs = load_tx_fixture() * rep
 ctx = Context(0)
 gens = BulletproofGens(ctx, 256, table_bits=16)
 chunk = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 bv = BlockVerifier(ctx, gens, chunk=chunk)
-bv.set_tx_format(int(os.environ.get("TX_BENCH_FORMAT", bv.TXFORMAT_RECOLLECTED_V1)) | (bv.TXFORMAT_HASH_ON_DEVICE if DEVICE_HASHING else 0))
+bv.set_tx_format(int(os.environ.get("TX_BENCH_FORMAT", bv.TXFORMAT_RECOLLECTED_V1)) | (bv.TXFORMAT_HASH_ON_DEVICE if DEVICE_HASHING else 0)
+                 | (bv.TXFORMAT_SIGN_ON_DEVICE if DEVICE_SIGNING else 0))
 if len(sys.argv) > 3:
     bv.set_tx_chunk(int(sys.argv[3]))
 HT = HOST_THREADS if HOST_THREADS is not None else int(sys.argv[4]) if len(sys.argv) > 4 else 0
@@ -48,7 +54,7 @@ assert os.environ.get("ZKGPU_TEST_TX_FREE_HASHING") == "1" or not any(st)      #
 offs = np.zeros(len(lens) + 1, dtype=np.uint64)
 np.cumsum(np.asarray(lens, dtype=np.uint64), out=offs[1:])
 bmb, stb = C.create_string_buffer((len(lens) + 7) // 8), C.create_string_buffer(len(lens))
-for _ in range(3):
+for _ in range(CALLS):
     t0 = time.perf_counter()
     rc = bv.lib.zkgpu_tx_verify_batch(bv.h, len(lens), blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), HT, bmb, stb)
     dt = time.perf_counter() - t0
@@ -64,6 +70,8 @@ if IN_FLIGHT:
 if DEVICE_HASHING:
     import struct
     print("transaction IDs from the device so far: %d" % struct.unpack("<Q", ctx.debug_read("tx_hashed_on_device", 8)), file=sys.stderr)
+if DEVICE_SIGNING:
+    print("signature challenges from the device so far: %d" % struct.unpack("<Q", ctx.debug_read("tx_signed_on_device", 8)), file=sys.stderr)
 ctx.profile(True); ctx.profile_reset()
 bm, st = bv.verify_txs(txs)
 ctx.profile(False)

@@ -1048,21 +1048,7 @@ class HostTxDevice : public TxDevice {
     const unsigned us = delay();
     s.th = std::thread([=, &s] {
       std::this_thread::sleep_for(std::chrono::microseconds(us));
-      for (size_t r = 0; r < rows; ++r) {
-        Scalar sb;
-        if (!Scalar::from_canonical(bsc + 32 * r, sb)) continue;
-        ge acc;
-        base_mul(acc, sb);
-        bool ok = true;
-        for (uint64_t t = doff[r]; t < doff[r + 1]; ++t) {
-          ge X, aX;
-          Scalar a;
-          if (!decode_host(X, dpt + 32 * t) || !Scalar::from_canonical(dsc + 32 * t, a)) { ok = false; break; }
-          ge_scalarmult_host(aX, a, X);
-          ge_add(acc, acc, aX);
-        }
-        if (ok && ge_is_identity(acc)) s.ok[r / 8] |= (uint8_t)(1u << (r % 8));
-      }
+      sig_rows_check(s, rows, dsc, dpt, doff, bsc);
       s.done = true;
     });
     return 0;
@@ -1079,7 +1065,25 @@ class HostTxDevice : public TxDevice {
   std::string last_error() override { return err_.empty() ? "injected device fault" : err_; }
   size_t leaked() { std::lock_guard<std::mutex> lk(mu_); return staged_total_ - released_total_; }
 
- private:
+ protected:
+  struct Stage;
+  void sig_rows_check(Stage& s, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc) {
+    for (size_t r = 0; r < rows; ++r) {
+      Scalar sb;
+      if (!Scalar::from_canonical(bsc + 32 * r, sb)) continue;
+      ge acc;
+      base_mul(acc, sb);
+      bool ok = true;
+      for (uint64_t t = doff[r]; t < doff[r + 1]; ++t) {
+        ge X, aX;
+        Scalar a;
+        if (!decode_host(X, dpt + 32 * t) || !Scalar::from_canonical(dsc + 32 * t, a)) { ok = false; break; }
+        ge_scalarmult_host(aX, a, X);
+        ge_add(acc, acc, aX);
+      }
+      if (ok && ge_is_identity(acc)) s.ok[r / 8] |= (uint8_t)(1u << (r % 8));
+    }
+  }
   struct Stage { std::thread th; std::atomic<bool> done{false}; std::vector<uint8_t> ok, values; };
   struct Proofs { size_t ring_slot = 0; std::vector<TxProofSource> src; std::vector<uint8_t> bits; std::thread th; std::atomic<bool> done{false}; };
   unsigned delay() { std::lock_guard<std::mutex> lk(mu_); return (unsigned)(rng_() % 400); }
@@ -1257,14 +1261,14 @@ class HostHashingTxDevice : public HostTxDevice {
     if (!s.th.joinable()) { herr_ = "nothing to collect in this hash slot"; return -1; }
     s.th.join();
     if (hash_failing()) { herr_ = "injected fault of the hashing stage"; return -3; }
-    std::memcpy(txids, s.ids.data(), 32 * s.tape.n_tx());
+    if (txids) std::memcpy(txids, s.ids.data(), 32 * s.tape.n_tx());
     hashed_ += s.tape.n_tx();
     return 0;
   }
   std::string last_error() override { return herr_.empty() ? HostTxDevice::last_error() : herr_; }
   uint64_t hashed() const { return hashed_; }
 
- private:
+ protected:
   struct HashStage { TxHashTape tape; std::thread th; std::atomic<bool> done{true}; std::vector<uint32_t> slots, ids; };
   bool hash_failing() { return hash_fail_at_ >= 0 && hops_++ == hash_fail_at_; }
   HashStage h_[2];
@@ -1293,6 +1297,176 @@ extern "C" int zkhost_txcall_hashing_selftest(size_t batch, const uint8_t* txs, 
   }
   *leaked = dev.leaked();
   *hashed = dev.hashed();
+  if (rc != 0) {
+    std::memset(accept_bitmap, 0, (batch + 7) / 8);
+    for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;
+  }
+  return rc;
+}
+
+
+// ---- the signature challenge of a flagged call (tx_sig_rows.hpp: ZKGPU_TXFORMAT_SIGN_ON_DEVICE) on the CPU: `count`
+// ---- transactions as ONE chunk the way a chaining call treats it -- the taped second pass, the tape interpreted (the IDs
+// ---- in the tape's order), the aggregated keys with the reference arithmetic, the chunk's signature rows with a_i in place,
+// ---- the row -> tape map -- and tx_sig_row, the function k_tx_sig_rows runs per lane, over every row.  Beside it,
+// ---- tx_finish_signature over the same statements.  Out, per transaction (zero where the VM did not accept it): status, the
+// ---- number of keys, the ID, the aggregated key, R, and `cap` scalars each of a_i, of what tx_sig_row wrote and of what
+// ---- tx_finish_signature wrote.  -> rows run, or -1 a plan the tape cannot hold, -2 no script, -3 more than `cap` keys
+#include "tx_sig_rows.hpp"
+extern "C" long long zkhost_tx_sig_rows(const uint8_t* txs, const uint64_t* offs, size_t count, int threads, size_t cap, uint8_t* status, uint32_t* n_keys,
+                                        uint8_t* txid, uint8_t* agg, uint8_t* R, uint8_t* a_in, uint8_t* from_rows, uint8_t* from_host) {
+  using namespace zk::zkvm;
+  TxHashTape tape;
+  tape.reset(count);
+  std::vector<TxStatement> st(count);
+  std::atomic<int> bad{0};
+  zk::host_parallel((count + 7) / 8, threads, [&](size_t g) {
+    const uint8_t* p[8]; size_t l[8];
+    const size_t first = 8 * g, n = std::min<size_t>(8, count - first);
+    for (size_t i = 0; i < n; ++i) { p[i] = txs + offs[first + i]; l[i] = (size_t)(offs[first + i + 1] - offs[first + i]); }
+    if (!tx_prepare_many_taped(p, l, &st[first], n, tape, first)) bad = 1;
+  });
+  std::memset(n_keys, 0, 4 * count); std::memset(txid, 0, 32 * count); std::memset(agg, 0, 32 * count); std::memset(R, 0, 32 * count);
+  std::memset(a_in, 0, 32 * cap * count); std::memset(from_rows, 0, 32 * cap * count); std::memset(from_host, 0, 32 * cap * count);
+  for (size_t i = 0; i < count; ++i) status[i] = (uint8_t)st[i].status;
+  if (bad) return -1;
+  tape.finish(threads);
+  std::vector<uint32_t> protos, sl, ids;
+  std::vector<uint8_t> labels;
+  hash_tape_constants(protos, labels);
+  hash_tape_run_host(tape.block(), protos, labels, sl, ids);
+  SigScript script;
+  if (!sig_script(script)) return -2;
+  std::vector<size_t> live;
+  for (size_t i = 0; i < count; ++i) if (st[i].status == TX_OK) live.push_back(i);
+  std::vector<uint32_t> at(count, TAPE_IDLE), pos(live.size());
+  for (size_t t = 0; t < tape.n_tx(); ++t) at[tape.position(t)] = (uint32_t)t;
+  std::vector<uint64_t> soff(live.size() + 1, 0);
+  for (size_t q = 0; q < live.size(); ++q) {
+    const size_t k = st[live[q]].sig_scalars.size() / 32 - 2;
+    if (k > cap || at[live[q]] == TAPE_IDLE) return -3;
+    pos[q] = at[live[q]];
+    soff[q + 1] = soff[q] + k + 1;
+  }
+  std::vector<uint32_t> ssc(8 * soff.back() + 8), spt(8 * soff.back() + 8), aggw(8 * live.size() + 8, 0);
+  uint8_t base[32];
+  { ge B; B.X = fe_BASE_X(); B.Y = fe_BASE_Y(); B.Z = fe_one(); B.T = fe_BASE_T(); encode_point(base, B); }
+  for (size_t q = 0; q < live.size(); ++q) {
+    TxStatement& t = st[live[q]];
+    const size_t i = live[q], k = t.sig_scalars.size() / 32 - 2;
+    std::memcpy(&ssc[8 * soff[q]], t.sig_scalars.data() + 32, 32 * (k + 1));
+    std::memcpy(&spt[8 * soff[q]], t.sig_points.data() + 32, 32 * (k + 1));
+    ge acc;
+    ge_identity(acc);
+    bool ok = true;
+    for (size_t j = 0; j < k && ok; ++j) {
+      ge X, aX;
+      Scalar a;
+      if (!decode_host(X, &t.sig_points[32 * (2 + j)]) || !Scalar::from_canonical(&t.sig_scalars[32 * (2 + j)], a)) { ok = false; break; }
+      ge_scalarmult_host(aX, a, X);
+      ge_add(acc, acc, aX);
+    }
+    if (ok) encode_point((uint8_t*)&aggw[8 * q], acc);             // (a key that does not decode: zeros, as the key stage leaves them)
+    n_keys[i] = (uint32_t)k;
+    std::memcpy(txid + 32 * i, &ids[8 * pos[q]], 32);
+    std::memcpy(agg + 32 * i, &aggw[8 * q], 32);
+    std::memcpy(R + 32 * i, &t.sig_points[32], 32);
+    std::memcpy(a_in + 32 * cap * i, &t.sig_scalars[64], 32 * k);
+    TxStatement h = t;
+    std::memcpy(h.txid, &ids[8 * pos[q]], 32);
+    tx_finish_signature(h, base, (const uint8_t*)&aggw[8 * q]);
+    std::memcpy(from_host + 32 * cap * i, &h.sig_scalars[64], 32 * k);
+  }
+  SigRowsView v{&script, ids.data(), pos.data(), aggw.data(), soff.data(), spt.data(), ssc.data(), (uint32_t)live.size()};
+  sig_rows_run_host(v);
+  for (size_t q = 0; q < live.size(); ++q)
+    std::memcpy(from_rows + 32 * cap * live[q], &ssc[8 * (soff[q] + 1)], 32 * (size_t)n_keys[live[q]]);
+  return (long long)live.size();
+}
+
+// ---- the scheduling of a call that CHAINS (TxDevice::chains) on the CPU: the hashing stand-in above, plus a signature stage
+// ---- that waits -- on its own thread, as the device waits on events -- for the key stage of key_slot and the tape of hash_slot,
+// ---- forms the challenges with tx_sig_row and then checks the rows like the unchained stage.  sig_fail_at: the n-th
+// ---- sigs_enqueue_chained / sigs_collect reports an error (-1: none).  *signed_rows: rows whose challenge the stand-in produced.
+namespace {
+class HostChainingTxDevice : public HostHashingTxDevice {
+ public:
+  HostChainingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int sig_fail_at)
+      : HostHashingTxDevice(txs, offs, batch, proof_ok, seed, -1), crng_(seed ^ 0x51ed270bu), sig_fail_at_(sig_fail_at) { have_script_ = sig_script(script_); }
+  bool chains() const override { return true; }
+  int sigs_enqueue(int, size_t, const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*) override {
+    cerr_ = "an unchained signature stage on a device that chains";
+    return -1;
+  }
+  int sigs_enqueue_chained(int slot, int key_slot, int hash_slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff,
+                           const uint8_t* bsc, const uint32_t* tape_pos) override {
+    Stage& s = sigs_[slot];
+    Stage& ks = keys_[key_slot];
+    HashStage& hs = h_[hash_slot];
+    if (!have_script_) { cerr_ = "no script of the signature transcript"; return -1; }
+    if (s.th.joinable()) { cerr_ = "signature slot reused before it was collected"; return -1; }
+    if (!ks.th.joinable() || !hs.th.joinable()) { cerr_ = "a chained signature stage without its key stage or its tape in flight"; return -1; }
+    if (ks.values.size() != 32 * rows) { cerr_ = "the key stage of the slot has other rows than the signature stage"; return -1; }
+    for (size_t r = 0; r < rows; ++r) if (tape_pos[r] >= hs.tape.n_tx()) { cerr_ = "a row names a transaction the tape does not hold"; return -1; }
+    if (sig_failing()) { cerr_ = "injected fault of the chained signature stage"; return -3; }
+    s.done = false;
+    s.ok.assign((rows + 7) / 8 + 1, 0);
+    s.values.assign(dsc, dsc + 32 * doff[rows]);          // (the stage's own copy of the scalars, as the device's buffer is: -c a_i go here)
+    const unsigned us = (unsigned)(crng_() % 400);
+    s.th = std::thread([=, &s, &ks, &hs] {
+      std::this_thread::sleep_for(std::chrono::microseconds(us));
+      while (!ks.done || !hs.done) std::this_thread::sleep_for(std::chrono::microseconds(20));
+      std::vector<uint32_t> sc(s.values.size() / 4 + 8), pt(8 * doff[rows] + 8), agg(8 * rows + 8);
+      std::memcpy(sc.data(), s.values.data(), s.values.size());
+      std::memcpy(pt.data(), dpt, 32 * doff[rows]);
+      std::memcpy(agg.data(), ks.values.data(), 32 * rows);
+      SigRowsView v{&script_, hs.ids.data(), tape_pos, agg.data(), doff, pt.data(), sc.data(), (uint32_t)rows};
+      sig_rows_run_host(v);
+      std::memcpy(s.values.data(), sc.data(), s.values.size());
+      sig_rows_check(s, rows, s.values.data(), dpt, doff, bsc);
+      signed_ += rows;
+      s.done = true;
+    });
+    return 0;
+  }
+  int sigs_collect(int slot, uint8_t* bits, uint8_t* why) override {
+    const int rc = HostHashingTxDevice::sigs_collect(slot, bits, why);
+    if (rc == 0 && sig_failing()) { cerr_ = "injected fault of the chained signature stage"; return -3; }
+    return rc;
+  }
+  std::string last_error() override { return cerr_.empty() ? HostHashingTxDevice::last_error() : cerr_; }
+  uint64_t signed_rows() const { return signed_; }
+
+ private:
+  bool sig_failing() { return sig_fail_at_ >= 0 && sops_++ == sig_fail_at_; }
+  SigScript script_;
+  bool have_script_ = false;
+  std::mt19937 crng_;
+  const int sig_fail_at_;
+  int sops_ = 0;
+  std::atomic<uint64_t> signed_{0};
+  std::string cerr_;
+};
+}  // namespace
+
+extern "C" int zkhost_txcall_chaining_selftest(size_t batch, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok, int host_threads,
+                                               size_t chunk, uint32_t delay_seed, int sig_fail_at, int n_slots, uint8_t* accept_bitmap,
+                                               uint8_t* status, size_t* n_chunks, size_t* n_sig_stages, size_t* leaked, uint64_t* hashed,
+                                               uint64_t* signed_rows) {
+  std::memset(accept_bitmap, 0, (batch + 7) / 8);
+  std::memset(status, TX_INVALID, batch);
+  std::vector<TxStatement> store;
+  HostChainingTxDevice dev(txs, offs, batch, proof_ok, delay_seed, sig_fail_at);
+  int rc;
+  {
+    TxCall call(dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, accept_bitmap, status, n_slots);
+    *n_chunks = call.n_chunks();
+    *n_sig_stages = call.n_sig_stages_planned();
+    rc = call.run();
+  }
+  *leaked = dev.leaked();
+  *hashed = dev.hashed();
+  *signed_rows = dev.signed_rows();
   if (rc != 0) {
     std::memset(accept_bitmap, 0, (batch + 7) / 8);
     for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;

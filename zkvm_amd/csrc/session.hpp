@@ -15,6 +15,7 @@
 #include "comm_frame.hpp"
 #include "tx_call.hpp"
 #include "tx_hash_kernels.hpp"
+#include "tx_sig_rows.hpp"
 #include "zkvm_tx.hpp"
 
 #include <deque>
@@ -113,6 +114,12 @@ struct zkgpu_verifier {
   };
   TxHashStage tx_hash[2];
   Buffer tx_hash_const;
+  bool tx_sign_on_device = false;                       // the flag ZKGPU_TXFORMAT_SIGN_ON_DEVICE (only beside the one above)
+  // what the signature's challenge needs beside its slot's signature context (tx_sig_rows.hpp): the rows' places on the tape,
+  // the events that order it behind the slot's key stage and hashing stage; once per verifier, the script of the transcript
+  struct TxSigStage { Buffer d_pos; hipEvent_t ev_keys = nullptr, ev_ids = nullptr; size_t rows = 0; };
+  TxSigStage tx_sig[2];
+  Buffer tx_sig_const;
   // zkgpu_tx_verify_batch: two contexts of their own for the key and the signature stages (each a pair of streams beside
   // the lanes'), and a ring of staging areas (pinned host + device, grow-only) for the cloak statements of the chunks in
   // flight -- nothing on that path allocates or frees device memory once the sizes have been seen (hipFree synchronises)
@@ -384,7 +391,7 @@ int zkgpu_verifier_create(zkgpu_ctx* ctx, const zkgpu_pointset* ps, size_t gens_
   batches_in_flight = std::min(batches_in_flight, 1 + MAX_FORKS);
   zkgpu_verifier* v = new zkgpu_verifier();
   v->root = ctx; v->ps = ps; v->gens_capacity = gens_capacity;
-  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; }
+  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; ctx->tx_signed_on_device = 0; }
   v->lanes.push_back(ctx);
   v->lanes_requested = batches_in_flight;
   // A lane is worth having only if its light stream -- the latency-bound kernels of its batch: transcript, Horner chains,
@@ -468,6 +475,12 @@ void zkgpu_verifier_destroy(zkgpu_verifier* v) {
       for (Buffer* b : {&hs.d_tape, &hs.d_slots, &hs.d_txid}) if (b->p) (void)hipFree(b->p);
     }
     if (v->tx_hash_const.p) (void)hipFree(v->tx_hash_const.p);
+    for (auto& ss : v->tx_sig) {
+      if (ss.ev_keys) (void)hipEventDestroy(ss.ev_keys);
+      if (ss.ev_ids) (void)hipEventDestroy(ss.ev_ids);
+      if (ss.d_pos.p) (void)hipFree(ss.d_pos.p);
+    }
+    if (v->tx_sig_const.p) (void)hipFree(v->tx_sig_const.p);
   }
   for (auto& kv : v->plans) if (kv.second) zkgpu_cloak_plan_destroy(kv.second);
   delete v;
@@ -1635,11 +1648,14 @@ int zkgpu_verifier_verify_sharded(zkgpu_verifier* v, zkgpu_comm* cm, size_t batc
 // (the verdicts stay with their tickets / runs) -- a synchronous call on a context with a batch in flight would
 // overwrite that batch's status words and pinned result buffer (and is refused by the context: refuse_if_pending).
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
-  const int base = format & ~ZKGPU_TXFORMAT_HASH_ON_DEVICE;          // (the flag goes with a format: alone it names none)
+  const int base = format & ~(ZKGPU_TXFORMAT_HASH_ON_DEVICE | ZKGPU_TXFORMAT_SIGN_ON_DEVICE);     // (the flags go with a format: alone they name none)
   if (!v || (format != 0 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS)) return ZKGPU_EINVAL;
+  // (the challenge reads the transaction ID where the hashing stage left it: no signing on the device without hashing there)
+  if ((format & ZKGPU_TXFORMAT_SIGN_ON_DEVICE) && !(format & ZKGPU_TXFORMAT_HASH_ON_DEVICE)) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> lk(v->mu);
   v->tx_format = base;
   v->tx_hash_on_device = (format & ZKGPU_TXFORMAT_HASH_ON_DEVICE) != 0;
+  v->tx_sign_on_device = (format & ZKGPU_TXFORMAT_SIGN_ON_DEVICE) != 0;
   return ZKGPU_OK;
 }
 
@@ -1727,6 +1743,26 @@ bool split_done(zkgpu_ctx* c) {
   return hipStreamQuery(c->split.stream) != hipErrorNotReady;
 }
 
+// rows that already lie in the context's input buffers (c->mu held, the device set): kernels and result copy queued
+int verify_ps_enqueue_resident(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, uint64_t nd, uint64_t ns, uint64_t max_dyn_row) {
+  Job job;
+  job.d_dyn_scalars = (const uint32_t*)c->in_scalars.p;
+  job.d_dyn_points = (const uint32_t*)c->in_points.p;
+  job.d_dyn_offsets = (const uint64_t*)c->in_offsets.p;
+  job.n_dyn = nd;
+  job.d_st_scalars = (const uint32_t*)c->in_st_scalars.p;
+  job.d_st_index = (const uint32_t*)c->in_st_index.p;
+  job.d_st_offsets = (const uint64_t*)c->in_st_offsets.p;
+  job.n_static = ns;
+  job.d_static_rows = ps->rows;
+  job.n_msm = (uint32_t)batch;
+  job.max_dyn_row = max_dyn_row;
+  const int rc = (ps->table && ns) ? batch_device_tables_enqueue(c, job, ps) : batch_device_enqueue(c, job, false);
+  if (rc != ZKGPU_OK) { c->split = zkgpu_ctx::SplitOp{}; return rc; }
+  c->pending = true; c->pending_batch = batch;
+  return ZKGPU_OK;
+}
+
 // the same for rows of dynamic terms + terms on the resident set's tables (the signature equations)
 int verify_ps_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, const uint8_t* dyn_scalars, const uint8_t* dyn_points,
                       const uint64_t* dyn_offsets, const uint8_t* static_scalars, const uint32_t* static_index, const uint64_t* static_offsets) {
@@ -1740,22 +1776,7 @@ int verify_ps_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, cons
   TRY(upload(c, c->in_st_scalars, static_scalars, ns * 32));
   TRY(upload(c, c->in_st_index, static_index, ns * 4));
   TRY(upload(c, c->in_st_offsets, static_offsets, (batch + 1) * 8));
-  Job job;
-  job.d_dyn_scalars = (const uint32_t*)c->in_scalars.p;
-  job.d_dyn_points = (const uint32_t*)c->in_points.p;
-  job.d_dyn_offsets = (const uint64_t*)c->in_offsets.p;
-  job.n_dyn = nd;
-  job.d_st_scalars = (const uint32_t*)c->in_st_scalars.p;
-  job.d_st_index = (const uint32_t*)c->in_st_index.p;
-  job.d_st_offsets = (const uint64_t*)c->in_st_offsets.p;
-  job.n_static = ns;
-  job.d_static_rows = ps->rows;
-  job.n_msm = (uint32_t)batch;
-  job.max_dyn_row = longest_row(dyn_offsets, batch);
-  const int rc = (ps->table && ns) ? batch_device_tables_enqueue(c, job, ps) : batch_device_enqueue(c, job, false);
-  if (rc != ZKGPU_OK) { c->split = zkgpu_ctx::SplitOp{}; return rc; }
-  c->pending = true; c->pending_batch = batch;
-  return ZKGPU_OK;
+  return verify_ps_enqueue_resident(c, ps, batch, nd, ns, longest_row(dyn_offsets, batch));
 }
 
 }  // namespace
@@ -1786,10 +1807,37 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   // and 1, areas 0 .. RING - 1; two rounds in flight: one slot and one set of areas each)
   // reasons: a format-2 call -- every stage also brings back one reason byte per row (tx_reason_kernels.hpp)
   // hashes: the format's flag ZKGPU_TXFORMAT_HASH_ON_DEVICE -- the transaction IDs of every chunk come from k_tx_hash
-  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false, bool hashes = false)
-      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes) {}
+  // chains: ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the signature's challenge comes from k_tx_sig_rows
+  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false, bool hashes = false, bool chains = false)
+      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes), chains_(hashes && chains) {}
   bool reasons() const override { return reasons_; }
   bool hashes() const override { return hashes_; }
+  bool chains() const override { return chains_; }
+  // the rows up, the challenge kernel behind the slot's key stage and tape (events), the equations behind it: all on the
+  // signature context's stream, nothing waited for
+  int sigs_enqueue_chained(int slot, int key_slot, int hash_slot, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points,
+                           const uint64_t* dyn_offsets, const uint8_t* base_scalars, const uint32_t* tape_pos) override {
+    zkgpu_ctx* c = sigs(slot);
+    sidx_[slot].assign(rows, 0);
+    soff_[slot].resize(rows + 1);
+    for (size_t q = 0; q <= rows; ++q) soff_[slot][q] = q;
+    if (reasons_) { const int rc = seen(stage_reasons_reserve(c, rows, false), c); if (rc != ZKGPU_OK) return rc; }
+    // (a profiled call: the stage's context takes the root's switch for this stage alone -- profile_to_root clears it when
+    // the stage is collected, and here on every error, after which sigs_collect is not asked)
+    bool profiled = false;
+    { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); profiled = v_->root->profiling; }
+    int rc = chain_queue(slot, key_slot, hash_slot, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, tape_pos, profiled);
+    if (rc != ZKGPU_OK) err_ = std::string("signature challenge stage: ") + zkgpu_last_error(c);
+    if (rc == ZKGPU_OK) {
+      std::lock_guard<std::recursive_mutex> lk(c->mu);
+      DeviceGuard g(c->device);
+      rc = seen(verify_ps_enqueue_resident(c, v_->ps, rows, dyn_offsets[rows], rows, longest_row(dyn_offsets, rows)), c);
+    }
+    if (rc == ZKGPU_OK) sig(slot).rows = rows;
+    if (rc == ZKGPU_OK && reasons_) rc = seen(stage_reasons_enqueue(c, ZKGPU_TXSTATUS_SIGNATURE), c);
+    if (rc != ZKGPU_OK && profiled) profile_to_root(c);
+    return rc;
+  }
   zk::zkvm::TxHashTape* hash_tape(int slot) override { return &hash(slot).tape; }
   // one copy up, one launch, one copy of the IDs down, on the stage's own high-priority stream
   int hash_enqueue(int slot, const zk::zkvm::TxHashTape& tape) override {
@@ -1884,13 +1932,87 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   }
   bool sigs_done(int slot) override { return split_done(sigs(slot)); }
   int sigs_collect(int slot, uint8_t* bits, uint8_t* why) override {
-    return seen(split_collect_why(sigs(slot), bits, nullptr, reasons_ ? why : nullptr), sigs(slot));
+    const int rc = seen(split_collect_why(sigs(slot), bits, nullptr, reasons_ ? why : nullptr), sigs(slot));
+    if (chains_) {
+      zkgpu_ctx* c = sigs(slot);
+      const size_t rows = sig(slot).rows;
+      sig(slot).rows = 0;
+      if (rc == ZKGPU_OK) { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_signed_on_device += rows; }
+      bool profiled = false;
+      { std::lock_guard<std::recursive_mutex> lk(c->mu); profiled = c->profiling; }
+      if (profiled) profile_to_root(c);                  // (only a call made with zkgpu_profile_enable on: nothing of it otherwise)
+    }
+    return rc;
   }
   std::string last_error() override { return err_; }
 
  private:
   struct Staged { zkgpu_txblock* blk = nullptr; zkgpu_verifier::BlockRun* run = nullptr; };
   zkgpu_verifier::TxHashStage& hash(int slot) const { return v_->tx_hash[(sb_ + slot) & 1]; }
+  zkgpu_verifier::TxSigStage& sig(int slot) const { return v_->tx_sig[(sb_ + slot) & 1]; }
+  // a profiled stage's launches go to the root's profile, where zkgpu_profile_get is asked for them (the stage's context is
+  // not the caller's to ask), and the context's switch is off again: it is on for one stage of a profiled call and never else
+  void profile_to_root(zkgpu_ctx* c) {
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    std::lock_guard<std::recursive_mutex> rl(v_->root->mu);
+    for (const ProfEntry& e : c->prof) { ProfEntry& to = v_->root->prof[(size_t)prof_index(v_->root, e.name)]; to.launches += e.launches; to.ms += e.ms; }
+    c->prof.clear();
+    c->profiling = false;
+  }
+  int chain_queue(int slot, int key_slot, int hash_slot, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points,
+                  const uint64_t* dyn_offsets, const uint8_t* base_scalars, const uint32_t* tape_pos, bool profiled) {
+    using namespace zk::zkvm;
+    zkgpu_ctx* c = sigs(slot);
+    zkgpu_ctx* kc = keys(key_slot);
+    zkgpu_verifier::TxHashStage& hs = hash(hash_slot);
+    zkgpu_verifier::TxSigStage& ss = sig(slot);
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    TRY(refuse_if_pending(c));
+    DeviceGuard g(c->device);
+    // what the kernel indexes blindly: the key stage in flight in that slot has exactly these rows (its values: 32 bytes per
+    // row), the tape in flight holds every transaction named, every row has R and at least one key
+    hipStream_t key_stream = nullptr;
+    {
+      std::lock_guard<std::recursive_mutex> kl(kc->mu);
+      if (!kc->pending || kc->split.kind != 1 || !kc->split.values || kc->split.batch != rows) { c->last_error = "no key stage of these rows in flight in the slot"; return ZKGPU_EINVAL; }
+      key_stream = kc->split.stream;
+    }
+    if (rows == 0 || rows >= (1ull << 31) || hs.n_tx == 0 || !hs.stream) { c->last_error = "no tape in flight in the slot"; return ZKGPU_EINVAL; }
+    for (size_t r = 0; r < rows; ++r)
+      if (tape_pos[r] >= hs.n_tx || dyn_offsets[r + 1] < dyn_offsets[r] + 2) { c->last_error = "a signature row without its ID, its R or a key"; return ZKGPU_EINVAL; }
+    if (!v_->tx_sig_const.p) {                           // once per verifier: what tx_finish_signature hashes, written down
+      SigScript sc;
+      if (!sig_script(sc)) { c->last_error = "the signature transcript does not fit the device's script"; return ZKGPU_EINVAL; }
+      Buffer made;
+      TRY(ensure(c, made, sizeof sc));
+      const hipError_t e = hipMemcpy(made.p, &sc, sizeof sc, hipMemcpyHostToDevice);
+      if (e != hipSuccess) { (void)hipFree(made.p); HIP_TRY(c, e); }
+      v_->tx_sig_const = made;
+    }
+    if (!ss.ev_keys) HIP_TRY(c, hipEventCreateWithFlags(&ss.ev_keys, hipEventDisableTiming));
+    if (!ss.ev_ids) HIP_TRY(c, hipEventCreateWithFlags(&ss.ev_ids, hipEventDisableTiming));
+    const uint64_t nd = dyn_offsets[rows];
+    TRY(upload(c, c->in_scalars, dyn_scalars, nd * 32));
+    TRY(upload(c, c->in_points, dyn_points, nd * 32));
+    TRY(upload(c, c->in_offsets, dyn_offsets, (rows + 1) * 8));
+    TRY(upload(c, c->in_st_scalars, base_scalars, rows * 32));
+    TRY(upload(c, c->in_st_index, sidx_[slot].data(), rows * 4));
+    TRY(upload(c, c->in_st_offsets, soff_[slot].data(), (rows + 1) * 8));
+    TRY(upload(c, ss.d_pos, tape_pos, rows * 4));
+    HIP_TRY(c, hipEventRecord(ss.ev_keys, key_stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, ss.ev_keys, 0));
+    HIP_TRY(c, hipEventRecord(ss.ev_ids, hs.stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, ss.ev_ids, 0));
+    c->profiling = profiled;
+    SigRowsView view{(const SigScript*)v_->tx_sig_const.p, (const uint32_t*)hs.d_txid.p, (const uint32_t*)ss.d_pos.p, (const uint32_t*)kc->values.p,
+                     (const uint64_t*)c->in_offsets.p, (const uint32_t*)c->in_points.p, (uint32_t*)c->in_scalars.p, (uint32_t)rows};
+    {
+      Launch l(c, "k_tx_sig_rows", c->stream);
+      hipLaunchKernelGGL(zk::k_tx_sig_rows, dim3(blocks_for(rows, 64)), dim3(64), 0, c->stream, view);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return ZKGPU_OK;
+  }
   // (errors are kept by the slot's key context, whose runtime-call macros these are)
   static int pinned_grow(zkgpu_ctx* c, void*& p, size_t& cap, size_t bytes) {
     if (bytes <= cap) return ZKGPU_OK;
@@ -1940,7 +2062,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
       hipLaunchKernelGGL(zk::k_tx_hash, dim3(h.n_lanes / 64), dim3(64), 0, hs.stream, view, h.n_lanes);
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));
+    if (!chains_) HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));   // (a chain reads them on the device)
     hs.n_tx = h.n_tx;
     return ZKGPU_OK;
   }
@@ -1953,7 +2075,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     hs.n_tx = 0;
     if (n == 0) return ZKGPU_OK;
     HIP_TRY(c, hipStreamSynchronize(hs.stream));
-    memcpy(txids, hs.h_out, 32 * n);
+    if (txids && !chains_) memcpy(txids, hs.h_out, 32 * n);
     { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_hashed_on_device += n; }
     return ZKGPU_OK;
   }
@@ -1963,7 +2085,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   zkgpu_verifier* v_;
   const int sb_;
   const size_t ab_;
-  const bool reasons_, hashes_;
+  const bool reasons_, hashes_, chains_;
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];
   std::string err_;
@@ -2039,7 +2161,8 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   TRY(tx_call_prepare(v));
   // (format 2 reads the same bytes and gives the same bits; what differs is what the status bytes say -- with no status
   // array there is nothing to say, and the call is the format-1 call)
-  GpuTxDevice dev(v, 0, 0, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS && status != nullptr, v->tx_hash_on_device);
+  GpuTxDevice dev(v, 0, 0, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS && status != nullptr, v->tx_hash_on_device,
+                  v->tx_sign_on_device);
   int rc;
   try {
     TxCall call(dev, v->tx_statements, v->tx_statements_kept, batch, txs, tx_offsets, host_threads, v->tx_chunk, accept_bitmap, status);
@@ -2174,7 +2297,8 @@ void tx_engine_main(zkgpu_verifier* v) {
         r.rc = tx_call_prepare(v, !active[0] && !active[1]);
         if (r.rc == ZKGPU_OK) {
           try {
-            r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS, v->tx_hash_on_device));
+            r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS, v->tx_hash_on_device,
+                                        v->tx_sign_on_device));
             r.call.reset(new TxCall(*r.dev, set ? v->tx_statements_b : v->tx_statements, v->tx_statements_kept, r.pieces, threads, v->tx_chunk,
                                     r.bits.data(), r.status.data(), 1));
             r.call->set_on_news([&] { { std::lock_guard<std::mutex> nl(news_mu); news = true; } news_cv.notify_one(); });

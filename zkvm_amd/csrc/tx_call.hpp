@@ -32,6 +32,15 @@
 // one copy of the IDs down) and hands the IDs to the statements when they are back; the signature transcripts of a chunk then
 // wait for its IDs as they wait for its keys.  Two tapes may be in flight (one when two calls share the stage contexts).  There
 // is no host fallback: an error of the stage is an error of the call.
+//
+// A device that CHAINS (TxDevice::chains(), only beside hashes(): the format flag ZKGPU_TXFORMAT_SIGN_ON_DEVICE) also forms the
+// signature's challenge itself (tx_sig_rows.hpp), from the IDs and the aggregated keys where the two stages left them: a chunk's
+// key stage, its tape and its signature stage are then ONE chain on the device, ordered by events, and nothing between
+// keys_enqueue and sigs_collect of a chunk waits for the host.  The staging thread makes a chunk's signature rows in the FIRST
+// pass, beside its key rows, with the MuSig coefficients a_i where -c a_i belong; there is one signature stage per chunk
+// (the runs of ~10 000 exist for the host's transcripts), queued as soon as the chunk's keys and tape are; the key stage's
+// bits and the signature bits of a chunk are collected together, when its signature stage is through, and that is when its
+// slot is free again (the IDs are not brought down: nothing on the host reads them).  A row whose key did not decode runs through all the same: its bit is ANDed with the key's.
 #pragma once
 #include "host_pool.hpp"
 #include "tx_hash_tape.hpp"
@@ -83,12 +92,19 @@ class TxDevice {
   virtual bool reasons() const { return false; }                            // does every stage bring back reason bytes?
   // transaction IDs on the device.  hashes(): does the device take them?  hash_tape(slot): the flattener of that slot, kept
   // by the device between calls (the staging thread fills it).  hash_enqueue queues the finished tape; hash_collect waits
-  // and writes 32 bytes per transaction of the tape, in the tape's order.  A device that does not hash is never asked.
+  // and writes 32 bytes per transaction of the tape, in the tape's order -- nowhere when the pointer is null: a device that
+  // chains is only waited for, its IDs stay where its signature stage read them.  A device that does not hash is never asked.
   virtual bool hashes() const { return false; }
   virtual TxHashTape* hash_tape(int) { return nullptr; }
   virtual int hash_enqueue(int, const TxHashTape&) { return -1; }
   virtual bool hash_done(int) { return true; }                              // never blocks
   virtual int hash_collect(int, uint8_t*, uint8_t*) { return -1; }
+  // the signature's challenge on the device.  chains(): does the device form it?  (Asked only of a device that hashes.)
+  // sigs_enqueue_chained: sigs_enqueue with the coefficients a_i in place of -c a_i, for the rows of ONE chunk in the order of
+  // its key stage's rows; the stage waits ON THE DEVICE for the key stage queued last in key_slot (its row r holds the
+  // aggregated key of row r) and for the tape queued last in hash_slot (tape_pos[r]: which of its transactions row r signs).
+  virtual bool chains() const { return false; }
+  virtual int sigs_enqueue_chained(int, int, int, size_t, const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint32_t*) { return -1; }
 };
 
 class TxCall {
@@ -103,7 +119,7 @@ class TxCall {
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(batch), threads_(host_threads), accept_(accept_bitmap),
-        status_(status), reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        status_(status), reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.resize(batch); len_.resize(batch);
     for (size_t i = 0; i < batch; ++i) { ptr_[i] = txs + tx_offsets[i]; len_[i] = (size_t)(tx_offsets[i + 1] - tx_offsets[i]); }
     plan(chunk_override, kept);
@@ -114,7 +130,7 @@ class TxCall {
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
-        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
     for (const Piece& pc : pieces)
       for (size_t i = 0; i < pc.batch; ++i) { ptr_.push_back(pc.txs + pc.tx_offsets[i]); len_.push_back((size_t)(pc.tx_offsets[i + 1] - pc.tx_offsets[i])); }
@@ -228,6 +244,7 @@ class TxCall {
     std::vector<size_t> keyed;                           // global live indices of the transactions whose keys all decode
     std::vector<uint64_t> soff;
     std::vector<uint8_t> ssc, spt, sst, bits, why;
+    std::vector<uint32_t> pos;                           // (a device that chains) per row, its transaction on the chunk's tape
     bool pending = false;
   };
   struct Span { size_t first, last; };
@@ -266,6 +283,12 @@ class TxCall {
       runs_.push_back({first, c});
       if (c == n && c - first > 1) { sig_plan_.push_back({first, c - 1}); sig_plan_.push_back({c - 1, c}); }
       else sig_plan_.push_back({first, c});
+    }
+    if (chains_) {                                       // one stage per chunk, all of them there from the start: chain_rows_[c] publishes c's rows
+      sig_plan_.clear();
+      for (size_t c = 0; c < n; ++c) { sig_plan_.push_back({c, c + 1}); sig_stages_.emplace_back(new SigStage()); sig_stages_[c]->first = c; sig_stages_[c]->last = c + 1; }
+      n_sig_stages_ = sig_next_ = n; all_sigs_made_ = true;
+      chain_rows_.assign(n, 0);
     }
     sig_stages_.reserve(sig_plan_.size());               // the calling thread indexes it while the staging thread appends: it never moves
     staged_.assign(n, 0); arena_free_.assign(n, 0); key_rows_.assign(n, 0); keys_arrived_.assign(n, 0);
@@ -343,6 +366,32 @@ class TxCall {
     std::lock_guard<std::mutex> lk(hm_);
     t_keys_host_ += now() - t0;
     key_rows_[ci] = 1;
+    news();
+  }
+  // (a device that chains) the rows of the chunk's signature equations, one per live transaction in the order of its key
+  // rows: (-1, R), (a_i, X_i) ..., and s on the basepoint -- everything but c -> the calling thread
+  void chain_rows_out(size_t ci) {
+    const double t0 = now();
+    const Chunk& k = *chunks_[ci];
+    SigStage& sg = *sig_stages_[ci];
+    const size_t ns = k.live.size();
+    sg.keyed.resize(ns);
+    for (size_t q = 0; q < ns; ++q) sg.keyed[q] = k.g0 + q;
+    sg.bits.assign((ns + 7) / 8 + 1, 0);
+    if (reasons_) sg.why.assign(ns, (uint8_t)WHY_NONE);
+    sg.soff.assign(ns + 1, 0);
+    for (size_t q = 0; q < ns; ++q) sg.soff[q + 1] = sg.soff[q] + statement(k.lo + k.live[q]).sig_scalars.size() / 32 - 1;
+    sg.ssc.resize(32 * sg.soff.back()); sg.spt.resize(32 * sg.soff.back());
+    sg.sst.resize(32 * ns);
+    host_parallel(ns, threads_, [&](size_t q) {
+      const TxStatement& t = statement(k.lo + k.live[q]);
+      memcpy(&sg.sst[32 * q], t.sig_scalars.data(), 32);
+      memcpy(sg.ssc.data() + 32 * sg.soff[q], t.sig_scalars.data() + 32, t.sig_scalars.size() - 32);
+      memcpy(sg.spt.data() + 32 * sg.soff[q], t.sig_points.data() + 32, t.sig_points.size() - 32);
+    });
+    std::lock_guard<std::mutex> lk(hm_);
+    t_sig_host_ += now() - t0;
+    chain_rows_[ci] = 1;
     news();
   }
   bool gather(size_t ci, Chunk& k) {                    // the chunk's cloak statements into its staging area; false: the call is over
@@ -430,10 +479,12 @@ class TxCall {
           if (!gather(ci, k)) return;
           vm_pass(k, P_MUSIG);
           key_rows_out(ci, sg);
+          if (chains_) chain_rows_out(ci);
         } else {
           vm_pass(k, P_MUSIG);
           scan(k, sg);
           key_rows_out(ci, sg);
+          if (chains_) chain_rows_out(ci);
           if (!gather(ci, k)) return;
         }
       }
@@ -460,6 +511,7 @@ class TxCall {
         hashed_upto_ = ids_upto_ = ci + 1;
       }
     }
+    if (chains_) return;                                 // (every stage was made in the first pass)
     std::unique_lock<std::mutex> lk(hm_);
     for (;;) {
       make_sig_stages(lk, ids_upto_);
@@ -496,17 +548,18 @@ class TxCall {
     t_wait_ += now() - t0;
     mark("signatures collected, stage", s);
   }
-  // the IDs of chunk c, from the device to the statements; the staging thread is told (ids_upto_)
-  void hash_collect(size_t c) {
+  // the IDs of chunk c, from the device to the statements; the staging thread is told (ids_upto_).  (to_host = false, a
+  // device that chains: nothing on the host reads them -- the slot's tape is collected and nothing is copied)
+  void hash_collect(size_t c, bool to_host = true) {
     Chunk& k = *chunks_[c];
     if (hash_pending_[c]) {
       hash_pending_[c] = 0;
       const double t0 = now();
       const TxHashTape& tape = *dev_.hash_tape((int)(c % n_slots_));
       hash_ids_.resize(32 * tape.n_tx() + 32);
-      const int rc = dev_.hash_collect((int)(c % n_slots_), hash_ids_.data(), nullptr);
+      const int rc = dev_.hash_collect((int)(c % n_slots_), to_host ? hash_ids_.data() : nullptr, nullptr);
       if (rc != OK) note(rc, dev_.last_error());
-      else for (size_t t = 0; t < tape.n_tx(); ++t) memcpy(statement(k.lo + tape.position(t)).txid, &hash_ids_[32 * t], 32);
+      else if (to_host) for (size_t t = 0; t < tape.n_tx(); ++t) memcpy(statement(k.lo + tape.position(t)).txid, &hash_ids_[32 * t], 32);
       t_wait_ += now() - t0;
       mark("transaction IDs collected, chunk", c);
     }
@@ -551,6 +604,7 @@ class TxCall {
   bool step() {
     if (finished_) return false;
     if (rc_ != OK) { finished_ = true; return true; }
+    if (chains_) return step_chained();
     const size_t n_seg = seg_.size(), n_chunks = chunks_.size();
     bool progress = false, sigs_all, rows = false, st_ready = false, ring_free = true, tape_ready = false;
     size_t sig_avail;
@@ -630,6 +684,98 @@ class TxCall {
     return progress;
   }
  private:
+  // The same for a device that chains.  Per chunk, in order: its key stage and its tape go out when the staging thread has
+  // made them and the chunk that used their slot last has been collected; its signature stage as soon as both are queued
+  // (the device orders the three); its proofs as before.  What a chunk brought back -- signature bits, key bits -- is
+  // collected when its signature stage is through, oldest chunk first (its tape's slot is released then too: the IDs
+  // themselves stay on the device); nothing else is waited for.
+  bool step_chained() {
+    const size_t n_chunks = chunks_.size();
+    bool progress = false, rows = false, st_ready = false, ring_free = true, tape_ready = false, sig_rows = false;
+    {
+      std::lock_guard<std::mutex> lk(hm_);
+      if (stager_failed_) { note(ENOMEM_, "out of host memory while staging the transactions"); finished_ = true; return true; }
+      if (next_key_ < n_chunks) rows = key_rows_[next_key_] != 0;
+      if (next_stage_ < n_chunks) st_ready = staged_[next_stage_] != 0;
+      if (next_stage_ >= RING) ring_free = arena_free_[next_stage_ - RING] != 0;
+      if (next_hash_ < n_chunks) tape_ready = tape_ready_[next_hash_] != 0;
+      if (next_sig_ < n_chunks) sig_rows = chain_rows_[next_sig_] != 0;
+      if (tape_failed_) note(EINVAL_, "a transaction's hash plan does not fit the device's tape");
+    }
+    if (next_chain_ == n_chunks && next_stage_ == n_chunks) { finished_ = true; return true; }
+    if (rc_ == OK && rows && next_chain_ + n_slots_ > next_key_) {
+      Segment& sg = seg_[next_key_];
+      mark("key rows ready, segment", next_key_);
+      const double t0 = now();
+      if (sg.g_hi > sg.g_lo) {
+        const int rc = dev_.keys_enqueue((int)(next_key_ % n_slots_), sg.ksc.data(), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo);
+        if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
+      }
+      t_keys_ += now() - t0;
+      mark("keys queued, segment", next_key_);
+      ++next_key_;
+      progress = true;
+    }
+    if (rc_ == OK && tape_ready && next_chain_ + n_slots_ > next_hash_) {
+      const TxHashTape& tape = *dev_.hash_tape((int)(next_hash_ % n_slots_));
+      const double t0 = now();
+      if (tape.n_tx()) {
+        const int rc = dev_.hash_enqueue((int)(next_hash_ % n_slots_), tape);
+        if (rc != OK) note(rc, dev_.last_error()); else hash_pending_[next_hash_] = 1;
+      }
+      t_keys_ += now() - t0;
+      mark("transaction-ID tape queued, chunk", next_hash_);
+      ++next_hash_;
+      progress = true;
+    }
+    if (rc_ == OK && sig_rows && next_sig_ < next_key_ && next_sig_ < next_hash_) {
+      const double t0 = now();
+      chain_enqueue(next_sig_);
+      t_sigs_ += now() - t0;
+      mark("signatures queued, stage", next_sig_);
+      ++next_sig_;
+      progress = true;
+    }
+    // (a chunk's proofs after its keys -- unless its keys wait for a slot: a slot is free again only when a whole chain has been
+    // collected, the first chain needs the first tape, and the staging thread writes tapes after it has gathered every chunk of
+    // the run, for which the ring's areas must come free -- the proofs must not wait for keys that wait for them)
+    if (rc_ == OK && next_stage_ < n_chunks && (proofs_first_ || next_stage_ < next_key_ || next_key_ >= next_chain_ + n_slots_)) {
+      if (!ring_free) {
+        Chunk& old = *chunks_[next_stage_ - RING];
+        if (!old.handle || !old.started || dev_.proofs_done(old.handle)) { proofs_collect(old); progress = true; }
+      }
+      if (st_ready) { enqueue_proofs(next_stage_++); progress = true; }
+    }
+    if (rc_ == OK && next_chain_ < next_sig_ && (!sig_stages_[next_chain_]->pending || dev_.sigs_done((int)(next_chain_ % n_slots_)))) {
+      sigs_collect(next_chain_);
+      keys_collect(next_chain_);
+      hash_collect(next_chain_, false);
+      next_kcollect_ = next_hcollect_ = ++next_chain_;
+      progress = true;
+    }
+    if (rc_ != OK) { finished_ = true; return true; }
+    if (timing_) device_marks();
+    return progress;
+  }
+  // chunk c's signature stage behind its key stage and its tape (both queued, or empty like the stage itself)
+  void chain_enqueue(size_t c) {
+    const Chunk& k = *chunks_[c];
+    SigStage& sg = *sig_stages_[c];
+    const size_t ns = sg.keyed.size();
+    if (ns == 0) return;
+    const TxHashTape& tape = *dev_.hash_tape((int)(c % n_slots_));
+    std::vector<uint32_t> at(k.n, TAPE_IDLE);
+    for (size_t t = 0; t < tape.n_tx(); ++t) if (tape.position(t) < k.n) at[tape.position(t)] = (uint32_t)t;
+    sg.pos.resize(ns);
+    for (size_t q = 0; q < ns; ++q) {
+      sg.pos[q] = at[k.live[q]];
+      if (sg.pos[q] == TAPE_IDLE) { note(EINVAL_, "a transaction the VM accepted has no ID on its chunk's tape"); return; }
+    }
+    if (!seg_[c].pending || !hash_pending_[c]) { note(EINVAL_, "a signature stage without its key stage or its tape"); return; }
+    const int slot = (int)(c % n_slots_);
+    const int rc = dev_.sigs_enqueue_chained(slot, slot, slot, ns, sg.ssc.data(), sg.spt.data(), sg.soff.data(), sg.sst.data(), sg.pos.data());
+    if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
+  }
   // (timing only) when the device is through with a chunk's proofs / a signature stage, as seen by the polling thread
   void device_marks() {
     if (seen_pdone_.size() != chunks_.size()) seen_pdone_.assign(chunks_.size(), 0);
@@ -640,8 +786,10 @@ class TxCall {
   }
   void verdicts() {
     std::vector<uint8_t> sig_ok(live_all_.size(), 0);
+    // (key_ok_ matters for a chained stage alone, whose rows include those with an undecodable key; an unchained stage's
+    // `keyed` holds only rows whose keys decoded, and the test is always true there)
     for (const auto& sg : sig_stages_)
-      for (size_t q = 0; q < sg->keyed.size(); ++q) if ((sg->bits[q / 8] >> (q % 8)) & 1) sig_ok[sg->keyed[q]] = 1;
+      for (size_t q = 0; q < sg->keyed.size(); ++q) if (((sg->bits[q / 8] >> (q % 8)) & 1) && key_ok_[sg->keyed[q]]) sig_ok[sg->keyed[q]] = 1;
     for (const auto& kp : chunks_) {
       const Chunk& k = *kp;
       for (size_t j = 0; j < k.live.size(); ++j) {
@@ -698,6 +846,7 @@ class TxCall {
   uint8_t* const status_;
   const bool reasons_;                                   // the device brings back reason bytes, and there is a status array to write them to
   const bool hashes_;                                    // the device hashes the transaction IDs (tapes instead of the host's second-pass hashing)
+  const bool chains_;                                    // ... and forms the signature's challenge: a chunk's three stages are one chain on the device
   const bool timing_;
   const double t00_;
   const size_t n_slots_;                                 // key / signature stages in flight at once (2; 1 when two calls share the stage contexts)
@@ -716,7 +865,7 @@ class TxCall {
   std::vector<char> staged_, arena_free_, key_rows_, keys_arrived_;
   // (a device that hashes) tape_ready_[c]: the staging thread has finished chunk c's tape; ids_upto_: chunks whose transaction
   // IDs are in the statements (without such a device: = hashed_upto_); tape_failed_: a plan the tape cannot hold
-  std::vector<char> tape_ready_;
+  std::vector<char> tape_ready_, chain_rows_;            // | (a device that chains) chunk c's signature rows are made
   size_t ids_upto_ = 0;
   bool tape_failed_ = false;
   std::vector<std::unique_ptr<SigStage>> sig_stages_;
@@ -730,6 +879,7 @@ class TxCall {
   std::thread stager_;
   // calling thread only
   size_t next_key_ = 0, next_kcollect_ = 0, next_stage_ = 0, next_sig_ = 0, next_hash_ = 0, next_hcollect_ = 0;
+  size_t next_chain_ = 0;                                // (a device that chains) chunks whose chain has been collected
   std::vector<char> hash_pending_;
   std::vector<uint8_t> hash_ids_;
   bool finished_ = false;

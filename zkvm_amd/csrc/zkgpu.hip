@@ -162,7 +162,7 @@ struct zkgpu_ctx {
   size_t ev_next = 0;
   int forced_w = 0, last_w = 0;
   DecodeRoutes decode_routes;   // DECODE launches and points by form (kernels.hpp; zkgpu_debug_read "decode_routes")
-  uint64_t last_adds = 0, tx_hashed_on_device = 0;   // | root context of a verifier: transaction IDs its device produced (session.hpp: GpuTxDevice::hash_collect)
+  uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0;   // | root context of a verifier: transaction IDs / signature challenges its device produced (session.hpp: GpuTxDevice)
 };
 
 namespace {
@@ -3790,6 +3790,12 @@ long long zkgpu_debug_read(zkgpu_ctx* c, const char* what, void* out, size_t byt
     if (bytes < sizeof(uint64_t)) return ZKGPU_EINVAL;         // the verifier made last on this context, since it was made
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     memcpy(out, &c->tx_hashed_on_device, sizeof(uint64_t));
+    return (long long)sizeof(uint64_t);
+  }
+  if (strcmp(what, "tx_signed_on_device") == 0) {      // ... whose signature challenge it produced (ZKGPU_TXFORMAT_SIGN_ON_DEVICE)
+    if (bytes < sizeof(uint64_t)) return ZKGPU_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    memcpy(out, &c->tx_signed_on_device, sizeof(uint64_t));
     return (long long)sizeof(uint64_t);
   }
   if (strcmp(what, "decode_routes") != 0) return debug_read_buffers(c, what, out, bytes);

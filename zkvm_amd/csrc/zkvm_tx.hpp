@@ -582,8 +582,8 @@ inline void tx_apply_challenge(TxStatement& st, const uint8_t basepoint[32], con
     (-(c * ai)).to_bytes(&st.sig_scalars[32 * (2 + i)]);
   }
 }
-inline void tx_finish_signature(TxStatement& st, const uint8_t basepoint[32], const uint8_t agg_key[32]) {
-  Transcript t = proto_transcript(P_SIGNTX);
+template <class T = Transcript> inline void tx_finish_signature(TxStatement& st, const uint8_t basepoint[32], const uint8_t agg_key[32], T* tap = nullptr) {
+  T t = tap ? *tap : T(proto_transcript(P_SIGNTX));      // (tap: tx_sig_rows.hpp writes down what is hashed here, for the device)
   t.append_message("txid", st.txid, 32);
   t.append_message("dom-sep", (const uint8_t*)"schnorr-signature v1", 20);
   t.append_point("X", agg_key);

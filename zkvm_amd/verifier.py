@@ -320,6 +320,7 @@ class BlockVerifier:
     TXFORMAT_RECOLLECTED_V1 = 1
     TXFORMAT_RECOLLECTED_V1_REASONS = 2    # the same bytes and the same bitmap; the status bytes say WHY (tx_errors)
     TXFORMAT_HASH_ON_DEVICE = 0x100        # a flag or-ed to either: contract IDs, anchors and the transaction ID hashed on the device
+    TXFORMAT_SIGN_ON_DEVICE = 0x200        # a flag or-ed to a format WITH the one above: the signature's challenge formed on the device
     # status bytes (include/zkgpu.h: ZKGPU_TXSTATUS_*); 16 .. 21 only with TXFORMAT_RECOLLECTED_V1_REASONS, lowest code first
     TXSTATUS_ACCEPTED = 0
     TXSTATUS_REJECTED = 1                  # rejected, no reason known (format 1, or any error)
@@ -338,7 +339,8 @@ class BlockVerifier:
         none -- every transaction is reported as outside the subset; TXFORMAT_RECOLLECTED_V1: the payment subset of
         DESIGN.md sec 4.5, an UNPINNED recollection of the ZkVM wire format (opt-in for exactly that reason);
         TXFORMAT_RECOLLECTED_V1_REASONS: the same, with a reason code in the status byte of every rejected transaction.
-        Either may be or-ed with TXFORMAT_HASH_ON_DEVICE (same verdicts; most of the VM's hashing moves to the device)."""
+        Either may be or-ed with TXFORMAT_HASH_ON_DEVICE (same verdicts; most of the VM's hashing moves to the device), and
+        then also with TXFORMAT_SIGN_ON_DEVICE (same verdicts; the signature's challenge is formed on the device as well)."""
         self._check(self.lib.zkgpu_verifier_set_tx_format(self.h, fmt))
 
     def set_tx_chunk(self, transactions: int) -> None:
