@@ -34,7 +34,7 @@ PRODUCT_STRICT = ["zkvm_amd/csrc/r1cs_verifier.hpp", "zkvm_amd/csrc/transcript_t
 ORACLE_STRICT = ["oracle/r1cs.c", "oracle/merlin.c", "oracle/cloak.c", "oracle/zkvm_tx.c"]
 # searched for catalogued values only (large files full of other text)
 PRODUCT_EXTRA = ["zkvm_amd/csrc/zkgpu.hip", "zkvm_amd/csrc/prep_kernels.hpp", "zkvm_amd/csrc/zkvm_tx_build.hpp", "zkvm_amd/csrc/curve.hpp",
-                 "zkvm_amd/csrc/session.hpp"]
+                 "zkvm_amd/csrc/session.hpp", "zkvm_amd/csrc/tx_device.hpp"]
 ORACLE_EXTRA = ["oracle/pyref.py", "oracle/gadgets.c", "oracle/ristretto.c"]
 
 # lines that hold text for people, not protocol bytes

@@ -941,6 +941,17 @@ bool decode_host(ge& p, const uint8_t enc[32]) {
   std::memcpy(w, enc, 32);
   return ristretto_decode(p, w);
 }
+// acc += sum of sc[t] pt[t] over the terms [lo, hi); false: a point that does not decode or a scalar that is not canonical
+bool add_terms(ge& acc, const uint8_t* sc, const uint8_t* pt, uint64_t lo, uint64_t hi) {
+  for (uint64_t t = lo; t < hi; ++t) {
+    ge X, aX;
+    Scalar a;
+    if (!decode_host(X, pt + 32 * t) || !Scalar::from_canonical(sc + 32 * t, a)) return false;
+    ge_scalarmult_host(aX, a, X);
+    ge_add(acc, acc, aX);
+  }
+  return true;
+}
 
 class HostTxDevice : public TxDevice {
  public:
@@ -968,15 +979,7 @@ class HostTxDevice : public TxDevice {
       for (size_t r = 0; r < rows; ++r) {
         ge acc;
         ge_identity(acc);
-        bool ok = true;
-        for (uint64_t t = off[r]; t < off[r + 1]; ++t) {
-          ge X, aX;
-          Scalar a;
-          if (!decode_host(X, pt + 32 * t) || !Scalar::from_canonical(sc + 32 * t, a)) { ok = false; break; }
-          ge_scalarmult_host(aX, a, X);
-          ge_add(acc, acc, aX);
-        }
-        if (ok) { s.ok[r / 8] |= (uint8_t)(1u << (r % 8)); encode_point(&s.values[32 * r], acc); }
+        if (add_terms(acc, sc, pt, off[r], off[r + 1])) { s.ok[r / 8] |= (uint8_t)(1u << (r % 8)); encode_point(&s.values[32 * r], acc); }
       }
       s.done = true;
     });
@@ -1039,7 +1042,8 @@ class HostTxDevice : public TxDevice {
     { std::lock_guard<std::mutex> lk(mu_); ring_busy_[p->ring_slot] = false; ++released_total_; }
     delete p;
   }
-  int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc) override {
+  int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc, const SigChain* chain) override {
+    if (chain) { err_ = "a chained signature stage on a device that does not chain"; return -1; }
     if (failing()) return -3;
     Stage& s = sigs_[slot];
     if (s.th.joinable()) { err_ = "signature slot reused before it was collected"; return -1; }
@@ -1073,15 +1077,7 @@ class HostTxDevice : public TxDevice {
       if (!Scalar::from_canonical(bsc + 32 * r, sb)) continue;
       ge acc;
       base_mul(acc, sb);
-      bool ok = true;
-      for (uint64_t t = doff[r]; t < doff[r + 1]; ++t) {
-        ge X, aX;
-        Scalar a;
-        if (!decode_host(X, dpt + 32 * t) || !Scalar::from_canonical(dsc + 32 * t, a)) { ok = false; break; }
-        ge_scalarmult_host(aX, a, X);
-        ge_add(acc, acc, aX);
-      }
-      if (ok && ge_is_identity(acc)) s.ok[r / 8] |= (uint8_t)(1u << (r % 8));
+      if (add_terms(acc, dsc, dpt, doff[r], doff[r + 1]) && ge_is_identity(acc)) s.ok[r / 8] |= (uint8_t)(1u << (r % 8));
     }
   }
   struct Stage { std::thread th; std::atomic<bool> done{false}; std::vector<uint8_t> ok, values; };
@@ -1104,24 +1100,35 @@ class HostTxDevice : public TxDevice {
 };
 }  // namespace
 
-// -> the call's return code; *n_chunks, *n_sig_stages: what was planned; *leaked: staged chunks never released (must be 0)
-extern "C" int zkhost_txcall_selftest(size_t batch, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok, int host_threads,
-                                      size_t chunk, uint32_t delay_seed, int fail_at, uint8_t* accept_bitmap, uint8_t* status,
-                                      size_t* n_chunks, size_t* n_sig_stages, size_t* leaked) {
+// One call over a stand-in device, fail-closed in both outputs.  -> the call's return code; *n_chunks, *n_sig_stages: what was
+// planned; *leaked: staged chunks never released (must be 0)
+namespace {
+int txcall_selftest(HostTxDevice& dev, size_t batch, const uint8_t* txs, const uint64_t* offs, int host_threads, size_t chunk, int n_slots,
+                    uint8_t* accept_bitmap, uint8_t* status, size_t* n_chunks, size_t* n_sig_stages, size_t* leaked) {
   std::memset(accept_bitmap, 0, (batch + 7) / 8);
   std::memset(status, TX_INVALID, batch);
   std::vector<TxStatement> store;
-  HostTxDevice dev(txs, offs, batch, proof_ok, delay_seed, fail_at);
   int rc;
   {
-    TxCall call(dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, accept_bitmap, status);
+    TxCall call(dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, accept_bitmap, status, n_slots);
     *n_chunks = call.n_chunks();
     *n_sig_stages = call.n_sig_stages_planned();
     rc = call.run();
   }
   *leaked = dev.leaked();
-  if (rc != 0) std::memset(accept_bitmap, 0, (batch + 7) / 8);
+  if (rc != 0) {
+    std::memset(accept_bitmap, 0, (batch + 7) / 8);
+    for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;
+  }
   return rc;
+}
+}  // namespace
+
+extern "C" int zkhost_txcall_selftest(size_t batch, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok, int host_threads,
+                                      size_t chunk, uint32_t delay_seed, int fail_at, uint8_t* accept_bitmap, uint8_t* status,
+                                      size_t* n_chunks, size_t* n_sig_stages, size_t* leaked) {
+  HostTxDevice dev(txs, offs, batch, proof_ok, delay_seed, fail_at);
+  return txcall_selftest(dev, batch, txs, offs, host_threads, chunk, 2, accept_bitmap, status, n_chunks, n_sig_stages, leaked);
 }
 
 // TWO calls driven by ONE thread through start / step / done / finish, one stage slot each -- how the engine of
@@ -1183,20 +1190,25 @@ extern "C" int zkhost_txcall_pair_selftest(size_t batch, size_t split, const uin
 // ---- three protocols write (the others are the host's MuSig slots, which the tape leaves zero).
 // ---- -> transactions on the tape, or -1 a plan the tape cannot hold, -2 the block fails hash_tape_check, -3 an output too small
 #include "tx_hash_tape.hpp"
+namespace {
+// the taped second pass over `count` transactions as ONE chunk, the tape not yet finished; false: a plan the tape cannot hold
+bool tape_one_chunk(const uint8_t* txs, const uint64_t* offs, size_t count, int threads, zk::zkvm::TxHashTape& tape, zk::zkvm::TxStatement* st) {
+  std::atomic<int> bad{0};
+  tape.reset(count);
+  zk::zkvm::tx_groups_of_eight(count, threads, [&](size_t i) { return std::make_pair(txs + offs[i], (size_t)(offs[i + 1] - offs[i])); },
+                               [&](const uint8_t** p, const size_t* l, size_t first, size_t n) {
+                                 if (!zk::zkvm::tx_prepare_many_taped(p, l, st + first, n, tape, first)) bad = 1;
+                               });
+  return !bad;
+}
+}  // namespace
 extern "C" long long zkhost_tx_hash_tape(const uint8_t* txs, const uint64_t* offs, size_t count, int threads, uint8_t* status,
                                          uint32_t* head16, uint32_t* pieces, size_t pieces_cap, uint32_t* lanes, size_t lanes_cap, uint32_t* tx_shape, uint64_t* tx_slot0,
                                          uint8_t* txid, uint8_t* slots_tape, uint8_t* slots_plan, uint8_t* slot_kept, size_t slots_cap) {
   using namespace zk::zkvm;
   TxHashTape tape;
-  tape.reset(count);
   std::vector<TxStatement> st(count);
-  std::atomic<int> bad{0};
-  zk::host_parallel((count + 7) / 8, threads, [&](size_t g) {
-    const uint8_t* p[8]; size_t l[8];
-    const size_t first = 8 * g, n = std::min<size_t>(8, count - first);
-    for (size_t i = 0; i < n; ++i) { p[i] = txs + offs[first + i]; l[i] = (size_t)(offs[first + i + 1] - offs[first + i]); }
-    if (!tx_prepare_many_taped(p, l, &st[first], n, tape, first)) bad = 1;
-  });
+  const bool bad = !tape_one_chunk(txs, offs, count, threads, tape, st.data());
   for (size_t i = 0; i < count; ++i) { status[i] = (uint8_t)st[i].status; tx_shape[i] = TAPE_IDLE; tx_slot0[i] = 0; }
   std::memset(txid, 0, 32 * count);
   if (bad) return -1;
@@ -1256,7 +1268,7 @@ class HostHashingTxDevice : public HostTxDevice {
     return 0;
   }
   bool hash_done(int slot) override { return h_[slot].done; }
-  int hash_collect(int slot, uint8_t* txids, uint8_t*) override {
+  int hash_collect(int slot, uint8_t* txids) override {
     HashStage& s = h_[slot];
     if (!s.th.joinable()) { herr_ = "nothing to collect in this hash slot"; return -1; }
     s.th.join();
@@ -1285,22 +1297,10 @@ class HostHashingTxDevice : public HostTxDevice {
 extern "C" int zkhost_txcall_hashing_selftest(size_t batch, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok, int host_threads,
                                               size_t chunk, uint32_t delay_seed, int hash_fail_at, int n_slots, uint8_t* accept_bitmap,
                                               uint8_t* status, size_t* n_chunks, size_t* leaked, uint64_t* hashed) {
-  std::memset(accept_bitmap, 0, (batch + 7) / 8);
-  std::memset(status, TX_INVALID, batch);
-  std::vector<TxStatement> store;
   HostHashingTxDevice dev(txs, offs, batch, proof_ok, delay_seed, hash_fail_at);
-  int rc;
-  {
-    TxCall call(dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, accept_bitmap, status, n_slots);
-    *n_chunks = call.n_chunks();
-    rc = call.run();
-  }
-  *leaked = dev.leaked();
+  size_t n_sig_stages;
+  const int rc = txcall_selftest(dev, batch, txs, offs, host_threads, chunk, n_slots, accept_bitmap, status, n_chunks, &n_sig_stages, leaked);
   *hashed = dev.hashed();
-  if (rc != 0) {
-    std::memset(accept_bitmap, 0, (batch + 7) / 8);
-    for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;
-  }
   return rc;
 }
 
@@ -1317,15 +1317,8 @@ extern "C" long long zkhost_tx_sig_rows(const uint8_t* txs, const uint64_t* offs
                                         uint8_t* txid, uint8_t* agg, uint8_t* R, uint8_t* a_in, uint8_t* from_rows, uint8_t* from_host) {
   using namespace zk::zkvm;
   TxHashTape tape;
-  tape.reset(count);
   std::vector<TxStatement> st(count);
-  std::atomic<int> bad{0};
-  zk::host_parallel((count + 7) / 8, threads, [&](size_t g) {
-    const uint8_t* p[8]; size_t l[8];
-    const size_t first = 8 * g, n = std::min<size_t>(8, count - first);
-    for (size_t i = 0; i < n; ++i) { p[i] = txs + offs[first + i]; l[i] = (size_t)(offs[first + i + 1] - offs[first + i]); }
-    if (!tx_prepare_many_taped(p, l, &st[first], n, tape, first)) bad = 1;
-  });
+  const bool bad = !tape_one_chunk(txs, offs, count, threads, tape, st.data());
   std::memset(n_keys, 0, 4 * count); std::memset(txid, 0, 32 * count); std::memset(agg, 0, 32 * count); std::memset(R, 0, 32 * count);
   std::memset(a_in, 0, 32 * cap * count); std::memset(from_rows, 0, 32 * cap * count); std::memset(from_host, 0, 32 * cap * count);
   for (size_t i = 0; i < count; ++i) status[i] = (uint8_t)st[i].status;
@@ -1358,15 +1351,7 @@ extern "C" long long zkhost_tx_sig_rows(const uint8_t* txs, const uint64_t* offs
     std::memcpy(&spt[8 * soff[q]], t.sig_points.data() + 32, 32 * (k + 1));
     ge acc;
     ge_identity(acc);
-    bool ok = true;
-    for (size_t j = 0; j < k && ok; ++j) {
-      ge X, aX;
-      Scalar a;
-      if (!decode_host(X, &t.sig_points[32 * (2 + j)]) || !Scalar::from_canonical(&t.sig_scalars[32 * (2 + j)], a)) { ok = false; break; }
-      ge_scalarmult_host(aX, a, X);
-      ge_add(acc, acc, aX);
-    }
-    if (ok) encode_point((uint8_t*)&aggw[8 * q], acc);             // (a key that does not decode: zeros, as the key stage leaves them)
+    if (add_terms(acc, t.sig_scalars.data(), t.sig_points.data(), 2, 2 + k)) encode_point((uint8_t*)&aggw[8 * q], acc);             // (a key that does not decode: zeros, as the key stage leaves them)
     n_keys[i] = (uint32_t)k;
     std::memcpy(txid + 32 * i, &ids[8 * pos[q]], 32);
     std::memcpy(agg + 32 * i, &aggw[8 * q], 32);
@@ -1387,22 +1372,19 @@ extern "C" long long zkhost_tx_sig_rows(const uint8_t* txs, const uint64_t* offs
 // ---- the scheduling of a call that CHAINS (TxDevice::chains) on the CPU: the hashing stand-in above, plus a signature stage
 // ---- that waits -- on its own thread, as the device waits on events -- for the key stage of key_slot and the tape of hash_slot,
 // ---- forms the challenges with tx_sig_row and then checks the rows like the unchained stage.  sig_fail_at: the n-th
-// ---- sigs_enqueue_chained / sigs_collect reports an error (-1: none).  *signed_rows: rows whose challenge the stand-in produced.
+// ---- chained sigs_enqueue / sigs_collect reports an error (-1: none).  *signed_rows: rows whose challenge the stand-in produced.
 namespace {
 class HostChainingTxDevice : public HostHashingTxDevice {
  public:
   HostChainingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int sig_fail_at)
       : HostHashingTxDevice(txs, offs, batch, proof_ok, seed, -1), crng_(seed ^ 0x51ed270bu), sig_fail_at_(sig_fail_at) { have_script_ = sig_script(script_); }
   bool chains() const override { return true; }
-  int sigs_enqueue(int, size_t, const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*) override {
-    cerr_ = "an unchained signature stage on a device that chains";
-    return -1;
-  }
-  int sigs_enqueue_chained(int slot, int key_slot, int hash_slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff,
-                           const uint8_t* bsc, const uint32_t* tape_pos) override {
+  int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc, const SigChain* chain) override {
+    if (!chain) { cerr_ = "an unchained signature stage on a device that chains"; return -1; }
+    const uint32_t* tape_pos = chain->tape_pos;
     Stage& s = sigs_[slot];
-    Stage& ks = keys_[key_slot];
-    HashStage& hs = h_[hash_slot];
+    Stage& ks = keys_[chain->key_slot];
+    HashStage& hs = h_[chain->hash_slot];
     if (!have_script_) { cerr_ = "no script of the signature transcript"; return -1; }
     if (s.th.joinable()) { cerr_ = "signature slot reused before it was collected"; return -1; }
     if (!ks.th.joinable() || !hs.th.joinable()) { cerr_ = "a chained signature stage without its key stage or its tape in flight"; return -1; }
@@ -1453,23 +1435,9 @@ extern "C" int zkhost_txcall_chaining_selftest(size_t batch, const uint8_t* txs,
                                                size_t chunk, uint32_t delay_seed, int sig_fail_at, int n_slots, uint8_t* accept_bitmap,
                                                uint8_t* status, size_t* n_chunks, size_t* n_sig_stages, size_t* leaked, uint64_t* hashed,
                                                uint64_t* signed_rows) {
-  std::memset(accept_bitmap, 0, (batch + 7) / 8);
-  std::memset(status, TX_INVALID, batch);
-  std::vector<TxStatement> store;
   HostChainingTxDevice dev(txs, offs, batch, proof_ok, delay_seed, sig_fail_at);
-  int rc;
-  {
-    TxCall call(dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, accept_bitmap, status, n_slots);
-    *n_chunks = call.n_chunks();
-    *n_sig_stages = call.n_sig_stages_planned();
-    rc = call.run();
-  }
-  *leaked = dev.leaked();
+  const int rc = txcall_selftest(dev, batch, txs, offs, host_threads, chunk, n_slots, accept_bitmap, status, n_chunks, n_sig_stages, leaked);
   *hashed = dev.hashed();
   *signed_rows = dev.signed_rows();
-  if (rc != 0) {
-    std::memset(accept_bitmap, 0, (batch + 7) / 8);
-    for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;
-  }
   return rc;
 }

@@ -1659,128 +1659,6 @@ int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
   return ZKGPU_OK;
 }
 
-namespace {
-
-// host arrays -> the context's input buffers -> kernels and result copy queued (batch_device_enqueue, value mode);
-// msm_values_collect finishes.  The arrays must stay alive until then; the context is marked busy meanwhile.
-int msm_values_enqueue(zkgpu_ctx* c, const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t batch) {
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  TRY(refuse_if_pending(c));
-  DeviceGuard g(c->device);
-  const uint64_t n = offsets[batch];
-  TRY(upload(c, c->in_scalars, scalars, n * 32));
-  TRY(upload(c, c->in_points, points, n * 32));
-  TRY(upload(c, c->in_offsets, offsets, (batch + 1) * 8));
-  Job job;
-  job.d_dyn_scalars = (const uint32_t*)c->in_scalars.p;
-  job.d_dyn_points = (const uint32_t*)c->in_points.p;
-  job.d_dyn_offsets = (const uint64_t*)c->in_offsets.p;
-  job.n_dyn = n;
-  job.n_msm = (uint32_t)batch;
-  job.max_dyn_row = longest_row(offsets, batch);
-  const int rc = batch_device_enqueue(c, job, true);
-  if (rc != ZKGPU_OK) { c->split = zkgpu_ctx::SplitOp{}; return rc; }
-  c->pending = true; c->pending_batch = batch;
-  return ZKGPU_OK;
-}
-
-int split_collect(zkgpu_ctx* c, uint8_t* bitmap, uint8_t* values) {
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  c->pending = false;
-  return batch_collect(c, bitmap, values);
-}
-
-// Reason bytes of a key or signature stage (tx_reason_kernels.hpp: k_tx_reason_stage), in two halves like the stage itself.
-// They lie behind everything else the stage copies to the context's pinned result buffer -- bitmap | 64 status bytes | the
-// values of a key stage -- so the buffer is brought to size BEFORE the stage is queued (it never shrinks, and the context is
-// idle then); the kernel and its copy are queued behind the stage's own on the same stream, and the one wait of
-// batch_collect covers them.
-size_t stage_reasons_offset(size_t batch, bool values) { return (batch + 7) / 8 + 64 + (values ? 32 * batch : 0); }
-int stage_reasons_reserve(zkgpu_ctx* c, size_t batch, bool values) {
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  TRY(refuse_if_pending(c));
-  DeviceGuard g(c->device);
-  return ensure_pinned(c, stage_reasons_offset(batch, values) + batch);
-}
-int stage_reasons_enqueue(zkgpu_ctx* c, uint8_t code_when_clear) {
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  const size_t B = c->split.batch;
-  if (c->split.kind == 0 || B == 0) return ZKGPU_OK;
-  auto queue = [&]() -> int {
-    TRY(ensure(c, c->tx_reason, B));
-    {
-      Launch l(c, "k_tx_reason_stage", c->split.stream);
-      hipLaunchKernelGGL(k_tx_reason_stage, dim3(blocks_for(B, 256)), dim3(256), 0, c->split.stream, (const uint8_t*)c->bitmap.p, (uint32_t)B,
-                         (uint32_t)code_when_clear, (uint8_t*)c->tx_reason.p);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync((char*)c->pinned + stage_reasons_offset(B, c->split.values), c->tx_reason.p, B, hipMemcpyDeviceToHost, c->split.stream));
-    return ZKGPU_OK;
-  };
-  const int rc = queue();
-  if (rc != ZKGPU_OK) { c->split = zkgpu_ctx::SplitOp{}; c->pending = false; }     // (the failed call has drained the device: the stage is not in flight any more)
-  return rc;
-}
-// split_collect, and the stage's reason bytes with it (why may be NULL)
-int split_collect_why(zkgpu_ctx* c, uint8_t* bitmap, uint8_t* values, uint8_t* why) {
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  const size_t B = c->split.batch;
-  const bool vals = c->split.values;
-  const int rc = split_collect(c, bitmap, values);
-  if (!why) return rc;
-  if (rc != ZKGPU_OK) { memset(why, ZKGPU_TXSTATUS_REJECTED, B); return rc; }
-  if (B) memcpy(why, (const char*)c->pinned + stage_reasons_offset(B, vals), B);
-  return rc;
-}
-
-// has everything queued by the last *_enqueue on this context run?  (never blocks)
-bool split_done(zkgpu_ctx* c) {
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  if (c->split.kind == 0 || c->split.batch == 0) return true;
-  DeviceGuard g(c->device);
-  return hipStreamQuery(c->split.stream) != hipErrorNotReady;
-}
-
-// rows that already lie in the context's input buffers (c->mu held, the device set): kernels and result copy queued
-int verify_ps_enqueue_resident(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, uint64_t nd, uint64_t ns, uint64_t max_dyn_row) {
-  Job job;
-  job.d_dyn_scalars = (const uint32_t*)c->in_scalars.p;
-  job.d_dyn_points = (const uint32_t*)c->in_points.p;
-  job.d_dyn_offsets = (const uint64_t*)c->in_offsets.p;
-  job.n_dyn = nd;
-  job.d_st_scalars = (const uint32_t*)c->in_st_scalars.p;
-  job.d_st_index = (const uint32_t*)c->in_st_index.p;
-  job.d_st_offsets = (const uint64_t*)c->in_st_offsets.p;
-  job.n_static = ns;
-  job.d_static_rows = ps->rows;
-  job.n_msm = (uint32_t)batch;
-  job.max_dyn_row = max_dyn_row;
-  const int rc = (ps->table && ns) ? batch_device_tables_enqueue(c, job, ps) : batch_device_enqueue(c, job, false);
-  if (rc != ZKGPU_OK) { c->split = zkgpu_ctx::SplitOp{}; return rc; }
-  c->pending = true; c->pending_batch = batch;
-  return ZKGPU_OK;
-}
-
-// the same for rows of dynamic terms + terms on the resident set's tables (the signature equations)
-int verify_ps_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, const uint8_t* dyn_scalars, const uint8_t* dyn_points,
-                      const uint64_t* dyn_offsets, const uint8_t* static_scalars, const uint32_t* static_index, const uint64_t* static_offsets) {
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  TRY(refuse_if_pending(c));
-  DeviceGuard g(c->device);
-  const uint64_t nd = dyn_offsets[batch], ns = static_offsets[batch];
-  TRY(upload(c, c->in_scalars, dyn_scalars, nd * 32));
-  TRY(upload(c, c->in_points, dyn_points, nd * 32));
-  TRY(upload(c, c->in_offsets, dyn_offsets, (batch + 1) * 8));
-  TRY(upload(c, c->in_st_scalars, static_scalars, ns * 32));
-  TRY(upload(c, c->in_st_index, static_index, ns * 4));
-  TRY(upload(c, c->in_st_offsets, static_offsets, (batch + 1) * 8));
-  return verify_ps_enqueue_resident(c, ps, batch, nd, ns, longest_row(dyn_offsets, batch));
-}
-
-}  // namespace
-
 int zkgpu_verifier_set_tx_statements_kept(zkgpu_verifier* v, size_t transactions) {
   if (!v || transactions >= ((size_t)1 << 31)) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> lk(v->mu);
@@ -1795,301 +1673,9 @@ int zkgpu_verifier_set_tx_chunk(zkgpu_verifier* v, size_t transactions) {
   return ZKGPU_OK;
 }
 
+#include "tx_device.hpp"   // GpuTxDevice: the device side of a transaction call
+
 namespace {
-
-// The device side of a transaction call (tx_call.hpp: TxDevice) on a verifier: key stages on aux_keys[slot], signature
-// stages on aux_sigs[slot] (contexts of their own, each a pair of streams beside the lanes'), cloak proofs as blocks of
-// mixed shapes on the lanes, staged through the verifier's ring of pinned / device areas.  v->mu is held by the call.
-static_assert(zk::zkvm::TxCall::OK == ZKGPU_OK && zk::zkvm::TxCall::ENOMEM_ == ZKGPU_ENOMEM && zk::zkvm::TxCall::EINVAL_ == ZKGPU_EINVAL, "tx_call.hpp restates three status codes");
-class GpuTxDevice : public zk::zkvm::TxDevice {
- public:
-  // slot_base / arena_base: which of the verifier's stage contexts and staging areas this call uses (a call alone: slots 0
-  // and 1, areas 0 .. RING - 1; two rounds in flight: one slot and one set of areas each)
-  // reasons: a format-2 call -- every stage also brings back one reason byte per row (tx_reason_kernels.hpp)
-  // hashes: the format's flag ZKGPU_TXFORMAT_HASH_ON_DEVICE -- the transaction IDs of every chunk come from k_tx_hash
-  // chains: ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the signature's challenge comes from k_tx_sig_rows
-  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false, bool hashes = false, bool chains = false)
-      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes), chains_(hashes && chains) {}
-  bool reasons() const override { return reasons_; }
-  bool hashes() const override { return hashes_; }
-  bool chains() const override { return chains_; }
-  // the rows up, the challenge kernel behind the slot's key stage and tape (events), the equations behind it: all on the
-  // signature context's stream, nothing waited for
-  int sigs_enqueue_chained(int slot, int key_slot, int hash_slot, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points,
-                           const uint64_t* dyn_offsets, const uint8_t* base_scalars, const uint32_t* tape_pos) override {
-    zkgpu_ctx* c = sigs(slot);
-    sidx_[slot].assign(rows, 0);
-    soff_[slot].resize(rows + 1);
-    for (size_t q = 0; q <= rows; ++q) soff_[slot][q] = q;
-    if (reasons_) { const int rc = seen(stage_reasons_reserve(c, rows, false), c); if (rc != ZKGPU_OK) return rc; }
-    // (a profiled call: the stage's context takes the root's switch for this stage alone -- profile_to_root clears it when
-    // the stage is collected, and here on every error, after which sigs_collect is not asked)
-    bool profiled = false;
-    { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); profiled = v_->root->profiling; }
-    int rc = chain_queue(slot, key_slot, hash_slot, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, tape_pos, profiled);
-    if (rc != ZKGPU_OK) err_ = std::string("signature challenge stage: ") + zkgpu_last_error(c);
-    if (rc == ZKGPU_OK) {
-      std::lock_guard<std::recursive_mutex> lk(c->mu);
-      DeviceGuard g(c->device);
-      rc = seen(verify_ps_enqueue_resident(c, v_->ps, rows, dyn_offsets[rows], rows, longest_row(dyn_offsets, rows)), c);
-    }
-    if (rc == ZKGPU_OK) sig(slot).rows = rows;
-    if (rc == ZKGPU_OK && reasons_) rc = seen(stage_reasons_enqueue(c, ZKGPU_TXSTATUS_SIGNATURE), c);
-    if (rc != ZKGPU_OK && profiled) profile_to_root(c);
-    return rc;
-  }
-  zk::zkvm::TxHashTape* hash_tape(int slot) override { return &hash(slot).tape; }
-  // one copy up, one launch, one copy of the IDs down, on the stage's own high-priority stream
-  int hash_enqueue(int slot, const zk::zkvm::TxHashTape& tape) override {
-    const int rc = hash_queue(slot, tape);
-    if (rc != ZKGPU_OK) err_ = std::string("transaction-ID hashing stage: ") + zkgpu_last_error(keys(slot));
-    return rc;
-  }
-  bool hash_done(int slot) override {
-    zkgpu_verifier::TxHashStage& hs = hash(slot);
-    if (!hs.stream || hs.n_tx == 0) return true;
-    DeviceGuard g(v_->root->device);
-    return hipStreamQuery(hs.stream) != hipErrorNotReady;
-  }
-  int hash_collect(int slot, uint8_t* txids, uint8_t*) override {
-    const int rc = hash_wait(slot, txids);
-    if (rc != ZKGPU_OK) err_ = std::string("transaction-ID hashing stage: ") + zkgpu_last_error(keys(slot));
-    return rc;
-  }
-  const uint8_t* basepoint() override { return v_->basepoint; }
-  int keys_enqueue(int slot, const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t rows) override {
-    if (reasons_) { const int rc = seen(stage_reasons_reserve(keys(slot), rows, true), keys(slot)); if (rc != ZKGPU_OK) return rc; }
-    const int rc = seen(msm_values_enqueue(keys(slot), scalars, points, offsets, rows), keys(slot));
-    return (rc == ZKGPU_OK && reasons_) ? seen(stage_reasons_enqueue(keys(slot), ZKGPU_TXSTATUS_KEY), keys(slot)) : rc;
-  }
-  bool keys_done(int slot) override { return split_done(keys(slot)); }
-  int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values, uint8_t* why) override {
-    return seen(split_collect_why(keys(slot), ok_bits, values, reasons_ ? why : nullptr), keys(slot));
-  }
-  // (staging thread: touches the plans -- plans_mu -- the given arena and nothing else of the verifier)
-  int proofs_stage(size_t ring_slot, size_t n, const zk::zkvm::TxProofSource* src, int host_threads, void** handle, std::string* err) override {
-    zkgpu_txblock* blk = nullptr;
-    const int rc = txblock_stage_host(v_, n, src, nullptr, host_threads, &blk, &v_->tx_arenas[ab_ + ring_slot], err);
-    if (rc != ZKGPU_OK) return rc;
-    Staged* st = new Staged();
-    st->blk = blk;
-    *handle = st;
-    return ZKGPU_OK;
-  }
-  int proofs_start(size_t ring_slot, void* handle) override {
-    Staged* st = (Staged*)handle;
-    // one copy to HBM, and the chunk's batches queued on the lanes
-    int rc = txblock_upload(v_, st->blk, &v_->tx_arenas[ab_ + ring_slot]);
-    if (rc != ZKGPU_OK) { err_ = v_->last_error; return rc; }
-    // a chunk of one shape goes to the device as few, large batches (measured: the last chunk in batches short enough for
-    // the one-wavefront-per-transaction transcript, or cut in two, does not shorten the tail of the call)
-    const size_t saved_chunk = v_->chunk;
-    v_->chunk = std::max<size_t>(saved_chunk, 4096);
-    st->run = block_start(v_, st->blk, true, reasons_);
-    v_->chunk = saved_chunk;
-    if (!st->run) { err_ = v_->last_error; return ZKGPU_ENOMEM; }
-    if (st->run->rc != ZKGPU_OK) {
-      // One device batch of the block could not be queued.  The call releases a chunk that was not started WITHOUT finishing
-      // it, and the block goes with it -- but batches of the block's other shapes may already be on lanes, and their requests
-      // refer to the block through the run: they are collected here, before the error leaves (found by injecting a fault at
-      // every runtime call of a call of four shapes: the next call collected such a request and read the freed block).
-      const int rc = st->run->rc;
-      err_ = v_->last_error;
-      std::vector<uint8_t> none((zkgpu_txblock_size(st->blk) + 7) / 8 + 1, 0);
-      (void)block_finish(v_, st->run, none.data(), nullptr);
-      st->run = nullptr;
-      return rc;
-    }
-    return ZKGPU_OK;
-  }
-  bool proofs_done(void* handle) override {                // have the lanes finished every batch of this block?  (never blocks)
-    Staged* st = (Staged*)handle;
-    if (!st->run) return true;
-    return block_done(v_, st->run);
-  }
-  int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t* why) override {
-    Staged* st = (Staged*)handle;
-    int rc = ZKGPU_OK;
-    if (st->run) { rc = block_finish(v_, st->run, accept_bits, reasons_ ? why : nullptr); if (rc != ZKGPU_OK) err_ = v_->last_error; }
-    proofs_release(handle);
-    return rc;
-  }
-  void proofs_release(void* handle) override {
-    Staged* st = (Staged*)handle;
-    if (st->blk) zkgpu_txblock_destroy(st->blk);
-    delete st;
-  }
-  int sigs_enqueue(int slot, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points, const uint64_t* dyn_offsets,
-                   const uint8_t* base_scalars) override {
-    // one term per row on the resident set's tables: index 0 = the basepoint B
-    sidx_[slot].assign(rows, 0);
-    soff_[slot].resize(rows + 1);
-    for (size_t q = 0; q <= rows; ++q) soff_[slot][q] = q;
-    if (reasons_) { const int rc = seen(stage_reasons_reserve(sigs(slot), rows, false), sigs(slot)); if (rc != ZKGPU_OK) return rc; }
-    const int rc = seen(verify_ps_enqueue(sigs(slot), v_->ps, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, sidx_[slot].data(),
-                                          soff_[slot].data()), sigs(slot));
-    return (rc == ZKGPU_OK && reasons_) ? seen(stage_reasons_enqueue(sigs(slot), ZKGPU_TXSTATUS_SIGNATURE), sigs(slot)) : rc;
-  }
-  bool sigs_done(int slot) override { return split_done(sigs(slot)); }
-  int sigs_collect(int slot, uint8_t* bits, uint8_t* why) override {
-    const int rc = seen(split_collect_why(sigs(slot), bits, nullptr, reasons_ ? why : nullptr), sigs(slot));
-    if (chains_) {
-      zkgpu_ctx* c = sigs(slot);
-      const size_t rows = sig(slot).rows;
-      sig(slot).rows = 0;
-      if (rc == ZKGPU_OK) { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_signed_on_device += rows; }
-      bool profiled = false;
-      { std::lock_guard<std::recursive_mutex> lk(c->mu); profiled = c->profiling; }
-      if (profiled) profile_to_root(c);                  // (only a call made with zkgpu_profile_enable on: nothing of it otherwise)
-    }
-    return rc;
-  }
-  std::string last_error() override { return err_; }
-
- private:
-  struct Staged { zkgpu_txblock* blk = nullptr; zkgpu_verifier::BlockRun* run = nullptr; };
-  zkgpu_verifier::TxHashStage& hash(int slot) const { return v_->tx_hash[(sb_ + slot) & 1]; }
-  zkgpu_verifier::TxSigStage& sig(int slot) const { return v_->tx_sig[(sb_ + slot) & 1]; }
-  // a profiled stage's launches go to the root's profile, where zkgpu_profile_get is asked for them (the stage's context is
-  // not the caller's to ask), and the context's switch is off again: it is on for one stage of a profiled call and never else
-  void profile_to_root(zkgpu_ctx* c) {
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    std::lock_guard<std::recursive_mutex> rl(v_->root->mu);
-    for (const ProfEntry& e : c->prof) { ProfEntry& to = v_->root->prof[(size_t)prof_index(v_->root, e.name)]; to.launches += e.launches; to.ms += e.ms; }
-    c->prof.clear();
-    c->profiling = false;
-  }
-  int chain_queue(int slot, int key_slot, int hash_slot, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points,
-                  const uint64_t* dyn_offsets, const uint8_t* base_scalars, const uint32_t* tape_pos, bool profiled) {
-    using namespace zk::zkvm;
-    zkgpu_ctx* c = sigs(slot);
-    zkgpu_ctx* kc = keys(key_slot);
-    zkgpu_verifier::TxHashStage& hs = hash(hash_slot);
-    zkgpu_verifier::TxSigStage& ss = sig(slot);
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    TRY(refuse_if_pending(c));
-    DeviceGuard g(c->device);
-    // what the kernel indexes blindly: the key stage in flight in that slot has exactly these rows (its values: 32 bytes per
-    // row), the tape in flight holds every transaction named, every row has R and at least one key
-    hipStream_t key_stream = nullptr;
-    {
-      std::lock_guard<std::recursive_mutex> kl(kc->mu);
-      if (!kc->pending || kc->split.kind != 1 || !kc->split.values || kc->split.batch != rows) { c->last_error = "no key stage of these rows in flight in the slot"; return ZKGPU_EINVAL; }
-      key_stream = kc->split.stream;
-    }
-    if (rows == 0 || rows >= (1ull << 31) || hs.n_tx == 0 || !hs.stream) { c->last_error = "no tape in flight in the slot"; return ZKGPU_EINVAL; }
-    for (size_t r = 0; r < rows; ++r)
-      if (tape_pos[r] >= hs.n_tx || dyn_offsets[r + 1] < dyn_offsets[r] + 2) { c->last_error = "a signature row without its ID, its R or a key"; return ZKGPU_EINVAL; }
-    if (!v_->tx_sig_const.p) {                           // once per verifier: what tx_finish_signature hashes, written down
-      SigScript sc;
-      if (!sig_script(sc)) { c->last_error = "the signature transcript does not fit the device's script"; return ZKGPU_EINVAL; }
-      Buffer made;
-      TRY(ensure(c, made, sizeof sc));
-      const hipError_t e = hipMemcpy(made.p, &sc, sizeof sc, hipMemcpyHostToDevice);
-      if (e != hipSuccess) { (void)hipFree(made.p); HIP_TRY(c, e); }
-      v_->tx_sig_const = made;
-    }
-    if (!ss.ev_keys) HIP_TRY(c, hipEventCreateWithFlags(&ss.ev_keys, hipEventDisableTiming));
-    if (!ss.ev_ids) HIP_TRY(c, hipEventCreateWithFlags(&ss.ev_ids, hipEventDisableTiming));
-    const uint64_t nd = dyn_offsets[rows];
-    TRY(upload(c, c->in_scalars, dyn_scalars, nd * 32));
-    TRY(upload(c, c->in_points, dyn_points, nd * 32));
-    TRY(upload(c, c->in_offsets, dyn_offsets, (rows + 1) * 8));
-    TRY(upload(c, c->in_st_scalars, base_scalars, rows * 32));
-    TRY(upload(c, c->in_st_index, sidx_[slot].data(), rows * 4));
-    TRY(upload(c, c->in_st_offsets, soff_[slot].data(), (rows + 1) * 8));
-    TRY(upload(c, ss.d_pos, tape_pos, rows * 4));
-    HIP_TRY(c, hipEventRecord(ss.ev_keys, key_stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, ss.ev_keys, 0));
-    HIP_TRY(c, hipEventRecord(ss.ev_ids, hs.stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, ss.ev_ids, 0));
-    c->profiling = profiled;
-    SigRowsView view{(const SigScript*)v_->tx_sig_const.p, (const uint32_t*)hs.d_txid.p, (const uint32_t*)ss.d_pos.p, (const uint32_t*)kc->values.p,
-                     (const uint64_t*)c->in_offsets.p, (const uint32_t*)c->in_points.p, (uint32_t*)c->in_scalars.p, (uint32_t)rows};
-    {
-      Launch l(c, "k_tx_sig_rows", c->stream);
-      hipLaunchKernelGGL(zk::k_tx_sig_rows, dim3(blocks_for(rows, 64)), dim3(64), 0, c->stream, view);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return ZKGPU_OK;
-  }
-  // (errors are kept by the slot's key context, whose runtime-call macros these are)
-  static int pinned_grow(zkgpu_ctx* c, void*& p, size_t& cap, size_t bytes) {
-    if (bytes <= cap) return ZKGPU_OK;
-    if (p) HIP_TRY(c, hipHostFree(p));
-    p = nullptr; cap = 0;
-    HIP_TRY(c, hipHostMalloc(&p, bytes + bytes / 8 + 4096, hipHostMallocDefault));
-    cap = bytes + bytes / 8 + 4096;
-    return ZKGPU_OK;
-  }
-  int hash_queue(int slot, const zk::zkvm::TxHashTape& tape) {
-    using namespace zk::zkvm;
-    zkgpu_ctx* c = keys(slot);
-    zkgpu_verifier::TxHashStage& hs = hash(slot);
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    hs.n_tx = 0;
-    if (!hs.stream) {
-      int least = 0, greatest = 0;
-      HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-      HIP_TRY(c, hipStreamCreateWithPriority(&hs.stream, hipStreamNonBlocking, greatest));
-    }
-    if (!v_->tx_hash_const.p) {                          // once per verifier: the protocols' initial transcripts, the label table
-      std::vector<uint32_t> protos;
-      std::vector<uint8_t> labels;
-      hash_tape_constants(protos, labels);
-      const size_t pb = 4 * protos.size();
-      Buffer made;
-      TRY(ensure(c, made, pb + labels.size()));
-      hipError_t e = hipMemcpy(made.p, protos.data(), pb, hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy((char*)made.p + pb, labels.data(), labels.size(), hipMemcpyHostToDevice);
-      if (e != hipSuccess) { (void)hipFree(made.p); HIP_TRY(c, e); }
-      v_->tx_hash_const = made;
-    }
-    const HashTapeHead& h = tape.head();
-    const size_t bytes = tape.bytes(), id_bytes = 32 * (size_t)h.n_tx;
-    TRY(pinned_grow(c, hs.h_in, hs.h_in_cap, bytes));
-    TRY(pinned_grow(c, hs.h_out, hs.h_out_cap, id_bytes));
-    TRY(ensure(c, hs.d_tape, bytes));
-    TRY(ensure(c, hs.d_slots, 32 * (size_t)h.n_slots + 32));
-    TRY(ensure(c, hs.d_txid, id_bytes));
-    memcpy(hs.h_in, tape.block(), bytes);
-    HIP_TRY(c, hipMemcpyAsync(hs.d_tape.p, hs.h_in, bytes, hipMemcpyHostToDevice, hs.stream));
-    HashTapeView view{(const uint32_t*)hs.d_tape.p, (const uint32_t*)v_->tx_hash_const.p,
-                      (const uint8_t*)v_->tx_hash_const.p + 4 * (size_t)N_PROTO * TAPE_PROTO_WORDS, (uint32_t*)hs.d_slots.p, (uint32_t*)hs.d_txid.p};
-    {
-      Launch l(c, "k_tx_hash", hs.stream);
-      hipLaunchKernelGGL(zk::k_tx_hash, dim3(h.n_lanes / 64), dim3(64), 0, hs.stream, view, h.n_lanes);
-    }
-    HIP_TRY(c, hipGetLastError());
-    if (!chains_) HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));   // (a chain reads them on the device)
-    hs.n_tx = h.n_tx;
-    return ZKGPU_OK;
-  }
-  int hash_wait(int slot, uint8_t* txids) {
-    zkgpu_ctx* c = keys(slot);
-    zkgpu_verifier::TxHashStage& hs = hash(slot);
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    DeviceGuard g(c->device);
-    const size_t n = hs.n_tx;
-    hs.n_tx = 0;
-    if (n == 0) return ZKGPU_OK;
-    HIP_TRY(c, hipStreamSynchronize(hs.stream));
-    if (txids && !chains_) memcpy(txids, hs.h_out, 32 * n);
-    { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_hashed_on_device += n; }
-    return ZKGPU_OK;
-  }
-  int seen(int rc, zkgpu_ctx* where) { if (rc != ZKGPU_OK) err_ = zkgpu_last_error(where); return rc; }
-  zkgpu_ctx* keys(int slot) const { return v_->aux_keys[(sb_ + slot) & 1]; }
-  zkgpu_ctx* sigs(int slot) const { return v_->aux_sigs[(sb_ + slot) & 1]; }
-  zkgpu_verifier* v_;
-  const int sb_;
-  const size_t ab_;
-  const bool reasons_, hashes_, chains_;
-  std::vector<uint32_t> sidx_[2];
-  std::vector<uint64_t> soff_[2];
-  std::string err_;
-};
 
 // what a transaction call needs of the verifier before it starts (v->mu held): nothing in flight on the lanes, the stage
 // contexts, the basepoint's encoding, the ring of staging areas
@@ -2143,7 +1729,7 @@ int tx_call_prepare(zkgpu_verifier* v, bool collect_lanes = true) {
 }  // namespace
 
 // The scheduling of a call -- chunks, stages, the staging thread and the calling thread -- is csrc/tx_call.hpp (TxCall); the
-// device side is GpuTxDevice above.  The calling thread is the one that talks to the device.
+// device side is csrc/tx_device.hpp (GpuTxDevice).  The calling thread is the one that talks to the device.
 int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets, int host_threads,
                           uint8_t* accept_bitmap, uint8_t* status) {
   using namespace zk::zkvm;

@@ -4,7 +4,7 @@
 //
 // Until round 3 this was one 480-line function of fifteen capturing lambdas inside session.hpp (the
 // round-2 and round-3 advisors each found a hazard in it).  It is a class now, and it does not know HIP: the same code is
-// driven (a) by the verifier in libzkgpu (session.hpp: GpuTxDevice) and (b) in libzkhost by a CPU stand-in whose
+// driven (a) by the verifier in libzkgpu (tx_device.hpp: GpuTxDevice) and (b) in libzkhost by a CPU stand-in whose
 // "device" finishes its work on threads of its own after random delays (hostlib.cpp: zkhost_txcall_selftest), which the
 // sanitizer tier runs under ThreadSanitizer -- the flags, the ring, the stage cuts and the hand-overs between the two
 // threads are exercised on the CPU with no GPU in sight.
@@ -26,21 +26,25 @@
 // order upstream would meet the faults in: decoding and the VM (16, host), r1cs::Verifier::verify (17 .. 19), the keys the
 // signature covers (20), the deferred signature check (21).  The bits are formed exactly as without reasons.
 //
-// A device that HASHES (TxDevice::hashes(): the format flag ZKGPU_TXFORMAT_HASH_ON_DEVICE) takes the contract IDs, the anchor
-// ratchets and the transaction-ID tree of every chunk off the staging thread: the second pass writes the chunk's plans into a
-// tape (tx_hash_tape.hpp) instead of running them, the calling thread queues the tape (hash_enqueue: one copy up, one launch,
-// one copy of the IDs down) and hands the IDs to the statements when they are back; the signature transcripts of a chunk then
-// wait for its IDs as they wait for its keys.  Two tapes may be in flight (one when two calls share the stage contexts).  There
-// is no host fallback: an error of the stage is an error of the call.
-//
-// A device that CHAINS (TxDevice::chains(), only beside hashes(): the format flag ZKGPU_TXFORMAT_SIGN_ON_DEVICE) also forms the
-// signature's challenge itself (tx_sig_rows.hpp), from the IDs and the aggregated keys where the two stages left them: a chunk's
-// key stage, its tape and its signature stage are then ONE chain on the device, ordered by events, and nothing between
-// keys_enqueue and sigs_collect of a chunk waits for the host.  The staging thread makes a chunk's signature rows in the FIRST
-// pass, beside its key rows, with the MuSig coefficients a_i where -c a_i belong; there is one signature stage per chunk
-// (the runs of ~10 000 exist for the host's transcripts), queued as soon as the chunk's keys and tape are; the key stage's
-// bits and the signature bits of a chunk are collected together, when its signature stage is through, and that is when its
-// slot is free again (the IDs are not brought down: nothing on the host reads them).  A row whose key did not decode runs through all the same: its bit is ANDed with the key's.
+// ONE scheduler, two switches the device sets (format flags of the verifier; neither has a host fallback: an error of a stage is an
+// error of the call):
+//   TxDevice::hashes() (ZKGPU_TXFORMAT_HASH_ON_DEVICE) takes the contract IDs, the anchor ratchets and the transaction-ID tree of
+//     every chunk off the staging thread: the second pass writes the chunk's plans into a tape (tx_hash_tape.hpp) instead of
+//     running them, the calling thread queues the tape (hash_enqueue: one copy up, one launch, one copy of the IDs down) and
+//     hands the IDs to the statements when they are back; the signature transcripts of a chunk then wait for its IDs as they
+//     wait for its keys.  Two tapes may be in flight (one when two calls share the stage contexts).
+//   TxDevice::chains() (ZKGPU_TXFORMAT_SIGN_ON_DEVICE, only beside hashes()) also leaves the signature's challenge to the device
+//     (tx_sig_rows.hpp), formed from the IDs and the aggregated keys where the two stages left them: a chunk's key stage, its
+//     tape and its signature stage are then ONE chain on the device, ordered by events, and nothing between keys_enqueue and
+//     sigs_collect of a chunk waits for the host.  The staging thread makes a chunk's signature rows in the FIRST pass, beside
+//     its key rows, with the MuSig coefficients a_i where -c a_i belong; there is one signature stage per chunk (the runs of
+//     ~10 000 exist for the host's transcripts), queued as soon as the chunk's keys and tape are; the key stage's bits and the
+//     signature bits of a chunk are collected together, when its signature stage is through, and that is when its slot is
+//     free again (the IDs are not brought down: nothing on the host reads them).  A row whose key did not decode runs through
+//     all the same: its bit is ANDed with the key's.
+// The calling thread's sub-steps (snapshot, queue_keys, queue_tape, proofs_turn, the collects, end_step) are the same whatever
+// the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run: step_host_signed()
+// and step_chained(), which say why.
 #pragma once
 #include "host_pool.hpp"
 #include "tx_hash_tape.hpp"
@@ -57,12 +61,29 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace zk {
 namespace zkvm {
 
 struct TxProofSource { uint32_t n_in, n_out; const uint8_t* com; const uint8_t* proof; uint64_t proof_len; };
+// What a signature stage of a device that chains waits for ON THE DEVICE: the key stage queued last in key_slot (its row r holds
+// the aggregated key of row r) and the tape queued last in hash_slot (tape_pos[r]: which of its transactions row r signs).
+struct SigChain { int key_slot, hash_slot; const uint32_t* tape_pos; };
+
+// f(p, l, first, cnt) for every group of eight of `count` transactions -- the groups the VM hashes in lockstep -- with p[q],
+// l[q] = where(first + q): where transaction first + q lies and how long it is
+template <class Where, class F>
+inline void tx_groups_of_eight(size_t count, int threads, Where where, F f) {
+  host_parallel((count + 7) / 8, threads, [&](size_t g) {
+    const uint8_t* p[8];
+    size_t l[8];
+    const size_t first = 8 * g, cnt = std::min<size_t>(8, count - first);
+    for (size_t q = 0; q < cnt; ++q) { const auto at = where(first + q); p[q] = at.first; l[q] = at.second; }
+    f(p, l, first, cnt);
+  });
+}
 
 // What a call needs of the device.  Status codes are the library's (0 = ok).  `slot` is 0 or 1: two stages of a kind may be
 // in flight, and TxCall never reuses a slot before it has collected what the slot held.
@@ -83,9 +104,11 @@ class TxDevice {
   virtual bool proofs_done(void* handle) = 0;                               // never blocks: would proofs_finish return at once?
   virtual int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t* why) = 0;
   virtual void proofs_release(void* handle) = 0;
-  // signature equations: per row dynamic terms (scalars, points) + one term on the basepoint's table -> "is the identity"
+  // signature equations: per row dynamic terms (scalars, points) + one term on the basepoint's table -> "is the identity".
+  // chain (NULL: the scalars are final; otherwise only to a device that chains()): the rows of ONE chunk in the order of its key
+  // stage's rows, with the coefficients a_i in place of -c a_i -- the device forms c behind what `chain` names
   virtual int sigs_enqueue(int slot, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points, const uint64_t* dyn_offsets,
-                           const uint8_t* base_scalars) = 0;
+                           const uint8_t* base_scalars, const SigChain* chain) = 0;
   virtual bool sigs_done(int slot) = 0;                                     // never blocks
   virtual int sigs_collect(int slot, uint8_t* bits, uint8_t* why) = 0;
   virtual std::string last_error() = 0;
@@ -98,13 +121,9 @@ class TxDevice {
   virtual TxHashTape* hash_tape(int) { return nullptr; }
   virtual int hash_enqueue(int, const TxHashTape&) { return -1; }
   virtual bool hash_done(int) { return true; }                              // never blocks
-  virtual int hash_collect(int, uint8_t*, uint8_t*) { return -1; }
+  virtual int hash_collect(int, uint8_t*) { return -1; }
   // the signature's challenge on the device.  chains(): does the device form it?  (Asked only of a device that hashes.)
-  // sigs_enqueue_chained: sigs_enqueue with the coefficients a_i in place of -c a_i, for the rows of ONE chunk in the order of
-  // its key stage's rows; the stage waits ON THE DEVICE for the key stage queued last in key_slot (its row r holds the
-  // aggregated key of row r) and for the tape queued last in hash_slot (tape_pos[r]: which of its transactions row r signs).
   virtual bool chains() const { return false; }
-  virtual int sigs_enqueue_chained(int, int, int, size_t, const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const uint32_t*) { return -1; }
 };
 
 class TxCall {
@@ -114,19 +133,14 @@ class TxCall {
   // status bytes of a call with reasons (ZKGPU_TXSTATUS_*, restated for the same reason; session.hpp asserts them)
   enum : uint8_t { WHY_NONE = 1, WHY_TX_INVALID = 16, WHY_PROOF_FIRST = 17, WHY_KEY = 20, WHY_SIGNATURE = 21 };
 
+  // several callers' transactions as ONE call (zkgpu_tx_verify_submit: calls in flight are merged as tickets are): the
+  // pieces in order, transaction i of the merged call = the i-th transaction counted through them
+  struct Piece { const uint8_t* txs; const uint64_t* tx_offsets; size_t batch; };
   // store: what the VM leaves per transaction, kept by the caller between calls (fresh memory costs a page fault per 4 KB);
   // at most `kept` entries of it are used, the rest of a longer call lives in the call.
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
-      : dev_(dev), store_(store), batch_(batch), threads_(host_threads), accept_(accept_bitmap),
-        status_(status), reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
-    ptr_.resize(batch); len_.resize(batch);
-    for (size_t i = 0; i < batch; ++i) { ptr_[i] = txs + tx_offsets[i]; len_[i] = (size_t)(tx_offsets[i + 1] - tx_offsets[i]); }
-    plan(chunk_override, kept);
-  }
-  // several callers' transactions as ONE call (zkgpu_tx_verify_submit: calls in flight are merged as tickets are): the
-  // pieces in order, transaction i of the merged call = the i-th transaction counted through them
-  struct Piece { const uint8_t* txs; const uint64_t* tx_offsets; size_t batch; };
+      : TxCall(dev, store, kept, std::vector<Piece>{Piece{txs, tx_offsets, batch}}, host_threads, chunk_override, accept_bitmap, status, n_slots) {}
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
@@ -307,32 +321,24 @@ class TxCall {
   }
 
   // ================================================ staging thread ================================================
+  // f(p, l, first, cnt) over the chunk's groups of eight; `first` counts from the chunk's first transaction
+  template <class F> void chunk_groups(const Chunk& k, F f) {
+    tx_groups_of_eight(k.n, threads_, [&](size_t i) { return std::make_pair(ptr_[k.lo + i], len_[k.lo + i]); }, f);
+  }
   void vm_pass(Chunk& k, uint8_t only) {                // the VM over the chunk, hashing the jobs of `only` alone
     const double t0 = now();
-    const size_t t_lo = k.lo, t_hi = k.lo + k.n;
-    host_parallel((t_hi - t_lo + 7) / 8, threads_, [&](size_t g) {
-      const uint8_t* p[8];
-      size_t l[8];
-      const size_t first = t_lo + 8 * g, cnt = std::min<size_t>(8, t_hi - first);
-      for (size_t q = 0; q < cnt; ++q) { p[q] = ptr_[first + q]; l[q] = len_[first + q]; }
-      // (consecutive statements: the store's, or the overflow's -- a group of eight never straddles the two)
-      tx_prepare_many(p, l, &statement(first), cnt, true, only);
-    });
+    // (consecutive statements: the store's, or the overflow's -- a group of eight never straddles the two)
+    chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) { tx_prepare_many(p, l, &statement(k.lo + first), cnt, true, only); });
     std::lock_guard<std::mutex> lk(hm_);
     (only == ALL_PROTOS ? t_vm_ : t_keys_host_) += now() - t0;
   }
   // the second pass of a chunk on a device that hashes: the plans into the slot's tape, the MuSig jobs alone on the host
   void vm_pass_taped(Chunk& k, TxHashTape& tape) {
     const double t0 = now();
-    const size_t t_lo = k.lo, t_hi = k.lo + k.n;
     std::atomic<int> bad{0};
     tape.reset(k.n);
-    host_parallel((t_hi - t_lo + 7) / 8, threads_, [&](size_t g) {
-      const uint8_t* p[8];
-      size_t l[8];
-      const size_t first = t_lo + 8 * g, cnt = std::min<size_t>(8, t_hi - first);
-      for (size_t q = 0; q < cnt; ++q) { p[q] = ptr_[first + q]; l[q] = len_[first + q]; }
-      if (!tx_prepare_many_taped(p, l, &statement(first), cnt, tape, 8 * g)) bad = 1;
+    chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) {
+      if (!tx_prepare_many_taped(p, l, &statement(k.lo + first), cnt, tape, first)) bad = 1;
     });
     tape.finish(threads_);
     std::lock_guard<std::mutex> lk(hm_);
@@ -368,27 +374,38 @@ class TxCall {
     key_rows_[ci] = 1;
     news();
   }
+  // The rows of a signature stage, one per entry of sg.keyed, row q from the statement row(q): (x_0, R), (x_i, X_i) ... in ssc /
+  // spt from soff[q] on, s for the basepoint in sst -- as the statement holds them when its row is copied.  form(first, cnt):
+  // what is still to be done to the statements of rows [first, first + cnt), a group of eight, before they are copied.
+  template <class Row, class Form> void lay_rows(SigStage& sg, Row row, Form form) {
+    const size_t ns = sg.keyed.size();
+    sg.bits.assign((ns + 7) / 8 + 1, 0);
+    if (reasons_) sg.why.assign(ns, (uint8_t)WHY_NONE);
+    if (ns == 0) return;
+    sg.soff.assign(ns + 1, 0);
+    for (size_t q = 0; q < ns; ++q) sg.soff[q + 1] = sg.soff[q] + row(q).sig_scalars.size() / 32 - 1;
+    sg.ssc.resize(32 * sg.soff.back()); sg.spt.resize(32 * sg.soff.back());
+    sg.sst.resize(32 * ns);
+    host_parallel((ns + 7) / 8, threads_, [&](size_t g) {
+      const size_t first = 8 * g, cnt = std::min<size_t>(8, ns - first);
+      form(first, cnt);
+      for (size_t q = first; q < first + cnt; ++q) {
+        const TxStatement& t = row(q);
+        memcpy(&sg.sst[32 * q], t.sig_scalars.data(), 32);
+        memcpy(sg.ssc.data() + 32 * sg.soff[q], t.sig_scalars.data() + 32, t.sig_scalars.size() - 32);
+        memcpy(sg.spt.data() + 32 * sg.soff[q], t.sig_points.data() + 32, t.sig_points.size() - 32);
+      }
+    });
+  }
   // (a device that chains) the rows of the chunk's signature equations, one per live transaction in the order of its key
   // rows: (-1, R), (a_i, X_i) ..., and s on the basepoint -- everything but c -> the calling thread
   void chain_rows_out(size_t ci) {
     const double t0 = now();
     const Chunk& k = *chunks_[ci];
     SigStage& sg = *sig_stages_[ci];
-    const size_t ns = k.live.size();
-    sg.keyed.resize(ns);
-    for (size_t q = 0; q < ns; ++q) sg.keyed[q] = k.g0 + q;
-    sg.bits.assign((ns + 7) / 8 + 1, 0);
-    if (reasons_) sg.why.assign(ns, (uint8_t)WHY_NONE);
-    sg.soff.assign(ns + 1, 0);
-    for (size_t q = 0; q < ns; ++q) sg.soff[q + 1] = sg.soff[q] + statement(k.lo + k.live[q]).sig_scalars.size() / 32 - 1;
-    sg.ssc.resize(32 * sg.soff.back()); sg.spt.resize(32 * sg.soff.back());
-    sg.sst.resize(32 * ns);
-    host_parallel(ns, threads_, [&](size_t q) {
-      const TxStatement& t = statement(k.lo + k.live[q]);
-      memcpy(&sg.sst[32 * q], t.sig_scalars.data(), 32);
-      memcpy(sg.ssc.data() + 32 * sg.soff[q], t.sig_scalars.data() + 32, t.sig_scalars.size() - 32);
-      memcpy(sg.spt.data() + 32 * sg.soff[q], t.sig_points.data() + 32, t.sig_points.size() - 32);
-    });
+    sg.keyed.resize(k.live.size());
+    for (size_t q = 0; q < k.live.size(); ++q) sg.keyed[q] = k.g0 + q;
+    lay_rows(sg, [&](size_t q) -> TxStatement& { return statement(k.lo + k.live[q]); }, [](size_t, size_t) {});
     std::lock_guard<std::mutex> lk(hm_);
     t_sig_host_ += now() - t0;
     chain_rows_[ci] = 1;
@@ -422,27 +439,13 @@ class TxCall {
     const size_t g_lo = chunks_[sg.first]->g0, g_hi = chunks_[sg.last - 1]->g0 + chunks_[sg.last - 1]->live.size();
     sg.keyed.clear();
     for (size_t g = g_lo; g < g_hi; ++g) if (key_ok_[g]) sg.keyed.push_back(g);
-    const size_t ns = sg.keyed.size();
-    sg.bits.assign((ns + 7) / 8 + 1, 0);
-    if (reasons_) sg.why.assign(ns, (uint8_t)WHY_NONE);
-    if (ns == 0) return;
-    sg.soff.assign(ns + 1, 0);
-    for (size_t q = 0; q < ns; ++q) sg.soff[q + 1] = sg.soff[q] + statement(live_all_[sg.keyed[q]]).sig_scalars.size() / 32 - 1;
-    sg.ssc.resize(32 * sg.soff.back()); sg.spt.resize(32 * sg.soff.back());
-    sg.sst.resize(32 * ns);
     const uint8_t* B = dev_.basepoint();
-    host_parallel((ns + 7) / 8, threads_, [&](size_t g) {              // eight challenges c = H(txid, X, R) at a time
+    const auto row = [&](size_t q) -> TxStatement& { return statement(live_all_[sg.keyed[q]]); };
+    lay_rows(sg, row, [&](size_t first, size_t cnt) {                  // eight challenges c = H(txid, X, R) at a time
       TxStatement* tp[8];
       const uint8_t* ap[8];
-      const size_t first = 8 * g, cnt = std::min<size_t>(8, ns - first);
-      for (size_t q = 0; q < cnt; ++q) { tp[q] = &statement(live_all_[sg.keyed[first + q]]); ap[q] = &agg_[32 * sg.keyed[first + q]]; }
+      for (size_t q = 0; q < cnt; ++q) { tp[q] = &row(first + q); ap[q] = &agg_[32 * sg.keyed[first + q]]; }
       tx_finish_signature_many(tp, ap, B, cnt);
-      for (size_t q = first; q < first + cnt; ++q) {
-        const TxStatement& t = *tp[q - first];
-        memcpy(&sg.sst[32 * q], t.sig_scalars.data(), 32);
-        memcpy(sg.ssc.data() + 32 * sg.soff[q], t.sig_scalars.data() + 32, t.sig_scalars.size() - 32);
-        memcpy(sg.spt.data() + 32 * sg.soff[q], t.sig_points.data() + 32, t.sig_points.size() - 32);
-      }
     });
   }
   void news() { hcv_.notify_all(); if (on_news_) on_news_(); }     // (hm_ held)
@@ -557,7 +560,7 @@ class TxCall {
       const double t0 = now();
       const TxHashTape& tape = *dev_.hash_tape((int)(c % n_slots_));
       hash_ids_.resize(32 * tape.n_tx() + 32);
-      const int rc = dev_.hash_collect((int)(c % n_slots_), to_host ? hash_ids_.data() : nullptr, nullptr);
+      const int rc = dev_.hash_collect((int)(c % n_slots_), to_host ? hash_ids_.data() : nullptr);
       if (rc != OK) note(rc, dev_.last_error());
       else if (to_host) for (size_t t = 0; t < tape.n_tx(); ++t) memcpy(statement(k.lo + tape.position(t)).txid, &hash_ids_[32 * t], 32);
       t_wait_ += now() - t0;
@@ -594,67 +597,93 @@ class TxCall {
     t_stage_ += now() - t0;
     mark("proofs queued, chunk", ci);
   }
+  // ---- the sub-steps of step(): each does, without blocking, the one thing its name says if it can be done now, and says
+  // whether it did.  What the staging thread has published is read once per step, under hm_:
+  struct Ready {
+    bool rows = false, staged = false, ring_free = true, tape = false, sig_rows = false;     // of next_key_ / next_stage_ (and its ring slot) / next_hash_ / next_sig_ (chained)
+    bool sigs_all = false;                                                                   // every signature stage of the call is made,
+    size_t sig_avail = 0;                                                                    // so many of them so far
+  };
+  bool snapshot(Ready& r) {                              // false: the staging thread has failed, and the call is over
+    const size_t n = chunks_.size();
+    std::lock_guard<std::mutex> lk(hm_);
+    if (stager_failed_) { note(ENOMEM_, "out of host memory while staging the transactions"); finished_ = true; return false; }
+    r.sig_avail = n_sig_stages_; r.sigs_all = all_sigs_made_;
+    if (next_key_ < n) r.rows = key_rows_[next_key_] != 0;
+    if (next_stage_ < n) r.staged = staged_[next_stage_] != 0;
+    if (next_stage_ >= RING) r.ring_free = arena_free_[next_stage_ - RING] != 0;
+    if (hashes_ && next_hash_ < n) r.tape = tape_ready_[next_hash_] != 0;
+    if (chains_ && next_sig_ < n) r.sig_rows = chain_rows_[next_sig_] != 0;
+    if (tape_failed_) note(EINVAL_, "a transaction's hash plan does not fit the device's tape");
+    return true;
+  }
+  // the key stage of segment next_key_.  go: its slot is free -- what held it last has been collected -- and the mode queues it now
+  // (rc_ is the caller's to ask: step_host_signed() does not, and a key stage may follow a tape that failed in the same step --
+  // finish() collects it)
+  bool queue_keys(const Ready& r, bool go) {
+    if (!r.rows || !go) return false;
+    Segment& sg = seg_[next_key_];
+    mark("key rows ready, segment", next_key_);
+    const double t0 = now();
+    if (sg.g_hi > sg.g_lo) {
+      const int rc = dev_.keys_enqueue((int)(next_key_ % n_slots_), sg.ksc.data(), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo);
+      if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
+    }
+    t_keys_ += now() - t0;
+    mark("keys queued, segment", next_key_);
+    ++next_key_;
+    return true;
+  }
+  // the tape of chunk next_hash_ (a device that hashes).  slot_free: as for the keys
+  bool queue_tape(const Ready& r, bool slot_free) {
+    if (rc_ != OK || !r.tape || !slot_free) return false;
+    const TxHashTape& tape = *dev_.hash_tape((int)(next_hash_ % n_slots_));
+    const double t0 = now();
+    if (tape.n_tx()) {
+      const int rc = dev_.hash_enqueue((int)(next_hash_ % n_slots_), tape);
+      if (rc != OK) note(rc, dev_.last_error()); else hash_pending_[next_hash_] = 1;
+    }
+    t_keys_ += now() - t0;
+    mark("transaction-ID tape queued, chunk", next_hash_);
+    ++next_hash_;
+    return true;
+  }
+  // the proofs of chunk next_stage_, if the mode lets them start now: the ring slot's last chunk is collected as soon as the
+  // device is through with it, and the chunk's proofs go out when the staging thread has staged them
+  bool proofs_turn(const Ready& r, bool may_start) {
+    if (rc_ != OK || next_stage_ >= chunks_.size() || !may_start) return false;
+    bool progress = false;
+    if (!r.ring_free) {
+      Chunk& old = *chunks_[next_stage_ - RING];
+      if (!old.handle || !old.started || dev_.proofs_done(old.handle)) { proofs_collect(old); progress = true; }
+    }
+    if (r.staged) { enqueue_proofs(next_stage_++); progress = true; }
+    return progress;
+  }
+  bool end_step(bool progress) {
+    if (rc_ != OK) { finished_ = true; return true; }
+    if (timing_) device_marks();
+    return progress;
+  }
   // The calling thread never waits for one thing while another could be queued: it looks, in turn, for the key rows of a
   // chunk (its key stage goes out, before any of its proofs: what follows the keys is a chain, keys -> host transcripts ->
   // equations, and queued behind the proofs' chip-filling kernels its short kernels would wait for CUs), for a chunk the
   // staging thread has finished (its proofs go out), for aggregated keys that have arrived (the staging thread is told), and
   // for signature stages that are ready (the equations go out); with nothing to do it sleeps until the staging thread has
-  // news, 50 us at most (what the device has finished is found out by asking).
- public:
-  bool step() {
-    if (finished_) return false;
-    if (rc_ != OK) { finished_ = true; return true; }
-    if (chains_) return step_chained();
-    const size_t n_seg = seg_.size(), n_chunks = chunks_.size();
-    bool progress = false, sigs_all, rows = false, st_ready = false, ring_free = true, tape_ready = false;
-    size_t sig_avail;
-    {
-      std::lock_guard<std::mutex> lk(hm_);
-      if (stager_failed_) { note(ENOMEM_, "out of host memory while staging the transactions"); finished_ = true; return true; }
-      sig_avail = n_sig_stages_; sigs_all = all_sigs_made_;
-      if (next_key_ < n_seg) rows = key_rows_[next_key_] != 0;
-      if (next_stage_ < n_chunks) st_ready = staged_[next_stage_] != 0;
-      if (next_stage_ >= RING) ring_free = arena_free_[next_stage_ - RING] != 0;
-      if (hashes_ && next_hash_ < n_chunks) tape_ready = tape_ready_[next_hash_] != 0;
-      if (tape_failed_) note(EINVAL_, "a transaction's hash plan does not fit the device's tape");
-    }
-    if (next_kcollect_ == n_seg && next_stage_ == n_chunks && sigs_all && next_sig_ == sig_avail && (!hashes_ || next_hcollect_ == n_chunks)) { finished_ = true; return true; }
-    if (rc_ == OK && tape_ready && next_hcollect_ + n_slots_ > next_hash_) {       // (its slot is free once chunk next_hash - n_slots is collected)
-      const TxHashTape& tape = *dev_.hash_tape((int)(next_hash_ % n_slots_));
-      const double t0 = now();
-      if (tape.n_tx()) {
-        const int rc = dev_.hash_enqueue((int)(next_hash_ % n_slots_), tape);
-        if (rc != OK) note(rc, dev_.last_error()); else hash_pending_[next_hash_] = 1;
-      }
-      t_keys_ += now() - t0;
-      mark("transaction-ID tape queued, chunk", next_hash_);
-      ++next_hash_;
-      progress = true;
-    }
+  // news, 50 us at most (what the device has finished is found out by asking).  On a device that hashes, a chunk's tape and
+  // the IDs that are back come first of all: the transcripts wait for them.
+  bool step_host_signed(const Ready& r) {
+    const size_t n = chunks_.size();
+    if (next_kcollect_ == n && next_stage_ == n && r.sigs_all && next_sig_ == r.sig_avail && (!hashes_ || next_hcollect_ == n)) { finished_ = true; return true; }
+    bool progress = queue_tape(r, next_hcollect_ + n_slots_ > next_hash_);     // (its slot is free once chunk next_hash - n_slots is collected)
     if (rc_ == OK && next_hcollect_ < next_hash_ && (!hash_pending_[next_hcollect_] || dev_.hash_done((int)(next_hcollect_ % n_slots_)))) {
       hash_collect(next_hcollect_++);
       progress = true;
     }
-    if (rows && next_kcollect_ + n_slots_ > next_key_) {                     // (its slot is free once segment next_key - n_slots is collected)
-      Segment& sg = seg_[next_key_];
-      mark("key rows ready, segment", next_key_);
-      const double t0 = now();
-      if (sg.g_hi > sg.g_lo) {
-        const int rc = dev_.keys_enqueue((int)(next_key_ % n_slots_), sg.ksc.data(), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo);
-        if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
-      }
-      t_keys_ += now() - t0;
-      mark("keys queued, segment", next_key_);
-      ++next_key_;
-      progress = true;
-    }
-    if (rc_ == OK && next_stage_ < n_chunks && (proofs_first_ || next_stage_ < next_key_)) {     // (a chunk's proofs after its keys, unless the call is one chunk)
-      if (!ring_free) {                                   // the ring slot's last chunk: collected as soon as the device is through with it
-        Chunk& old = *chunks_[next_stage_ - RING];
-        if (!old.handle || !old.started || dev_.proofs_done(old.handle)) { proofs_collect(old); progress = true; }
-      }
-      if (st_ready) { enqueue_proofs(next_stage_++); progress = true; }
-    }
+    // (... once segment next_key - n_slots is collected.  Unlike its siblings, and unlike step_chained(), the keys are queued
+    // without asking rc_: this order always has queued them in the step in which a tape failed; finish() collects the stage)
+    progress |= queue_keys(r, next_kcollect_ + n_slots_ > next_key_);
+    progress |= proofs_turn(r, proofs_first_ || next_stage_ < next_key_);      // (a chunk's proofs after its keys, unless the call is one chunk)
     if (rc_ == OK && next_kcollect_ < next_key_ && (!seg_[next_kcollect_].pending || dev_.keys_done((int)(next_kcollect_ % n_slots_)))) {
       keys_collect(next_kcollect_);
       { std::lock_guard<std::mutex> lk(hm_); keys_arrived_[next_kcollect_] = 1; }
@@ -662,7 +691,7 @@ class TxCall {
       ++next_kcollect_;
       progress = true;
     }
-    while (rc_ == OK && next_sig_ < sig_avail) {
+    while (rc_ == OK && next_sig_ < r.sig_avail) {
       const double t0 = now();
       if (next_sig_ >= n_slots_) {                                            // the stage that used this slot last: collected once it is done
         if (sig_stages_[next_sig_ - n_slots_]->pending && !dev_.sigs_done((int)(next_sig_ % n_slots_))) break;
@@ -671,7 +700,7 @@ class TxCall {
       SigStage& sg = *sig_stages_[next_sig_];
       const size_t ns = sg.keyed.size();
       if (ns) {
-        const int rc = dev_.sigs_enqueue((int)(next_sig_ % n_slots_), ns, sg.ssc.data(), sg.spt.data(), sg.soff.data(), sg.sst.data());
+        const int rc = dev_.sigs_enqueue((int)(next_sig_ % n_slots_), ns, sg.ssc.data(), sg.spt.data(), sg.soff.data(), sg.sst.data(), nullptr);
         if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
       }
       t_sigs_ += now() - t0;
@@ -679,56 +708,19 @@ class TxCall {
       ++next_sig_;
       progress = true;
     }
-    if (rc_ != OK) { finished_ = true; return true; }
-    if (timing_) device_marks();
-    return progress;
+    return end_step(progress);
   }
- private:
   // The same for a device that chains.  Per chunk, in order: its key stage and its tape go out when the staging thread has
   // made them and the chunk that used their slot last has been collected; its signature stage as soon as both are queued
   // (the device orders the three); its proofs as before.  What a chunk brought back -- signature bits, key bits -- is
   // collected when its signature stage is through, oldest chunk first (its tape's slot is released then too: the IDs
   // themselves stay on the device); nothing else is waited for.
-  bool step_chained() {
-    const size_t n_chunks = chunks_.size();
-    bool progress = false, rows = false, st_ready = false, ring_free = true, tape_ready = false, sig_rows = false;
-    {
-      std::lock_guard<std::mutex> lk(hm_);
-      if (stager_failed_) { note(ENOMEM_, "out of host memory while staging the transactions"); finished_ = true; return true; }
-      if (next_key_ < n_chunks) rows = key_rows_[next_key_] != 0;
-      if (next_stage_ < n_chunks) st_ready = staged_[next_stage_] != 0;
-      if (next_stage_ >= RING) ring_free = arena_free_[next_stage_ - RING] != 0;
-      if (next_hash_ < n_chunks) tape_ready = tape_ready_[next_hash_] != 0;
-      if (next_sig_ < n_chunks) sig_rows = chain_rows_[next_sig_] != 0;
-      if (tape_failed_) note(EINVAL_, "a transaction's hash plan does not fit the device's tape");
-    }
-    if (next_chain_ == n_chunks && next_stage_ == n_chunks) { finished_ = true; return true; }
-    if (rc_ == OK && rows && next_chain_ + n_slots_ > next_key_) {
-      Segment& sg = seg_[next_key_];
-      mark("key rows ready, segment", next_key_);
-      const double t0 = now();
-      if (sg.g_hi > sg.g_lo) {
-        const int rc = dev_.keys_enqueue((int)(next_key_ % n_slots_), sg.ksc.data(), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo);
-        if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
-      }
-      t_keys_ += now() - t0;
-      mark("keys queued, segment", next_key_);
-      ++next_key_;
-      progress = true;
-    }
-    if (rc_ == OK && tape_ready && next_chain_ + n_slots_ > next_hash_) {
-      const TxHashTape& tape = *dev_.hash_tape((int)(next_hash_ % n_slots_));
-      const double t0 = now();
-      if (tape.n_tx()) {
-        const int rc = dev_.hash_enqueue((int)(next_hash_ % n_slots_), tape);
-        if (rc != OK) note(rc, dev_.last_error()); else hash_pending_[next_hash_] = 1;
-      }
-      t_keys_ += now() - t0;
-      mark("transaction-ID tape queued, chunk", next_hash_);
-      ++next_hash_;
-      progress = true;
-    }
-    if (rc_ == OK && sig_rows && next_sig_ < next_key_ && next_sig_ < next_hash_) {
+  bool step_chained(const Ready& r) {
+    const size_t n = chunks_.size();
+    if (next_chain_ == n && next_stage_ == n) { finished_ = true; return true; }
+    bool progress = queue_keys(r, rc_ == OK && next_chain_ + n_slots_ > next_key_);
+    progress |= queue_tape(r, next_chain_ + n_slots_ > next_hash_);
+    if (rc_ == OK && r.sig_rows && next_sig_ < next_key_ && next_sig_ < next_hash_) {
       const double t0 = now();
       chain_enqueue(next_sig_);
       t_sigs_ += now() - t0;
@@ -739,13 +731,7 @@ class TxCall {
     // (a chunk's proofs after its keys -- unless its keys wait for a slot: a slot is free again only when a whole chain has been
     // collected, the first chain needs the first tape, and the staging thread writes tapes after it has gathered every chunk of
     // the run, for which the ring's areas must come free -- the proofs must not wait for keys that wait for them)
-    if (rc_ == OK && next_stage_ < n_chunks && (proofs_first_ || next_stage_ < next_key_ || next_key_ >= next_chain_ + n_slots_)) {
-      if (!ring_free) {
-        Chunk& old = *chunks_[next_stage_ - RING];
-        if (!old.handle || !old.started || dev_.proofs_done(old.handle)) { proofs_collect(old); progress = true; }
-      }
-      if (st_ready) { enqueue_proofs(next_stage_++); progress = true; }
-    }
+    progress |= proofs_turn(r, proofs_first_ || next_stage_ < next_key_ || next_key_ >= next_chain_ + n_slots_);
     if (rc_ == OK && next_chain_ < next_sig_ && (!sig_stages_[next_chain_]->pending || dev_.sigs_done((int)(next_chain_ % n_slots_)))) {
       sigs_collect(next_chain_);
       keys_collect(next_chain_);
@@ -753,10 +739,17 @@ class TxCall {
       next_kcollect_ = next_hcollect_ = ++next_chain_;
       progress = true;
     }
-    if (rc_ != OK) { finished_ = true; return true; }
-    if (timing_) device_marks();
-    return progress;
+    return end_step(progress);
   }
+ public:
+  bool step() {
+    if (finished_) return false;
+    if (rc_ != OK) { finished_ = true; return true; }
+    Ready r;
+    if (!snapshot(r)) return true;
+    return chains_ ? step_chained(r) : step_host_signed(r);
+  }
+ private:
   // chunk c's signature stage behind its key stage and its tape (both queued, or empty like the stage itself)
   void chain_enqueue(size_t c) {
     const Chunk& k = *chunks_[c];
@@ -773,7 +766,8 @@ class TxCall {
     }
     if (!seg_[c].pending || !hash_pending_[c]) { note(EINVAL_, "a signature stage without its key stage or its tape"); return; }
     const int slot = (int)(c % n_slots_);
-    const int rc = dev_.sigs_enqueue_chained(slot, slot, slot, ns, sg.ssc.data(), sg.spt.data(), sg.soff.data(), sg.sst.data(), sg.pos.data());
+    const SigChain chain{slot, slot, sg.pos.data()};
+    const int rc = dev_.sigs_enqueue(slot, ns, sg.ssc.data(), sg.spt.data(), sg.soff.data(), sg.sst.data(), &chain);
     if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
   }
   // (timing only) when the device is through with a chunk's proofs / a signature stage, as seen by the polling thread

@@ -162,7 +162,7 @@ struct zkgpu_ctx {
   size_t ev_next = 0;
   int forced_w = 0, last_w = 0;
   DecodeRoutes decode_routes;   // DECODE launches and points by form (kernels.hpp; zkgpu_debug_read "decode_routes")
-  uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0;   // | root context of a verifier: transaction IDs / signature challenges its device produced (session.hpp: GpuTxDevice)
+  uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0;   // | root context of a verifier: transaction IDs / signature challenges its device produced (tx_device.hpp: GpuTxDevice)
 };
 
 namespace {
