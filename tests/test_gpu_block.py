@@ -963,6 +963,140 @@ def test_failed_groups_are_located_and_every_pattern_of_bad_transactions_resolve
         gens.close()
 
 
+def _pipeline_launch_sequences(ctx, oracle):
+    """A fixed set of small calls, one per route through the batch pipeline and the paths beside it, each profiled on its
+    own -> {call: [[profile entry, launches], ...]} in the order the entries were first queued.  Every call's verdict bits
+    are held against the oracle here, so a sequence that verifies nothing is never recorded or compared."""
+    import random
+    from gpu_util import GADGET_LABEL, describe_range, points
+    from zkvm_amd import PointSet
+    from zkvm_amd.native import R1csDescription
+    from zkvm_amd.verifier import BulletproofGens, MixedR1csVerifier, R1csVerifier, Verifier
+    out = {}
+
+    def profiled(name, fn, want):
+        ctx.profile_reset()
+        got = fn()
+        assert got == want, name
+        out[name] = [[k, v[0]] for k, v in ctx.profile_read().items()]
+
+    fix, n_in, n_out, plen = load_cloak_fixture()
+    n = 16 * 12 + 5
+    coms = [bytearray(fix[i][0]) for i in range(n)]
+    proofs = [bytearray(fix[i][1]) for i in range(n)]
+    for i in (16 * 0 + 7, 16 * 3 + 2):                                          # one culprit; two culprits ...
+        proofs[i][1 + 32 * 11 + (i % 29)] ^= 1 << (i % 8)
+    a = (int.from_bytes(proofs[16 * 3 + 9][-64:-32], "little") + 1) % L
+    proofs[16 * 3 + 9][-64:-32] = a.to_bytes(32, "little")
+    coms[16 * 5 + 4][32:64] = bytes.fromhex("01" + "00" * 31)                   # ... one left-out point
+    r = hashlib.shake_256(b"launch sequences").digest(64 * n)
+    com_b, proof_b = b"".join(bytes(c) for c in coms), b"".join(bytes(p) for p in proofs)
+    want = list(oracle.cloak_verify_batch(com_b, n_in, n_out, proof_b, plen, r, threads=16))
+    assert want.count(0) == 4
+    gens = BulletproofGens(ctx, 256, table_bits=10)
+    v = Verifier(ctx, gens)
+    cloak = lambda: bits(v.verify_packed_gpu(n_in, n_out, n, com_b, proof_b, plen, r), n)      # noqa: E731
+    rv = mv = ps = None
+    dev = []
+    ctx.profile(True)
+    try:
+        ctx.set_group_size(1)
+        profiled("cloak 197, group 1", cloak, want)
+        ctx.set_group_size(16)
+        for tail in (0, 1):
+            ctx.set_tail_mode(tail)
+            for horner in (1, 2) if tail == 0 else (0,):
+                ctx.set_horner_mode(horner)
+                for locate in (1, 2, 3):
+                    ctx.set_locate_mode(locate)
+                    profiled("cloak 197, group 16, tail %d, horner %d, locate %d" % (tail, horner, locate), cloak, want)
+        ctx.set_tail_mode(0); ctx.set_horner_mode(0); ctx.set_locate_mode(0)
+        ctx.set_serial(True)
+        profiled("cloak 197, group 16, serial", cloak, want)
+        ctx.set_serial(False)
+        ctx.set_window_bits(8)                                                  # off the pipeline: the synchronous tables path
+        profiled("cloak 197, window bits forced", cloak, want)
+        ctx.set_window_bits(0)
+        # rows only (no proofs: prep is null), submitted to the pipeline
+        rng = random.Random(23)
+        n_gen, rows = 64, 12
+        gpts = points(oracle, "launch gens", n_gen)
+        ps = PointSet(ctx, gpts)
+        ps.build_tables(8)
+        dyn_sc, dyn_pt, st_sc, st_idx, st_off = b"", b"", b"", [], [0]
+        gen_sc, gen_pt, gen_off = b"", b"", [0]
+        for i in range(rows):
+            idx = rng.sample(range(n_gen), rng.choice([1, 8, 64]))
+            ks = [rng.randrange(L) for _ in idx]
+            tot = oracle.encode(oracle.msm_points("vartime", ks, [oracle.decode(gpts[32 * j: 32 * j + 32]) for j in idx]))
+            extra = ((L - 1) if i % 5 else (L - 2)).to_bytes(32, "little")     # every 5th check is wrong
+            ksb = b"".join(k.to_bytes(32, "little") for k in ks)
+            st_sc += ksb; st_idx += idx; st_off.append(st_off[-1] + len(idx))
+            dyn_sc += extra; dyn_pt += tot
+            gen_sc += ksb + extra; gen_pt += b"".join(gpts[32 * j: 32 * j + 32] for j in idx) + tot
+            gen_off.append(gen_off[-1] + len(idx) + 1)
+        want_rows = bits(oracle.verify_batch(gen_sc, gen_pt, gen_off), rows)
+        assert want_rows == [1 if i % 5 else 0 for i in range(rows)]
+        u64 = lambda xs: b"".join(x.to_bytes(8, "little") for x in xs)        # noqa: E731
+        dev = [ctx.to_device(x) for x in (dyn_sc, dyn_pt, u64(range(rows + 1)), st_sc, b"".join(x.to_bytes(4, "little") for x in st_idx), u64(st_off))]
+
+        def rows_only():
+            ctx.verify_batch_ps_submit_dev(ps, rows, dev[0], dev[1], dev[2], rows, dev[3], dev[4], dev[5], len(st_idx))
+            return bits(ctx.verify_wait(), rows)
+        profiled("rows only, submitted", rows_only, want_rows)
+        # zkgpu_verify_batch: 64 rows of 4 terms (per-point tables), 8 rows one of which has 300 terms (buckets)
+        for name, sizes in (("verify_batch, 64 rows of 4", [4] * 64), ("verify_batch, 8 rows, one of 300", [4] * 7 + [300])):
+            sc, pt, offs = b"", b"", [0]
+            for i, m in enumerate(sizes):
+                p = points(oracle, "launch rows", m // 2, distinct=min(m // 2, 16))[: 32 * (m // 2)]
+                ks = [rng.randrange(L) for _ in range(m // 2)]
+                sc += b"".join(k.to_bytes(32, "little") + ((L - k + (i % 3 == 1)) % L).to_bytes(32, "little") for k in ks)
+                pt += b"".join(p[32 * j: 32 * j + 32] * 2 for j in range(m // 2))
+                offs.append(offs[-1] + m)
+            want_vb = bits(oracle.verify_batch(sc, pt, offs), len(sizes))
+            assert 0 in want_vb and 1 in want_vb
+            profiled(name, lambda: bits(ctx.verify_batch(sc, pt, offs), len(sizes)), want_vb)
+        # a grouped mixed call of two plans: two range(8) statements and two cloaks, a check of two per generator key
+        m_, n1, nm, labels, cons = describe_range(8)
+        rv = R1csVerifier(ctx, gens, R1csDescription(GADGET_LABEL, m_, n1, nm, labels, cons))
+        mv = MixedR1csVerifier(ctx, gens, [rv, (n_in, n_out)])
+        mc, mp = [], []
+        for i in range(2):
+            rc, com, proof = oracle.gadget_prove(1, 8, [17 + i], hashlib.sha256(b"launch mixed %d" % i).digest())
+            assert rc == 0
+            mc.append(com); mp.append(proof)
+        mc += [bytes(coms[1]), bytes(coms[7])]; mp += [bytes(proofs[1]), bytes(proofs[7])]
+        mr = hashlib.shake_256(b"launch mixed").digest(64 * 4)
+        want_mx = [int(oracle.gadget_verify(1, 8, mc[i], mp[i], mr[64 * i: 64 * i + 64])) for i in range(2)]
+        want_mx += [int(oracle.cloak_verify(mc[i], n_in, n_out, mp[i], mr[64 * i: 64 * i + 64])) for i in (2, 3)]
+        assert want_mx == [1, 1, 1, 0]
+        profiled("mixed, two plans, grouped", lambda: bits(mv.verify([0, 0, 1, 1], mc, mp, mr), 4), want_mx)
+        assert ctx.mixed_group_stats() == (2, 4, 1, 2)
+    finally:
+        ctx.profile(False)
+        ctx.set_group_size(16); ctx.set_tail_mode(0); ctx.set_horner_mode(0); ctx.set_locate_mode(0)
+        ctx.set_serial(False); ctx.set_window_bits(0)
+        for d in dev:
+            ctx.free_device(d)
+        for x in (mv, rv, ps, v, gens):
+            if x is not None:
+                x.close()
+    return out
+
+
+def test_pipeline_launch_sequences_are_the_recorded_ones(ctx, oracle):
+    """Which kernels a call queues, in which order and how often -- the batch pipeline ungrouped, grouped under every
+    Horner arrangement x way of locating a failed group's culprit with the fused and the unfused tail, on one stream, a
+    rows-only submit, the synchronous tables path, zkgpu_verify_batch on the small and on the bucket path, a grouped mixed
+    call -- is what tests/golden/pipe_launch_sequences.json holds: recorded before the enqueue code was rearranged into a
+    plan, a workspace function and one launcher per kernel, and never regenerated from the code under test."""
+    gold = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "pipe_launch_sequences.json")))
+    got = _pipeline_launch_sequences(ctx, oracle)
+    assert sorted(got) == sorted(gold)
+    for name in gold:
+        assert got[name] == gold[name], name
+
+
 @pytest.mark.parametrize("kind,param", [(1, 32), (1, 64), (2, 2), (2, 5), (2, 9)])
 def test_described_constraint_systems_on_device(ctx, oracle, kind, param):
     """zkgpu_r1cs_plan_create: a constraint system handed over as data -- a bare range proof

@@ -802,6 +802,20 @@ extern "C" long long zkhost_mixed_plan(const uint64_t* infos, size_t n_infos, co
   return (long long)mp.t_end;
 }
 
+// the plan of one device batch of the verification pipeline (pipe_plan.hpp).  in[11]: n_msm n_dyn n_static W whole_proof ns |
+// group_size locate_mode locate_parts forced_parts want_reasons.  out[36]: PipePlan's fields in their order
+#include "pipe_plan.hpp"
+extern "C" void zkhost_pipe_plan(const int64_t* in, uint64_t* out) {
+  const PipePlan p = plan_pipe(PipeShape{(uint64_t)in[0], (uint64_t)in[1], (uint64_t)in[2], (int)in[3], in[4] != 0, (uint32_t)in[5]},
+                               PipeKnobs{(int)in[6], (int)in[7], (int)in[8], (int)in[9], in[10] != 0});
+  const uint64_t flat[36] = {
+      p.nbytes, (uint64_t)p.P, p.n_lanes, p.group, p.n_groups, p.locate, p.spec, p.grp_rows, (uint64_t)p.Pg, (uint64_t)p.Pf, (uint64_t)p.Pl,
+      p.grp_sc, p.grp_digits, p.grp_partials, p.grp_ok, p.row_map, p.grp_fail, p.grp_fail_sum, p.grp_ws, p.grp_wf, p.grp_dyn, p.rechk_pts,
+      p.accept, p.accept2, p.bitmap, p.pinned, p.status, p.digits, p.st_partials, p.dynsum,
+      p.small.dyn_rows, p.small.window_sums, p.small.window_flags, p.small.msm_fail, p.small.small_tbl, p.small.recoded};
+  std::memcpy(out, flat, sizeof flat);
+}
+
 #include "comm_frame.hpp"
 extern "C" size_t zkhost_comm_slot_bytes(const uint64_t* cuts, int world) { return commframe::slot_bytes(cuts, world); }
 extern "C" void zkhost_comm_pack(uint8_t* out, size_t slot, const uint64_t* cuts, int rank, const uint8_t* local_bitmap, int local_status) {

@@ -43,6 +43,7 @@
 #include "host_pool.hpp"
 #include "ticket_cut.hpp"
 #include "mixed_plan.hpp"
+#include "pipe_plan.hpp"
 
 using namespace zk;
 
@@ -310,11 +311,10 @@ inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + pe
 // sets of shared chip-filling streams per parent context (consecutive forks alternate between them) and the
 // fork limit that keeps the process under the ~22 hardware queues the runtime hands out before it
 // multiplexes them in software (measured: 100-200 ms per step beyond that)
-constexpr int TAIL_THREADS = 512;   // threads per row in k_recheck_fused (shares of the row's generator sum)
 constexpr int LOCATE_THREADS = 512; // ... in k_locate_fused: one wavefront per SIMD, so that the naming of the culprit has 512 registers and no scratch
 constexpr int STREAM_SETS = 2;
 constexpr int MAX_FORKS = 9;
-constexpr size_t LOCATE_MIN_BATCH = 2048;      // transactions per batch from which failed groups are located instead of re-checked in full
+static_assert(PLAN_EXT_WORDS == EXT_WORDS && PLAN_NIELS_WORDS == NIELS_WORDS && PLAN_SMALL_TBL == SMALL_TBL, "pipe_plan.hpp sizes the kernels' rows");
 constexpr size_t COOP_TRANSCRIPT_MAX = 1536;   // transactions per batch up to which the transcript runs one wavefront each
 
 // window width minimising  W * (terms + 2 * 2^(w-1) * msms)  point additions
@@ -619,11 +619,110 @@ int msm_device(zkgpu_ctx* c, const void* d_scalars, const void* d_points, size_t
 // ---- batch ------------------------------------------------------------------------
 // values != nullptr: "value mode" -- write the 32-byte encoding of every MSM to
 // values[32 * i] (host) and make bit i mean "all points of MSM i decoded".
-int small_msm_launch(zkgpu_ctx* c, const Job& job, hipStream_t st); int tx_reasons_enqueue(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, hipStream_t st, char* h_out); int tx_reasons_parked(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, int rc);   // (session.hpp)
+int small_msm_launch(zkgpu_ctx* c, const Job& job, hipStream_t st);
+int tx_reasons_enqueue(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, hipStream_t st, char* h_out);      // (session.hpp)
+int tx_reasons_parked(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, int rc);
+
+// The small-window block of a batch (pipe_plan.hpp); the per-point tables and the recoded scalars only with_tables: the paths
+// that have the scalars at hand leave those to small_tables_launch
+int small_window_workspace(zkgpu_ctx* c, const SmallWindowBytes& b, bool with_tables) {
+  TRY(ensure(c, c->dyn_rows, b.dyn_rows));
+  TRY(ensure(c, c->window_sums, b.window_sums));
+  TRY(ensure(c, c->window_flags, b.window_flags));
+  TRY(ensure(c, c->msm_fail, b.msm_fail));
+  if (with_tables) TRY(ensure(c, c->small_tbl, b.small_tbl));
+  return with_tables ? ensure(c, c->recoded, b.recoded) : ZKGPU_OK;
+}
+
+// ---- one launcher per kernel that is queued from more than one place: the context, the stream, and what differs between
+// ---- the places; the casts and the fixed arguments are held here once
+// status words 8 and 9: rows queued for a check of their own, failed groups -- counted on the device
+uint32_t* n_recheck_dev(zkgpu_ctx* c) { return (uint32_t*)((char*)c->status.p + 32); }
+uint32_t* n_fail_dev(zkgpu_ctx* c) { return (uint32_t*)((char*)c->status.p + 36); }
+
+void batch_init_launch(zkgpu_ctx* c, hipStream_t s, size_t B, bool with_wellformed) {
+  Launch l(c, "k_batch_init", s);
+  hipLaunchKernelGGL(k_batch_init, dim3(blocks_for(B, 256)), dim3(256), 0, s, (uint32_t*)c->status.p, (uint32_t*)c->msm_fail.p,
+                     with_wellformed ? (uint32_t*)c->prep_wf.p : (uint32_t*)nullptr, (uint32_t)B);
+}
+
+// The Horner chains of n rows (window_sums, window_flags, msm_fail -> accept), which also gives nothing more, the rows'
+// encodings (values) or their sums (dynsum); or of n groups' summed windows (grp_ws, grp_wf -> grp_dyn).  failed_of: only
+// the rows of the groups (of `group` rows) marked failed there.
+enum class Horner { ACCEPT_ONLY, VALUES, SUMS, GROUP_SUMS };
+void msm_finish_launch(zkgpu_ctx* c, hipStream_t s, size_t n, int w, int n_windows, Horner what, const uint32_t* failed_of = nullptr, uint32_t group = 0) {
+  const bool groups = what == Horner::GROUP_SUMS;
+  Launch l(c, "k_msm_finish_quad", s);
+  hipLaunchKernelGGL(k_msm_finish_quad, dim3(blocks_for(4 * (uint64_t)n, 256)), dim3(256), 0, s,
+                     (const uint32_t*)(groups ? c->grp_ws.p : c->window_sums.p), (const uint32_t*)(groups ? c->grp_wf.p : c->window_flags.p),
+                     groups ? (const uint32_t*)nullptr : (const uint32_t*)c->msm_fail.p, groups ? (uint8_t*)nullptr : (uint8_t*)c->accept.p,
+                     what == Horner::VALUES ? (uint32_t*)c->values.p : (uint32_t*)nullptr,
+                     groups ? (uint32_t*)c->grp_dyn.p : what == Horner::SUMS ? (uint32_t*)c->dynsum.p : (uint32_t*)nullptr, (uint32_t)n, w,
+                     n_windows, failed_of, group);
+}
+
+void pack_bitmap_launch(zkgpu_ctx* c, hipStream_t s, size_t B, const Buffer& accept, const uint32_t* d_wellformed) {
+  Launch l(c, "k_pack_bitmap", s);
+  hipLaunchKernelGGL(k_pack_bitmap, dim3(blocks_for((B + 7) / 8, 256)), dim3(256), 0, s, (const uint8_t*)accept.p, d_wellformed,
+                     (uint8_t*)c->bitmap.p, (uint32_t)B);
+}
+
+// the rows a generator-sum launch works on: all of them, or the rows a kernel before it has queued on the device (row_map,
+// their number in *n_rows_dev; the grid is sized for every row, lanes beyond the count leave at once)
+struct RowQueue { const uint32_t* row_map = nullptr; const uint32_t* n_rows_dev = nullptr; };
+
+// digits of n generator scalars -> c->digits.  ns: terms per queued row.  fold: the sums get encoded (small negatives folded)
+void static_digits_launch(zkgpu_ctx* c, hipStream_t s, const zkgpu_pointset* ps, const uint32_t* d_scalars, uint64_t n, RowQueue q = {},
+                          uint32_t ns = 0, uint32_t fold = 0) {
+  Launch l(c, "k_static_digits", s);
+  hipLaunchKernelGGL(k_static_digits, dim3(blocks_for(n, 256)), dim3(256), 0, s, d_scalars, (int16_t*)c->digits.p, n, ps->tbl_w,
+                     ps->tbl_W, (uint32_t*)c->status.p, q.row_map, q.n_rows_dev, ns, fold);
+}
+
+// one generator-sum launch: `rows` rows of n_terms terms in all (CSR: d_offsets, d_index), `parts` lanes per (row, window),
+// digits -> partials.  kinds, skip_zeros: the prover's rows (msm_ps_dev)
+struct StaticRows { uint32_t rows; uint64_t n_terms; int parts; const Buffer* digits; const Buffer* partials; RowQueue queue = {}; };
+void static_accumulate_launch(zkgpu_ctx* c, hipStream_t s, const zkgpu_pointset* ps, const uint64_t* d_offsets, const uint32_t* d_index,
+                              const StaticRows& r, uint32_t kinds = 1, bool skip_zeros = false) {
+  Launch l(c, "k_static_accumulate", s);
+  hipLaunchKernelGGL(skip_zeros ? k_static_accumulate<true> : k_static_accumulate<false>,
+                     dim3(blocks_for((uint64_t)r.rows * ps->tbl_W * r.parts, 256)), dim3(256), 0, s, (const int16_t*)r.digits->p,
+                     d_offsets, d_index, (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, ps->tbl_W, r.parts, r.rows, r.n_terms,
+                     (uint32_t*)r.partials->p, r.queue.row_map, r.queue.n_rows_dev, kinds);
+}
+
+// the rows' generator sums (st_partials, `lanes` partial sums per row) + their proof-point sums (with_dyn: dynsum, accept)
+// -> accept2; of a queue of rows: their sums are kept as well (rechk_pts)
+void static_combine_launch(zkgpu_ctx* c, hipStream_t s, size_t B, int lanes, bool with_dyn, RowQueue q = {}) {
+  Launch l(c, "k_static_combine", s);
+  hipLaunchKernelGGL(k_static_combine, dim3(blocks_for((uint64_t)B * COMBINE_LANES, 64)), dim3(64), 0, s, (const uint32_t*)c->st_partials.p,
+                     (uint32_t)lanes, with_dyn ? (const uint32_t*)c->dynsum.p : (const uint32_t*)nullptr,
+                     with_dyn ? (const uint8_t*)c->accept.p : (const uint8_t*)nullptr, q.row_map, q.n_rows_dev, (uint32_t)B,
+                     (uint8_t*)c->accept2.p, q.row_map ? (uint32_t*)c->rechk_pts.p : (uint32_t*)nullptr);
+}
+
+// the rows queued in row_map checked alone, generator sum and verdict in one launch sized for `rows` of them (workgroups
+// past the device-side count leave at once).  keep_sums: the rows' sums -> rechk_pts
+void recheck_fused_launch(zkgpu_ctx* c, hipStream_t s, const zkgpu_pointset* ps, const Job& job, uint32_t rows, bool keep_sums) {
+  Launch l(c, "k_recheck_fused", s);
+  hipLaunchKernelGGL(k_recheck_fused, dim3(rows), dim3(TAIL_THREADS), 0, s, (const int16_t*)c->digits.p, job.d_st_offsets, job.d_st_index,
+                     (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, ps->tbl_W, (uint64_t)job.n_static, (uint32_t*)c->st_partials.p,
+                     (const uint32_t*)c->dynsum.p, (const uint8_t*)c->accept.p, (const uint32_t*)c->row_map.p,
+                     (const uint32_t*)n_recheck_dev(c), (uint8_t*)c->accept2.p, keep_sums ? (uint32_t*)c->rechk_pts.p : (uint32_t*)nullptr);
+}
+
+// the accept bitmap and the first status_bytes of the status words to the pinned block, behind everything queued on s
+int results_enqueue(zkgpu_ctx* c, hipStream_t s, size_t nbytes, size_t status_bytes) {
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(c->pinned, c->bitmap.p, nbytes, hipMemcpyDeviceToHost, s));
+  HIP_TRY(c, hipMemcpyAsync((char*)c->pinned + nbytes, c->status.p, status_bytes, hipMemcpyDeviceToHost, s));
+  return ZKGPU_OK;
+}
+
+void mark_pending(zkgpu_ctx* c, size_t B) { c->pending = true; c->pending_batch = B; c->sync_result_valid = false; }
 
 int batch_device_enqueue(zkgpu_ctx* c, const Job& job, bool values) {
-  const size_t B = job.n_msm;
-  const size_t nbytes = (B + 7) / 8;
+  const size_t B = job.n_msm, nbytes = (B + 7) / 8;
   c->split = zkgpu_ctx::SplitOp{1, B, values, c->stream};
   if (B == 0) return ZKGPU_OK;
   JobDesc jd;
@@ -636,16 +735,9 @@ int batch_device_enqueue(zkgpu_ctx* c, const Job& job, bool values) {
     hipStream_t s = c->stream;
     jd.w = 4; jd.n_windows = 64;
     c->last_w = 4;
-    TRY(ensure(c, c->dyn_rows, std::max<uint64_t>(job.n_dyn, 1) * NIELS_WORDS * 4));
-    TRY(ensure(c, c->window_sums, (size_t)B * 64 * EXT_WORDS * 4));
-    TRY(ensure(c, c->window_flags, (size_t)B * 64 * 4));
-    TRY(ensure(c, c->msm_fail, (size_t)B * 4));
+    TRY(small_window_workspace(c, small_window_bytes(B, job.n_dyn), /*with_tables=*/false));
     TRY(ensure(c, c->status, 64));
-    {
-      Launch l(c, "k_batch_init", s);
-      hipLaunchKernelGGL(k_batch_init, dim3(blocks_for(B, 256)), dim3(256), 0, s, (uint32_t*)c->status.p, (uint32_t*)c->msm_fail.p,
-                         (uint32_t*)nullptr, (uint32_t)B);
-    }
+    batch_init_launch(c, s, B, /*with_wellformed=*/false);
     decompress_launch(c, job, s);
     TRY(small_msm_launch(c, job, s));
   } else {
@@ -655,24 +747,10 @@ int batch_device_enqueue(zkgpu_ctx* c, const Job& job, bool values) {
   TRY(ensure(c, c->bitmap, nbytes));
   TRY(ensure_pinned(c, nbytes + 64 + (values ? 32 * B : 0)));
   if (values) TRY(ensure(c, c->values, 32 * B));
-  {
-    Launch l(c, "k_msm_finish_quad");
-    hipLaunchKernelGGL(k_msm_finish_quad, dim3(blocks_for(4 * B, 256)), dim3(256), 0, c->stream,
-                       (const uint32_t*)c->window_sums.p, (const uint32_t*)c->window_flags.p,
-                       (const uint32_t*)c->msm_fail.p, (uint8_t*)c->accept.p,
-                       values ? (uint32_t*)c->values.p : (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t)B, jd.w,
-                       jd.n_windows, (const uint32_t*)nullptr, 0u);
-  }
-  {
-    Launch l(c, "k_pack_bitmap");
-    hipLaunchKernelGGL(k_pack_bitmap, dim3(blocks_for(nbytes, 256)), dim3(256), 0, c->stream,
-                       (const uint8_t*)c->accept.p, job.d_wellformed, (uint8_t*)c->bitmap.p, (uint32_t)B);
-  }
-  HIP_TRY(c, hipGetLastError());
-  char* h = (char*)c->pinned;
-  HIP_TRY(c, hipMemcpyAsync(h, c->bitmap.p, nbytes, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(h + nbytes, c->status.p, 16, hipMemcpyDeviceToHost, c->stream));
-  if (values) HIP_TRY(c, hipMemcpyAsync(h + nbytes + 64, c->values.p, 32 * B, hipMemcpyDeviceToHost, c->stream));
+  msm_finish_launch(c, c->stream, B, jd.w, jd.n_windows, values ? Horner::VALUES : Horner::ACCEPT_ONLY);
+  pack_bitmap_launch(c, c->stream, B, c->accept, job.d_wellformed);
+  TRY(results_enqueue(c, c->stream, nbytes, 16));
+  if (values) HIP_TRY(c, hipMemcpyAsync((char*)c->pinned + nbytes + 64, c->values.p, 32 * B, hipMemcpyDeviceToHost, c->stream));
   return ZKGPU_OK;
 }
 
@@ -738,18 +816,13 @@ int small_msm_launch(zkgpu_ctx* c, const Job& job, hipStream_t st) {
 // summed straight out of the tables (no sort, no buckets, no doublings); only
 // the proof-specific terms go through the Pippenger pipeline.
 int batch_device_tables_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps) {
-  const size_t B = job.n_msm;
-  const size_t nbytes = (B + 7) / 8;
+  const size_t B = job.n_msm, nbytes = (B + 7) / 8;
   c->split = zkgpu_ctx::SplitOp{2, B, false, c->stream};
   if (B == 0) return ZKGPU_OK;
   hipStream_t s = c->stream, s2 = c->stream2;
   const bool has_dyn = job.n_dyn > 0;
   const int W = ps->tbl_W;
-  int P = c->forced_parts;
-  if (P <= 0) {
-    P = (int)((131072 + B * W - 1) / (B * W));
-    P = std::max(1, std::min(16, P));
-  }
+  const int P = static_parts(B, W, c->forced_parts);
   const uint64_t n_lanes = (uint64_t)B * W * P;
   TRY(ensure(c, c->accept, B));
   TRY(ensure(c, c->accept2, B));
@@ -773,54 +846,22 @@ int batch_device_tables_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_points
       // few proof-specific points per transaction: one wavefront per transaction, no global sort
       jd.w = 4; jd.n_windows = 64;
       c->last_w = 4;
-      TRY(ensure(c, c->dyn_rows, std::max<uint64_t>(job.n_dyn, 1) * NIELS_WORDS * 4));
-      TRY(ensure(c, c->window_sums, (size_t)B * 64 * EXT_WORDS * 4));
-      TRY(ensure(c, c->window_flags, (size_t)B * 64 * 4));
-      TRY(ensure(c, c->msm_fail, (size_t)B * 4));
+      TRY(small_window_workspace(c, small_window_bytes(B, job.n_dyn), /*with_tables=*/false));
       HIP_TRY(c, hipMemsetAsync(c->msm_fail.p, 0, (size_t)B * 4, s));
       decompress_launch(c, job, s);
       TRY(small_msm_launch(c, job, s));
     } else {
       TRY(run_to_windows(c, dj, jd, /*reset_status=*/false));
     }
-    Launch l(c, "k_msm_finish_quad");
-    hipLaunchKernelGGL(k_msm_finish_quad, dim3(blocks_for(4 * B, 256)), dim3(256), 0, s,
-                       (const uint32_t*)c->window_sums.p, (const uint32_t*)c->window_flags.p,
-                       (const uint32_t*)c->msm_fail.p, (uint8_t*)c->accept.p, (uint32_t*)nullptr,
-                       (uint32_t*)c->dynsum.p, (uint32_t)B, jd.w, jd.n_windows, (const uint32_t*)nullptr, 0u);
+    msm_finish_launch(c, s, B, jd.w, jd.n_windows, Horner::SUMS);
   }
-  if (job.n_static) {
-    Launch l(c, "k_static_digits", s2);
-    hipLaunchKernelGGL(k_static_digits, dim3(blocks_for(job.n_static, 256)), dim3(256), 0, s2, job.d_st_scalars,
-                       (int16_t*)c->digits.p, job.n_static, ps->tbl_w, W, (uint32_t*)c->status.p,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, 0u);
-  }
-  {
-    Launch l(c, "k_static_accumulate", s2);
-    hipLaunchKernelGGL(k_static_accumulate<false>, dim3(blocks_for(n_lanes, 256)), dim3(256), 0, s2,
-                       (const int16_t*)c->digits.p, job.d_st_offsets, job.d_st_index, (const uint32_t*)ps->table,
-                       (uint32_t)ps->n, ps->tbl_H, W, P, (uint32_t)B, job.n_static, (uint32_t*)c->st_partials.p,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, 1u);
-  }
+  if (job.n_static) static_digits_launch(c, s2, ps, job.d_st_scalars, job.n_static);
+  static_accumulate_launch(c, s2, ps, job.d_st_offsets, job.d_st_index, {(uint32_t)B, job.n_static, P, &c->digits, &c->st_partials});
   HIP_TRY(c, hipEventRecord(c->ev_join, s2));
   HIP_TRY(c, hipStreamWaitEvent(s, c->ev_join, 0));
-  {
-    Launch l(c, "k_static_combine");
-    hipLaunchKernelGGL(k_static_combine, dim3(blocks_for((uint64_t)B * COMBINE_LANES, 64)), dim3(64), 0, s, (const uint32_t*)c->st_partials.p,
-                       (uint32_t)(W * P), has_dyn ? (const uint32_t*)c->dynsum.p : (const uint32_t*)nullptr,
-                       has_dyn ? (const uint8_t*)c->accept.p : (const uint8_t*)nullptr, (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr, (uint32_t)B, (uint8_t*)c->accept2.p, (uint32_t*)nullptr);
-  }
-  {
-    Launch l(c, "k_pack_bitmap");
-    hipLaunchKernelGGL(k_pack_bitmap, dim3(blocks_for(nbytes, 256)), dim3(256), 0, s, (const uint8_t*)c->accept2.p,
-                       job.d_wellformed, (uint8_t*)c->bitmap.p, (uint32_t)B);
-  }
-  HIP_TRY(c, hipGetLastError());
-  char* h = (char*)c->pinned;
-  HIP_TRY(c, hipMemcpyAsync(h, c->bitmap.p, nbytes, hipMemcpyDeviceToHost, s));
-  HIP_TRY(c, hipMemcpyAsync(h + nbytes, c->status.p, 16, hipMemcpyDeviceToHost, s));
-  return ZKGPU_OK;
+  static_combine_launch(c, s, B, W * P, /*with_dyn=*/has_dyn);
+  pack_bitmap_launch(c, s, B, c->accept2, job.d_wellformed);
+  return results_enqueue(c, s, nbytes, 16);
 }
 
 int batch_device_tables(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, uint8_t* accept_bitmap) {
@@ -861,6 +902,24 @@ bool coop_transcript(const zkgpu_ctx* c, size_t batch) {
   return c->transcript_mode == 2 || (c->transcript_mode == 0 && batch <= COOP_TRANSCRIPT_MAX);
 }
 
+// the proofs' bytes -> words (prep_pw), malformed ones marked (prep_wf)
+void proof_unpack_launch(zkgpu_ctx* c, hipStream_t s, const PrepLaunch& pl, uint32_t B) {
+  const PrepShape& sh = pl.plan.sh;
+  Launch l(c, "k_proof_unpack", s);
+  hipLaunchKernelGGL(k_proof_unpack, dim3(blocks_for((uint64_t)B * sh.proof_words, 256)), dim3(256), 0, s, pl.d_proofs,
+                     (uint64_t)pl.proof_len, (uint32_t*)c->prep_pw.p, sh.proof_words, B, (uint32_t*)c->prep_wf.p,
+                     proof_is_compact(sh, pl.proof_len));
+}
+
+// the transcript replayed one lane per statement -> challenges (prep_ch).  grouped: with the statements' weights in their groups
+void transcript_launch(zkgpu_ctx* c, hipStream_t s, const PrepLaunch& pl, uint32_t B, bool grouped) {
+  const PrepPlan& d = pl.plan;
+  Launch l(c, "k_transcript", s);
+  hipLaunchKernelGGL(k_transcript, dim3(blocks_for(B, 64)), dim3(64), 0, s, d.sh, d.init, d.tape, d.n_ops, pl.d_com,
+                     (const uint32_t*)c->prep_pw.p, pl.d_r, B, (uint32_t*)c->prep_ch.p, (uint32_t*)c->prep_wf.p, d.mono_chal, d.mono_pow,
+                     grouped ? 1u : 0u);
+}
+
 // k_prepare on stream s, or for a plan past a CU's LDS the launches of large_prep.hpp.  with_points (the synchronous path):
 // k_gather_dyn_points follows, inside k_prepare's profile entry, or for a large plan inside one of its own name.
 int prepare_launch(zkgpu_ctx* c, hipStream_t s, const PrepLaunch& pl, uint32_t B, bool with_points) {
@@ -886,6 +945,26 @@ bool pipe_eligible(const zkgpu_ctx* c, const zkgpu_pointset* ps, uint64_t n_msm,
   return pipe_tables(c, ps) && pipe_rows_fit(n_msm, n_dyn, n_static);
 }
 
+// The workspace of a batch as planned (pipe_plan.hpp).  The order is kept: a buffer that grows is a hipFree and a hipMalloc,
+// and the fault tests fail the runtime calls of a run by their number.
+int pipe_workspace(zkgpu_ctx* c, const PipePlan& p) {
+  const std::pair<Buffer*, size_t> of_groups[] = {
+      {&c->grp_sc, p.grp_sc}, {&c->grp_digits, p.grp_digits}, {&c->grp_partials, p.grp_partials}, {&c->grp_ok, p.grp_ok},
+      {&c->row_map, p.row_map}, {&c->grp_fail, p.grp_fail}, {&c->grp_fail_sum, p.grp_fail_sum}, {&c->grp_ws, p.grp_ws},
+      {&c->grp_wf, p.grp_wf}, {&c->grp_dyn, p.grp_dyn}, {&c->rechk_pts, p.rechk_pts}};
+  if (p.group > 1) for (const auto& b : of_groups) TRY(ensure(c, *b.first, b.second));
+  TRY(ensure(c, c->accept, p.accept));
+  TRY(ensure(c, c->accept2, p.accept2));
+  TRY(ensure(c, c->bitmap, p.bitmap));
+  TRY(ensure_pinned(c, p.pinned));
+  TRY(ensure(c, c->status, p.status));
+  TRY(ensure(c, c->digits, p.digits));
+  TRY(ensure(c, c->st_partials, p.st_partials));
+  TRY(ensure(c, c->dynsum, p.dynsum));
+  c->last_w = 4;
+  return small_window_workspace(c, p.small, /*with_tables=*/true);
+}
+
 int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const PrepLaunch* prep) {
   static_assert(std::is_trivially_copyable<Job>::value && std::is_trivially_copyable<PrepLaunch>::value, "kept as bytes");
   {
@@ -896,80 +975,22 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
     c->last.ps = ps; c->last.has_prep = prep != nullptr; c->last.valid = true; c->last.mixed = false;
   }
   const size_t B = job.n_msm;
-  const size_t nbytes = (B + 7) / 8;
-  hipStream_t L = c->stream_l, H1 = c->serial ? L : c->stream, H2 = c->serial ? L : c->stream2;
-  const hipStream_t H3s = c->serial ? L : c->stream3;
-  const int W = ps->tbl_W;
-  int P = c->forced_parts;
-  if (P <= 0) {
-    P = (int)((131072 + B * W - 1) / (B * W));
-    P = std::max(1, std::min(16, P));
-  }
-  const uint64_t n_lanes = (uint64_t)B * W * P;
-  // group checks (k_group_combine): only for whole proofs (the weights come from k_transcript)
-  const uint32_t group = (prep && c->group_size > 1) ? (uint32_t)std::min<size_t>(c->group_size, B) : 1;
-  const uint32_t n_groups = (uint32_t)((B + group - 1) / group);
+  hipStream_t L = c->stream_l, H1 = c->serial ? L : c->stream, H2 = c->serial ? L : c->stream2, H3s = c->serial ? L : c->stream3;
   const uint32_t ns = prep ? prep->plan.sh.n_static : 0;
-  // locating the culprit of a failed group saves work (one multiscalar multiplication instead of `group`) at the
-  // price of two more dependent stages: worth it once the batch is large enough for the work to matter.  Mode 3 forms the
-  // locating sums of ALL groups beside the group sums (twice the rows in the same multiplication), so that a failed group's
-  // culprit is named by k_group_combine itself: no extra stage, ~3 % more point arithmetic per batch.
-  const bool locate = group > 1 && (c->locate_mode >= 2 || (c->locate_mode == 0 && B >= LOCATE_MIN_BATCH));
-  const bool spec = locate && c->locate_mode == 3;
-  const uint32_t grp_rows = spec ? 2 * n_groups : n_groups;
-  // parts per (check, window) of the group launch and of the individual re-check (few checks each:
-  // short chains of additions per lane keep their latency down)
-  int Pg = 1;
-  const int Pf = 32;
-  // the locating multiplication runs for the failed groups only, on the tail of the batch: many short chains (its grid is
-  // sized for every group failing; lanes beyond the device-side count leave at once)
-  const int Pl = c->locate_parts > 0 ? c->locate_parts : 32;
-  if (group > 1) {
-    Pg = (int)std::max<uint64_t>(1, std::min<uint64_t>(32, (65536 + (uint64_t)grp_rows * W - 1) / ((uint64_t)grp_rows * W)));
-    TRY(ensure(c, c->grp_sc, (size_t)grp_rows * ns * 32));
-    TRY(ensure(c, c->grp_digits, (size_t)grp_rows * ns * W * 2));
-    TRY(ensure(c, c->grp_partials, (size_t)grp_rows * std::max<size_t>((size_t)W * std::max(Pg, locate && !spec ? Pl : 0), TAIL_THREADS) * EXT_WORDS * 4));
-    TRY(ensure(c, c->grp_ok, n_groups));
-    TRY(ensure(c, c->row_map, B * 4));
-    TRY(ensure(c, c->grp_fail, (size_t)n_groups * 12));
-    TRY(ensure(c, c->grp_fail_sum, (size_t)n_groups * EXT_WORDS * 4));
-    TRY(ensure(c, c->grp_ws, (size_t)n_groups * 64 * EXT_WORDS * 4));
-    TRY(ensure(c, c->grp_wf, (size_t)n_groups * 64 * 4));
-    TRY(ensure(c, c->grp_dyn, (size_t)n_groups * EXT_WORDS * 4));
-    TRY(ensure(c, c->rechk_pts, B * EXT_WORDS * 4));
-  }
-  TRY(ensure(c, c->accept, B));
-  TRY(ensure(c, c->accept2, B));
-  TRY(ensure(c, c->bitmap, nbytes));
-  TRY(ensure_pinned(c, nbytes + 64 + (c->want_reasons ? B : 0)));
-  TRY(ensure(c, c->status, 64));
-  TRY(ensure(c, c->digits, std::max<uint64_t>(job.n_static, 1) * W * 2));
-  TRY(ensure(c, c->st_partials, std::max<uint64_t>(n_lanes, group > 1 ? (uint64_t)B * std::max(W * Pf, TAIL_THREADS) : 0) * EXT_WORDS * 4));
-  TRY(ensure(c, c->dynsum, B * EXT_WORDS * 4));
-  TRY(ensure(c, c->dyn_rows, std::max<uint64_t>(job.n_dyn, 1) * NIELS_WORDS * 4));
-  TRY(ensure(c, c->window_sums, (size_t)B * 64 * EXT_WORDS * 4));
-  TRY(ensure(c, c->window_flags, (size_t)B * 64 * 4));
-  TRY(ensure(c, c->msm_fail, (size_t)B * 4));
-  TRY(ensure(c, c->small_tbl, std::max<uint64_t>(job.n_dyn, 1) * SMALL_TBL * EXT_WORDS * 4));
-  TRY(ensure(c, c->recoded, std::max<uint64_t>(job.n_dyn, 1) * 32));
-  c->last_w = 4;
+  const PipePlan pp = plan_pipe(PipeShape{job.n_msm, job.n_dyn, job.n_static, ps->tbl_W, prep != nullptr, ns},
+                                PipeKnobs{c->group_size, c->locate_mode, c->locate_parts, c->forced_parts, c->want_reasons});
+  const int W = ps->tbl_W, P = pp.P, Pg = pp.Pg, Pf = pp.Pf, Pl = pp.Pl;
+  const uint32_t group = pp.group, n_groups = pp.n_groups, grp_rows = pp.grp_rows;
+  const bool locate = pp.locate, spec = pp.spec;
+  TRY(pipe_workspace(c, pp));
   if (c->reserve_only) return ZKGPU_OK;                 // (the workspace now fits a batch of this shape and size: nothing is launched)
   const int phase = prep ? c->enqueue_phase : (int)zkgpu_ctx::ENQ_ALL;        // (two halves: whole proofs only)
+  // ---- front: what needs the proof bytes alone, on the light stream
   if (phase == zkgpu_ctx::ENQ_ALL || phase == zkgpu_ctx::ENQ_FRONT) {
-  {
-    Launch l(c, "k_batch_init", L);
-    hipLaunchKernelGGL(k_batch_init, dim3(blocks_for(B, 256)), dim3(256), 0, L, (uint32_t*)c->status.p,
-                       (uint32_t*)c->msm_fail.p, prep ? (uint32_t*)c->prep_wf.p : (uint32_t*)nullptr, (uint32_t)B);
-  }
+  batch_init_launch(c, L, B, /*with_wellformed=*/prep != nullptr);
   if (prep) {
-    const PrepPlan& d = prep->plan;
-    const PrepShape& sh = d.sh;
-    {
-      Launch l(c, "k_proof_unpack", L);
-      hipLaunchKernelGGL(k_proof_unpack, dim3(blocks_for((uint64_t)B * sh.proof_words, 256)), dim3(256), 0, L,
-                         prep->d_proofs, (uint64_t)prep->proof_len, (uint32_t*)c->prep_pw.p, sh.proof_words,
-                         (uint32_t)B, (uint32_t*)c->prep_wf.p, proof_is_compact(sh, prep->proof_len));
-    }
+    const PrepPlan& d = prep->plan; const PrepShape& sh = d.sh;
+    proof_unpack_launch(c, L, *prep, (uint32_t)B);
     HIP_TRY(c, hipEventRecord(c->ev_u, L));
     if (d.n_seg && coop_transcript(c, B)) {
       {
@@ -990,15 +1011,13 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
                            (uint32_t*)c->prep_wf.p, d.mono_chal, d.mono_pow, group > 1 ? 1u : 0u);
       }
     } else {
-      Launch l(c, "k_transcript", L);
-      hipLaunchKernelGGL(k_transcript, dim3(blocks_for(B, 64)), dim3(64), 0, L, sh, d.init, d.tape, d.n_ops, prep->d_com,
-                         (const uint32_t*)c->prep_pw.p, prep->d_r, (uint32_t)B, (uint32_t*)c->prep_ch.p,
-                         (uint32_t*)c->prep_wf.p, d.mono_chal, d.mono_pow, group > 1 ? 1u : 0u);
+      transcript_launch(c, L, *prep, (uint32_t)B, /*grouped=*/group > 1);
     }
   }
   HIP_TRY(c, hipEventRecord(c->ev_t, L));
-  }                                                     // (front)
+  }
   if (phase == zkgpu_ctx::ENQ_FRONT) { HIP_TRY(c, hipGetLastError()); c->awaiting_back = true; return ZKGPU_OK; }
+  // ---- mid: the proof points' decoding and tables, chip-filling
   if (prep && (phase == zkgpu_ctx::ENQ_ALL || phase == zkgpu_ctx::ENQ_MID)) {
     // the proof-specific points need the proof bytes only: gather, decompress and build their small tables on the shared
     // stream while the transcript is replayed.  Queued AFTER the transcript: k_points_tables takes every register of the chip
@@ -1015,6 +1034,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
     HIP_TRY(c, hipEventRecord(c->ev_dig, H1));      // msm_fail is final: the group sums leave such transactions out
   }
   if (phase == zkgpu_ctx::ENQ_MID) { HIP_TRY(c, hipGetLastError()); return ZKGPU_OK; }
+  // ---- back: everything that waits for the transcript
   c->awaiting_back = false;
   if (prep) {
     HIP_TRY(c, hipStreamWaitEvent(H3s, c->ev_t, 0));
@@ -1023,7 +1043,6 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   HIP_TRY(c, hipEventRecord(c->ev_p, prep ? H3s : L));
   HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_p, 0));
   HIP_TRY(c, hipStreamWaitEvent(H2, c->ev_p, 0));
-  uint32_t* n_recheck = (uint32_t*)((char*)c->status.p + 32);
   if (group > 1) {
     HIP_TRY(c, hipStreamWaitEvent(H2, c->ev_dig, 0));
     {
@@ -1032,36 +1051,14 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
                          job.d_st_scalars, (uint32_t)B, ns, group, (uint32_t*)c->grp_sc.p, (int16_t*)c->grp_digits.p,
                          ps->tbl_w, W, (const uint32_t*)c->msm_fail.p, job.d_wellformed, spec ? 1u : 0u);
     }
-    {
-      Launch l(c, "k_static_accumulate", H2);
-      hipLaunchKernelGGL(k_static_accumulate<false>, dim3(blocks_for((uint64_t)grp_rows * W * Pg, 256)), dim3(256), 0, H2,
-                         (const int16_t*)c->grp_digits.p, job.d_st_offsets, job.d_st_index, (const uint32_t*)ps->table,
-                         (uint32_t)ps->n, ps->tbl_H, W, Pg, grp_rows, (uint64_t)grp_rows * ns,
-                         (uint32_t*)c->grp_partials.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 1u);
-    }
-    HIP_TRY(c, hipEventRecord(c->ev_sa, H2));
+    static_accumulate_launch(c, H2, ps, job.d_st_offsets, job.d_st_index, {grp_rows, (uint64_t)grp_rows * ns, Pg, &c->grp_digits, &c->grp_partials});
   } else {
-    {
-      Launch l(c, "k_static_digits", H2);
-      hipLaunchKernelGGL(k_static_digits, dim3(blocks_for(job.n_static, 256)), dim3(256), 0, H2, job.d_st_scalars,
-                         (int16_t*)c->digits.p, job.n_static, ps->tbl_w, W, (uint32_t*)c->status.p,
-                         (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, 0u);
-    }
-    {
-      Launch l(c, "k_static_accumulate", H2);
-      hipLaunchKernelGGL(k_static_accumulate<false>, dim3(blocks_for(n_lanes, 256)), dim3(256), 0, H2,
-                         (const int16_t*)c->digits.p, job.d_st_offsets, job.d_st_index, (const uint32_t*)ps->table,
-                         (uint32_t)ps->n, ps->tbl_H, W, P, (uint32_t)B, job.n_static, (uint32_t*)c->st_partials.p,
-                         (const uint32_t*)nullptr, (const uint32_t*)nullptr, 1u);
-    }
-    HIP_TRY(c, hipEventRecord(c->ev_sa, H2));
+    static_digits_launch(c, H2, ps, job.d_st_scalars, job.n_static);
+    static_accumulate_launch(c, H2, ps, job.d_st_offsets, job.d_st_index, {(uint32_t)B, job.n_static, P, &c->digits, &c->st_partials});
   }
-  if (prep) {
-    TRY(small_accumulate_launch(c, job, H1));       // points and tables were done beside the transcript
-  } else {
-    decompress_launch(c, job, H1);
-    TRY(small_msm_launch(c, job, H1));
-  }
+  HIP_TRY(c, hipEventRecord(c->ev_sa, H2));
+  if (!prep) decompress_launch(c, job, H1);
+  TRY(prep ? small_accumulate_launch(c, job, H1) : small_msm_launch(c, job, H1));       // (whole proofs: points and tables were done beside the transcript)
   HIP_TRY(c, hipEventRecord(c->ev_sm, H1));
   HIP_TRY(c, hipStreamWaitEvent(L, c->ev_sm, 0));
   // Horner chains (the longest dependent chain of a batch): one per GROUP over the summed windows of its transactions,
@@ -1073,29 +1070,17 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   zkgpu_ctx* root = c->parent ? c->parent : c;
   const bool group_first = group > 1 && !spec && (c->horner_mode == 2 || (c->horner_mode == 0 && root->last_failed_groups.load() == 0));
   if (group_first) {
-    {
-      Launch l(c, "k_group_windows", L);
-      hipLaunchKernelGGL(k_group_windows, dim3(blocks_for((uint64_t)n_groups * 64, 256)), dim3(256), 0, L,
-                         (const uint32_t*)c->window_sums.p, (const uint32_t*)c->window_flags.p, (const uint32_t*)c->msm_fail.p,
-                         job.d_wellformed, (uint32_t)B, group, 64u, (uint32_t*)c->grp_ws.p, (uint32_t*)c->grp_wf.p);
-    }
-    Launch l(c, "k_msm_finish_quad", L);
-    hipLaunchKernelGGL(k_msm_finish_quad, dim3(blocks_for(4 * (uint64_t)n_groups, 256)), dim3(256), 0, L,
-                       (const uint32_t*)c->grp_ws.p, (const uint32_t*)c->grp_wf.p, (const uint32_t*)nullptr, (uint8_t*)nullptr,
-                       (uint32_t*)nullptr, (uint32_t*)c->grp_dyn.p, n_groups, 4, 64, (const uint32_t*)nullptr, 0u);
-  } else {
-    Launch l(c, "k_msm_finish_quad", L);
-    hipLaunchKernelGGL(k_msm_finish_quad, dim3(blocks_for(4 * B, 256)), dim3(256), 0, L,
-                       (const uint32_t*)c->window_sums.p, (const uint32_t*)c->window_flags.p,
-                       (const uint32_t*)c->msm_fail.p, (uint8_t*)c->accept.p, (uint32_t*)nullptr,
-                       (uint32_t*)c->dynsum.p, (uint32_t)B, 4, 64, (const uint32_t*)nullptr, 0u);
+    Launch l(c, "k_group_windows", L);
+    hipLaunchKernelGGL(k_group_windows, dim3(blocks_for((uint64_t)n_groups * 64, 256)), dim3(256), 0, L,
+                       (const uint32_t*)c->window_sums.p, (const uint32_t*)c->window_flags.p, (const uint32_t*)c->msm_fail.p,
+                       job.d_wellformed, (uint32_t)B, group, 64u, (uint32_t*)c->grp_ws.p, (uint32_t*)c->grp_wf.p);
   }
+  msm_finish_launch(c, L, group_first ? n_groups : B, 4, 64, group_first ? Horner::GROUP_SUMS : Horner::SUMS);
   HIP_TRY(c, hipStreamWaitEvent(L, c->ev_sa, 0));
   if (group > 1) {
-    uint32_t* n_fail = (uint32_t*)((char*)c->status.p + 36);
-    uint32_t* fail_list = (uint32_t*)c->grp_fail.p;
-    uint32_t* cand = fail_list + n_groups;
-    uint32_t* grp_state = cand + n_groups;
+    uint32_t *n_recheck = n_recheck_dev(c), *n_fail = n_fail_dev(c);
+    const RowQueue queued = {(const uint32_t*)c->row_map.p, n_recheck};      // the rows k_group_combine / the locating step queue for a check alone
+    uint32_t *fail_list = (uint32_t*)c->grp_fail.p, *cand = fail_list + n_groups, *grp_state = cand + n_groups;
     {
       Launch l(c, "k_group_combine", L);        // verdicts of the groups; a failed group also gets its locating scalars
       hipLaunchKernelGGL(spec ? k_group_combine<true> : k_group_combine<false>, dim3(n_groups), dim3(256), 0, L, (const uint32_t*)c->grp_partials.p,
@@ -1106,13 +1091,7 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
                          (int16_t*)c->grp_digits.p, ps->tbl_w, W, spec ? 2u : locate ? 1u : 0u, (uint32_t*)c->row_map.p, n_recheck, cand,
                          (int16_t*)c->digits.p);
     }
-    if (group_first) {
-      Launch l(c, "k_msm_finish_quad", L);      // Horner chains of the transactions of the failed groups only
-      hipLaunchKernelGGL(k_msm_finish_quad, dim3(blocks_for(4 * B, 256)), dim3(256), 0, L,
-                         (const uint32_t*)c->window_sums.p, (const uint32_t*)c->window_flags.p,
-                         (const uint32_t*)c->msm_fail.p, (uint8_t*)c->accept.p, (uint32_t*)nullptr,
-                         (uint32_t*)c->dynsum.p, (uint32_t)B, 4, 64, (const uint32_t*)grp_state, group);
-    }
+    if (group_first) msm_finish_launch(c, L, B, 4, 64, Horner::SUMS, /*failed_of=*/grp_state, group);      // the transactions of the failed groups only
     // failed groups (kernels.hpp, "group checks"): one more multiscalar multiplication each LOCATES the bad
     // transaction, which alone is then checked on its own.  Grids are sized for the worst case; lanes beyond the
     // device-side counts leave at once (no failed group: four near-empty launches).
@@ -1125,18 +1104,10 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
                          (const uint32_t*)fail_list, (const uint32_t*)n_fail, (const uint32_t*)c->grp_fail_sum.p,
                          (uint32_t*)c->row_map.p, n_recheck, cand, job.d_st_scalars, ns, (int16_t*)c->digits.p, ps->tbl_w, W);
     }
-    if (locate && !spec && !fused_tail) {
-      Launch l(c, "k_static_accumulate", L);
-      hipLaunchKernelGGL(k_static_accumulate<false>, dim3(blocks_for((uint64_t)n_groups * W * Pl, 256)), dim3(256), 0, L,
-                         (const int16_t*)c->grp_digits.p, job.d_st_offsets, job.d_st_index, (const uint32_t*)ps->table,
-                         (uint32_t)ps->n, ps->tbl_H, W, Pl, n_groups, (uint64_t)n_groups * ns,
-                         (uint32_t*)c->grp_partials.p, (const uint32_t*)nullptr, (const uint32_t*)n_fail, 1u);
-    }
+    if (locate && !spec && !fused_tail)         // the failed groups' locating rows (slots 0 .. *n_fail - 1: no map)
+      static_accumulate_launch(c, L, ps, job.d_st_offsets, job.d_st_index, {n_groups, (uint64_t)n_groups * ns, Pl, &c->grp_digits, &c->grp_partials, RowQueue{nullptr, n_fail}});
     if (!locate) {
-      Launch l(c, "k_static_digits", L);        // digits of the queued transactions only
-      hipLaunchKernelGGL(k_static_digits, dim3(blocks_for(job.n_static, 256)), dim3(256), 0, L, job.d_st_scalars,
-                         (int16_t*)c->digits.p, job.n_static, ps->tbl_w, W, (uint32_t*)c->status.p,
-                         (const uint32_t*)c->row_map.p, (const uint32_t*)n_recheck, ns, 0u);
+      static_digits_launch(c, L, ps, job.d_st_scalars, job.n_static, queued, ns);        // digits of the queued transactions only
     } else if (!spec && !fused_tail) {
       Launch l(c, "k_locate_combine", L);       // names the culprit (or queues the whole group) and writes the digits of the queued
       hipLaunchKernelGGL(k_locate_combine, dim3(n_groups), dim3(256), 0, L, (const uint32_t*)c->grp_partials.p,
@@ -1146,54 +1117,27 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
                          (int16_t*)c->digits.p, ps->tbl_w, W);
     }
     if (fused_tail) {
-      Launch l(c, "k_recheck_fused", L);
-      hipLaunchKernelGGL(k_recheck_fused, dim3((unsigned)B), dim3(TAIL_THREADS), 0, L, (const int16_t*)c->digits.p, job.d_st_offsets, job.d_st_index,
-                         (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, W, (uint64_t)job.n_static, (uint32_t*)c->st_partials.p,
-                         (const uint32_t*)c->dynsum.p, (const uint8_t*)c->accept.p, (const uint32_t*)c->row_map.p,
-                         (const uint32_t*)n_recheck, (uint8_t*)c->accept2.p, (uint32_t*)c->rechk_pts.p);
+      recheck_fused_launch(c, L, ps, job, (uint32_t)B, /*keep_sums=*/true);
     } else {
-      {
-      Launch l(c, "k_static_accumulate", L);
-      hipLaunchKernelGGL(k_static_accumulate<false>, dim3(blocks_for((uint64_t)B * W * Pf, 256)), dim3(256), 0, L,
-                         (const int16_t*)c->digits.p, job.d_st_offsets, job.d_st_index, (const uint32_t*)ps->table,
-                         (uint32_t)ps->n, ps->tbl_H, W, Pf, (uint32_t)B, job.n_static, (uint32_t*)c->st_partials.p,
-                         (const uint32_t*)c->row_map.p, (const uint32_t*)n_recheck, 1u);
-    }
-    {
-      Launch l(c, "k_static_combine", L);
-      hipLaunchKernelGGL(k_static_combine, dim3(blocks_for((uint64_t)B * COMBINE_LANES, 64)), dim3(64), 0, L, (const uint32_t*)c->st_partials.p,
-                         (uint32_t)(W * Pf), (const uint32_t*)c->dynsum.p, (const uint8_t*)c->accept.p,
-                         (const uint32_t*)c->row_map.p, (const uint32_t*)n_recheck, (uint32_t)B, (uint8_t*)c->accept2.p,
-                         (uint32_t*)c->rechk_pts.p);
-    }
+      static_accumulate_launch(c, L, ps, job.d_st_offsets, job.d_st_index, {(uint32_t)B, job.n_static, Pf, &c->digits, &c->st_partials, queued});
+      static_combine_launch(c, L, B, W * Pf, /*with_dyn=*/true, queued);
     }
     {
       Launch l(c, "k_pack_bitmap_groups", L);   // with the verdict of the located groups' other transactions: S1 - E_b
-      hipLaunchKernelGGL(k_pack_bitmap_groups, dim3(blocks_for(nbytes, 256)), dim3(256), 0, L, (const uint8_t*)c->accept2.p,
+      hipLaunchKernelGGL(k_pack_bitmap_groups, dim3(blocks_for(pp.nbytes, 256)), dim3(256), 0, L, (const uint8_t*)c->accept2.p,
                          job.d_wellformed, (const uint32_t*)c->msm_fail.p, (uint8_t*)c->bitmap.p, (uint32_t)B, group,
                          (const uint32_t*)grp_state, (const uint32_t*)c->grp_fail_sum.p, (const uint32_t*)cand,
                          (const uint32_t*)c->row_map.p, (const uint32_t*)c->rechk_pts.p, (uint32_t*)c->status.p,
                          c->force_unresolved ? 1u : 0u);
     }
   } else {
-    Launch l(c, "k_static_combine", L);
-    hipLaunchKernelGGL(k_static_combine, dim3(blocks_for((uint64_t)B * COMBINE_LANES, 64)), dim3(64), 0, L, (const uint32_t*)c->st_partials.p,
-                       (uint32_t)(W * P), (const uint32_t*)c->dynsum.p, (const uint8_t*)c->accept.p,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t)B, (uint8_t*)c->accept2.p, (uint32_t*)nullptr);
+    static_combine_launch(c, L, B, W * P, /*with_dyn=*/true);
+    pack_bitmap_launch(c, L, B, c->accept2, job.d_wellformed);
   }
-  if (group <= 1) {
-    Launch l(c, "k_pack_bitmap", L);
-    hipLaunchKernelGGL(k_pack_bitmap, dim3(blocks_for(nbytes, 256)), dim3(256), 0, L, (const uint8_t*)c->accept2.p,
-                       job.d_wellformed, (uint8_t*)c->bitmap.p, (uint32_t)B);
-  }
-  HIP_TRY(c, hipGetLastError());
-  char* h = (char*)c->pinned;
-  HIP_TRY(c, hipMemcpyAsync(h, c->bitmap.p, nbytes, hipMemcpyDeviceToHost, L));
-  HIP_TRY(c, hipMemcpyAsync(h + nbytes, c->status.p, 48, hipMemcpyDeviceToHost, L));
-  if (c->want_reasons) TRY(tx_reasons_enqueue(c, job.d_wellformed, B, L, h + nbytes + 64)); HIP_TRY(c, hipEventRecord(c->ev_done, L));
-  c->pending = true;
-  c->pending_batch = B;
-  c->sync_result_valid = false;
+  TRY(results_enqueue(c, L, pp.nbytes, 48));
+  if (c->want_reasons) TRY(tx_reasons_enqueue(c, job.d_wellformed, B, L, (char*)c->pinned + pp.nbytes + 64));
+  HIP_TRY(c, hipEventRecord(c->ev_done, L));
+  mark_pending(c, B);
   return ZKGPU_OK;
 }
 
@@ -1968,18 +1912,8 @@ int msm_ps_core(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, uint64_t n
   TRY(ensure(c, c->values, 32 * batch));
   TRY(ensure_pinned(c, 32 * batch + 64));
   HIP_TRY(c, hipMemsetAsync(c->status.p, 0, 8, s));
-  if (n) {
-    Launch l(c, "k_static_digits");
-    hipLaunchKernelGGL(k_static_digits, dim3(blocks_for(n, 256)), dim3(256), 0, s, d_scalars,
-                       (int16_t*)c->digits.p, n, ps->tbl_w, W, (uint32_t*)c->status.p, (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr, 0u, 0u);
-  }
-  {
-    Launch l(c, "k_static_accumulate");
-    hipLaunchKernelGGL(k_static_accumulate<false>, dim3(blocks_for(n_lanes, 256)), dim3(256), 0, s, (const int16_t*)c->digits.p,
-                       d_offsets, d_index, (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, W, P, (uint32_t)batch, n,
-                       (uint32_t*)c->st_partials.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 1u);
-  }
+  if (n) static_digits_launch(c, s, ps, d_scalars, n);
+  static_accumulate_launch(c, s, ps, d_offsets, d_index, {(uint32_t)batch, n, P, &c->digits, &c->st_partials});
   {
     Launch l(c, "k_static_values");
     hipLaunchKernelGGL(k_static_values, dim3((unsigned)batch), dim3(64), 0, s, (const uint32_t*)c->st_partials.p,
@@ -2110,17 +2044,9 @@ int msm_ps_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t rows, uint64_t n, 
   TRY(ensure(c, c->status, 64));
   TRY(ensure(c, c->digits, std::max<uint64_t>(n, 1) * W * 2));
   TRY(ensure(c, c->st_partials, n_lanes * EXT_WORDS * 4));
-  if (n) {
-    Launch l(c, "k_static_digits");
-    hipLaunchKernelGGL(k_static_digits, dim3(blocks_for(n, 256)), dim3(256), 0, s, d_scalars, (int16_t*)c->digits.p, n, ps->tbl_w, W,
-                       (uint32_t*)c->status.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0u, 1u);     // (results are encoded: small negatives folded)
-  }
-  {
-    Launch l(c, "k_static_accumulate");
-    hipLaunchKernelGGL(k_static_accumulate<true>, dim3(blocks_for(n_lanes, 256)), dim3(256), 0, s, (const int16_t*)c->digits.p, d_offsets,
-                       d_index, (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, W, P, (uint32_t)rows, n,
-                       (uint32_t*)c->st_partials.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, rows % kinds == 0 ? kinds : 1u);
-  }
+  if (n) static_digits_launch(c, s, ps, d_scalars, n, {}, 0, /*fold=*/1);      // (results are encoded: small negatives folded)
+  static_accumulate_launch(c, s, ps, d_offsets, d_index, {(uint32_t)rows, n, P, &c->digits, &c->st_partials}, rows % kinds == 0 ? kinds : 1u,
+                           /*skip_zeros=*/true);
   TRY(ensure(c, c->rechk_pts, rows * EXT_WORDS * 4));       // (free while a prover runs: the verifier's re-check sums)
   {
     Launch l(c, "k_static_row_sums");
@@ -3052,18 +2978,8 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
   if (c->reserve_only) return ZKGPU_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream_l));      // uploads, if any, were queued on the light stream
   HIP_TRY(c, hipMemsetAsync(c->prep_wf.p, 0xff, (size_t)B * 4, s));
-  {
-    Launch l(c, "k_proof_unpack");
-    hipLaunchKernelGGL(k_proof_unpack, dim3(blocks_for((uint64_t)B * sh.proof_words, 256)), dim3(256), 0, s,
-                       d_proofs, (uint64_t)proof_len, (uint32_t*)c->prep_pw.p, sh.proof_words, B,
-                       (uint32_t*)c->prep_wf.p, proof_is_compact(sh, proof_len));
-  }
-  {
-    Launch l(c, "k_transcript");
-    hipLaunchKernelGGL(k_transcript, dim3(blocks_for(B, 64)), dim3(64), 0, s, sh, pl.plan.init, pl.plan.tape, pl.plan.n_ops, d_com,
-                       (const uint32_t*)c->prep_pw.p, d_r, B, (uint32_t*)c->prep_ch.p, (uint32_t*)c->prep_wf.p,
-                       pl.plan.mono_chal, pl.plan.mono_pow, 0u);
-  }
+  proof_unpack_launch(c, s, pl, B);
+  transcript_launch(c, s, pl, B, /*grouped=*/false);
   TRY(prepare_launch(c, s, pl, B, /*with_points=*/true));
   HIP_TRY(c, hipGetLastError());
   return tx_reasons_parked(c, job.d_wellformed, B, run_sync_and_park(c, job, ps));
@@ -3504,7 +3420,7 @@ struct MixGroupTable {
 int mixed_group_reserve(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const MixGroupTable& gt, int* Pg_out) {
   const size_t B = job.n_msm;
   const int W = ps->tbl_W;
-  const int Pg = (int)std::max<uint64_t>(1, std::min<uint64_t>(32, (65536 + (uint64_t)gt.n_checks * W - 1) / ((uint64_t)gt.n_checks * W)));
+  const int Pg = group_parts(gt.n_checks, W);
   *Pg_out = Pg;
   TRY(ensure(c, c->grp_digits, gt.n_rows * W * 2));
   TRY(ensure(c, c->mx_grp_index, gt.n_rows * 4));
@@ -3518,12 +3434,7 @@ int mixed_group_reserve(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, 
   TRY(ensure(c, c->digits, std::max<uint64_t>(job.n_static, 1) * W * 2));
   TRY(ensure(c, c->st_partials, (size_t)gt.n_grouped * TAIL_THREADS * EXT_WORDS * 4));
   TRY(ensure(c, c->dynsum, B * EXT_WORDS * 4));
-  TRY(ensure(c, c->dyn_rows, std::max<uint64_t>(job.n_dyn, 1) * NIELS_WORDS * 4));
-  TRY(ensure(c, c->window_sums, B * 64 * EXT_WORDS * 4));
-  TRY(ensure(c, c->window_flags, B * 64 * 4));
-  TRY(ensure(c, c->msm_fail, B * 4));
-  TRY(ensure(c, c->small_tbl, std::max<uint64_t>(job.n_dyn, 1) * SMALL_TBL * EXT_WORDS * 4));
-  TRY(ensure(c, c->recoded, std::max<uint64_t>(job.n_dyn, 1) * 32));
+  TRY(small_window_workspace(c, small_window_bytes(B, job.n_dyn), /*with_tables=*/true));
   c->last_w = 4;
   return ZKGPU_OK;
 }
@@ -3534,11 +3445,9 @@ int mixed_group_reserve(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, 
 //     H1: k_small_tables -> k_small_accumulate (every statement's own dynamic row)
 //     L:  k_msm_finish_quad (one chain per statement) -> k_mx_group_combine -> k_recheck_fused -> k_pack_bitmap
 int mixed_group_tail(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const MixGroupTable& gt, int Pg) {
-  const size_t B = job.n_msm, nbytes = (B + 7) / 8;
+  const size_t B = job.n_msm;
   hipStream_t L = c->stream_l, H1 = c->serial ? L : c->stream, H2 = c->serial ? L : c->stream2;
   const int W = ps->tbl_W;
-  uint32_t* n_recheck = (uint32_t*)((char*)c->status.p + 32);
-  uint32_t* n_fail = (uint32_t*)((char*)c->status.p + 36);
   HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_p, 0));
   HIP_TRY(c, hipStreamWaitEvent(H2, c->ev_p, 0));
   HIP_TRY(c, hipStreamWaitEvent(H2, c->ev_dig, 0));
@@ -3548,51 +3457,25 @@ int mixed_group_tail(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, con
                        gt.d_members, job.d_st_scalars, job.d_st_index, (const uint32_t*)c->msm_fail.p, job.d_wellformed, gt.n_rows,
                        (int16_t*)c->grp_digits.p, (uint32_t*)c->mx_grp_index.p, ps->tbl_w, W);
   }
-  {
-    Launch l(c, "k_static_accumulate", H2);
-    hipLaunchKernelGGL(k_static_accumulate<false>, dim3(blocks_for((uint64_t)gt.n_checks * W * Pg, 256)), dim3(256), 0, H2,
-                       (const int16_t*)c->grp_digits.p, gt.d_row_offsets, (const uint32_t*)c->mx_grp_index.p,
-                       (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, W, Pg, gt.n_checks, gt.n_rows,
-                       (uint32_t*)c->grp_partials.p, (const uint32_t*)nullptr, (const uint32_t*)nullptr, 1u);
-  }
+  static_accumulate_launch(c, H2, ps, gt.d_row_offsets, (const uint32_t*)c->mx_grp_index.p, {gt.n_checks, gt.n_rows, Pg, &c->grp_digits, &c->grp_partials});
   HIP_TRY(c, hipEventRecord(c->ev_sa, H2));
   TRY(small_msm_launch(c, job, H1));
   HIP_TRY(c, hipEventRecord(c->ev_sm, H1));
   HIP_TRY(c, hipStreamWaitEvent(L, c->ev_sm, 0));
-  {
-    Launch l(c, "k_msm_finish_quad", L);
-    hipLaunchKernelGGL(k_msm_finish_quad, dim3(blocks_for(4 * B, 256)), dim3(256), 0, L, (const uint32_t*)c->window_sums.p,
-                       (const uint32_t*)c->window_flags.p, (const uint32_t*)c->msm_fail.p, (uint8_t*)c->accept.p, (uint32_t*)nullptr,
-                       (uint32_t*)c->dynsum.p, (uint32_t)B, 4, 64, (const uint32_t*)nullptr, 0u);
-  }
+  msm_finish_launch(c, L, B, 4, 64, Horner::SUMS);
   HIP_TRY(c, hipStreamWaitEvent(L, c->ev_sa, 0));
   {
     Launch l(c, "k_mx_group_combine", L);
     hipLaunchKernelGGL(k_mx_group_combine, dim3(gt.n_checks), dim3(256), 0, L, (const uint32_t*)c->grp_partials.p, (uint32_t)(W * Pg),
                        (const uint32_t*)c->dynsum.p, (const uint32_t*)c->msm_fail.p, job.d_wellformed, gt.d_stmts, gt.d_groups,
-                       gt.d_members, job.d_st_scalars, job.n_static, (uint8_t*)c->accept2.p, n_fail, (uint32_t*)c->row_map.p,
-                       n_recheck, (int16_t*)c->digits.p, ps->tbl_w, W);
+                       gt.d_members, job.d_st_scalars, job.n_static, (uint8_t*)c->accept2.p, n_fail_dev(c), (uint32_t*)c->row_map.p,
+                       n_recheck_dev(c), (int16_t*)c->digits.p, ps->tbl_w, W);
   }
-  {
-    Launch l(c, "k_recheck_fused", L);     // sized for every check failing; workgroups past the device-side count leave at once
-    hipLaunchKernelGGL(k_recheck_fused, dim3(gt.n_grouped), dim3(TAIL_THREADS), 0, L, (const int16_t*)c->digits.p, job.d_st_offsets,
-                       job.d_st_index, (const uint32_t*)ps->table, (uint32_t)ps->n, ps->tbl_H, W, (uint64_t)job.n_static,
-                       (uint32_t*)c->st_partials.p, (const uint32_t*)c->dynsum.p, (const uint8_t*)c->accept.p,
-                       (const uint32_t*)c->row_map.p, (const uint32_t*)n_recheck, (uint8_t*)c->accept2.p, (uint32_t*)nullptr);
-  }
-  {
-    Launch l(c, "k_pack_bitmap", L);
-    hipLaunchKernelGGL(k_pack_bitmap, dim3(blocks_for(nbytes, 256)), dim3(256), 0, L, (const uint8_t*)c->accept2.p,
-                       job.d_wellformed, (uint8_t*)c->bitmap.p, (uint32_t)B);
-  }
-  HIP_TRY(c, hipGetLastError());
-  char* h = (char*)c->pinned;
-  HIP_TRY(c, hipMemcpyAsync(h, c->bitmap.p, nbytes, hipMemcpyDeviceToHost, L));
-  HIP_TRY(c, hipMemcpyAsync(h + nbytes, c->status.p, 48, hipMemcpyDeviceToHost, L));
+  recheck_fused_launch(c, L, ps, job, gt.n_grouped, /*keep_sums=*/false);     // sized for every check failing
+  pack_bitmap_launch(c, L, B, c->accept2, job.d_wellformed);
+  TRY(results_enqueue(c, L, (B + 7) / 8, 48));
   HIP_TRY(c, hipEventRecord(c->ev_done, L));
-  c->pending = true;
-  c->pending_batch = B;
-  c->sync_result_valid = false;
+  mark_pending(c, B);
   c->last.valid = false;               // (nothing of this call is ever re-run by zkgpu_verify_wait)
   c->last.mixed = false;
   return ZKGPU_OK;
@@ -3663,9 +3546,7 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
   int Pg = 1;
   if (grouped) {
     TRY(mixed_group_reserve(c, job, ps, gt, &Pg));
-    Launch l(c, "k_batch_init", L);
-    hipLaunchKernelGGL(k_batch_init, dim3(blocks_for(B, 256)), dim3(256), 0, L, (uint32_t*)c->status.p, (uint32_t*)c->msm_fail.p,
-                       (uint32_t*)nullptr, B);
+    batch_init_launch(c, L, B, /*with_wellformed=*/false);
   }
   const PrepPlan* d_plans = (const PrepPlan*)(dt + mp.t_plans);
   const MixStmt* d_stmts = (const MixStmt*)(dt + mp.t_stmts);
