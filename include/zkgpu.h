@@ -265,6 +265,8 @@ int zkgpu_r1cs_verify_batch_gpu(zkgpu_ctx *ctx, const zkgpu_pointset *ps, zkgpu_
                                 const uint8_t *r_bytes, uint8_t *accept_bitmap);
 int zkgpu_r1cs_verify_submit(zkgpu_ctx *ctx, const zkgpu_pointset *ps, zkgpu_r1cs_plan *plan, size_t batch,
                              const uint8_t *commitments, const uint8_t *proofs, size_t proof_len, const uint8_t *r_bytes);
+/* d_r NULL: the verifier randomness is drawn by the library, per device batch (see zkgpu_cloak_verify_batch_gpu_dev) -- the
+ * recommended form. */
 int zkgpu_r1cs_verify_submit_dev(zkgpu_ctx *ctx, const zkgpu_pointset *ps, zkgpu_r1cs_plan *plan, size_t batch,
                                  const void *d_commitments, const void *d_proofs, size_t proof_len, const void *d_r);
 int zkgpu_r1cs_verify_batch(zkgpu_ctx *ctx, const zkgpu_pointset *ps, const zkgpu_r1cs_desc *desc, size_t gens_capacity,
@@ -329,7 +331,13 @@ int zkgpu_r1cs_prove_batch(zkgpu_ctx *ctx, const zkgpu_pointset *ps, const zkgpu
  * multiplications).  The round-1 arrangement (host threads in lockstep) remains behind a hook (zkgpu_hooks.h). */
 
 /* The same with commitments, proofs and verifier randomness already resident in HBM
- * (device pointers; this is what bench.py times as one step). */
+ * (device pointers; this is what bench.py times as one step).
+ * d_r NULL: the verifier randomness is drawn by the library, per device batch -- 32 bytes from the OS (getrandom(2)) per
+ * batch, expanded on the device: statement i gets the first 64 bytes of SHAKE256(seed || LE64(i)), as the host-pointer
+ * variants draw theirs.  This is the recommended form: r is the soundness parameter of the group checks (below), and a
+ * buffer that is reused across batches, filled from a non-cryptographic generator or left zero makes the groups' weights
+ * predictable -- two crafted statements whose errors cancel then pass as a group.  No randomness from the OS: ZKGPU_EINVAL
+ * ("getrandom failed"), the bitmap all zero.  Holds for every *_dev entry point that takes a d_r. */
 int zkgpu_cloak_verify_batch_gpu_dev(zkgpu_ctx *ctx, const zkgpu_pointset *ps, zkgpu_cloak_plan *plan, size_t batch,
                                      const void *d_commitments, const void *d_proofs, size_t proof_len,
                                      const void *d_r, uint8_t *accept_bitmap);
@@ -378,6 +386,8 @@ int zkgpu_upload(zkgpu_ctx* ctx, void* d_dst, const void* src, size_t bytes);
 int zkgpu_cloak_verify_submit(zkgpu_ctx* ctx, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
                               const uint8_t* commitments, const uint8_t* proofs, size_t proof_len,
                               const uint8_t* r_bytes);
+/* d_r NULL: drawn by the library, per device batch (recommended; see zkgpu_cloak_verify_batch_gpu_dev).  The drawn bytes live in
+ * the context until zkgpu_verify_wait has collected the batch. */
 int zkgpu_cloak_verify_submit_dev(zkgpu_ctx* ctx, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
                                   const void* d_commitments, const void* d_proofs, size_t proof_len, const void* d_r);
 int zkgpu_verify_batch_ps_submit_dev(zkgpu_ctx* ctx, const zkgpu_pointset* ps, size_t batch, const void* d_dyn_scalars,
@@ -494,9 +504,14 @@ int zkgpu_verifier_set_merge(zkgpu_verifier *v, size_t transactions);
  * batches vary in shape and size (blocks of mixed shapes; since round 4 a block's batches are merged with those of the other
  * blocks in flight, up to the merge target).  Optional: without it workspaces grow on demand and are never shrunk. */
 int zkgpu_verifier_reserve(zkgpu_verifier *v, uint32_t n_in, uint32_t n_out, size_t transactions);
+/* d_r NULL: the ticket's verifier randomness is drawn by the library, per DEVICE batch -- one seed from the OS for each device
+ * batch the verifier forms, and a statement's r derived from the seed and its position in that batch (tickets that bring an
+ * r of their own keep it, byte for byte, beside such tickets in the same device batch).  This is the recommended form: r is
+ * the soundness parameter of the group checks (see zkgpu_cloak_verify_batch_gpu_dev). */
 int zkgpu_verifier_submit_dev(zkgpu_verifier *v, uint32_t n_in, uint32_t n_out, size_t batch, const void *d_commitments,
                               const void *d_proofs, size_t proof_len, const void *d_r, uint64_t *ticket);
-/* the same for `count` batches of one shape and size at once (arrays of count device pointers; tickets[count]) */
+/* the same for `count` batches of one shape and size at once (arrays of count device pointers; tickets[count]).  d_r or any
+ * d_r[i] may be NULL: drawn by the library, per device batch (recommended). */
 int zkgpu_verifier_submit_many_dev(zkgpu_verifier *v, uint32_t n_in, uint32_t n_out, size_t count, size_t batch_each,
                                    const void *const *d_commitments, const void *const *d_proofs, size_t proof_len,
                                    const void *const *d_r, uint64_t *tickets);

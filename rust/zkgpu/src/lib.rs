@@ -30,7 +30,7 @@
 #![allow(clippy::too_many_arguments)]
 
 use std::ffi::CStr;
-use std::os::raw::c_int;
+use std::os::raw::{c_int, c_void};
 use std::ptr;
 
 use zkgpu_sys as sys;
@@ -457,6 +457,25 @@ impl GpuVerifier {
                     &mut id,
                 )
             },
+            self.err(),
+        )?;
+        Ok(Ticket { id, batch })
+    }
+
+    /// Queues `batch` statements of ONE shape that already lie in device memory (HBM) and returns at once.  `d_randomness`:
+    /// `None` (recommended) lets the library draw the verifier randomness itself, once per device batch -- it is the soundness
+    /// parameter of the group checks, and a reused or predictable buffer weakens them; `Some(p)`: 64 bytes per statement at `p`.
+    ///
+    /// # Safety
+    /// `d_commitments` (`batch * 64 * (n_in + n_out)` bytes), `d_proofs` (`batch * proof_len` bytes) and the randomness, when
+    /// given, are device pointers of this verifier's device, and stay valid and unchanged until the ticket has been waited for.
+    pub unsafe fn submit_dev(&self, n_in: u32, n_out: u32, batch: usize, d_commitments: *const c_void, d_proofs: *const c_void, proof_len: usize, d_randomness: Option<*const c_void>) -> Result<Ticket, Error> {
+        if batch == 0 || d_commitments.is_null() || d_proofs.is_null() || d_randomness.map_or(false, |r| r.is_null()) {
+            return Err(Error::InvalidArgument("submit_dev: null device pointer or empty batch".into()));
+        }
+        let mut id = 0u64;
+        check(
+            sys::zkgpu_verifier_submit_dev(self.v, n_in, n_out, batch, d_commitments, d_proofs, proof_len, d_randomness.unwrap_or(ptr::null()), &mut id),
             self.err(),
         )?;
         Ok(Ticket { id, batch })

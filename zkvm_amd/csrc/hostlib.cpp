@@ -816,6 +816,11 @@ extern "C" void zkhost_pipe_plan(const int64_t* in, uint64_t* out) {
   std::memcpy(out, flat, sizeof flat);
 }
 
+// verifier randomness the library draws itself (draw_r.hpp): r(seed, first) .. r(seed, first + count - 1), 64 bytes each -- the
+// host side of the function k_draw_r runs on the device
+#include "draw_r.hpp"
+extern "C" void zkhost_draw_r(const uint8_t seed[32], uint64_t first, size_t count, uint8_t* out) { draw_r_bytes(seed, first, count, out); }
+
 #include "comm_frame.hpp"
 extern "C" size_t zkhost_comm_slot_bytes(const uint64_t* cuts, int world) { return commframe::slot_bytes(cuts, world); }
 extern "C" void zkhost_comm_pack(uint8_t* out, size_t slot, const uint64_t* cuts, int rank, const uint8_t* local_bitmap, int local_status) {

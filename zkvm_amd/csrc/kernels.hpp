@@ -1626,7 +1626,7 @@ k_encode_rows(const uint32_t* __restrict__ ext, uint32_t n_rows, uint32_t* __res
 struct MergeSources {
   const uint4* com[16];
   const uint8_t* proofs[16];
-  const uint4* r[16];
+  const uint4* r[16];        // NULL: that batch brought no verifier randomness -- its part of r is drawn, not copied (session.hpp)
   uint32_t first[17];        // first transaction of each source in the merged batch; first[n] = total
   uint32_t n;
 };
@@ -1643,7 +1643,7 @@ k_merge_inputs(MergeSources src, uint32_t com_vec /*uint4 per transaction*/, uin
   }
   for (uint64_t g = g0; g < n_r; g += stride) {
     const uint32_t tx = (uint32_t)(g / 4), k = source_of(tx);
-    r[g] = src.r[k][g - (uint64_t)src.first[k] * 4];
+    if (src.r[k]) r[g] = src.r[k][g - (uint64_t)src.first[k] * 4];
   }
   // proofs: byte-aligned sources (a proof is 1 + 32 k bytes): four bytes per lane of the destination -- from two ALIGNED
   // words of the source and a funnel shift wherever the four bytes lie inside one source and not at its very end (a word
@@ -2059,3 +2059,4 @@ k_pack_bitmap_groups(const uint8_t* __restrict__ accept, const uint32_t* __restr
 }  // namespace zk
 
 #include "tx_reason_kernels.hpp"   // (reason bytes of a format-2 transaction call: queued for nothing else)
+#include "draw_r.hpp"              // (k_draw_r: verifier randomness for batches handed over without any)

@@ -1044,6 +1044,18 @@ int ticket_dispatch(zkgpu_verifier* v, bool force) {       // v->mu held
     zkgpu_cloak_plan* plan = verifier_plan(v, head->n_in, head->n_out, &rc, &plan_err);   // rc != OK: no plan THIS time -> the tickets fail with it
     if (rc != ZKGPU_OK) v->last_error = plan_err;                                          // (v->mu held)
     const void *p_com = pick[0]->d_com, *p_proofs = pick[0]->d_proofs, *p_r = pick[0]->d_r;
+    // Tickets that brought no verifier randomness (d_r NULL) get it here, once per DEVICE batch: one seed from the OS, and
+    // statement i of the device batch gets r(seed, i) (draw_r.hpp) in the lane's coal_r -- also a lone unmerged ticket, so that
+    // nothing of the caller's is aliased.  Tickets with an r of their own keep their bytes.  No seed: the batch fails.
+    bool draw = false;
+    for (zkgpu_request* r : pick) draw = draw || !r->d_r;
+    uint8_t seed[32] = {0};
+    const bool runs = rc == ZKGPU_OK && plan && proof_len_fits(plan->dev.sh, head->proof_len);
+    if (runs && draw && !os_random(seed, sizeof seed)) {
+      std::lock_guard<std::recursive_mutex> lk(L->mu);
+      L->last_error = "getrandom failed";
+      rc = ZKGPU_EINVAL;
+    }
     // batches of blocks whose copy to HBM is still queued on the copy stream: whoever reads their inputs waits for it
     if (pick.size() == 1) {
       if (pick[0]->ready) { std::lock_guard<std::recursive_mutex> lk(L->mu); L->dep_event = pick[0]->ready; }
@@ -1071,7 +1083,7 @@ int ticket_dispatch(zkgpu_verifier* v, bool force) {       // v->mu held
         const size_t base = off;
         while (at < pick.size() && ms.n < 16) {
           zkgpu_request* r = pick[at];
-          aligned = aligned && ((uintptr_t)r->d_com % 16 == 0) && ((uintptr_t)r->d_r % 16 == 0);
+          aligned = aligned && ((uintptr_t)r->d_com % 16 == 0) && ((uintptr_t)r->d_r % 16 == 0);     // (no r: NULL, drawn below)
           ms.com[ms.n] = (const uint4*)r->d_com; ms.proofs[ms.n] = (const uint8_t*)r->d_proofs; ms.r[ms.n] = (const uint4*)r->d_r;
           ms.first[ms.n] = (uint32_t)(off - base);
           off += r->batch;
@@ -1090,7 +1102,7 @@ int ticket_dispatch(zkgpu_verifier* v, bool force) {       // v->mu held
             const size_t nb = ms.first[k + 1] - ms.first[k];
             hipError_t e = hipMemcpyAsync((char*)L->coal_com.p + o2 * wcom, ms.com[k], nb * wcom, hipMemcpyDeviceToDevice, L->stream_l);
             if (e == hipSuccess) e = hipMemcpyAsync((char*)L->coal_proofs.p + o2 * head->proof_len, ms.proofs[k], nb * head->proof_len, hipMemcpyDeviceToDevice, L->stream_l);
-            if (e == hipSuccess) e = hipMemcpyAsync((char*)L->coal_r.p + o2 * 64, ms.r[k], nb * 64, hipMemcpyDeviceToDevice, L->stream_l);
+            if (e == hipSuccess && ms.r[k]) e = hipMemcpyAsync((char*)L->coal_r.p + o2 * 64, ms.r[k], nb * 64, hipMemcpyDeviceToDevice, L->stream_l);
             if (e != hipSuccess) { L->last_error = hipGetErrorString(e); rc = ZKGPU_EHIP; }
             o2 += nb;
           }
@@ -1098,13 +1110,26 @@ int ticket_dispatch(zkgpu_verifier* v, bool force) {       // v->mu held
       }
       p_com = L->coal_com.p; p_proofs = L->coal_proofs.p; p_r = L->coal_r.p;
     }
+    if (rc == ZKGPU_OK && runs && draw) {
+      std::lock_guard<std::recursive_mutex> lk(L->mu);
+      DeviceGuard g(L->device);
+      rc = ensure(L, L->coal_r, total * 64);
+      size_t off = 0;
+      for (size_t at = 0; at < pick.size() && rc == ZKGPU_OK;) {      // one launch per run of neighbouring tickets without r
+        if (pick[at]->d_r) { off += pick[at]->batch; ++at; continue; }
+        const size_t first = off;
+        while (at < pick.size() && !pick[at]->d_r) { off += pick[at]->batch; ++at; }
+        rc = draw_r_launch(L, L->stream_l, seed, first, (uint32_t)(off - first), (char*)L->coal_r.p + first * 64);
+      }
+      p_r = L->coal_r.p;
+    }
     bool front_only = false;
     if (rc == ZKGPU_OK && plan) {
       bool why = false;                                   // statements of a format-2 transaction call among them: the batch also says why
       for (zkgpu_request* r : pick) why = why || r->reasons;
       { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_FRONT; L->awaiting_back = false; L->want_reasons = why; L->reasons_src = 0; }
       rc = zkgpu_cloak_verify_submit_dev(L, v->ps, plan, total, p_com, p_proofs, head->proof_len, p_r);
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; front_only = rc == ZKGPU_OK && L->awaiting_back; if (rc != ZKGPU_OK) L->want_reasons = false; }
+      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; front_only = rc == ZKGPU_OK && L->awaiting_back; if (rc != ZKGPU_OK) L->want_reasons = false; if (draw) memcpy(L->r_seed, seed, sizeof seed); }
       if (front_only) fronts.push_back(Front{lane, plan, total, head->proof_len, p_com, p_proofs, p_r});
     }
     size_t off = 0;
@@ -1391,7 +1416,7 @@ int zkgpu_verifier_set_merge(zkgpu_verifier* v, size_t transactions) {
 
 int zkgpu_verifier_submit_dev(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, size_t batch, const void* d_commitments,
                               const void* d_proofs, size_t proof_len, const void* d_r, uint64_t* ticket) {
-  if (!v || !ticket || batch == 0 || batch >= (1ull << 24) || !d_commitments || !d_proofs || !d_r) return ZKGPU_EINVAL;
+  if (!v || !ticket || batch == 0 || batch >= (1ull << 24) || !d_commitments || !d_proofs) return ZKGPU_EINVAL;     // (d_r NULL: drawn per device batch, ticket_dispatch)
   std::lock_guard<std::mutex> lk(v->mu);
   zkgpu_request* r = new zkgpu_request();
   r->id = v->next_id++;
@@ -1407,14 +1432,14 @@ int zkgpu_verifier_submit_dev(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, 
 int zkgpu_verifier_submit_many_dev(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, size_t count, size_t batch_each,
                                    const void* const* d_commitments, const void* const* d_proofs, size_t proof_len,
                                    const void* const* d_r, uint64_t* tickets) {
-  if (!v || !tickets || !d_commitments || !d_proofs || !d_r || batch_each == 0 || batch_each >= (1ull << 24)) return ZKGPU_EINVAL;
-  for (size_t i = 0; i < count; ++i) if (!d_commitments[i] || !d_proofs[i] || !d_r[i]) return ZKGPU_EINVAL;
+  if (!v || !tickets || !d_commitments || !d_proofs || batch_each == 0 || batch_each >= (1ull << 24)) return ZKGPU_EINVAL;
+  for (size_t i = 0; i < count; ++i) if (!d_commitments[i] || !d_proofs[i]) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> lk(v->mu);
   for (size_t i = 0; i < count; ++i) {
     zkgpu_request* r = new zkgpu_request();
     r->id = v->next_id++;
     r->n_in = n_in; r->n_out = n_out; r->batch = batch_each; r->proof_len = proof_len;
-    r->d_com = d_commitments[i]; r->d_proofs = d_proofs[i]; r->d_r = d_r[i];
+    r->d_com = d_commitments[i]; r->d_proofs = d_proofs[i]; r->d_r = d_r ? d_r[i] : nullptr;       // (d_r or d_r[i] NULL: drawn per device batch)
     v->requests[r->id] = r;
     v->queue.push_back(r);
     tickets[i] = r->id;

@@ -135,7 +135,7 @@ struct zkgpu_ctx {
   std::atomic<uint32_t> last_failed_groups{0};   // root context: failed groups in the batch finished last (any fork)
   hipEvent_t ev_dig = nullptr, ev_u = nullptr;
   Buffer prep_com, prep_proofs, prep_r, prep_pw, prep_ch, prep_wf, prep_dyn_sc, prep_dyn_pt, prep_st_sc;
-  Buffer coal_com, coal_proofs, coal_r, tx_reason;  // merged inputs of the batches a zkgpu_verifier runs as one (session.hpp, tickets) | reason bytes
+  Buffer coal_com, coal_proofs, coal_r, tx_reason, r_draw;  // merged inputs of the batches a zkgpu_verifier runs as one (session.hpp, tickets) | reason bytes | verifier randomness this context drew for a whole-proof batch handed over without any (draw_r_if_none), kept until the batch is collected
   Buffer ipa_lv, ipa_rv, ipa_cg, ipa_ch, ipa_w, ipa_u;   // prover: the inner-product argument's vectors (ipa_kernels.hpp)
   // the device prover (prover_kernels.hpp): constant tables, per-proof state, inputs, the rows of the phases' multiscalar
   // multiplications with their offsets / generator indices, the points coming back, the proofs
@@ -162,7 +162,7 @@ struct zkgpu_ctx {
   std::vector<std::pair<int, int>> ev_used;   // (prof index, pool index)
   size_t ev_next = 0;
   int forced_w = 0, last_w = 0;
-  DecodeRoutes decode_routes;   // DECODE launches and points by form (kernels.hpp; zkgpu_debug_read "decode_routes")
+  DecodeRoutes decode_routes; uint8_t r_seed[32] = {0};  // DECODE launches and points by form (kernels.hpp; zkgpu_debug_read "decode_routes") | the seed of the last draw into r_draw or a lane's coal_r ("r_seed"); zero when the last batch brought its own r
   uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0;   // | root context of a verifier: transaction IDs / signature challenges its device produced (tx_device.hpp: GpuTxDevice)
 };
 
@@ -1480,7 +1480,7 @@ void zkgpu_destroy(zkgpu_ctx* c) {
                     &c->digits, &c->st_partials, &c->dynsum, &c->accept2, &c->bin_order, &c->class_count, &c->part_hist, &c->part_entries, &c->part_lo, &c->dec_scratch, &c->heavy, &c->small_tbl, &c->recoded, &c->grp_sc, &c->grp_digits, &c->grp_partials, &c->grp_ok, &c->row_map, &c->grp_fail, &c->grp_fail_sum, &c->rechk_pts, &c->grp_ws, &c->grp_wf, &c->grp_dyn, &c->pv_plan, &c->pv_state, &c->pv_in, &c->pv_rows0, &c->pv_rows1, &c->pv_rows2, &c->pv_rows3, &c->pv_lay, &c->pv_pts, &c->pv_com, &c->pv_ab, &c->pv_proofs, &c->prep_com, &c->prep_proofs, &c->prep_r,
                     &c->prep_pw, &c->prep_ch, &c->prep_wf, &c->prep_dyn_sc, &c->prep_dyn_pt, &c->prep_st_sc,
                     &c->prep_absorb, &c->prep_raw, &c->ipa_lv, &c->ipa_rv, &c->ipa_cg, &c->ipa_ch, &c->ipa_w, &c->ipa_u,
-                    &c->coal_com, &c->coal_proofs, &c->coal_r, &c->mx_tab, &c->mx_st_index, &c->tx_reason};
+                    &c->coal_com, &c->coal_proofs, &c->coal_r, &c->r_draw, &c->mx_tab, &c->mx_st_index, &c->tx_reason};
   for (Buffer* b : bufs) if (b->p) (void)hipFree(b->p);
   if (c->pinned) (void)hipHostFree(c->pinned);
   if (c->pinned_in) (void)hipHostFree(c->pinned_in);
@@ -2837,7 +2837,7 @@ int zkgpu_cloak_plan_layout(const zkgpu_cloak_plan* p, uint32_t out[8]) {
 // replay (one lane per transaction), scalar preparation (one workgroup per transaction),
 // then the multiscalar multiplications.  All `batch` statements have the plan's shape.
 namespace {
-// shared body: d_com / d_proofs / d_r are device pointers
+int draw_r_if_none(zkgpu_ctx* c, uint32_t B, const uint32_t** d_r);      // (below: d_r NULL -> drawn.)  Shared body: d_com / d_proofs / d_r are device pointers
 int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
                              const uint32_t* d_com, const uint8_t* d_proofs, const uint32_t* d_r, size_t proof_len);
 int cloak_verify_gpu_body(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
@@ -2894,7 +2894,7 @@ int zkgpu_cloak_verify_batch_gpu_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, zkg
   if (!c || !ps || !plan || plan->device != c->device || ps->ctx->device != c->device || !accept_bitmap) return ZKGPU_EINVAL;
   memset(accept_bitmap, 0, (batch + 7) / 8);
   if (batch == 0) return ZKGPU_OK;
-  if (!d_commitments || !d_proofs || !d_r || batch >= (1ull << 24)) return ZKGPU_EINVAL;
+  if (!d_commitments || !d_proofs || batch >= (1ull << 24)) return ZKGPU_EINVAL;       // (d_r NULL: drawn here, cloak_verify_gpu_enqueue)
   if (!proof_len_fits(plan->dev.sh, proof_len)) return ZKGPU_OK;
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   DeviceGuard g(c->device);
@@ -2915,7 +2915,7 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
     HIP_TRY(c, hipStreamWaitEvent(c->stream_l, ev, 0));
   }
   const PrepShape& sh = plan->dev.sh;
-  const uint32_t B = (uint32_t)batch;
+  const uint32_t B = (uint32_t)batch; TRY(draw_r_if_none(c, B, &d_r));      // (d_r NULL: drawn into c->r_draw, on the light stream)
   TRY(ensure(c, c->prep_pw, (size_t)B * sh.proof_words * 4));
   TRY(ensure(c, c->prep_ch, (size_t)B * sh.n_ch_ext * 32));
   if (plan->large) TRY(ensure(c, c->prep_large, lp_ws_bytes(lp_layout(sh).slots, B)));
@@ -3001,7 +3001,7 @@ int cloak_verify_gpu_body(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_pl
 int zkgpu_cloak_verify_submit_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
                                   const void* d_commitments, const void* d_proofs, size_t proof_len, const void* d_r) {
   if (!c || !ps || !plan || plan->device != c->device || ps->ctx->device != c->device) return ZKGPU_EINVAL;
-  if (batch == 0 || !d_commitments || !d_proofs || !d_r || batch >= (1ull << 24)) return ZKGPU_EINVAL;
+  if (batch == 0 || !d_commitments || !d_proofs || batch >= (1ull << 24)) return ZKGPU_EINVAL;
   {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     if (c->pending) return ZKGPU_EINVAL;
@@ -3347,6 +3347,40 @@ int zkgpu_set_window_bits(zkgpu_ctx* c, int w) {
   return ZKGPU_OK;
 }
 
+namespace {
+// Verifier randomness drawn on the device (draw_r.hpp): r(seed, first + i) -> out[64 i ..], i < count, queued on `s` ahead of
+// the kernels that read it.  The launch is collected here: a draw that was not made must fail the batch, not leave the bytes of
+// an earlier one in its place.
+int draw_r_launch(zkgpu_ctx* c, hipStream_t s, const uint8_t seed[32], uint64_t first, uint32_t count, void* out) {
+  {
+    Launch l(c, "k_draw_r", s);
+    hipLaunchKernelGGL(k_draw_r, dim3((count + 63) / 64), dim3(64), 0, s, draw_seed(seed), first, count, (uint4*)out);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return ZKGPU_OK;
+}
+
+// Verifier randomness of a whole-proof batch (cloak_verify_gpu_enqueue): the caller's, or (*d_r NULL) drawn here -- 32 bytes from
+// the OS per batch, expanded on the device into a buffer of this context's own that lives until the batch has been collected
+// (the failed groups' re-check and the ungrouped re-run of pipe_wait read it again).  Queued on the light stream, whose
+// kernels read r first.  A batch queued in pieces (enqueue_phase) draws with its first piece; the later ones find the same
+// bytes.  reserve_only: the buffer is sized, nothing is launched.  No randomness from the OS: the batch fails.
+int draw_r_if_none(zkgpu_ctx* c, uint32_t B, const uint32_t** d_r) {
+  const bool draws = !c->reserve_only && (c->enqueue_phase == zkgpu_ctx::ENQ_ALL || c->enqueue_phase == zkgpu_ctx::ENQ_FRONT);
+  if (*d_r) {
+    if (draws) memset(c->r_seed, 0, sizeof c->r_seed);
+    return ZKGPU_OK;
+  }
+  TRY(ensure(c, c->r_draw, (size_t)B * 64));
+  if (draws) {
+    if (!os_random(c->r_seed, sizeof c->r_seed)) { memset(c->r_seed, 0, sizeof c->r_seed); c->last_error = "getrandom failed"; return ZKGPU_EINVAL; }
+    TRY(draw_r_launch(c, c->stream_l, c->r_seed, 0, B, c->r_draw.p));
+  }
+  *d_r = (const uint32_t*)c->r_draw.p;
+  return ZKGPU_OK;
+}
+}  // namespace
+
 }  // extern "C"
 
 #include "session.hpp"
@@ -3678,6 +3712,12 @@ long long zkgpu_debug_read(zkgpu_ctx* c, const char* what, void* out, size_t byt
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     memcpy(out, &c->tx_signed_on_device, sizeof(uint64_t));
     return (long long)sizeof(uint64_t);
+  }
+  if (strcmp(what, "r_seed") == 0) {                   // the seed of the last draw of verifier randomness on this context (draw_r.hpp);
+    if (bytes < sizeof(c->r_seed)) return ZKGPU_EINVAL;        // zero: the last whole-proof batch brought its own r
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    memcpy(out, c->r_seed, sizeof(c->r_seed));
+    return (long long)sizeof(c->r_seed);
   }
   if (strcmp(what, "decode_routes") != 0) return debug_read_buffers(c, what, out, bytes);
   if (bytes < sizeof(c->decode_routes.n)) return ZKGPU_EINVAL;

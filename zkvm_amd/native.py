@@ -235,9 +235,9 @@ def runtime_hint(apply: bool = True) -> Tuple[int, str]:
     return rc, text
 
 
-def _ptr(x) -> int:
-    """Device pointer of a torch tensor (or a raw int)."""
-    return x if isinstance(x, int) else x.data_ptr()
+def _ptr(x):
+    """Device pointer of a torch tensor (or a raw int); None stays None (NULL: verifier randomness the library draws)."""
+    return x if x is None or isinstance(x, int) else x.data_ptr()
 
 
 def _u64arr(xs: Sequence[int]):

@@ -238,8 +238,9 @@ class BlockVerifier:
         """zkgpu_verifier_reserve: every lane's workspace sized for device batches of that many statements of the shape"""
         self._check(self.lib.zkgpu_verifier_reserve(self.h, n_in, n_out, transactions))
 
-    def submit_dev(self, n_in: int, n_out: int, batch: int, d_commitments, d_proofs, proof_len: int, d_r) -> int:
-        """zkgpu_verifier_submit_dev: queue one uniform batch (device buffers); -> ticket"""
+    def submit_dev(self, n_in: int, n_out: int, batch: int, d_commitments, d_proofs, proof_len: int, d_r=None) -> int:
+        """zkgpu_verifier_submit_dev: queue one uniform batch (device buffers); -> ticket.  d_r None (recommended): the
+        library draws the verifier randomness itself, per device batch."""
         from .native import _ptr
         t = C.c_uint64(0)
         self._check(self.lib.zkgpu_verifier_submit_dev(self.h, n_in, n_out, batch, _ptr(d_commitments), _ptr(d_proofs), proof_len,
@@ -248,12 +249,13 @@ class BlockVerifier:
         return int(t.value)
 
     def submit_many_dev(self, n_in: int, n_out: int, batch_each: int, d_commitments: Sequence, d_proofs: Sequence, proof_len: int,
-                        d_r: Sequence) -> List[int]:
-        """zkgpu_verifier_submit_many_dev: queue len(d_commitments) uniform batches in one call; -> tickets"""
+                        d_r: Optional[Sequence] = None) -> List[int]:
+        """zkgpu_verifier_submit_many_dev: queue len(d_commitments) uniform batches in one call; -> tickets.  d_r None, or
+        None entries in it: those batches' verifier randomness is drawn by the library, per device batch."""
         from .native import _ptr
         count = len(d_commitments)
-        assert len(d_proofs) == count and len(d_r) == count
-        arr = lambda xs: (C.c_void_p * max(count, 1))(*[_ptr(x) for x in xs])
+        assert len(d_proofs) == count and (d_r is None or len(d_r) == count)
+        arr = lambda xs: None if xs is None else (C.c_void_p * max(count, 1))(*[_ptr(x) for x in xs])
         t = (C.c_uint64 * max(count, 1))()
         self._check(self.lib.zkgpu_verifier_submit_many_dev(self.h, n_in, n_out, count, batch_each, arr(d_commitments), arr(d_proofs),
                                                             proof_len, arr(d_r), t))
@@ -647,8 +649,9 @@ class Verifier:
         return bm.raw[: (batch + 7) // 8]
 
     def verify_packed_gpu_dev(self, n_in: int, n_out: int, batch: int, d_commitments, d_proofs, proof_len: int,
-                              d_r) -> bytes:
-        """zkgpu_cloak_verify_batch_gpu_dev: inputs are device buffers (torch tensors or raw pointers)."""
+                              d_r=None) -> bytes:
+        """zkgpu_cloak_verify_batch_gpu_dev: inputs are device buffers (torch tensors or raw pointers).  d_r None
+        (recommended): the library draws the verifier randomness itself, on the device."""
         from .native import _ptr
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
         rc = self.ctx.lib.zkgpu_cloak_verify_batch_gpu_dev(self.ctx.h, self.bp_gens.points.h, self._plan(n_in, n_out),
@@ -657,10 +660,10 @@ class Verifier:
         self.ctx._check(rc)
         return bm.raw[: (batch + 7) // 8]
 
-    def submit_packed_gpu_dev(self, n_in: int, n_out: int, batch: int, d_commitments, d_proofs, proof_len: int, d_r,
+    def submit_packed_gpu_dev(self, n_in: int, n_out: int, batch: int, d_commitments, d_proofs, proof_len: int, d_r=None,
                               ctx: Optional[Context] = None) -> Context:
         """zkgpu_cloak_verify_submit_dev on `ctx` (this verifier's context or one of its forks): returns once the
-        batch is queued; `ctx.verify_wait()` yields the accept bitmap."""
+        batch is queued; `ctx.verify_wait()` yields the accept bitmap.  d_r None: drawn by the library."""
         from .native import _ptr
         c = ctx or self.ctx
         c._check(c.lib.zkgpu_cloak_verify_submit_dev(c.h, self.bp_gens.points.h, self._plan(n_in, n_out), batch,
