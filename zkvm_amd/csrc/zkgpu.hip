@@ -2931,8 +2931,8 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
   const uint32_t* d_st_index;
   {
     std::lock_guard<std::mutex> plk(plan->mu);
-    if (plan->cached_batch < batch) {
-      const size_t nb = std::max(batch, 2 * plan->cached_batch);
+    if (plan->cached_batch < batch + 1) {      // rows a launch indexes: with locate mode 3, 2 * ceil(batch / group) -- batch + 1 for groups of two over an odd batch
+      const size_t nb = std::max(batch + 1, 2 * plan->cached_batch);
       std::vector<uint64_t> doff(nb + 1), soff(nb + 1);
       for (size_t i = 0; i <= nb; ++i) { doff[i] = i * sh.n_dyn; soff[i] = i * sh.n_static; }
       std::vector<uint32_t> idx((size_t)nb * sh.n_static);
