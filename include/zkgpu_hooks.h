@@ -84,7 +84,14 @@ int zkgpu_debug_coop_selftest(zkgpu_ctx *ctx, const uint32_t *in, uint32_t *out,
  *        device evaluates the equation in this inversion-free form).
   * ("prover_slices": 4 bytes, the slices the last prover call on the context ran in.  "decode_routes": 4 x u64, which DECODE
   * ran since the context was created -- launches of the one-kernel k_decompress, the points they decoded, then the same for the
-  * split k_decompress_pre -> k_pow22523 -> k_decompress_post of 131072 points and more; both profile as "k_decompress".)
+  * split k_decompress_pre -> k_pow22523 -> k_decompress_post of 131072 points and more; both profile as "k_decompress".
+ * "msm_routes": 13 x u64, which forms of the multiscalar multiplication ran since the context was created (msm_route.hpp) --
+ * [0] launches of k_small_accumulate (the per-point tables), [1] the wavefronts per row of the last one; [2] runs of the bucket
+ * pipeline, [3] the window width of the last one; of those runs [4] sorted by partitions, [5] by count / scan / scatter,
+ * [6] reduced by k_bucket_reduce_quad, [7] by the one-lane k_bucket_reduce (both profile as "k_bucket_reduce"), [8] with
+ * k_window_partials; batches over a point set with tables whose proof-specific terms took [9] the per-point tables,
+ * [10] the bucket pipeline; [11] the fat and [12] the heavy bins of the last bucket-pipeline run, copied from the device
+ * behind everything queued when the record is read.)
  * Returns bytes copied.  zkgpu_cloak_plan_layout fills layout[0..7] = slots per transaction, challenge
  * slots proper, second-phase challenges, dynamic terms, static terms, k, m, monomials. */
 long long zkgpu_debug_read(zkgpu_ctx *ctx, const char *what, void *out, size_t bytes);

@@ -816,6 +816,21 @@ extern "C" void zkhost_pipe_plan(const int64_t* in, uint64_t* out) {
   std::memcpy(out, flat, sizeof flat);
 }
 
+// which form of the multiscalar multiplication a call takes, and its workspace (msm_route.hpp).  in[6]: n_msm n_dyn n_static
+// max_dyn_row (< 0: not known) forced_w entry (0 straight to the bucket pipeline, 1 batch, 2 batch over a set with tables).
+// out[40]: MsmRoute's fields in their order
+#include "msm_route.hpp"
+extern "C" void zkhost_msm_route(const int64_t* in, uint64_t* out) {
+  const MsmRoute r = plan_msm(MsmShape{(uint64_t)in[0], (uint64_t)in[1], (uint64_t)in[2], (uint64_t)in[3], (int)in[4], (int)in[5]});
+  const uint64_t flat[40] = {
+      r.small, (uint64_t)r.parts, (uint64_t)r.w, (uint64_t)r.n_windows, r.n_buckets, r.chunk_size, r.chunks, r.n_terms, r.n_wins, r.n_bins, r.n_tasks,
+      r.max_entries, r.too_large, r.part_sort, r.quad_reduce, r.window_partials, r.split_decode, r.scan_blocks, r.fat_cap, r.fat_blocks,
+      r.hi_bits, r.n_part, r.n_tiles,
+      r.dyn_rows, r.bins, r.block_sums, r.entries, r.buckets, r.partials, r.partial_flags, r.window_sums, r.window_flags, r.msm_fail, r.heavy,
+      r.class_count, r.bin_order, r.dec_scratch, r.part_hist, r.part_block_sums, r.part_entries};
+  std::memcpy(out, flat, sizeof flat);
+}
+
 // verifier randomness the library draws itself (draw_r.hpp): r(seed, first) .. r(seed, first + count - 1), 64 bytes each -- the
 // host side of the function k_draw_r runs on the device
 #include "draw_r.hpp"

@@ -44,6 +44,7 @@
 #include "ticket_cut.hpp"
 #include "mixed_plan.hpp"
 #include "pipe_plan.hpp"
+#include "msm_route.hpp"
 
 using namespace zk;
 
@@ -162,6 +163,11 @@ struct zkgpu_ctx {
   std::vector<std::pair<int, int>> ev_used;   // (prof index, pool index)
   size_t ev_next = 0;
   int forced_w = 0, last_w = 0;
+  // which forms of the multiscalar multiplication ran on this context since it was created (zkgpu_debug_read "msm_routes",
+  // include/zkgpu_hooks.h); counted on the host where the launch is queued
+  enum { RT_SMALL, RT_SMALL_PARTS, RT_BUCKET, RT_BUCKET_W, RT_PART_SORT, RT_COUNT_SCATTER, RT_QUAD_REDUCE, RT_LANE_REDUCE, RT_WINDOW_PARTIALS,
+         RT_TABLES_SMALL, RT_TABLES_BUCKET, RT_HOST_COUNTERS };
+  uint64_t msm_routes[RT_HOST_COUNTERS] = {};
   DecodeRoutes decode_routes; uint8_t r_seed[32] = {0};  // DECODE launches and points by form (kernels.hpp; zkgpu_debug_read "decode_routes") | the seed of the last draw into r_draw or a lane's coal_r ("r_seed"); zero when the last batch brought its own r
   uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0;   // | root context of a verifier: transaction IDs / signature challenges its device produced (tx_device.hpp: GpuTxDevice)
 };
@@ -301,11 +307,6 @@ void prof_collect(zkgpu_ctx* c) {
   c->ev_next = 0;
 }
 
-// wavefronts per MSM in k_small_accumulate: about three per SIMD (1024 SIMDs) over the whole launch
-inline int small_parts(uint64_t B) {
-  return (int)std::max<uint64_t>(1, std::min<uint64_t>(4, (3072 + B / 2) / std::max<uint64_t>(B, 1)));
-}
-
 inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 // sets of shared chip-filling streams per parent context (consecutive forks alternate between them) and the
@@ -315,21 +316,11 @@ constexpr int LOCATE_THREADS = 512; // ... in k_locate_fused: one wavefront per 
 constexpr int STREAM_SETS = 2;
 constexpr int MAX_FORKS = 9;
 static_assert(PLAN_EXT_WORDS == EXT_WORDS && PLAN_NIELS_WORDS == NIELS_WORDS && PLAN_SMALL_TBL == SMALL_TBL, "pipe_plan.hpp sizes the kernels' rows");
+static_assert(ROUTE_EXT_WORDS == EXT_WORDS && ROUTE_NIELS_WORDS == NIELS_WORDS && ROUTE_DEC_WORDS == DEC_WORDS && ROUTE_REDUCE_CHUNK == REDUCE_CHUNK &&
+              ROUTE_REDUCE_CHUNK_BIG == REDUCE_CHUNK_BIG && ROUTE_SCAN_TILE == SCAN_TILE && ROUTE_PART_TILE == PART_TILE &&
+              ROUTE_PART_LO_BITS == PART_LO_BITS && ROUTE_PART_IDX_BITS == PART_IDX_BITS && ROUTE_SIZE_CLASSES == SIZE_CLASSES &&
+              ROUTE_FAT_BIN == FAT_BIN && ROUTE_HEAVY_MAX == HEAVY_MAX && ROUTE_FAT_LANES == FAT_LANES, "msm_route.hpp routes and sizes the kernels' launches");
 constexpr size_t COOP_TRANSCRIPT_MAX = 1536;   // transactions per batch up to which the transcript runs one wavefront each
-
-// window width minimising  W * (terms + 2 * 2^(w-1) * msms)  point additions
-int choose_window(uint64_t n_terms, uint32_t n_msm) {
-  double per = (double)n_terms / (n_msm ? n_msm : 1);
-  int best = 4; double best_cost = 1e300;
-  for (int w = 4; w <= 16; ++w) {
-    double W = 255 / w + 1;
-    double reduce = 2.0 * (double)(1u << (w - 1));
-    if ((1u << (w - 1)) > (unsigned)REDUCE_CHUNK) reduce *= 1.3;  // chunk fix-up work
-    double cost = W * (per + reduce);
-    if (cost < best_cost) { best_cost = cost; best = w; }
-  }
-  return best;
-}
 
 struct Job {
   // device pointers
@@ -366,9 +357,10 @@ void decompress_launch(zkgpu_ctx* c, const Job& job, hipStream_t s) {
 //   c->msm_fail[m] != 0 when MSM m had an undecodable point
 //   c->status: [0] flags (bit 1: scalar >= 2^255), [2..3] u64 min bad point index
 int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status = true) {
-  const uint64_t n_terms = job.n_dyn + job.n_static;
-  int w = c->forced_w ? c->forced_w : choose_window(n_terms, job.n_msm);
-  w = std::max(2, std::min(16, w));
+  // the route of this call and the bytes of its workspace (msm_route.hpp); whoever calls has settled that it is the bucket pipeline
+  const MsmRoute rt = plan_msm(MsmShape{job.n_msm, job.n_dyn, job.n_static, job.max_dyn_row, c->forced_w, MSM_DIRECT});
+  const uint64_t n_terms = rt.n_terms;
+  const int w = rt.w;
   jd.dyn_scalars = job.d_dyn_scalars;
   jd.dyn_offsets = job.d_dyn_offsets;
   jd.n_dyn = job.n_dyn;
@@ -378,41 +370,38 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
   jd.n_static = job.n_static;
   jd.n_msm = job.n_msm;
   jd.w = w;
-  jd.n_windows = 255 / w + 1;
-  jd.n_buckets = 1u << (w - 1);
+  jd.n_windows = rt.n_windows;
+  jd.n_buckets = rt.n_buckets;
   c->last_w = w;
 
-  const uint64_t n_wins = (uint64_t)job.n_msm * jd.n_windows;
-  const uint64_t n_bins = n_wins * jd.n_buckets;
-  const uint32_t chunk_size = jd.n_buckets <= (uint32_t)REDUCE_CHUNK ? jd.n_buckets : (uint32_t)REDUCE_CHUNK_BIG;
-  const uint32_t chunks = (jd.n_buckets + chunk_size - 1) / chunk_size;
-  const uint64_t n_tasks = n_wins * chunks;
-  const uint64_t max_entries = n_terms * jd.n_windows;
-  if (max_entries >= (1ull << 32) || n_bins >= (1ull << 32) || job.n_dyn >= (1ull << 30) ||
-      job.n_static >= (1ull << 32)) {
+  const uint64_t n_wins = rt.n_wins, n_bins = rt.n_bins, n_tasks = rt.n_tasks;
+  const uint32_t chunk_size = rt.chunk_size, chunks = rt.chunks;
+  if (rt.too_large) {
     c->last_error = "job too large for 32-bit entry indices; split the batch";
     return ZKGPU_EINVAL;
   }
-  const unsigned scan_blocks = blocks_for(n_bins, SCAN_TILE);
+  const unsigned scan_blocks = rt.scan_blocks;
 
-  TRY(ensure(c, c->dyn_rows, std::max<uint64_t>(job.n_dyn, 1) * NIELS_WORDS * 4));
-  TRY(ensure(c, c->bins, (n_bins + 1) * 4));
-  TRY(ensure(c, c->block_sums, ((size_t)scan_blocks + 1) * 4));
-  TRY(ensure(c, c->entries, std::max<uint64_t>(max_entries, 1) * 4));
-  TRY(ensure(c, c->buckets, n_bins * EXT_WORDS * 4));
-  TRY(ensure(c, c->partials, n_tasks * EXT_WORDS * 4));
-  TRY(ensure(c, c->partial_flags, n_tasks * 4));
-  TRY(ensure(c, c->window_sums, n_wins * EXT_WORDS * 4));
-  TRY(ensure(c, c->window_flags, n_wins * 4));
-  TRY(ensure(c, c->msm_fail, (size_t)job.n_msm * 4));
+  TRY(ensure(c, c->dyn_rows, rt.dyn_rows));
+  TRY(ensure(c, c->bins, rt.bins));
+  TRY(ensure(c, c->block_sums, rt.block_sums));
+  TRY(ensure(c, c->entries, rt.entries));
+  TRY(ensure(c, c->buckets, rt.buckets));
+  TRY(ensure(c, c->partials, rt.partials));
+  TRY(ensure(c, c->partial_flags, rt.partial_flags));
+  TRY(ensure(c, c->window_sums, rt.window_sums));
+  TRY(ensure(c, c->window_flags, rt.window_flags));
+  TRY(ensure(c, c->msm_fail, rt.msm_fail));
   TRY(ensure(c, c->status, 64));
 
   // heavy list | fat list (kernels.hpp: bins summed by a workgroup each / by FAT_LANES lanes each)
-  const uint32_t fat_cap = (uint32_t)(max_entries / FAT_BIN + 64);
-  TRY(ensure(c, c->heavy, ((size_t)HEAVY_MAX + 1 + fat_cap + 1) * 4));
+  const uint32_t fat_cap = rt.fat_cap;
+  TRY(ensure(c, c->heavy, rt.heavy));
   uint32_t* heavy = (uint32_t*)c->heavy.p;
   uint32_t* fat = heavy + HEAVY_MAX + 1;
-  TRY(ensure(c, c->class_count, 2 * SIZE_CLASSES * 4));
+  TRY(ensure(c, c->class_count, rt.class_count));
+  c->msm_routes[zkgpu_ctx::RT_BUCKET] += 1;
+  c->msm_routes[zkgpu_ctx::RT_BUCKET_W] = (uint64_t)w;
 
   hipStream_t s = c->stream;
   // (every counter the sort and the bin order start from is cleared HERE, before anything runs: a memset between two kernels is
@@ -420,7 +409,7 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
   HIP_TRY(c, hipMemsetAsync(heavy, 0, 4, s));
   HIP_TRY(c, hipMemsetAsync(fat, 0, 4, s));
   HIP_TRY(c, hipMemsetAsync(c->class_count.p, 0, SIZE_CLASSES * 4, s));
-  const bool part_sort = job.n_msm == 1 && job.n_static == 0 && w - 1 >= PART_LO_BITS && n_terms >= 32768 && n_terms <= (1ull << PART_IDX_BITS);
+  const bool part_sort = rt.part_sort;
   if (!part_sort) HIP_TRY(c, hipMemsetAsync(c->bins.p, 0, (n_bins + 1) * 4, s));     // (the partition sort writes every bin's end offset itself)
   HIP_TRY(c, hipMemsetAsync(c->msm_fail.p, 0, (size_t)job.n_msm * 4, s));
   if (reset_status) {
@@ -431,11 +420,11 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
   unsigned long long* bad_index = (unsigned long long*)((char*)c->status.p + 8);
 
   bool decompress_aside = false;
-  if (job.n_dyn >= 131072) {
+  if (rt.split_decode) {
     // many points: run the squaring chain in its own lean kernel (kernels.hpp "split decompression"),
     // and on the second stream: the digit sort below needs the scalars only, is bound by LDS atomics
     // and memory while this is pure integer VALU work, so the two overlap; joined before the buckets
-    TRY(ensure(c, c->dec_scratch, job.n_dyn * DEC_WORDS * 4));
+    TRY(ensure(c, c->dec_scratch, rt.dec_scratch));
     hipStream_t sd = c->stream2 ? c->stream2 : s;
     decompress_aside = sd != s;
     if (decompress_aside) {
@@ -462,13 +451,13 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
     // single large MSM: two-level sort with LDS atomics only
     PartShape ps;
     ps.lo_bits = PART_LO_BITS;
-    ps.hi_bits = (uint32_t)(w - 1 - PART_LO_BITS);
-    ps.n_part = (uint32_t)jd.n_windows << ps.hi_bits;
-    ps.n_tiles = (uint32_t)blocks_for(n_terms, PART_TILE);
-    const uint64_t n_cells = (uint64_t)ps.n_part * ps.n_tiles;
-    TRY(ensure(c, c->part_hist, n_cells * 4));
-    TRY(ensure(c, c->block_sums, ((size_t)2 * ps.n_part + 4) * 4));        // totals[n_part] | part_base[n_part + 1] | ticket
-    TRY(ensure(c, c->part_entries, std::max<uint64_t>(max_entries, 1) * 4));
+    ps.hi_bits = rt.hi_bits;
+    ps.n_part = rt.n_part;
+    ps.n_tiles = rt.n_tiles;
+    TRY(ensure(c, c->part_hist, rt.part_hist));
+    TRY(ensure(c, c->block_sums, rt.part_block_sums));        // totals[n_part] | part_base[n_part + 1] | ticket
+    TRY(ensure(c, c->part_entries, rt.part_entries));
+    c->msm_routes[zkgpu_ctx::RT_PART_SORT] += 1;
     uint32_t* totals = (uint32_t*)c->block_sums.p;
     uint32_t* part_base = totals + ps.n_part;
     uint32_t* ticket = part_base + ps.n_part + 1;
@@ -493,6 +482,7 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
                          (const uint32_t*)c->part_entries.p, (uint32_t*)c->entries.p, (uint32_t*)c->bins.p, class_count);
     }
   } else {
+    c->msm_routes[zkgpu_ctx::RT_COUNT_SCATTER] += 1;
     if (n_terms) {
       Launch l(c, "k_digits_count");
       hipLaunchKernelGGL(k_digits_count, dim3(blocks_for(n_terms, 256)), dim3(256), 0, s, jd, (uint32_t*)c->bins.p,
@@ -512,7 +502,7 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
                          (uint32_t*)c->entries.p);
     }
   }
-  TRY(ensure(c, c->bin_order, n_bins * 4));
+  TRY(ensure(c, c->bin_order, rt.bin_order));
   {
     Launch l(c, "k_bin_order");
     if (!part_sort)                                      // (the partition sort counts the size classes of its bins itself)
@@ -526,7 +516,7 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
   {
     // one launch: its first workgroups sum the fat bins with FAT_LANES lanes each (they hold the longest chains and must start
     // first), the others one bin per lane
-    const unsigned fat_blocks = std::min<unsigned>(blocks_for((uint64_t)fat_cap * FAT_LANES, 256), 320u);
+    const unsigned fat_blocks = rt.fat_blocks;
     Launch l(c, "k_bucket_accumulate");
     hipLaunchKernelGGL(k_bucket_accumulate, dim3(fat_blocks + blocks_for(n_bins, 256)), dim3(256), 0, s,
                        (const uint32_t*)c->bins.p, (const uint32_t*)c->entries.p, job.d_static_rows,
@@ -545,14 +535,16 @@ int run_to_windows(zkgpu_ctx* c, const Job& job, JobDesc& jd, bool reset_status 
     // few tasks (one large multiscalar multiplication: 32 768): a quad of lanes per task, a third of the chain's depth; many
     // tasks (a batch of small ones): one lane each, a quarter of the instructions
     Launch l(c, "k_bucket_reduce");
-    if (n_tasks <= 65536)
+    c->msm_routes[rt.quad_reduce ? zkgpu_ctx::RT_QUAD_REDUCE : zkgpu_ctx::RT_LANE_REDUCE] += 1;
+    if (rt.quad_reduce)
       hipLaunchKernelGGL(k_bucket_reduce_quad, dim3(blocks_for(4 * n_tasks, 256)), dim3(256), 0, s, (const uint32_t*)c->bins.p,
                          (const uint32_t*)c->buckets.p, partials, pflags, n_tasks, jd.n_buckets, chunks, chunk_size);
     else
       hipLaunchKernelGGL(k_bucket_reduce, dim3(blocks_for(n_tasks, 256)), dim3(256), 0, s, (const uint32_t*)c->bins.p,
                          (const uint32_t*)c->buckets.p, partials, pflags, n_tasks, jd.n_buckets, chunks, chunk_size);
   }
-  if (chunks > 1) {
+  if (rt.window_partials) {
+    c->msm_routes[zkgpu_ctx::RT_WINDOW_PARTIALS] += 1;
     Launch l(c, "k_window_partials");
     hipLaunchKernelGGL(k_window_partials, dim3((unsigned)n_wins), dim3(256), 0, s, (const uint32_t*)c->partials.p,
                        (const uint32_t*)c->partial_flags.p, (uint32_t*)c->window_sums.p,
@@ -726,7 +718,7 @@ int batch_device_enqueue(zkgpu_ctx* c, const Job& job, bool values) {
   c->split = zkgpu_ctx::SplitOp{1, B, values, c->stream};
   if (B == 0) return ZKGPU_OK;
   JobDesc jd;
-  if (!c->forced_w && job.n_static == 0 && job.n_dyn && job.n_dyn <= 64ull * B && B >= 64 && job.max_dyn_row <= 256) {
+  if (plan_msm(MsmShape{job.n_msm, job.n_dyn, job.n_static, job.max_dyn_row, c->forced_w, MSM_BATCH}).small) {
     // many SMALL multiscalar multiplications (a few terms each: aggregated keys, signature equations): per-point tables
     // and one wavefront per row -- four launches, no global sort, no atomics -- instead of the bucket pipeline's seventeen.
     // EVERY row must be short, not just the average: one workgroup walks a row serially, and the tables are 1280 B per
@@ -801,6 +793,8 @@ int small_accumulate_launch(zkgpu_ctx* c, const Job& job, hipStream_t st) {
   const size_t B = job.n_msm;
   Launch l(c, "k_small_accumulate", st);
   const int parts = small_parts(B);
+  c->msm_routes[zkgpu_ctx::RT_SMALL] += 1;
+  c->msm_routes[zkgpu_ctx::RT_SMALL_PARTS] = (uint64_t)parts;
   hipLaunchKernelGGL(k_small_accumulate, dim3((unsigned)B), dim3(64 * parts), (size_t)(parts - 1) * 41 * 64 * 4, st,
                      (const uint32_t*)c->recoded.p, job.d_dyn_offsets, (const uint32_t*)c->small_tbl.p, (uint32_t)B,
                      (uint32_t*)c->window_sums.p, (uint32_t*)c->window_flags.p);
@@ -842,7 +836,9 @@ int batch_device_tables_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_points
     Job dj = job;
     dj.d_st_scalars = nullptr; dj.d_st_index = nullptr; dj.d_st_offsets = nullptr; dj.n_static = 0;
     JobDesc jd;
-    if (!c->forced_w && job.n_dyn <= 128ull * B) {
+    const bool small = plan_msm(MsmShape{job.n_msm, job.n_dyn, job.n_static, job.max_dyn_row, c->forced_w, MSM_TABLES}).small;
+    c->msm_routes[small ? zkgpu_ctx::RT_TABLES_SMALL : zkgpu_ctx::RT_TABLES_BUCKET] += 1;
+    if (small) {
       // few proof-specific points per transaction: one wavefront per transaction, no global sort
       jd.w = 4; jd.n_windows = 64;
       c->last_w = 4;
@@ -3718,6 +3714,23 @@ long long zkgpu_debug_read(zkgpu_ctx* c, const char* what, void* out, size_t byt
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     memcpy(out, c->r_seed, sizeof(c->r_seed));
     return (long long)sizeof(c->r_seed);
+  }
+  if (strcmp(what, "msm_routes") == 0) {               // which forms of the multiscalar multiplication ran (include/zkgpu_hooks.h): the host's
+    uint64_t rec[zkgpu_ctx::RT_HOST_COUNTERS + 2] = {};        // counters, then the fat and heavy bins of the last bucket-pipeline run
+    if (bytes < sizeof rec) return ZKGPU_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    memcpy(rec, c->msm_routes, sizeof(c->msm_routes));
+    if (c->msm_routes[zkgpu_ctx::RT_BUCKET] && c->heavy.p) {   // the lists' counts as k_bin_order left them, read behind everything queued
+      uint32_t heavy = 0, fat = 0;
+      if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&heavy, c->heavy.p, 4, hipMemcpyDeviceToHost) != hipSuccess ||
+          hipMemcpy(&fat, (const uint32_t*)c->heavy.p + HEAVY_MAX + 1, 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return ZKGPU_EHIP;
+      rec[zkgpu_ctx::RT_HOST_COUNTERS] = fat;
+      rec[zkgpu_ctx::RT_HOST_COUNTERS + 1] = heavy;
+    }
+    memcpy(out, rec, sizeof rec);
+    return (long long)sizeof rec;
   }
   if (strcmp(what, "decode_routes") != 0) return debug_read_buffers(c, what, out, bytes);
   if (bytes < sizeof(c->decode_routes.n)) return ZKGPU_EINVAL;

@@ -363,6 +363,17 @@ class Context:
         """zkgpu_debug_read "decode_routes" -> (one-kernel DECODE launches, their points, split DECODE launches, their points)"""
         return struct.unpack("<4Q", self.debug_read("decode_routes", 32))
 
+    def msm_routes(self) -> Dict[str, int]:
+        """zkgpu_debug_read "msm_routes": which forms of the multiscalar multiplication ran on this context since it was
+        created -- launches of the per-point tables (small) and the wavefronts per row of the last one (small_parts); runs of
+        the bucket pipeline (bucket) and the window width of the last one (bucket_w); of these, sorted by partitions or by
+        count / scan / scatter, reduced by a quad or by one lane per task, with k_window_partials; batches over a point
+        set with tables whose proof-specific terms took the per-point tables or the bucket pipeline; the fat and heavy
+        bins of the last bucket-pipeline run"""
+        names = ("small", "small_parts", "bucket", "bucket_w", "part_sort", "count_scatter", "quad_reduce", "lane_reduce", "window_partials",
+                 "tables_small", "tables_bucket", "fat", "heavy")
+        return dict(zip(names, struct.unpack("<13Q", self.debug_read("msm_routes", 104))))
+
     def mixed_group_stats(self) -> Tuple[int, int, int, int]:
         """zkgpu_debug_read "mixed_groups": the mixed call finished last on this context -> (groups of two or more
         statements, statements in them, groups that failed, statements re-checked alone because their group failed)"""
