@@ -587,6 +587,24 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * above (bitmap zero, status 1 for every transaction inside the subset, status 2 left alone).  The MuSig coefficients a_i
  * stay on the host: they are known from the transaction's own bytes before anything reaches the device.  Opt-in. */
 #define ZKGPU_TXFORMAT_SIGN_ON_DEVICE 512   /* 0x200 */
+/* A third FLAG, or-ed to any valid value above but 0 (valid values of the call: 0, and {1, 2} x {0, 0x100, 0x300} x {0, 0x400};
+ * alone, on a value that is invalid without it, or with any higher bit it is ZKGPU_EINVAL): the Ok side of upstream's
+ * Result<VerifiedTx, VMError> -- the TRANSACTION ID of every accepted transaction comes back with the verdicts.
+ *
+ *   !!  WITH THIS FLAG SET, THE `status` ARGUMENT OF zkgpu_tx_verify_batch AND zkgpu_tx_verify_wait POINTS AT  !!
+ *   !!  33 * batch BYTES, NOT batch.  A caller that sets the flag and passes batch bytes IS OVERRUN by 32 * batch.  !!
+ *
+ * Bytes [0, batch) are the status bytes, byte for byte what the same format writes without the flag.  Bytes
+ * [batch, 33 * batch) hold 32 bytes per transaction, in call order: beside status 0 and accept bit 1 the transaction ID,
+ * everywhere else -- a rejected transaction whatever the reason, status 2, every transaction of a call that returns an
+ * error -- 32 zero bytes.  Fail-closed like the rest: an ID is written at the very end, only beside a set bit; on any error
+ * the whole ID area is zero.  status == NULL stays legal (nothing is written, there are no IDs).  For a submitted call the
+ * layout is the one in force when zkgpu_tx_verify_submit QUEUED it, not the one at zkgpu_tx_verify_wait: the pending call
+ * remembers it.  The accept bitmap is unchanged in every case.  Nothing is hashed for it: the IDs are the ones the
+ * signature was checked against -- the host VM's, or with ZKGPU_TXFORMAT_HASH_ON_DEVICE the device's; all the flag adds on
+ * the device is one copy of 32 bytes per transaction beside ZKGPU_TXFORMAT_SIGN_ON_DEVICE, which otherwise leaves them
+ * there.  The IDs of the log's entries (contract IDs) do not come back: no argument can carry their number. */
+#define ZKGPU_TXFORMAT_RETURN_IDS 1024   /* 0x400 */
 #define ZKGPU_TXSTATUS_ACCEPTED 0
 #define ZKGPU_TXSTATUS_REJECTED 1                 /* rejected, reason not available (V1 format, or any error path) */
 #define ZKGPU_TXSTATUS_OUTSIDE_SUBSET 2

@@ -32,6 +32,7 @@
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
 use std::ptr;
+use std::sync::atomic::{AtomicBool, Ordering};
 
 use zkgpu_sys as sys;
 
@@ -168,6 +169,8 @@ pub struct TxCall<'v> {
     verifier: &'v GpuVerifier,
     id: u64,
     n: usize,
+    /// submitted under `ZKGPU_TXFORMAT_RETURN_IDS`: the library writes 33 * n status bytes for this call, whatever the format says later
+    ids: bool,
     waited: bool,
     _blob: Vec<u8>,
     _offsets: Vec<u64>,
@@ -177,9 +180,9 @@ impl Drop for TxCall<'_> {
     fn drop(&mut self) {
         if !self.waited {
             let mut bitmap = vec![0u8; (self.n + 7) / 8];
-            let mut status = vec![1u8; self.n];
-            // (the return code does not matter here: after this call the library no longer reads `_blob` / `_offsets`)
-            let _ = unsafe { sys::zkgpu_tx_verify_wait(self.verifier.v, self.id, bitmap.as_mut_ptr(), status.as_mut_ptr()) };
+            // (the return code does not matter here: after this call the library no longer reads `_blob` / `_offsets`; no
+            // status array: nothing of it is wanted, and its size depends on the format the call was submitted under)
+            let _ = unsafe { sys::zkgpu_tx_verify_wait(self.verifier.v, self.id, bitmap.as_mut_ptr(), ptr::null_mut()) };
         }
     }
 }
@@ -195,6 +198,9 @@ pub struct GpuVerifier {
     gens: Generators,
     v: *mut sys::zkgpu_verifier,
     warning: Option<String>,
+    /// the transaction format set last carries `ZKGPU_TXFORMAT_RETURN_IDS`: the library then writes 33 bytes per
+    /// transaction into the status array of a transaction call, and every call here sizes the array by this
+    return_ids: AtomicBool,
 }
 
 // the library serialises calls on a verifier with its own mutex, and hands out its error text as a per-thread copy made
@@ -248,7 +254,7 @@ impl GpuVerifier {
         match built {
             Ok((ps, v, warned)) => {
                 let warning = if warned { Some(text(unsafe { sys::zkgpu_verifier_last_error(v) })) } else { None };
-                Ok(GpuVerifier { ctx, gens: Generators { ps, capacity: gens_capacity }, v, warning })
+                Ok(GpuVerifier { ctx, gens: Generators { ps, capacity: gens_capacity }, v, warning, return_ids: AtomicBool::new(false) })
             }
             Err(e) => {
                 unsafe { sys::zkgpu_destroy(ctx) };
@@ -335,21 +341,29 @@ impl GpuVerifier {
     /// The serialized-transaction format `verify_txs` reads is a RECOLLECTION of the ZkVM notes: until
     /// a maintainer has compared it with the real `zkvm` crate and calls this, every transaction is `OutsideSubset`.
     pub fn enable_recollected_tx_format(&self) -> Result<(), Error> {
-        check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, sys::ZKGPU_TXFORMAT_RECOLLECTED_V1) }, self.err())
+        self.set_tx_format(sys::ZKGPU_TXFORMAT_RECOLLECTED_V1)
+    }
+
+    /// every `enable_*` goes through here: the wrapper must know whether the format makes the status array 33 bytes per
+    /// transaction.  Not to be raced with a transaction call on the same verifier (the format is a setting, made once).
+    fn set_tx_format(&self, format: c_int) -> Result<(), Error> {
+        check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, format) }, self.err())?;
+        self.return_ids.store(format & sys::ZKGPU_TXFORMAT_RETURN_IDS != 0, Ordering::SeqCst);
+        Ok(())
     }
 
     /// The same format, and every rejected transaction says why: `verify_txs` and `wait_txs` then return
     /// `TxVerdict::RejectedBecause(TxReject)` instead of `Rejected` (which remains what an error path leaves).  Same bytes
     /// read, same accept / reject decisions.
     pub fn enable_recollected_tx_format_with_reasons(&self) -> Result<(), Error> {
-        check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS) }, self.err())
+        self.set_tx_format(sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS)
     }
 
     /// Either format with `ZKGPU_TXFORMAT_HASH_ON_DEVICE`: contract IDs, anchors and the transaction ID are hashed on the
     /// device instead of on the host's threads.  Same verdicts; opt-in (whether it pays depends on the host's CPUs).
     pub fn enable_recollected_tx_format_hashing_on_device(&self, with_reasons: bool) -> Result<(), Error> {
         let base = if with_reasons { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS } else { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1 };
-        check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, base | sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE) }, self.err())
+        self.set_tx_format(base | sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE)
     }
 
     /// The same with `ZKGPU_TXFORMAT_SIGN_ON_DEVICE` beside it: the signature's challenge is formed on the device as well, from
@@ -357,12 +371,54 @@ impl GpuVerifier {
     pub fn enable_recollected_tx_format_signing_on_device(&self, with_reasons: bool) -> Result<(), Error> {
         let base = if with_reasons { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS } else { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1 };
         let flags = sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE | sys::ZKGPU_TXFORMAT_SIGN_ON_DEVICE;
-        check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, base | flags) }, self.err())
+        self.set_tx_format(base | flags)
+    }
+
+    /// Any of the above with `ZKGPU_TXFORMAT_RETURN_IDS` beside it: the `Ok` side of the reference's
+    /// `Result<VerifiedTx, VMError>` -- `verify_txs_with_ids` and `wait_txs_with_ids` then hand back the transaction ID of
+    /// every accepted transaction (the one its signature was checked against), from which a shim fills `VerifiedTx.id`.
+    /// `hash_on_device` / `sign_on_device` as in the two functions above (signing needs hashing).  Same verdicts.
+    pub fn enable_recollected_tx_format_returning_ids(&self, with_reasons: bool, hash_on_device: bool, sign_on_device: bool) -> Result<(), Error> {
+        if sign_on_device && !hash_on_device {
+            return Err(Error::InvalidArgument("signing on the device needs hashing on the device".into()));
+        }
+        let base = if with_reasons { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS } else { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1 };
+        let hash = if hash_on_device { sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE } else { 0 };
+        let sign = if sign_on_device { sys::ZKGPU_TXFORMAT_SIGN_ON_DEVICE } else { 0 };
+        self.set_tx_format(base | hash | sign | sys::ZKGPU_TXFORMAT_RETURN_IDS)
+    }
+
+    /// status array of a call of `n` transactions: `n` bytes, or `33 * n` under `ZKGPU_TXFORMAT_RETURN_IDS`
+    fn tx_status_len(n: usize, ids: bool) -> usize {
+        if ids { 33 * n } else { n }
+    }
+
+    /// status bytes (+ the ID area, if the call had one) and bitmap -> a verdict per transaction, and beside `Accepted` its ID
+    fn tx_verdicts_with_ids(n: usize, ids: bool, bitmap: &[u8], status: &[u8]) -> Vec<(TxVerdict, Option<[u8; 32]>)> {
+        (0..n)
+            .map(|i| {
+                let verdict = tx_verdict(status[i], (bitmap[i / 8] >> (i % 8)) & 1);
+                let id = if ids && verdict == TxVerdict::Accepted {
+                    let mut id = [0u8; 32];
+                    id.copy_from_slice(&status[n + 32 * i..n + 32 * i + 32]);
+                    Some(id)
+                } else {
+                    None
+                };
+                (verdict, id)
+            })
+            .collect()
     }
 
     /// Drop-in for `txs.iter().map(|tx| tx.verify(bp_gens))` on `Tx::encode()` bytes (payment subset): VM, transaction
     /// ID, MuSig / Schnorr signature and cloak proof.  `host_threads`: 0 = the CPUs the process may keep busy.
     pub fn verify_txs(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<TxVerdict>, Error> {
+        Ok(self.verify_txs_with_ids(txs, host_threads)?.into_iter().map(|(verdict, _)| verdict).collect())
+    }
+
+    /// `verify_txs`, and beside every `Accepted` the transaction ID -- `Some` only after
+    /// `enable_recollected_tx_format_returning_ids`, `None` beside every other verdict: the `VerifiedTx.id` of the reference.
+    pub fn verify_txs_with_ids(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<(TxVerdict, Option<[u8; 32]>)>, Error> {
         let n = txs.len();
         if n == 0 {
             return Ok(Vec::new());
@@ -374,15 +430,16 @@ impl GpuVerifier {
             blob.extend_from_slice(t);
             offs.push(blob.len() as u64);
         }
+        let ids = self.return_ids.load(Ordering::SeqCst);
         let mut bitmap = vec![0u8; (n + 7) / 8];
-        let mut status = vec![1u8; n];
+        let mut status = vec![1u8; Self::tx_status_len(n, ids)];
         check(
             unsafe {
                 sys::zkgpu_tx_verify_batch(self.v, n, blob.as_ptr(), offs.as_ptr(), host_threads as c_int, bitmap.as_mut_ptr(), status.as_mut_ptr())
             },
             self.err(),
         )?;
-        Ok((0..n).map(|i| tx_verdict(status[i], (bitmap[i / 8] >> (i % 8)) & 1)).collect())
+        Ok(Self::tx_verdicts_with_ids(n, ids, &bitmap, &status))
     }
 
     /// `verify_txs` in two halves, callable from many threads at once (upstream's `Tx::verify` is pure and `&self`): the
@@ -401,23 +458,30 @@ impl GpuVerifier {
             offsets.push(blob.len() as u64);
         }
         let mut id = 0u64;
+        let ids = self.return_ids.load(Ordering::SeqCst); // (the layout of the call's status array is the one in force now)
         // (the heap buffers of `blob` and `offsets` do not move when the vectors are moved into the handle)
         check(unsafe { sys::zkgpu_tx_verify_submit(self.v, n, blob.as_ptr(), offsets.as_ptr(), host_threads as c_int, &mut id) }, self.err())?;
-        Ok(TxCall { verifier: self, id, n, waited: false, _blob: blob, _offsets: offsets })
+        Ok(TxCall { verifier: self, id, n, ids, waited: false, _blob: blob, _offsets: offsets })
     }
 
     /// Blocks until the call's round is done: one verdict per transaction of THAT call.
-    pub fn wait_txs(&self, mut call: TxCall<'_>) -> Result<Vec<TxVerdict>, Error> {
+    pub fn wait_txs(&self, call: TxCall<'_>) -> Result<Vec<TxVerdict>, Error> {
+        Ok(self.wait_txs_with_ids(call)?.into_iter().map(|(verdict, _)| verdict).collect())
+    }
+
+    /// `wait_txs`, and beside every `Accepted` the transaction ID, as `verify_txs_with_ids` gives it -- `Some` if the call was
+    /// SUBMITTED after `enable_recollected_tx_format_returning_ids`.
+    pub fn wait_txs_with_ids(&self, mut call: TxCall<'_>) -> Result<Vec<(TxVerdict, Option<[u8; 32]>)>, Error> {
         if !ptr::eq(call.verifier, self) {
             return Err(Error::InvalidArgument("wait_txs: the call was submitted to another verifier".into())); // (its Drop waits there)
         }
         let n = call.n;
         let mut bitmap = vec![0u8; (n + 7) / 8];
-        let mut status = vec![1u8; n];
+        let mut status = vec![1u8; Self::tx_status_len(n, call.ids)];
         let rc = unsafe { sys::zkgpu_tx_verify_wait(self.v, call.id, bitmap.as_mut_ptr(), status.as_mut_ptr()) };
         call.waited = true; // (whatever it returned, the library is done with the call's bytes)
         check(rc, self.err())?;
-        Ok((0..n).map(|i| tx_verdict(status[i], (bitmap[i / 8] >> (i % 8)) & 1)).collect())
+        Ok(Self::tx_verdicts_with_ids(n, call.ids, &bitmap, &status))
     }
 
     /// Transactions per merged device batch (default 4096; the MI355X bench uses 10 240).

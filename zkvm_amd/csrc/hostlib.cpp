@@ -1101,6 +1101,9 @@ class HostTxDevice : public TxDevice {
     return 0;
   }
   std::string last_error() override { return err_.empty() ? "injected device fault" : err_; }
+  // a caller that is handed the transaction IDs (ZKGPU_TXFORMAT_RETURN_IDS): said before the call is made
+  bool ids() const override { return ids_; }
+  void set_ids(bool on) { ids_ = on; }
   size_t leaked() { std::lock_guard<std::mutex> lk(mu_); return staged_total_ - released_total_; }
 
  protected:
@@ -1131,6 +1134,7 @@ class HostTxDevice : public TxDevice {
   size_t staged_total_ = 0, released_total_ = 0;
   uint8_t base_[32];
   std::string err_;
+  bool ids_ = false;
 };
 }  // namespace
 
@@ -1282,8 +1286,9 @@ extern "C" long long zkhost_tx_hash_tape(const uint8_t* txs, const uint64_t* off
 namespace {
 class HostHashingTxDevice : public HostTxDevice {
  public:
-  HostHashingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int hash_fail_at)
-      : HostTxDevice(txs, offs, batch, proof_ok, seed, -1), hrng_(seed ^ 0x9e3779b9u), hash_fail_at_(hash_fail_at) { hash_tape_constants(protos_, labels_); }
+  HostHashingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int hash_fail_at,
+                      int fail_at = -1)
+      : HostTxDevice(txs, offs, batch, proof_ok, seed, fail_at), hrng_(seed ^ 0x9e3779b9u), hash_fail_at_(hash_fail_at) { hash_tape_constants(protos_, labels_); }
   ~HostHashingTxDevice() override { for (auto& s : h_) if (s.th.joinable()) s.th.join(); }
   bool hashes() const override { return true; }
   TxHashTape* hash_tape(int slot) override { return &h_[slot].tape; }
@@ -1307,12 +1312,13 @@ class HostHashingTxDevice : public HostTxDevice {
     if (!s.th.joinable()) { herr_ = "nothing to collect in this hash slot"; return -1; }
     s.th.join();
     if (hash_failing()) { herr_ = "injected fault of the hashing stage"; return -3; }
-    if (txids) std::memcpy(txids, s.ids.data(), 32 * s.tape.n_tx());
+    if (txids) { std::memcpy(txids, s.ids.data(), 32 * s.tape.n_tx()); ++id_asks_; }
     hashed_ += s.tape.n_tx();
     return 0;
   }
   std::string last_error() override { return herr_.empty() ? HostTxDevice::last_error() : herr_; }
   uint64_t hashed() const { return hashed_; }
+  uint64_t id_asks() const { return id_asks_; }           // collects that were given a host buffer for the IDs
 
  protected:
   struct HashStage { TxHashTape tape; std::thread th; std::atomic<bool> done{true}; std::vector<uint32_t> slots, ids; };
@@ -1323,7 +1329,7 @@ class HostHashingTxDevice : public HostTxDevice {
   std::mt19937 hrng_;
   const int hash_fail_at_;
   int hops_ = 0;
-  uint64_t hashed_ = 0;
+  uint64_t hashed_ = 0, id_asks_ = 0;
   std::string herr_;
 };
 }  // namespace
@@ -1410,8 +1416,9 @@ extern "C" long long zkhost_tx_sig_rows(const uint8_t* txs, const uint64_t* offs
 namespace {
 class HostChainingTxDevice : public HostHashingTxDevice {
  public:
-  HostChainingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int sig_fail_at)
-      : HostHashingTxDevice(txs, offs, batch, proof_ok, seed, -1), crng_(seed ^ 0x51ed270bu), sig_fail_at_(sig_fail_at) { have_script_ = sig_script(script_); }
+  HostChainingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int sig_fail_at,
+                       int hash_fail_at = -1, int fail_at = -1)
+      : HostHashingTxDevice(txs, offs, batch, proof_ok, seed, hash_fail_at, fail_at), crng_(seed ^ 0x51ed270bu), sig_fail_at_(sig_fail_at) { have_script_ = sig_script(script_); }
   bool chains() const override { return true; }
   int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc, const SigChain* chain) override {
     if (!chain) { cerr_ = "an unchained signature stage on a device that chains"; return -1; }
@@ -1474,4 +1481,68 @@ extern "C" int zkhost_txcall_chaining_selftest(size_t batch, const uint8_t* txs,
   *hashed = dev.hashed();
   *signed_rows = dev.signed_rows();
   return rc;
+}
+
+// ---- a call whose caller is handed the transaction IDs (TxDevice::ids: ZKGPU_TXFORMAT_RETURN_IDS) on the CPU, over any of the
+// ---- three stand-ins above -- kind 0: HostTxDevice, 1: hashing, 2: chaining -- laid out and fail-closed as session.hpp does it.
+// ---- split = 0: a lone call; status_a is 33 * batch bytes (batch when return_ids = 0), the IDs behind the status bytes.
+// ---- split > 0 (a multiple of 8, < batch): the transactions [0, split) and [split, batch) as two callers' pieces of ONE merged
+// ---- call, as a round of zkgpu_tx_verify_submit holds them: one bitmap and one status array for the round, handed out to
+// ---- status_a (33 * split bytes, or split) and status_b (33 * (batch - split), or batch - split), each with its own ID area.
+// ---- fail_at: the n-th operation of stage fail_stage fails (-1: none) -- 0 keys / proofs / unchained signatures, 1 the hashing
+// ---- stage, 2 the chained signature stage.  out[0] chunks, out[1] staged chunks never released, out[2] hash_collect calls
+// ---- that were given a host buffer, out[3] transactions whose ID the HOST's second pass hashed, out[4] IDs the stand-in's
+// ---- hashing stage produced, out[5] whether a failed call had left anything in an ID area before it was fail-closed (must be 0)
+extern "C" int zkhost_txcall_ids_selftest(int kind, int return_ids, size_t batch, size_t split, const uint8_t* txs, const uint64_t* offs,
+                                          const uint8_t* proof_ok, int host_threads, size_t chunk, uint32_t delay_seed, int fail_at, int fail_stage,
+                                          int n_slots, uint8_t* accept_bitmap, uint8_t* status_a, uint8_t* status_b, uint64_t* out) {
+  for (int q = 0; q < 6; ++q) out[q] = 0;
+  if (kind < 0 || kind > 2 || fail_stage < 0 || fail_stage > kind || !status_a || (split && (split >= batch || split % 8 || !status_b))) return -1;
+  const int f0 = fail_stage == 0 ? fail_at : -1, f1 = fail_stage == 1 ? fail_at : -1, f2 = fail_stage == 2 ? fail_at : -1;
+  std::unique_ptr<HostTxDevice> dev;
+  if (kind == 0) dev.reset(new HostTxDevice(txs, offs, batch, proof_ok, delay_seed, f0));
+  else if (kind == 1) dev.reset(new HostHashingTxDevice(txs, offs, batch, proof_ok, delay_seed, f1, f0));
+  else dev.reset(new HostChainingTxDevice(txs, offs, batch, proof_ok, delay_seed, f2, f1, f0));
+  dev->set_ids(return_ids != 0);
+  const size_t na = split ? split : batch, nb = split ? batch - split : 0;
+  uint8_t* const ids_a = return_ids ? status_a + na : nullptr;
+  uint8_t* const ids_b = return_ids && nb ? status_b + nb : nullptr;
+  std::memset(accept_bitmap, 0, (batch + 7) / 8);
+  std::memset(status_a, TX_INVALID, na);
+  if (nb) std::memset(status_b, TX_INVALID, nb);
+  if (ids_a) std::memset(ids_a, 0, 32 * na);
+  if (ids_b) std::memset(ids_b, 0, 32 * nb);
+  std::vector<uint8_t> round_bits((batch + 7) / 8 + 1, 0), round_status(split ? batch : 0, (uint8_t)TX_INVALID);
+  std::vector<TxStatement> store;
+  int rc;
+  {
+    std::unique_ptr<TxCall> call;
+    if (split == 0) {
+      call.reset(new TxCall(*dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, round_bits.data(), status_a, n_slots));
+    } else {
+      std::vector<TxCall::Piece> pieces{{txs, offs, na, ids_a}, {txs, offs + split, nb, ids_b}};
+      call.reset(new TxCall(*dev, store, (size_t)1 << 17, pieces, host_threads, chunk, round_bits.data(), round_status.data(), n_slots));
+    }
+    out[0] = call->n_chunks();
+    rc = call->run();
+    out[3] = call->n_host_hashed();
+  }
+  out[1] = dev->leaked();
+  if (kind >= 1) { out[2] = static_cast<HostHashingTxDevice*>(dev.get())->id_asks(); out[4] = static_cast<HostHashingTxDevice*>(dev.get())->hashed(); }
+  if (split) {                                           // (tx_round_distribute: a failed round keeps "outside the subset" alone)
+    for (size_t i = 0; i < batch; ++i) {
+      uint8_t& to = i < split ? status_a[i] : status_b[i - split];
+      if (rc == 0) to = round_status[i]; else if (round_status[i] == TX_UNSUPPORTED) to = TX_UNSUPPORTED;
+    }
+  }
+  if (rc != 0) {
+    for (size_t i = 0; ids_a && i < 32 * na; ++i) if (ids_a[i]) out[5] = 1;
+    for (size_t i = 0; ids_b && i < 32 * nb; ++i) if (ids_b[i]) out[5] = 1;
+    if (split == 0) for (size_t i = 0; i < batch; ++i) if (status_a[i] != TX_UNSUPPORTED) status_a[i] = TX_INVALID;
+    if (ids_a) std::memset(ids_a, 0, 32 * na);
+    if (ids_b) std::memset(ids_b, 0, 32 * nb);
+    return rc;
+  }
+  std::memcpy(accept_bitmap, round_bits.data(), (batch + 7) / 8);
+  return 0;
 }

@@ -115,6 +115,9 @@ struct zkgpu_verifier {
   TxHashStage tx_hash[2];
   Buffer tx_hash_const;
   bool tx_sign_on_device = false;                       // the flag ZKGPU_TXFORMAT_SIGN_ON_DEVICE (only beside the one above)
+  // the flag ZKGPU_TXFORMAT_RETURN_IDS: the status argument of a call is 33 * batch bytes, the IDs of what was accepted behind
+  // the status bytes.  (Atomic: zkgpu_tx_verify_submit reads it without `mu`, which a round in flight holds.)
+  std::atomic<bool> tx_return_ids{false};
   // what the signature's challenge needs beside its slot's signature context (tx_sig_rows.hpp): the rows' places on the tape,
   // the events that order it behind the slot's key stage and hashing stage; once per verifier, the script of the transcript
   struct TxSigStage { Buffer d_pos; hipEvent_t ev_keys = nullptr, ev_ids = nullptr; size_t rows = 0; };
@@ -149,6 +152,8 @@ struct zkgpu_verifier {
     int state = 0, rc = 0;                              // 0 queued, 1 in a round, 2 done
     std::chrono::steady_clock::time_point arrived;      // (the engine lets a small queue wait a little while a round is running)
     std::vector<uint8_t> bits, status;
+    bool return_ids = false;                            // the layout of its status argument, as the format said when it was SUBMITTED
+    std::vector<uint8_t> txids;                         // ... then 32 bytes per transaction: zero but beside a set bit
   };
   std::mutex tx_mu;
   std::condition_variable tx_cv;
@@ -1673,7 +1678,7 @@ int zkgpu_verifier_verify_sharded(zkgpu_verifier* v, zkgpu_comm* cm, size_t batc
 // (the verdicts stay with their tickets / runs) -- a synchronous call on a context with a batch in flight would
 // overwrite that batch's status words and pinned result buffer (and is refused by the context: refuse_if_pending).
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
-  const int base = format & ~(ZKGPU_TXFORMAT_HASH_ON_DEVICE | ZKGPU_TXFORMAT_SIGN_ON_DEVICE);     // (the flags go with a format: alone they name none)
+  const int base = format & ~(ZKGPU_TXFORMAT_HASH_ON_DEVICE | ZKGPU_TXFORMAT_SIGN_ON_DEVICE | ZKGPU_TXFORMAT_RETURN_IDS);     // (the flags go with a format: alone they name none)
   if (!v || (format != 0 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS)) return ZKGPU_EINVAL;
   // (the challenge reads the transaction ID where the hashing stage left it: no signing on the device without hashing there)
   if ((format & ZKGPU_TXFORMAT_SIGN_ON_DEVICE) && !(format & ZKGPU_TXFORMAT_HASH_ON_DEVICE)) return ZKGPU_EINVAL;
@@ -1681,6 +1686,7 @@ int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
   v->tx_format = base;
   v->tx_hash_on_device = (format & ZKGPU_TXFORMAT_HASH_ON_DEVICE) != 0;
   v->tx_sign_on_device = (format & ZKGPU_TXFORMAT_SIGN_ON_DEVICE) != 0;
+  v->tx_return_ids = (format & ZKGPU_TXFORMAT_RETURN_IDS) != 0;
   return ZKGPU_OK;
 }
 
@@ -1761,19 +1767,24 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   if (!v || !accept_bitmap) return ZKGPU_EINVAL;
   memset(accept_bitmap, 0, (batch + 7) / 8);
   if (status) memset(status, TX_INVALID, batch);
+  // (ZKGPU_TXFORMAT_RETURN_IDS: `status` is 33 * batch bytes.  The ID area is zero from here on, whichever way the call
+  // leaves; TxCall::verdicts writes into it beside the bits it sets, and an error zeroes it again below)
+  uint8_t* const txids = (status && v->tx_return_ids) ? status + batch : nullptr;
+  if (txids) memset(txids, 0, 32 * batch);
   if (batch == 0) return ZKGPU_OK;
   if (!txs || !tx_offsets || batch >= (1ull << 31)) return ZKGPU_EINVAL;
   for (size_t i = 0; i < batch; ++i) if (tx_offsets[i + 1] < tx_offsets[i]) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> vlk(v->mu);
   if (v->tx_format == 0) {                                        // no format enabled: nothing is inside the subset
     if (status) memset(status, TX_UNSUPPORTED, batch);
+    if (txids) memset(txids, 0, 32 * batch);                      // (a format set meanwhile: the layout is the one the call began with)
     return ZKGPU_OK;
   }
   TRY(tx_call_prepare(v));
   // (format 2 reads the same bytes and gives the same bits; what differs is what the status bytes say -- with no status
   // array there is nothing to say, and the call is the format-1 call)
   GpuTxDevice dev(v, 0, 0, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS && status != nullptr, v->tx_hash_on_device,
-                  v->tx_sign_on_device);
+                  v->tx_sign_on_device, txids != nullptr);
   int rc;
   try {
     TxCall call(dev, v->tx_statements, v->tx_statements_kept, batch, txs, tx_offsets, host_threads, v->tx_chunk, accept_bitmap, status);
@@ -1786,6 +1797,7 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   if (rc != ZKGPU_OK) {                                          // both outputs read "nothing accepted"
     memset(accept_bitmap, 0, (batch + 7) / 8);
     if (status) for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;     // (never a reason, never 0)
+    if (txids) memset(txids, 0, 32 * batch);                      // (and never an ID)
   }
   return rc;
 }
@@ -1821,6 +1833,7 @@ void tx_round_distribute(TxRound& r) {
   for (auto* p : r.calls) {
     p->bits.assign((p->batch + 7) / 8, 0);
     p->status.assign(p->batch, TX_INVALID);
+    if (r.rc != ZKGPU_OK) std::fill(p->txids.begin(), p->txids.end(), (uint8_t)0);      // (a failed round: no ID either)
     p->rc = r.rc;
     for (size_t i = 0; i < p->batch; ++i) {
       const size_t g = at + i;
@@ -1899,7 +1912,13 @@ void tx_engine_main(zkgpu_verifier* v) {
       if (!fresh[set]) continue;
       TxRound& r = *fresh[set];
       int threads = 0;
-      for (auto* p : r.calls) { r.pieces.push_back({p->txs, p->offsets, p->batch}); threads = std::max(threads, p->host_threads); }
+      // (a call submitted under ZKGPU_TXFORMAT_RETURN_IDS has its own ID area, zero until verdicts() writes beside a set bit)
+      bool want_ids = false;
+      for (auto* p : r.calls) {
+        if (p->return_ids) { p->txids.assign(32 * p->batch, 0); want_ids = true; }
+        r.pieces.push_back({p->txs, p->offsets, p->batch, p->return_ids ? p->txids.data() : nullptr});
+        threads = std::max(threads, p->host_threads);
+      }
       r.bits.assign((r.total + 7) / 8 + 1, 0);
       r.status.assign(r.total, TX_INVALID);
       if (v->tx_format == 0) {
@@ -1909,7 +1928,7 @@ void tx_engine_main(zkgpu_verifier* v) {
         if (r.rc == ZKGPU_OK) {
           try {
             r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS, v->tx_hash_on_device,
-                                        v->tx_sign_on_device));
+                                        v->tx_sign_on_device, want_ids));
             r.call.reset(new TxCall(*r.dev, set ? v->tx_statements_b : v->tx_statements, v->tx_statements_kept, r.pieces, threads, v->tx_chunk,
                                     r.bits.data(), r.status.data(), 1));
             r.call->set_on_news([&] { { std::lock_guard<std::mutex> nl(news_mu); news = true; } news_cv.notify_one(); });
@@ -1964,6 +1983,7 @@ int zkgpu_tx_verify_submit(zkgpu_verifier* v, size_t batch, const uint8_t* txs, 
   std::unique_ptr<zkgpu_verifier::TxPending> p(new zkgpu_verifier::TxPending());
   p->batch = batch; p->txs = txs; p->offsets = tx_offsets; p->host_threads = host_threads;
   p->arrived = std::chrono::steady_clock::now();
+  p->return_ids = v->tx_return_ids;                      // (the layout wait will write: the one in force now)
   std::lock_guard<std::mutex> lk(v->tx_mu);
   if (v->tx_engine_quit) return ZKGPU_EINVAL;
   if (!v->tx_engine.joinable()) {
@@ -1989,6 +2009,10 @@ int zkgpu_tx_verify_wait(zkgpu_verifier* v, uint64_t call_id, uint8_t* accept_bi
   memset(accept_bitmap, 0, (p->batch + 7) / 8);
   if (rc == ZKGPU_OK) memcpy(accept_bitmap, p->bits.data(), p->bits.size());
   if (status) memcpy(status, p->status.data(), p->batch);
+  if (status && p->return_ids) {                         // (submitted under ZKGPU_TXFORMAT_RETURN_IDS: 33 * batch bytes)
+    if (rc == ZKGPU_OK && p->txids.size() == 32 * p->batch) memcpy(status + p->batch, p->txids.data(), 32 * p->batch);
+    else memset(status + p->batch, 0, 32 * p->batch);
+  }
   v->tx_calls.erase(it);
   return rc;
 }

@@ -42,6 +42,11 @@
 //     signature bits of a chunk are collected together, when its signature stage is through, and that is when its slot is
 //     free again (the IDs are not brought down: nothing on the host reads them).  A row whose key did not decode runs through
 //     all the same: its bit is ANDed with the key's.
+// A third switch changes nothing of the schedule: TxDevice::ids() (ZKGPU_TXFORMAT_RETURN_IDS) hands the caller the transaction
+// ID of every ACCEPTED transaction -- 32 bytes each in an area of the caller's (Piece::ids; of a lone call, behind its status
+// bytes), written by verdicts() where it writes TX_OK and nowhere else, from the statement's txid: the one the VM's second
+// pass hashed for the signature, or the one the device's tape produced.  Nothing is hashed for it; all it adds is that a
+// device that chains copies its IDs down after all (hash_collect with a host buffer).
 // The calling thread's sub-steps (snapshot, queue_keys, queue_tape, proofs_turn, the collects, end_step) are the same whatever
 // the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run: step_host_signed()
 // and step_chained(), which say why.
@@ -124,6 +129,9 @@ class TxDevice {
   virtual int hash_collect(int, uint8_t*) { return -1; }
   // the signature's challenge on the device.  chains(): does the device form it?  (Asked only of a device that hashes.)
   virtual bool chains() const { return false; }
+  // does the caller want the transaction IDs of what was accepted?  (A device that chains then brings its IDs down like one
+  // that only hashes: hash_collect is given a host buffer.)
+  virtual bool ids() const { return false; }
 };
 
 class TxCall {
@@ -135,19 +143,25 @@ class TxCall {
 
   // several callers' transactions as ONE call (zkgpu_tx_verify_submit: calls in flight are merged as tickets are): the
   // pieces in order, transaction i of the merged call = the i-th transaction counted through them
-  struct Piece { const uint8_t* txs; const uint64_t* tx_offsets; size_t batch; };
+  // ids (only of a device with ids(); may be NULL): 32 * batch bytes of that caller's, zeroed by it, for the IDs of what is accepted
+  struct Piece { const uint8_t* txs; const uint64_t* tx_offsets; size_t batch; uint8_t* ids = nullptr; };
   // store: what the VM leaves per transaction, kept by the caller between calls (fresh memory costs a page fault per 4 KB);
   // at most `kept` entries of it are used, the rest of a longer call lives in the call.
+  // A lone call on a device with ids(): `status` points at 33 * batch bytes, the IDs behind the status bytes.
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
-      : TxCall(dev, store, kept, std::vector<Piece>{Piece{txs, tx_offsets, batch}}, host_threads, chunk_override, accept_bitmap, status, n_slots) {}
+      : TxCall(dev, store, kept, std::vector<Piece>{Piece{txs, tx_offsets, batch, dev.ids() && status ? status + batch : nullptr}}, host_threads,
+               chunk_override, accept_bitmap, status, n_slots) {}
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
-        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), ids_(dev.ids() && any_ids(pieces)), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
-    for (const Piece& pc : pieces)
+    if (ids_) id_out_.reserve(batch_);
+    for (const Piece& pc : pieces) {
+      if (ids_) for (size_t i = 0; i < pc.batch; ++i) id_out_.push_back(pc.ids ? pc.ids + 32 * i : nullptr);
       for (size_t i = 0; i < pc.batch; ++i) { ptr_.push_back(pc.txs + pc.tx_offsets[i]); len_.push_back((size_t)(pc.tx_offsets[i + 1] - pc.tx_offsets[i])); }
+    }
     plan(chunk_override, kept);
   }
   ~TxCall() { stop_stager(); }
@@ -224,7 +238,7 @@ class TxCall {
     }
     // (after an error: nothing is left pending on the device)
     for (size_t s = 0; s < seg_.size(); ++s) keys_collect(s);
-    while (next_hcollect_ < next_hash_) hash_collect(next_hcollect_++);
+    while (next_hcollect_ < next_hash_) hash_collect(next_hcollect_++, !chains_ || ids_);
     for (size_t s = 0; s < n_sig_made_locked(); ++s) sigs_collect(s);
     for (size_t c = 0; c < chunks_.size(); ++c) proofs_collect(*chunks_[c]);
     report();
@@ -235,6 +249,8 @@ class TxCall {
   const std::string& error_text() const { return error_; }
   size_t n_chunks() const { return chunks_.size(); }
   size_t n_sig_stages_planned() const { return sig_plan_.size(); }
+  // transactions whose second pass ran on the host with every protocol -- the transaction ID's among them (0 on a device that hashes)
+  size_t n_host_hashed() { std::lock_guard<std::mutex> lk(hm_); return n_host_hashed_; }
 
  private:
   struct Chunk {
@@ -264,6 +280,7 @@ class TxCall {
   struct Span { size_t first, last; };
 
   static size_t total_of(const std::vector<Piece>& pieces) { size_t n = 0; for (const Piece& p : pieces) n += p.batch; return n; }
+  static bool any_ids(const std::vector<Piece>& pieces) { for (const Piece& p : pieces) if (p.ids && p.batch) return true; return false; }
   static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
   void mark(const char* what, size_t i) const { if (timing_) fprintf(stderr, "    %7.3f ms  %s %zu\n", (now() - t00_) * 1e3, what, i); }
   TxStatement& statement(size_t i) { return i < store_.size() ? store_[i] : beyond_[i - store_.size()]; }
@@ -331,6 +348,7 @@ class TxCall {
     chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) { tx_prepare_many(p, l, &statement(k.lo + first), cnt, true, only); });
     std::lock_guard<std::mutex> lk(hm_);
     (only == ALL_PROTOS ? t_vm_ : t_keys_host_) += now() - t0;
+    if (only == ALL_PROTOS) n_host_hashed_ += k.n;
   }
   // the second pass of a chunk on a device that hashes: the plans into the slot's tape, the MuSig jobs alone on the host
   void vm_pass_taped(Chunk& k, TxHashTape& tape) {
@@ -552,7 +570,8 @@ class TxCall {
     mark("signatures collected, stage", s);
   }
   // the IDs of chunk c, from the device to the statements; the staging thread is told (ids_upto_).  (to_host = false, a
-  // device that chains: nothing on the host reads them -- the slot's tape is collected and nothing is copied)
+  // device that chains and a caller that does not ask for IDs: nothing on the host reads them -- the slot's tape is
+  // collected and nothing is copied)
   void hash_collect(size_t c, bool to_host = true) {
     Chunk& k = *chunks_[c];
     if (hash_pending_[c]) {
@@ -735,7 +754,7 @@ class TxCall {
     if (rc_ == OK && next_chain_ < next_sig_ && (!sig_stages_[next_chain_]->pending || dev_.sigs_done((int)(next_chain_ % n_slots_)))) {
       sigs_collect(next_chain_);
       keys_collect(next_chain_);
-      hash_collect(next_chain_, false);
+      hash_collect(next_chain_, ids_);
       next_kcollect_ = next_hcollect_ = ++next_chain_;
       progress = true;
     }
@@ -791,6 +810,7 @@ class TxCall {
         const size_t i = k.lo + k.live[j];
         accept_[i / 8] |= (uint8_t)(1u << (i % 8));
         if (status_) status_[i] = TX_OK;
+        if (ids_ && id_out_[i]) memcpy(id_out_[i], statement(i).txid, 32);   // (here alone: an ID leaves only beside a set bit)
       }
     }
     if (reasons_) reasons_out();
@@ -841,6 +861,8 @@ class TxCall {
   const bool reasons_;                                   // the device brings back reason bytes, and there is a status array to write them to
   const bool hashes_;                                    // the device hashes the transaction IDs (tapes instead of the host's second-pass hashing)
   const bool chains_;                                    // ... and forms the signature's challenge: a chunk's three stages are one chain on the device
+  const bool ids_;                                       // the IDs of accepted transactions go out (the device says so, and a piece has room for them)
+  std::vector<uint8_t*> id_out_;                         // ... per transaction of the call, where its 32 bytes go (NULL: its caller has no room)
   const bool timing_;
   const double t00_;
   const size_t n_slots_;                                 // key / signature stages in flight at once (2; 1 when two calls share the stage contexts)
@@ -863,7 +885,7 @@ class TxCall {
   size_t ids_upto_ = 0;
   bool tape_failed_ = false;
   std::vector<std::unique_ptr<SigStage>> sig_stages_;
-  size_t n_sig_stages_ = 0, sig_next_ = 0, hashed_upto_ = 0;
+  size_t n_sig_stages_ = 0, sig_next_ = 0, hashed_upto_ = 0, n_host_hashed_ = 0;
   bool all_sigs_made_ = false, quit_ = false, stager_failed_ = false;
   double t_keys_host_ = 0, t_sig_host_ = 0, t_stage_host_ = 0, t_vm_ = 0;
   // written by the staging thread BEFORE the flag that publishes them (key_rows_ / staged_ / n_sig_stages_), read by the

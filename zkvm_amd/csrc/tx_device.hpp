@@ -153,11 +153,15 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   // reasons: a format-2 call -- every stage also brings back one reason byte per row (tx_reason_kernels.hpp)
   // hashes: the format's flag ZKGPU_TXFORMAT_HASH_ON_DEVICE -- the transaction IDs of every chunk come from k_tx_hash
   // chains: ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the signature's challenge comes from k_tx_sig_rows
-  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false, bool hashes = false, bool chains = false)
-      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes), chains_(hashes && chains) {}
+  // ids: ZKGPU_TXFORMAT_RETURN_IDS -- the caller is handed the IDs of what it accepted; all it changes HERE is that a chained
+  // stage copies its IDs down as an unchained one does (one copy on the hashing stream, no launch)
+  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false, bool hashes = false, bool chains = false,
+                       bool ids = false)
+      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes), chains_(hashes && chains), ids_(ids) {}
   bool reasons() const override { return reasons_; }
   bool hashes() const override { return hashes_; }
   bool chains() const override { return chains_; }
+  bool ids() const override { return ids_; }
   zk::zkvm::TxHashTape* hash_tape(int slot) override { return &hash(slot).tape; }
   // one copy up, one launch, one copy of the IDs down, on the stage's own high-priority stream
   int hash_enqueue(int slot, const zk::zkvm::TxHashTape& tape) override {
@@ -387,7 +391,8 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
       hipLaunchKernelGGL(zk::k_tx_hash, dim3(h.n_lanes / 64), dim3(64), 0, hs.stream, view, h.n_lanes);
     }
     HIP_TRY(c, hipGetLastError());
-    if (!chains_) HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));   // (a chain reads them on the device)
+    // (a chain reads them on the device: they come down only for a caller that is handed them)
+    if (!chains_ || ids_) HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));
     hs.n_tx = h.n_tx;
     return ZKGPU_OK;
   }
@@ -400,7 +405,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     hs.n_tx = 0;
     if (n == 0) return ZKGPU_OK;
     HIP_TRY(c, hipStreamSynchronize(hs.stream));
-    if (txids && !chains_) memcpy(txids, hs.h_out, 32 * n);
+    if (txids && (!chains_ || ids_)) memcpy(txids, hs.h_out, 32 * n);
     { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_hashed_on_device += n; }
     return ZKGPU_OK;
   }
@@ -411,7 +416,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   zkgpu_verifier* v_;
   const int sb_;
   const size_t ab_;
-  const bool reasons_, hashes_, chains_;
+  const bool reasons_, hashes_, chains_, ids_;
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];
   std::string err_;

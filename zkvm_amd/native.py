@@ -214,6 +214,8 @@ HINT_APPLY, HINT_PRESENT, HINT_LATE = 0, 1, 2
 TXFORMAT_RECOLLECTED_V1, TXFORMAT_RECOLLECTED_V1_REASONS = 1, 2
 TXFORMAT_HASH_ON_DEVICE = 0x100        # a flag beside either format: the transaction IDs are hashed on the device
 TXFORMAT_SIGN_ON_DEVICE = 0x200        # a second flag, only beside the first: the signature's challenge is formed there too
+TXFORMAT_RETURN_IDS = 0x400            # a third, beside any of those: the status array of a transaction call is 33 bytes per
+                                       # transaction, the IDs of the accepted ones behind the status bytes
 TXSTATUS_ACCEPTED, TXSTATUS_REJECTED, TXSTATUS_OUTSIDE_SUBSET = 0, 1, 2
 TXSTATUS_TX_INVALID, TXSTATUS_PROOF_FORMAT, TXSTATUS_PROOF_POINT, TXSTATUS_PROOF_EQUATION, TXSTATUS_KEY, TXSTATUS_SIGNATURE = 16, 17, 18, 19, 20, 21
 

@@ -323,6 +323,7 @@ class BlockVerifier:
     TXFORMAT_RECOLLECTED_V1_REASONS = 2    # the same bytes and the same bitmap; the status bytes say WHY (tx_errors)
     TXFORMAT_HASH_ON_DEVICE = 0x100        # a flag or-ed to either: contract IDs, anchors and the transaction ID hashed on the device
     TXFORMAT_SIGN_ON_DEVICE = 0x200        # a flag or-ed to a format WITH the one above: the signature's challenge formed on the device
+    TXFORMAT_RETURN_IDS = 0x400            # a flag or-ed to any of those: the transaction ID of every accepted transaction comes back
     # status bytes (include/zkgpu.h: ZKGPU_TXSTATUS_*); 16 .. 21 only with TXFORMAT_RECOLLECTED_V1_REASONS, lowest code first
     TXSTATUS_ACCEPTED = 0
     TXSTATUS_REJECTED = 1                  # rejected, no reason known (format 1, or any error)
@@ -342,8 +343,25 @@ class BlockVerifier:
         DESIGN.md sec 4.5, an UNPINNED recollection of the ZkVM wire format (opt-in for exactly that reason);
         TXFORMAT_RECOLLECTED_V1_REASONS: the same, with a reason code in the status byte of every rejected transaction.
         Either may be or-ed with TXFORMAT_HASH_ON_DEVICE (same verdicts; most of the VM's hashing moves to the device), and
-        then also with TXFORMAT_SIGN_ON_DEVICE (same verdicts; the signature's challenge is formed on the device as well)."""
+        then also with TXFORMAT_SIGN_ON_DEVICE (same verdicts; the signature's challenge is formed on the device as well).
+        Any of those may be or-ed with TXFORMAT_RETURN_IDS: same verdicts, and verify_txs / wait_txs called with ids=True also
+        return the 32-byte transaction ID of every accepted transaction.  (The library then writes 33 bytes per transaction
+        into a call's status array; the arrays here are sized by what THIS method was given last, so set the format through it.)"""
         self._check(self.lib.zkgpu_verifier_set_tx_format(self.h, fmt))
+        self._tx_return_ids = bool(fmt & self.TXFORMAT_RETURN_IDS)
+
+    _tx_return_ids = False
+
+    def _tx_result(self, bm, st, batch: int, has_ids: bool, ids: bool):
+        """(bitmap, status bytes) of a transaction call, and with ids=True the call's ID area: 32 bytes per transaction, the ID
+        beside status 0 and zeros everywhere else"""
+        out = (bm.raw[: (batch + 7) // 8], st.raw[:batch])
+        if not ids:
+            return out
+        if not has_ids:
+            raise ValueError("ids=True needs a format with TXFORMAT_RETURN_IDS (set_tx_format)")
+        area = st.raw[batch: 33 * batch]
+        return out + ([area[32 * i: 32 * i + 32] for i in range(batch)],)
 
     def set_tx_chunk(self, transactions: int) -> None:
         """zkgpu_verifier_set_tx_chunk: transactions per chunk of the staged pipeline inside verify_txs (0 = automatic)"""
@@ -353,25 +371,29 @@ class BlockVerifier:
         """zkgpu_verifier_set_tx_statements_kept: how many transactions' VM results (700 B each) the verifier keeps between calls"""
         self._check(self.lib.zkgpu_verifier_set_tx_statements_kept(self.h, transactions))
 
-    def verify_txs(self, txs: Sequence[bytes], host_threads: int = 0):
+    def verify_txs(self, txs: Sequence[bytes], host_threads: int = 0, ids: bool = False):
         """zkgpu_tx_verify_batch: serialized ZkVM transactions (payment subset) -> (accept bitmap, status bytes:
         0 accepted, 1 rejected, 2 outside the subset).  Inert until set_tx_format names a format.  With
         TXFORMAT_RECOLLECTED_V1_REASONS the bitmap is the same and a rejected transaction reads one of TXSTATUS_TX_INVALID ..
         TXSTATUS_SIGNATURE instead of 1 (the lowest code that applies; 1 for every transaction after an error): tx_errors(status)
-        turns the bytes into upstream's error variants."""
-        return self.verify_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads)
+        turns the bytes into upstream's error variants.  ids=True (only under a format with TXFORMAT_RETURN_IDS): -> (bitmap,
+        status bytes, ids) with ids[i] the transaction ID beside status 0 and 32 zero bytes beside everything else."""
+        return self.verify_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads, ids=ids)
 
-    def verify_txs_packed(self, blob: bytes, lengths, host_threads: int = 0):
+    def verify_txs_packed(self, blob: bytes, lengths, host_threads: int = 0, ids: bool = False):
         """the same over one buffer of concatenated transactions and their lengths (same status bytes, reasons included)"""
         batch = len(lengths)
+        has_ids = self._tx_return_ids
+        if ids and not has_ids:
+            raise ValueError("ids=True needs a format with TXFORMAT_RETURN_IDS (set_tx_format)")
         offs = np.zeros(batch + 1, dtype=np.uint64)
         np.cumsum(lengths if isinstance(lengths, np.ndarray) and lengths.dtype == np.uint64 else np.asarray(lengths, dtype=np.uint64), out=offs[1:])
         if int(offs[-1]) != len(blob):
             raise ValueError("the lengths add up to %d bytes, the buffer holds %d" % (int(offs[-1]), len(blob)))
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
-        st = C.create_string_buffer(max(batch, 1))
+        st = C.create_string_buffer(max((33 if has_ids else 1) * batch, 1))      # (with the flag the library writes 33 bytes per transaction)
         self._check(self.lib.zkgpu_tx_verify_batch(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, bm, st))
-        return bm.raw[: (batch + 7) // 8], st.raw[:batch]
+        return self._tx_result(bm, st, batch, has_ids, ids)
 
     def submit_txs_packed(self, blob: bytes, lengths, host_threads: int = 0) -> int:
         """zkgpu_tx_verify_submit: the call is queued (calls in flight are merged into rounds); -> call id for wait_txs.  The
@@ -383,23 +405,27 @@ class BlockVerifier:
             raise ValueError("the lengths add up to %d bytes, the buffer holds %d" % (int(offs[-1]), len(blob)))
         cid = C.c_uint64(0)
         self._check(self.lib.zkgpu_tx_verify_submit(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, C.byref(cid)))
-        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch)
+        # (the layout of the call's status array is the one in force when it was queued: remembered with the call)
+        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch, self._tx_return_ids)
         return int(cid.value)
 
     def submit_txs(self, txs: Sequence[bytes], host_threads: int = 0) -> int:
         return self.submit_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads)
 
-    def wait_txs(self, call_id: int):
+    def wait_txs(self, call_id: int, ids: bool = False):
         """zkgpu_tx_verify_wait -> (accept bitmap, status bytes) of that call; the status bytes are those verify_txs gives for
-        the same transactions -- with TXFORMAT_RECOLLECTED_V1_REASONS the same reason codes, whatever round the call was merged into"""
-        _, _, batch = self.__dict__["_tx_calls"][call_id]
+        the same transactions -- with TXFORMAT_RECOLLECTED_V1_REASONS the same reason codes, whatever round the call was merged into.
+        ids=True (the call was submitted under a format with TXFORMAT_RETURN_IDS): -> (bitmap, status bytes, ids) as verify_txs"""
+        _, _, batch, has_ids = self.__dict__["_tx_calls"][call_id]
+        if ids and not has_ids:
+            raise ValueError("ids=True: the call was not submitted under a format with TXFORMAT_RETURN_IDS")
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
-        st = C.create_string_buffer(max(batch, 1))
+        st = C.create_string_buffer(max((33 if has_ids else 1) * batch, 1))
         try:
             self._check(self.lib.zkgpu_tx_verify_wait(self.h, call_id, bm, st))
         finally:
             del self.__dict__["_tx_calls"][call_id]
-        return bm.raw[: (batch + 7) // 8], st.raw[:batch]
+        return self._tx_result(bm, st, batch, has_ids, ids)
 
     def tx_stats(self):
         """zkgpu_tx_verify_stats -> (rounds the engine has run, calls they held in all)"""
