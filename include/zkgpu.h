@@ -151,7 +151,19 @@ int zkgpu_msm_ps_batch(zkgpu_ctx *ctx, const zkgpu_pointset *ps, size_t batch, c
  * statement (commitment blindings and the TranscriptRng's external randomness derive from it).
  * Out: commitments batch x 64 (n_in + n_out) B (quantity, flavor per value); proofs batch x
  * proof_stride B, *proof_len bytes of each used (R1CSProof wire format, 1 + 32 (16 + 2k)).
- * (Replaces: spacesuit::cloak + bulletproofs r1cs::Prover::prove per transaction.) */
+ * (Replaces: spacesuit::cloak + bulletproofs r1cs::Prover::prove per transaction.)
+ *
+ * seeds == NULL (recommended; also in zkgpu_r1cs_prove_batch): the library draws the call's randomness itself, as
+ * upstream's r1cs::Prover does with thread_rng().  It takes ONE 32-byte call seed from getrandom(2) per call; statement i
+ * of the call gets seed_i = the first 32 bytes of SHAKE256(call_seed || "statement" || LE64(i)), i being the statement's
+ * position in the CALL however the library cuts the call into slices, and the call then behaves exactly as the same call
+ * with seeds = seed_0 || seed_1 || ...: the same commitments and proofs, byte for byte, whatever the slicing, host_threads
+ * or prover mode.  The derivations run on the device (one kernel, two Keccak permutations per derived value); the call
+ * seed is wiped from host memory when the call returns.  If the OS gives no randomness the call returns ZKGPU_EINVAL
+ * ("getrandom failed"), commitments and proofs are zeroed, *proof_len is 0 and nothing has been launched.
+ * A caller who brings seeds owns this hazard: EVERYTHING secret in a proof -- the Pedersen blinding of every commitment
+ * and the TranscriptRng's external randomness -- is a function of the statement's seed alone.  A seed used for two
+ * statements with different values publishes V - V' = (v - v') B, from which 64-bit quantities are found by search. */
 int zkgpu_cloak_prove_batch(zkgpu_ctx *ctx, const zkgpu_pointset *ps, size_t gens_capacity, size_t batch,
                             uint32_t n_in, uint32_t n_out, const uint64_t *quantities, const uint8_t *flavors,
                             const uint8_t *seeds, int host_threads, uint8_t *commitments, uint8_t *proofs,
@@ -315,7 +327,9 @@ int zkgpu_r1cs_verify_mixed_submit(zkgpu_ctx *ctx, const zkgpu_pointset *ps, zkg
  *               assignment is given; NULL: every assignment is given.  Defined multipliers are evaluated in index
  *               order (second-phase ones after the challenges are drawn);
  *   given       batch x n_given x 64: (left, right) of the given multipliers, in index order;
- *   seeds       batch x 32: external randomness of the TranscriptRng (and the blindings when derived).
+ *   seeds       batch x 32: external randomness of the TranscriptRng (and the blindings when derived); or NULL
+ *               (recommended): drawn by the library as described at zkgpu_cloak_prove_batch.  NULL seeds with
+ *               blindings given: only the TranscriptRng's randomness is drawn; with blindings NULL: the blindings too.
  * Out: commitments batch x 32 m, proofs batch x proof_stride (*proof_len bytes of each used).  The provers run in
  * lockstep on host_threads threads; every phase of the whole batch is one multiscalar-multiplication call on the
  * tables of `ps` = [B, B_blinding, G.., H..]. */

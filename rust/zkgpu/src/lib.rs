@@ -623,6 +623,54 @@ impl GpuVerifier {
         })?;
         Ok(out)
     }
+
+    /// `spacesuit::cloak` + `r1cs::Prover::prove` for a batch of statements of ONE shape: `quantities` and 32-byte `flavors`
+    /// per value (inputs first).  Returns one `(commitments, proof)` per statement: 64 bytes per value, `R1CSProof` bytes.
+    ///
+    /// `seeds`: `None` is the documented default -- the library draws the call's randomness itself, one seed from the
+    /// operating system per call, as upstream's `Prover` does with `thread_rng()`.  `Some(s)`: 32 bytes per statement, for
+    /// reproducible proofs in tests.  EVERYTHING secret in a proof (the blinding of every commitment, the TranscriptRng's
+    /// external randomness) is a function of the statement's seed alone: a seed used for two statements with different
+    /// values publishes `V - V' = (v - v') B`, from which 64-bit quantities are found by search.
+    pub fn prove_cloak(&self, n_in: u32, n_out: u32, quantities: &[u64], flavors: &[u8], seeds: Option<&[u8]>, host_threads: i32) -> Result<Vec<(Vec<u8>, Vec<u8>)>, Error> {
+        let nv = n_in as usize + n_out as usize;
+        if nv == 0 || quantities.len() % nv != 0 || flavors.len() != 32 * quantities.len() {
+            return Err(Error::InvalidArgument("prove_cloak: one quantity and 32 flavor bytes per value".into()));
+        }
+        let batch = quantities.len() / nv;
+        if let Some(s) = seeds {
+            if s.len() != 32 * batch {
+                return Err(Error::InvalidArgument("seeds: 32 bytes per statement".into()));
+            }
+        }
+        let stride = 1 + 32 * (16 + 2 * 16);
+        let mut com = vec![0u8; 64 * nv * batch];
+        let mut proofs = vec![0u8; stride * batch];
+        let mut proof_len = 0usize;
+        let ctx = self.ctx;
+        check(
+            unsafe {
+                sys::zkgpu_cloak_prove_batch(
+                    ctx,
+                    self.gens.ps,
+                    self.gens.capacity,
+                    batch,
+                    n_in,
+                    n_out,
+                    quantities.as_ptr(),
+                    flavors.as_ptr(),
+                    seeds.map_or(ptr::null(), |s| s.as_ptr()),
+                    host_threads as c_int,
+                    com.as_mut_ptr(),
+                    proofs.as_mut_ptr(),
+                    stride,
+                    &mut proof_len,
+                )
+            },
+            move || text(unsafe { sys::zkgpu_last_error(ctx) }),
+        )?;
+        Ok((0..batch).map(|i| (com[64 * nv * i..64 * nv * (i + 1)].to_vec(), proofs[stride * i..stride * i + proof_len].to_vec())).collect())
+    }
 }
 
 /// A constraint system compiled for the device (`zkgpu_r1cs_plan_create`): what `verify_r1cs_mixed` checks statements

@@ -836,6 +836,23 @@ extern "C" void zkhost_msm_route(const int64_t* in, uint64_t* out) {
 #include "draw_r.hpp"
 extern "C" void zkhost_draw_r(const uint8_t seed[32], uint64_t first, size_t count, uint8_t* out) { draw_r_bytes(seed, first, count, out); }
 
+// prover randomness the library draws itself (prover_draw.hpp): statements first .. first + count - 1 of a call -- the host
+// side of the function k_pv_draw runs on the device.  table: m + 1 records of 24 bytes, the tag (NUL-padded to 16) and its
+// index as LE64; the first m are blindings (64 bytes reduced mod l), the last is the 32-byte rng seed.  out: count x 32 (m + 1).
+// -> 0, or -1 for a tag that is empty or longer than ten bytes
+#include "prover_draw.hpp"
+extern "C" int zkhost_prover_draw(const uint8_t call_seed[32], uint64_t first, size_t count, const uint8_t* table, size_t m, uint8_t* out) {
+  std::vector<uint32_t> t((m + 1) * PV_DRAW_ENTRY_WORDS);
+  for (size_t d = 0; d <= m; ++d) {
+    const uint8_t* rec = table + 24 * d;
+    uint64_t index = 0;
+    for (int k = 0; k < 8; ++k) index |= (uint64_t)rec[16 + k] << (8 * k);
+    if (!pv_draw_entry((const char*)rec, strnlen((const char*)rec, 16), index, &t[PV_DRAW_ENTRY_WORDS * d])) return -1;
+  }
+  pv_draw_bytes(call_seed, first, count, t.data(), m, out);
+  return 0;
+}
+
 #include "comm_frame.hpp"
 extern "C" size_t zkhost_comm_slot_bytes(const uint64_t* cuts, int world) { return commframe::slot_bytes(cuts, world); }
 extern "C" void zkhost_comm_pack(uint8_t* out, size_t slot, const uint64_t* cuts, int rank, const uint8_t* local_bitmap, int local_status) {

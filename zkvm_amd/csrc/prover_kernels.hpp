@@ -2,6 +2,7 @@
 // transcript, all threads on the vectors.
 #pragma once
 #include "prover_dev.hpp"
+#include "prover_draw.hpp"     // (k_pv_draw: prover randomness for calls handed over without seeds)
 
 namespace zk {
 

@@ -169,7 +169,7 @@ struct zkgpu_ctx {
          RT_TABLES_SMALL, RT_TABLES_BUCKET, RT_HOST_COUNTERS };
   uint64_t msm_routes[RT_HOST_COUNTERS] = {};
   DecodeRoutes decode_routes; uint8_t r_seed[32] = {0};  // DECODE launches and points by form (kernels.hpp; zkgpu_debug_read "decode_routes") | the seed of the last draw into r_draw or a lane's coal_r ("r_seed"); zero when the last batch brought its own r
-  uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0;   // | root context of a verifier: transaction IDs / signature challenges its device produced (tx_device.hpp: GpuTxDevice)
+  uint8_t prover_seed[32] = {0}; uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0;   // hooks enabled only: the seed the last prover call on this context drew for itself (prover_seed.hpp; "prover_seed") | root context of a verifier: transaction IDs / signature challenges its device produced (tx_device.hpp: GpuTxDevice)
 };
 
 namespace {
@@ -2022,7 +2022,7 @@ int ipa_on_device(zkgpu_ctx* c, const zkgpu_pointset* ps, std::vector<std::uniqu
 }
 
 // ---- the device prover ------------------------------------------------------------------------------------
-// (host_parallel: host_pool.hpp)
+#include "prover_seed.hpp"      // (host_parallel: host_pool.hpp; a call without seeds: PvCallSeed, pv_draw_launch)
 #ifndef PV_RNG_LANES_FROM
 #define PV_RNG_LANES_FROM ((size_t)1 << 40)      // (never, until the A/B of round 6 says otherwise)
 #endif
@@ -2068,11 +2068,11 @@ bool pv_rng_lanes_pay(const zkgpu_ctx* c, size_t batch_of_this_slice) {
 
 // Proves `batch` statements of one described system.  Host: the constant tables (once per call), the inputs' upload,
 // a queue of kernels; device: everything else.  values / blindings: batch x m x 32 bytes (any 256-bit values, reduced
-// on the device), given: batch x n_given x 64, rng_seeds: batch x 32.
+// on the device), given: batch x n_given x 64, rng_seeds: batch x 32.  call_seed (a call without seeds, prover_draw.hpp): rng_seeds is NULL and blindings may be -- k_pv_draw writes those regions of the input area from the call's seed and the positions first + 0 .. batch - 1 in the CALL; cloak_tags: which tag table
 int prove_device(zkgpu_ctx* c, const zkgpu_pointset* ps, const PvHostPlan& hp, size_t batch, const uint8_t* values, const uint8_t* blindings,
-                 const uint8_t* given, const uint8_t* rng_seeds, uint8_t* commitments, uint8_t* proofs, size_t proof_stride, size_t* proof_len) {
+                 const uint8_t* given, const uint8_t* rng_seeds, uint8_t* commitments, uint8_t* proofs, size_t proof_stride, size_t* proof_len, const uint8_t* call_seed = nullptr, uint64_t first = 0, bool cloak_tags = false) {
   const PvShape& sh = hp.sh;
-  if (sh.proof_len > proof_stride) return ZKGPU_EINVAL;
+  if (sh.proof_len > proof_stride || (call_seed ? rng_seeds != nullptr : !rng_seeds || (sh.m && !blindings))) return ZKGPU_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   TRY(refuse_if_pending(c));
   DeviceGuard g(c->device);
@@ -2088,7 +2088,7 @@ int prove_device(zkgpu_ctx* c, const zkgpu_pointset* ps, const PvHostPlan& hp, s
                o_to = put(hp.tgt_off), o_tinf = put(hp.term_info), o_pq = put(hp.prod_qm), o_pc = put(hp.prod_coef);
   std::vector<uint32_t> labels((hp.chal_labels.size() + 3) / 4, 0);
   memcpy(labels.data(), hp.chal_labels.data(), hp.chal_labels.size());
-  const size_t o_lab = put(labels);
+  const size_t o_lab = put(labels), o_dr = call_seed ? put(cloak_tags ? pv_draw_table_cloak(sh.m / 2) : pv_draw_table_desc(sh.m)) : 0;
   (void)put({sh.m, sh.n1, sh.n, sh.pn, sh.gens_capacity});   // part of the key the cached scaffolding goes by
   if (blob != c->pv_plan_host) {        // the same statement as in the last call: the tables are already there
     TRY(upload(c, c->pv_plan, blob.data(), blob.size() * 4));
@@ -2107,10 +2107,10 @@ int prove_device(zkgpu_ctx* c, const zkgpu_pointset* ps, const PvHostPlan& hp, s
   char* in = (char*)c->pv_in.p;
   if (b_val) {
     HIP_TRY(c, hipMemcpyAsync(in, values, b_val, hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemcpyAsync(in + b_val, blindings, b_val, hipMemcpyHostToDevice, s));
+    if (blindings) HIP_TRY(c, hipMemcpyAsync(in + b_val, blindings, b_val, hipMemcpyHostToDevice, s));
   }
   if (b_giv) HIP_TRY(c, hipMemcpyAsync(in + 2 * b_val, given, b_giv, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(in + 2 * b_val + b_giv, rng_seeds, b_seed, hipMemcpyHostToDevice, s));
+  if (call_seed) TRY(pv_draw_launch(c, s, call_seed, first, batch, sh.m, !blindings, base + o_dr, in + b_val, in + 2 * b_val + b_giv)); else HIP_TRY(c, hipMemcpyAsync(in + 2 * b_val + b_giv, rng_seeds, b_seed, hipMemcpyHostToDevice, s));
   // rows and their scaffolding (offsets and generator indices: kept on the device from call to call while statement and
   // batch size stay the same)
   const size_t cap = sh.gens_capacity;
@@ -2370,7 +2370,7 @@ int run_sliced(zkgpu_ctx* c, size_t batch, int host_threads, const std::function
 int cloak_prove_whole(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t gens_capacity, size_t batch, uint32_t n_in,
                       uint32_t n_out, const uint64_t* quantities, const uint8_t* flavors, const uint8_t* seeds,
                       int host_threads, uint8_t* commitments, uint8_t* proofs, size_t proof_stride,
-                      size_t* proof_len) {
+                      size_t* proof_len, const uint8_t* call_seed = nullptr, uint64_t first = 0) {
   const size_t nv = (size_t)n_in + n_out;
   if (c->prover_mode == 1)
     return prove_lockstep(c, ps, batch, host_threads, [&](size_t i) {
@@ -2387,27 +2387,27 @@ int cloak_prove_whole(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t gens_capaci
   } catch (const std::exception& e) { c->last_error = e.what(); return ZKGPU_EINVAL; }
   const double t1 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
   const size_t m = 2 * nv;
-  std::vector<uint8_t> vals(batch * m * 32), bl(batch * m * 32), giv(batch * (size_t)hp.sh.n_given * 64), rs(batch * 32);
+  std::vector<uint8_t> vals(batch * m * 32), bl(call_seed ? 0 : batch * m * 32), giv(batch * (size_t)hp.sh.n_given * 64), rs(call_seed ? 0 : batch * 32);   // (call_seed, a call without seeds: blinding factors and rng seeds are drawn on the device, prove_device)
   std::atomic<bool> bad{false};
   host_parallel(batch, host_threads, [&](size_t i) {
-    const uint8_t* seed = seeds + 32 * i;
+    const uint8_t* seed = call_seed ? nullptr : seeds + 32 * i;
     for (size_t j = 0; j < nv; ++j) {
       Scalar::from_u64(quantities[nv * i + j]).to_bytes(&vals[(i * m + 2 * j) * 32]);
       memcpy(&vals[(i * m + 2 * j + 1) * 32], flavors + 32 * (nv * i + j), 32);
-      R1csProver::derive_scalar(seed, "q_blinding", j).to_bytes(&bl[(i * m + 2 * j) * 32]);
-      R1csProver::derive_scalar(seed, "f_blinding", j).to_bytes(&bl[(i * m + 2 * j + 1) * 32]);
+      if (seed) R1csProver::derive_scalar(seed, "q_blinding", j).to_bytes(&bl[(i * m + 2 * j) * 32]);
+      if (seed) R1csProver::derive_scalar(seed, "f_blinding", j).to_bytes(&bl[(i * m + 2 * j + 1) * 32]);
     }
     std::vector<uint32_t> gw;
     pv_cloak_given(n_in, n_out, quantities + nv * i, flavors + 32 * nv * i, gw);
     if (gw.size() != 16 * (size_t)hp.sh.n_given) { bad = true; return; }
     memcpy(&giv[i * (size_t)hp.sh.n_given * 64], gw.data(), gw.size() * 4);
-    R1csProver::derive(seed, "rng", 0, &rs[32 * i], 32);
+    if (seed) R1csProver::derive(seed, "rng", 0, &rs[32 * i], 32);
   });
   if (bad) { c->last_error = "prover: the cloak witness does not fit the traced gadget"; return ZKGPU_EINVAL; }
   if (getenv("ZKGPU_PROVER_TIMING"))
     fprintf(stderr, "device prover: tracing the gadget + tables %.1f ms, blinding factors + witness queues %.1f ms\n", (t1 - t0) * 1e3,
             (std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t1) * 1e3);
-  return prove_device(c, ps, hp, batch, vals.data(), bl.data(), giv.data(), rs.data(), commitments, proofs, proof_stride, proof_len);
+  return prove_device(c, ps, hp, batch, vals.data(), call_seed ? nullptr : bl.data(), giv.data(), call_seed ? nullptr : rs.data(), commitments, proofs, proof_stride, proof_len, call_seed, first, true);
 }
 
 // Proves `batch` statements of ONE described constraint system (BASELINE.json configs[4]: "R1CS proving for a
@@ -2415,7 +2415,7 @@ int cloak_prove_whole(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t gens_capaci
 int r1cs_prove_whole(zkgpu_ctx* c, const zkgpu_pointset* ps, const zkgpu_r1cs_desc* d, const uint32_t* mult_def,
                      size_t gens_capacity, size_t batch, const uint8_t* values, const uint8_t* blindings,
                      const uint8_t* given, size_t n_given, const uint8_t* seeds, int host_threads,
-                     uint8_t* commitments, uint8_t* proofs, size_t proof_stride, size_t* proof_len) {
+                     uint8_t* commitments, uint8_t* proofs, size_t proof_stride, size_t* proof_len, const uint8_t* call_seed = nullptr, uint64_t first = 0) {
   R1csDesc desc;
   if (!desc_from_c(c, d, desc)) return ZKGPU_EINVAL;
   try { (void)plan_from_desc(desc); } catch (const std::exception& e) { c->last_error = e.what(); return ZKGPU_EINVAL; }
@@ -2443,13 +2443,13 @@ int r1cs_prove_whole(zkgpu_ctx* c, const zkgpu_pointset* ps, const zkgpu_r1cs_de
   PvHostPlan hp;
   try { hp = pv_build(desc, md, gens_capacity); } catch (const std::exception& e) { c->last_error = e.what(); return ZKGPU_EINVAL; }
   if (hp.sh.n_given != n_given) { c->last_error = "prover: n_given does not match the multipliers without defining constraints"; return ZKGPU_EINVAL; }
-  std::vector<uint8_t> bl, rs(batch * 32);
-  if (!blindings) bl.resize(batch * m * 32);
-  host_parallel(batch, host_threads, [&](size_t i) {
+  std::vector<uint8_t> bl, rs(call_seed ? 0 : batch * 32);      // (call_seed, a call without seeds: the rng seeds, and the blinding factors nobody gave, are drawn on the device)
+  if (!blindings && !call_seed) bl.resize(batch * m * 32);
+  host_parallel(call_seed ? 0 : batch, host_threads, [&](size_t i) {
     if (!blindings) for (size_t j = 0; j < m; ++j) R1csProver::derive_scalar(seeds + 32 * i, "blinding", j).to_bytes(&bl[(i * m + j) * 32]);
     R1csProver::derive(seeds + 32 * i, "rng", 0, &rs[32 * i], 32);
   });
-  return prove_device(c, ps, hp, batch, values, blindings ? blindings : bl.data(), given, rs.data(), commitments, proofs, proof_stride, proof_len);
+  return prove_device(c, ps, hp, batch, values, blindings || call_seed ? blindings : bl.data(), given, call_seed ? nullptr : rs.data(), commitments, proofs, proof_stride, proof_len, call_seed, first, false);
 }
 }  // namespace
 
@@ -2460,17 +2460,17 @@ int zkgpu_cloak_prove_batch(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t gens_
   if (!c || !ps || !commitments || !proofs || !proof_len) return ZKGPU_EINVAL;
   *proof_len = 0;
   if (batch == 0) return ZKGPU_OK;
-  if (!quantities || !flavors || !seeds || ps->n < 2 + 2 * gens_capacity || n_in + n_out == 0) return ZKGPU_EINVAL;
+  if (!quantities || !flavors || ps->n < 2 + 2 * gens_capacity || n_in + n_out == 0) return ZKGPU_EINVAL;      // (seeds NULL: drawn, PvCallSeed)
   if (!ps->table) { c->last_error = "zkgpu_cloak_prove_batch needs zkgpu_pointset_build_tables first"; return ZKGPU_EINVAL; }
   const size_t nv = (size_t)n_in + n_out;
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  std::lock_guard<std::recursive_mutex> lk(c->mu); PvCallSeed cs; std::atomic<size_t> len_out{0};
+  if (!cs.begin(c, &seeds, batch)) { memset(commitments, 0, 64 * nv * batch); memset(proofs, 0, proof_stride * batch); return ZKGPU_EINVAL; }
   if (c->prover_mode == 1)
-    return cloak_prove_whole(c, ps, gens_capacity, batch, n_in, n_out, quantities, flavors, seeds, host_threads, commitments, proofs, proof_stride, proof_len);
-  std::atomic<size_t> len_out{0};
+    return cs.closed(cloak_prove_whole(c, ps, gens_capacity, batch, n_in, n_out, quantities, flavors, seeds, host_threads, commitments, proofs, proof_stride, proof_len), commitments, 64 * nv * batch, proofs, proof_stride * batch, proof_len);
   const int rc = run_sliced(c, batch, host_threads, [&](zkgpu_ctx* t, size_t lo, size_t hi, int ht) {
     size_t pl = 0;
-    const int r = cloak_prove_whole(t, ps, gens_capacity, hi - lo, n_in, n_out, quantities + nv * lo, flavors + 32 * nv * lo, seeds + 32 * lo, ht,
-                                    commitments + 64 * nv * lo, proofs + proof_stride * lo, proof_stride, &pl);
+    const int r = cloak_prove_whole(t, ps, gens_capacity, hi - lo, n_in, n_out, quantities + nv * lo, flavors + 32 * nv * lo, seeds ? seeds + 32 * lo : nullptr, ht,
+                                    commitments + 64 * nv * lo, proofs + proof_stride * lo, proof_stride, &pl, cs.for_device(c), lo);      // (lo: the slice's first position in the CALL)
     if (r == ZKGPU_OK) len_out = pl;
     return r;
   });
@@ -2486,18 +2486,18 @@ int zkgpu_r1cs_prove_batch(zkgpu_ctx* c, const zkgpu_pointset* ps, const zkgpu_r
   if (!c || !ps || !d || !commitments || !proofs || !proof_len) return ZKGPU_EINVAL;
   *proof_len = 0;
   if (batch == 0) return ZKGPU_OK;
-  if (!seeds || ps->n < 2 + 2 * gens_capacity || (d->n_commitments && !values) || (n_given && !given)) return ZKGPU_EINVAL;
+  if (ps->n < 2 + 2 * gens_capacity || (d->n_commitments && !values) || (n_given && !given)) return ZKGPU_EINVAL;      // (seeds NULL: drawn, PvCallSeed)
   if (!ps->table) { c->last_error = "zkgpu_r1cs_prove_batch needs zkgpu_pointset_build_tables first"; return ZKGPU_EINVAL; }
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  if (c->prover_mode == 1)
-    return r1cs_prove_whole(c, ps, d, mult_def, gens_capacity, batch, values, blindings, given, n_given, seeds, host_threads, commitments, proofs, proof_stride, proof_len);
+  std::lock_guard<std::recursive_mutex> lk(c->mu); PvCallSeed cs; std::atomic<size_t> len_out{0};
   const size_t m = d->n_commitments;
-  std::atomic<size_t> len_out{0};
+  if (!cs.begin(c, &seeds, batch)) { memset(commitments, 0, 32 * m * batch); memset(proofs, 0, proof_stride * batch); return ZKGPU_EINVAL; }
+  if (c->prover_mode == 1)
+    return cs.closed(r1cs_prove_whole(c, ps, d, mult_def, gens_capacity, batch, values, blindings, given, n_given, seeds, host_threads, commitments, proofs, proof_stride, proof_len), commitments, 32 * m * batch, proofs, proof_stride * batch, proof_len);
   const int rc = run_sliced(c, batch, host_threads, [&](zkgpu_ctx* t, size_t lo, size_t hi, int ht) {
     size_t pl = 0;
     const int r = r1cs_prove_whole(t, ps, d, mult_def, gens_capacity, hi - lo, values ? values + 32 * m * lo : nullptr,
                                    blindings ? blindings + 32 * m * lo : nullptr, given ? given + 64 * n_given * lo : nullptr, n_given,
-                                   seeds + 32 * lo, ht, commitments + 32 * m * lo, proofs + proof_stride * lo, proof_stride, &pl);
+                                   seeds ? seeds + 32 * lo : nullptr, ht, commitments + 32 * m * lo, proofs + proof_stride * lo, proof_stride, &pl, cs.for_device(c), lo);
     if (r == ZKGPU_OK) len_out = pl;
     return r;
   });
@@ -3714,6 +3714,12 @@ long long zkgpu_debug_read(zkgpu_ctx* c, const char* what, void* out, size_t byt
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     memcpy(out, c->r_seed, sizeof(c->r_seed));
     return (long long)sizeof(c->r_seed);
+  }
+  if (strcmp(what, "prover_seed") == 0) {              // the seed the last prover call on this context drew for itself (prover_draw.hpp): kept
+    if (bytes < sizeof(c->prover_seed)) return ZKGPU_EINVAL;   // only with the hooks enabled at load; zero: the call brought its own seeds
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    memcpy(out, c->prover_seed, sizeof(c->prover_seed));
+    return (long long)sizeof(c->prover_seed);
   }
   if (strcmp(what, "msm_routes") == 0) {               // which forms of the multiscalar multiplication ran (include/zkgpu_hooks.h): the host's
     uint64_t rec[zkgpu_ctx::RT_HOST_COUNTERS + 2] = {};        // counters, then the fat and heavy bins of the last bucket-pipeline run

@@ -558,6 +558,11 @@ class Context:
             raise ZkGpuError(n, "zkgpu_debug_read(%s)" % what)
         return buf.raw[:n]
 
+    def prover_seed(self) -> bytes:
+        """The 32-byte seed the last prover call on this context drew for itself (seeds=None); all zero after a call that
+        brought its own seeds.  Kept by the library only when the hooks were enabled before it was loaded."""
+        return self.debug_read("prover_seed", 32)
+
     def last_window_bits(self) -> int:
         return int(self.lib.zkgpu_last_window_bits(self.h))
 

@@ -100,12 +100,13 @@ class Prover:
         self.bp_gens = bp_gens
         self.host_threads = host_threads
 
-    def prove_packed(self, n_in: int, n_out: int, batch: int, quantities, flavors: bytes, seeds: bytes):
+    def prove_packed(self, n_in: int, n_out: int, batch: int, quantities, flavors: bytes, seeds: Optional[bytes] = None):
         """zkgpu_cloak_prove_batch on contiguous inputs (quantities: ctypes array of batch x (n_in + n_out) u64; flavors 32 B
-        per value; seeds 32 B per statement) -> (commitments, proofs with stride 1569, proof_len); no per-proof Python work"""
+        per value; seeds: None -- the library draws the call's randomness itself, the recommended form -- or 32 B per
+        statement, never used for two statements) -> (commitments, proofs with stride 1569, proof_len); no per-proof Python work"""
         nv = n_in + n_out
-        if len(flavors) != 32 * nv * batch or len(seeds) != 32 * batch or len(quantities) != nv * batch:
-            raise ValueError("quantities: one per value; flavors: 32 bytes per value; seeds: 32 bytes per statement")
+        if len(flavors) != 32 * nv * batch or (seeds is not None and len(seeds) != 32 * batch) or len(quantities) != nv * batch:
+            raise ValueError("quantities: one per value; flavors: 32 bytes per value; seeds: 32 bytes per statement, or None")
         import time
         com = C.create_string_buffer(max(64 * nv * batch, 1))
         stride = 1 + 32 * (16 + 2 * 16)
@@ -119,8 +120,10 @@ class Prover:
         return com, proofs, plen.value
 
     def prove(self, n_in: int, n_out: int, quantities: Sequence[Sequence[int]], flavors: Sequence[Sequence[bytes]],
-              seeds: Sequence[bytes]) -> List[CloakTx]:
-        batch, nv = len(seeds), n_in + n_out
+              seeds: Optional[Sequence[bytes]] = None) -> List[CloakTx]:
+        """seeds: None -- the library draws the call's randomness itself (the batch is then len(quantities)) -- or one 32-byte
+        seed per statement, never used for two statements"""
+        batch, nv = len(quantities) if seeds is None else len(seeds), n_in + n_out
         assert len(quantities) == batch and len(flavors) == batch
         qa = (C.c_uint64 * max(batch * nv, 1))(*[q for row in quantities for q in row])
         fl = b"".join(f for row in flavors for f in row)
@@ -129,7 +132,7 @@ class Prover:
         proofs = C.create_string_buffer(max(stride * batch, 1))
         plen = C.c_size_t(0)
         import time
-        sd = b"".join(seeds)
+        sd = None if seeds is None else b"".join(seeds)
         t0 = time.perf_counter()
         rc = self.ctx.lib.zkgpu_cloak_prove_batch(
             self.ctx.h, self.bp_gens.points.h, self.bp_gens.gens_capacity, batch, n_in, n_out, qa, fl, sd,
@@ -460,23 +463,28 @@ class R1csProver:
         self.ctx, self.bp_gens, self.desc, self.host_threads = ctx, bp_gens, desc, host_threads
         self.mult_def = (C.c_uint32 * max(len(mult_def), 1))(*mult_def) if mult_def is not None else None
 
-    def prove(self, values: Sequence[Sequence[int]], given: Sequence[Sequence[tuple]], seeds: Sequence[bytes]):
+    def prove(self, values: Sequence[Sequence[int]], given: Sequence[Sequence[tuple]], seeds: Optional[Sequence[bytes]] = None,
+              blindings: Optional[Sequence[Sequence[int]]] = None):
         """values: per statement the m committed scalars; given: per statement the (left, right) assignments of the
-        multipliers not defined by constraints.  -> (commitments per statement, proofs per statement)"""
-        batch, m = len(seeds), self.desc.m
+        multipliers not defined by constraints; seeds: None -- the library draws the call's randomness itself (the batch is
+        then len(values)) -- or one 32-byte seed per statement, never used for two statements; blindings: per statement the
+        m blinding factors, or None to derive them.  -> (commitments per statement, proofs per statement)"""
+        batch, m = len(values) if seeds is None else len(seeds), self.desc.m
+        assert blindings is None or len(blindings) == batch
         n_given = len(given[0]) if batch else 0
         L = self.desc.L
         vb = b"".join(int(x % L).to_bytes(32, "little") for row in values for x in row)
         gb = b"".join(int(a % L).to_bytes(32, "little") + int(b % L).to_bytes(32, "little") for row in given for a, b in row)
+        bb = None if blindings is None else b"".join(int(x % L).to_bytes(32, "little") for row in blindings for x in row)
         com = C.create_string_buffer(max(32 * m * batch, 1))
         stride = 1 + 32 * (16 + 2 * 16)
         proofs = C.create_string_buffer(max(stride * batch, 1))
         plen = C.c_size_t(0)
         import time
-        sd = b"".join(seeds)
+        sd = None if seeds is None else b"".join(seeds)
         t0 = time.perf_counter()
         rc = self.ctx.lib.zkgpu_r1cs_prove_batch(
-            self.ctx.h, self.bp_gens.points.h, C.byref(self.desc.struct), self.mult_def, self.bp_gens.gens_capacity, batch, vb, None,
+            self.ctx.h, self.bp_gens.points.h, C.byref(self.desc.struct), self.mult_def, self.bp_gens.gens_capacity, batch, vb, bb,
             gb, n_given, sd, self.host_threads, com, proofs, stride, C.byref(plen))
         self.last_call_s = time.perf_counter() - t0          # the library call alone (bench.py)
         self.ctx._check(rc)
