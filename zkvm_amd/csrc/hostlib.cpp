@@ -8,6 +8,7 @@
 #include "transcript_tape.hpp"
 #include "keccak_coop.hpp"
 #include "prover_plan.hpp"
+#include "prover_call_plan.hpp"
 #include "zkvm_tx.hpp"
 
 #include <array>
@@ -501,32 +502,45 @@ int pv_emulate(const R1csDesc& d, const std::vector<uint32_t>& mult_def, const s
   B.ipa_lv = lv.data(); B.ipa_rv = rv.data(); B.ipa_cg = cg.data(); B.ipa_ch = ch.data(); B.ipa_w = w.data(); B.ipa_u = uu.data();
   PvHostEnv env;
   PvHostLaneEnv lane;
-  const bool staged = g_pv_staged != 0;
   std::vector<uint32_t> pts;
-  pv_phase0(env, sh, B, 0);
-  rows_points(gens, rows0.data(), pv_rows_pairs(sh.m), pts);
-  for (size_t i = 0; i < 8 * (size_t)sh.m; ++i) for (int b = 0; b < 4; ++b) commitments[4 * i + b] = (uint8_t)(pts[i] >> (8 * b));
-  if (staged) {
-    pv_phase1(lane, sh, P, B, 0, pts.data(), 1); pv_phase1(env, sh, P, B, 0, pts.data(), 2);
-    pv_phase1(lane, sh, P, B, 0, pts.data(), 4); pv_phase1(env, sh, P, B, 0, pts.data(), 8);
+  uint32_t* const rows[4] = {rows0.data(), rows1.data(), rows2.data(), rows3.data()};
+  auto msm = [&](uint32_t which, const PvRows& lay) {
+    rows_points(gens, rows[which], lay, pts);
+    if (which == 0) for (size_t i = 0; i < 8 * (size_t)sh.m; ++i) for (int b = 0; b < 4; ++b) commitments[4 * i + b] = (uint8_t)(pts[i] >> (8 * b));
+  };
+  auto stage = [&](auto& e, uint32_t phase, uint32_t st) {
+    if (phase == 1) pv_phase1(e, sh, P, B, 0, pts.data(), st);
+    else if (phase == 2) pv_phase2(e, sh, P, B, 0, pts.data(), st);
+    else if (phase == 3) pv_phase3(e, sh, P, B, 0, pts.data(), st);
+    else pv_phase4(e, sh, P, B, 0, pts.data(), st);
+  };
+  auto draws = [&](uint32_t phase) {
+    if (phase == 1) pv_rng_draw(sh, state.data(), rows1.data(), 0, sh.n1, PV_IBL1); else pv_rng_draw(sh, state.data(), rows2.data(), sh.n1, sh.n, PV_IBL2);
+  };
+  if (g_pv_staged) {
+    // the device's order: the steps prove_device walks, the rows of the plan for a batch of one
+    const PvCallPlan plan = plan_prover_call(hp, 1, 1, {});
+    for (const PvStep& s : plan.steps) switch (s.kind) {
+      case PvStepKind::phase0: pv_phase0(env, sh, B, 0); break;
+      case PvStepKind::msm: msm(s.phase, plan.rows_of((int)s.phase)); break;
+      case PvStepKind::lanes: stage(lane, s.phase, s.mask); break;
+      case PvStepKind::wg: stage(env, s.phase, s.mask); break;
+      case PvStepKind::rng: draws(s.phase); break;
+      case PvStepKind::ipa: case PvStepKind::finish: break;      // below, for both readings
+    }
   } else {
-    pv_phase1(env, sh, P, B, 0, pts.data());
+    // the independent reading: every phase whole, in the order the protocol gives
+    pv_phase0(env, sh, B, 0);
+    msm(0, pv_rows_pairs(sh.m));
+    stage(env, 1, PV_ALL); draws(1);
+    msm(1, pv_rows_commit(1, 0, sh.n1, cap, false));
+    stage(env, 2, PV_ALL); if (sh.n > sh.n1) draws(2);
+    msm(2, pv_rows_commit(1, sh.n1, sh.n, cap, true));
+    stage(env, 3, PV_ALL);
+    msm(3, pv_rows_pairs(5));
+    stage(env, 4, PV_ALL);
   }
-  pv_rng_draw(sh, state.data(), rows1.data(), 0, sh.n1, PV_IBL1);
-  rows_points(gens, rows1.data(), pv_rows_commit(1, 0, sh.n1, cap, false), pts);
-  if (staged) {
-    pv_phase2(lane, sh, P, B, 0, pts.data(), 1);
-    if (sh.n > sh.n1) { pv_phase2(env, sh, P, B, 0, pts.data(), 2); pv_phase2(lane, sh, P, B, 0, pts.data(), 4); pv_phase2(env, sh, P, B, 0, pts.data(), 8); }
-  } else {
-    pv_phase2(env, sh, P, B, 0, pts.data());
-  }
-  if (sh.n > sh.n1) pv_rng_draw(sh, state.data(), rows2.data(), sh.n1, sh.n, PV_IBL2);
-  rows_points(gens, rows2.data(), pv_rows_commit(1, sh.n1, sh.n, cap, true), pts);
-  if (staged) { pv_phase3(lane, sh, P, B, 0, pts.data(), 1); pv_phase3(env, sh, P, B, 0, pts.data(), 2); pv_phase3(lane, sh, P, B, 0, pts.data(), 4); }
-  else pv_phase3(env, sh, P, B, 0, pts.data());
-  rows_points(gens, rows3.data(), pv_rows_pairs(5), pts);
-  if (staged) { pv_phase4(lane, sh, P, B, 0, pts.data(), 1); pv_phase4(env, sh, P, B, 0, pts.data(), 2); }
-  else pv_phase4(env, sh, P, B, 0, pts.data());
+  const bool staged = g_pv_staged != 0;
   if (state[sh.o_flag]) return -2 - (int)state[sh.o_flag];
   // the inner-product rounds (on the device: k_ipa_round + the tables); here with the host's scalars
   std::vector<Scalar> L(sh.pn), R(sh.pn), G(sh.pn), H(sh.pn);
@@ -580,6 +594,23 @@ int pv_emulate(const R1csDesc& d, const std::vector<uint32_t>& mult_def, const s
   *proof_len_out = sh.proof_len;
   return 0;
 }
+
+// a constraint system handed over as arrays (the fields of zkgpu_r1cs_desc); false: a kind or a coefficient out of range
+bool pv_desc_of(R1csDesc& d, const char* label, uint32_t m, uint32_t n1, uint32_t n, uint32_t n_chal, const char* const* chal_labels, uint32_t n_cons,
+                const uint64_t* term_offsets, const uint8_t* kinds, const uint32_t* idx, const uint8_t* coeff, const int32_t* chal, const uint32_t* power) {
+  d.label = label; d.m = m; d.n1 = n1; d.n = n;
+  for (uint32_t i = 0; i < n_chal; ++i) d.chal_names.push_back(chal_labels[i]);
+  for (uint32_t q = 0; q < n_cons; ++q) {
+    std::vector<R1csDesc::Term> con;
+    for (uint64_t t = term_offsets[q]; t < term_offsets[q + 1]; ++t) {
+      Scalar c;
+      if (kinds[t] > 4 || !Scalar::from_canonical(coeff + 32 * t, c)) return false;
+      con.push_back(R1csDesc::Term{(VarKind)kinds[t], idx[t], c, chal[t], power[t]});
+    }
+    d.cons.push_back(std::move(con));
+  }
+  return true;
+}
 }  // namespace
 
 extern "C" {
@@ -608,17 +639,7 @@ int zkhost_prove_dev_r1cs(const char* label, uint32_t m, uint32_t n1, uint32_t n
                           const uint8_t* generators, size_t gens_capacity, uint8_t* commitments, uint8_t* proof, size_t proof_cap,
                           size_t* proof_len_out) {
   R1csDesc d;
-  d.label = label; d.m = m; d.n1 = n1; d.n = n;
-  for (uint32_t i = 0; i < n_chal; ++i) d.chal_names.push_back(chal_labels[i]);
-  for (uint32_t q = 0; q < n_cons; ++q) {
-    std::vector<R1csDesc::Term> con;
-    for (uint64_t t = term_offsets[q]; t < term_offsets[q + 1]; ++t) {
-      Scalar c;
-      if (kinds[t] > 4 || !Scalar::from_canonical(coeff + 32 * t, c)) return -1;
-      con.push_back(R1csDesc::Term{(VarKind)kinds[t], idx[t], c, chal[t], power[t]});
-    }
-    d.cons.push_back(std::move(con));
-  }
+  if (!pv_desc_of(d, label, m, n1, n, n_chal, chal_labels, n_cons, term_offsets, kinds, idx, coeff, chal, power)) return -1;
   std::vector<uint32_t> md(mult_def, mult_def + 2 * (size_t)n), vw, bw, gw;
   words_of(values, 8 * (size_t)m, vw);
   for (uint32_t i = 0; i < m; ++i) {
@@ -628,6 +649,54 @@ int zkhost_prove_dev_r1cs(const char* label, uint32_t m, uint32_t n1, uint32_t n
   }
   words_of(given, 16 * n_given, gw);
   return pv_emulate(d, md, vw, bw, gw, seed, generators, gens_capacity, commitments, proof, proof_cap, proof_len_out);
+}
+
+// The plan of one device prover call (prover_call_plan.hpp) -- of the cloak when n_in + n_out > 0, else of the system described
+// by the arrays (mult_def NULL: every multiplier given).  flags: 1 the call drew its seed, 2 the cloak's tag table, 4 the caller
+// brought blindings.  numbers[PV_CALL_PLAN_NUMBERS]: steps, blob words, scaffolding bytes, draw_blindings, terms of an
+// inner-product row | the input area: values blindings given seeds bytes | the blob's tables in PV_PLAN_TABLES order, then
+// chal_labels, draw | per multiplication 0..4: rows terms P kinds o_off o_idx | the workspace in PV_WORKSPACE order | the
+// shape the plan was made for (pv_build): m n1 n pn k n_given r1_terms r2_terms state_words proof_stride gens_capacity.
+// steps (3 words each: kind phase mask), blob, lay: written when not NULL, as many as numbers[0..2] say.
+// -> 0; -1 a description out of range; -3 one the device prover cannot serve; -4 scaffolding out of step;
+// -5 the numbers written are not PV_CALL_PLAN_NUMBERS (the lists above changed without it)
+enum { PV_CALL_PLAN_NUMBERS = 5 + 5 + 16 + 5 * 6 + 21 + 11 };
+int zkhost_prover_call_plan(const char* label, uint32_t m, uint32_t n1, uint32_t n, uint32_t n_chal, const char* const* chal_labels,
+                            uint32_t n_cons, const uint64_t* term_offsets, const uint8_t* kinds, const uint32_t* idx,
+                            const uint8_t* coeff, const int32_t* chal, const uint32_t* power, const uint32_t* mult_def,
+                            uint32_t n_in, uint32_t n_out, size_t gens_capacity, size_t batch, int W, uint32_t flags,
+                            uint64_t* numbers, uint32_t* steps, uint32_t* blob, uint8_t* lay) {
+  R1csDesc d;
+  std::vector<uint32_t> md;
+  PvHostPlan hp;
+  try {
+    if (n_in + n_out) {
+      PvCloakTrace::trace(n_in, n_out, d, md);
+    } else {
+      if (!pv_desc_of(d, label, m, n1, n, n_chal, chal_labels, n_cons, term_offsets, kinds, idx, coeff, chal, power)) return -1;
+      md.assign(2 * (size_t)n, PV_GIVEN);
+      if (mult_def) md.assign(mult_def, mult_def + 2 * (size_t)n);
+    }
+    hp = pv_build(d, md, gens_capacity);
+  } catch (const std::exception&) { return -3; }
+  const PvCallPlan p = plan_prover_call(hp, batch, W, {(flags & 1) != 0, (flags & 2) != 0, (flags & 4) != 0});
+  uint64_t* o = numbers;
+  *o++ = p.steps.size(); *o++ = p.blob.size(); *o++ = p.lay_bytes; *o++ = p.draw_blindings; *o++ = p.ipa_row_len;
+  *o++ = p.in.values; *o++ = p.in.blindings; *o++ = p.in.given; *o++ = p.in.seeds; *o++ = p.in.bytes;
+#define X(f) *o++ = p.at.f;
+  PV_PLAN_TABLES(X) X(chal_labels) X(draw)
+#undef X
+  for (const PvMsm& mm : p.msm) { *o++ = mm.rows; *o++ = mm.terms; *o++ = (uint64_t)mm.P; *o++ = mm.kinds; *o++ = mm.o_off; *o++ = mm.o_idx; }
+#define X(b) *o++ = p.ws.b;
+  PV_WORKSPACE(X)
+#undef X
+  const PvShape& sh = p.sh;
+  for (uint32_t v : {sh.m, sh.n1, sh.n, sh.pn, sh.k, sh.n_given, sh.r1_terms, sh.r2_terms, sh.state_words, sh.proof_stride, sh.gens_capacity}) *o++ = v;
+  if (o - numbers != PV_CALL_PLAN_NUMBERS) return -5;
+  if (steps) for (const PvStep& s : p.steps) { *steps++ = (uint32_t)s.kind; *steps++ = s.phase; *steps++ = s.mask; }
+  if (blob) std::memcpy(blob, p.blob.data(), p.blob.size() * 4);
+  if (lay && !p.fill_scaffolding(lay)) return -4;
+  return 0;
 }
 }  // extern "C"
 

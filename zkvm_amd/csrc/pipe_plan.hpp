@@ -25,6 +25,14 @@ inline int static_parts(uint64_t B, int W, int forced) {
 inline uint64_t static_lanes_room(uint64_t B, int W, int forced) {
   return forced > 0 ? B * W * forced : std::min<uint64_t>(MAX_PARTS * B * W, FILL_LANES - 1 + B * W);
 }
+// ... over `rows` rows whose values are wanted one by one (zkgpu_msm_ps_batch, the device prover's multiplications): 64 at
+// most, and the room for them that never shrinks as the rows grow
+constexpr uint64_t MAX_ROW_PARTS = 64;
+inline int row_parts(uint64_t rows, int W) {
+  const uint64_t cells = std::max<uint64_t>(rows * W, 1);
+  return (int)std::max<uint64_t>(1, std::min<uint64_t>(MAX_ROW_PARTS, (FILL_LANES + cells - 1) / cells));
+}
+inline uint64_t row_lanes_room(uint64_t rows, int W) { return std::min<uint64_t>(MAX_ROW_PARTS * rows * W, FILL_LANES - 1 + rows * W); }
 // ... over the rows of group checks (few checks each: short chains of additions per lane keep their latency down)
 inline int group_parts(uint64_t rows, int W) { return (int)std::max<uint64_t>(1, std::min<uint64_t>(32, (65536 + rows * W - 1) / (rows * W))); }
 

@@ -11,18 +11,25 @@
 
 namespace zk {
 
+// the word tables of a PvPlan, in the order a call's constant blob holds them (prover_call_plan.hpp); chal_labels, the one
+// table of bytes, follows them
+#define PV_PLAN_TABLES(X) \
+  X(init) X(mono_chal) X(mono_pow) X(con_off) X(t_kind) X(t_idx) X(t_mono) X(t_coef) X(mult_def) X(given_slot) X(tgt_off) \
+  X(term_info) X(prod_qm) X(prod_coef)
+
 struct PvHostPlan {
   PvShape sh{};
-  std::vector<uint32_t> init, mono_chal, mono_pow, con_off, t_kind, t_idx, t_mono, t_coef, mult_def, given_slot, tgt_off,
-      term_info, prod_qm, prod_coef;
+#define X(f) std::vector<uint32_t> f;
+  PV_PLAN_TABLES(X)
+#undef X
   std::vector<uint8_t> chal_labels;
 
-  PvPlan view() const {   // host pointers (the emulation); the library uploads the vectors and fills a PvPlan of device pointers
+  PvPlan view() const {   // host pointers (the emulation); the library uploads the tables as one blob: PvCallPlan::view
     PvPlan p;
-    p.init = init.data(); p.chal_labels = chal_labels.data(); p.mono_chal = mono_chal.data(); p.mono_pow = mono_pow.data();
-    p.con_off = con_off.data(); p.t_kind = t_kind.data(); p.t_idx = t_idx.data(); p.t_mono = t_mono.data(); p.t_coef = t_coef.data();
-    p.mult_def = mult_def.data(); p.given_slot = given_slot.data(); p.tgt_off = tgt_off.data(); p.term_info = term_info.data();
-    p.prod_qm = prod_qm.data(); p.prod_coef = prod_coef.data();
+#define X(f) p.f = f.data();
+    PV_PLAN_TABLES(X)
+#undef X
+    p.chal_labels = chal_labels.data();
     return p;
   }
 };

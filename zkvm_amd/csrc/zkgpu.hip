@@ -38,6 +38,7 @@
 #include "r1cs_prover.hpp"
 #include "ipa_kernels.hpp"
 #include "prover_plan.hpp"
+#include "prover_call_plan.hpp"
 #include "prover_kernels.hpp"
 #include "zkvm_tx.hpp"
 #include "host_pool.hpp"
@@ -1900,7 +1901,7 @@ int msm_ps_core(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, uint64_t n
                 const uint64_t* d_offsets, uint8_t* out) {
   hipStream_t s = c->stream;
   const int W = ps->tbl_W;
-  const int P = (int)std::max<uint64_t>(1, std::min<uint64_t>(64, (131072 + batch * W - 1) / (batch * W)));
+  const int P = row_parts(batch, W);
   const uint64_t n_lanes = (uint64_t)batch * W * P;
   TRY(ensure(c, c->status, 64));
   TRY(ensure(c, c->digits, std::max<uint64_t>(n, 1) * W * 2));
@@ -2027,34 +2028,51 @@ int ipa_on_device(zkgpu_ctx* c, const zkgpu_pointset* ps, std::vector<std::uniqu
 #define PV_RNG_LANES_FROM ((size_t)1 << 40)      // (never, until the A/B of round 6 says otherwise)
 #endif
 
-// values of `rows` multiscalar multiplications over the tables, everything resident: queued on the context's stream,
+double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// values of one multiscalar multiplication of a prover call over the tables (m: its rows, terms and lanes per (row, window) as
+// planned, prover_call_plan.hpp), everything resident and the workspace ensured by the caller: queued on the context's stream,
 // encodings written to d_out (32 bytes per row)
 // kinds: 1, or the rows come in groups of `kinds` rows of different make per proof (A_I, A_O, S): k_static_accumulate then puts
 // rows of one make side by side in its wavefronts, where their zero digits coincide and the additions nobody needs are skipped
-int msm_ps_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t rows, uint64_t n, const uint32_t* d_scalars, const uint32_t* d_index,
-               const uint64_t* d_offsets, uint32_t* d_out, uint32_t kinds = 1) {
+int msm_ps_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, const PvMsm& m, const uint32_t* d_scalars, const uint32_t* d_index,
+               const uint64_t* d_offsets, uint32_t* d_out) {
   hipStream_t s = c->stream;
   const int W = ps->tbl_W;
-  const int P = (int)std::max<uint64_t>(1, std::min<uint64_t>(64, (131072 + rows * W - 1) / (rows * W)));
-  const uint64_t n_lanes = (uint64_t)rows * W * P;
-  TRY(ensure(c, c->status, 64));
-  TRY(ensure(c, c->digits, std::max<uint64_t>(n, 1) * W * 2));
-  TRY(ensure(c, c->st_partials, n_lanes * EXT_WORDS * 4));
-  if (n) static_digits_launch(c, s, ps, d_scalars, n, {}, 0, /*fold=*/1);      // (results are encoded: small negatives folded)
-  static_accumulate_launch(c, s, ps, d_offsets, d_index, {(uint32_t)rows, n, P, &c->digits, &c->st_partials}, rows % kinds == 0 ? kinds : 1u,
-                           /*skip_zeros=*/true);
-  TRY(ensure(c, c->rechk_pts, rows * EXT_WORDS * 4));       // (free while a prover runs: the verifier's re-check sums)
+  if (m.terms) static_digits_launch(c, s, ps, d_scalars, m.terms, {}, 0, /*fold=*/1);      // (results are encoded: small negatives folded)
+  static_accumulate_launch(c, s, ps, d_offsets, d_index, {(uint32_t)m.rows, m.terms, m.P, &c->digits, &c->st_partials}, m.kinds, /*skip_zeros=*/true);
   {
-    Launch l(c, "k_static_row_sums");
-    hipLaunchKernelGGL(k_static_row_sums, dim3(blocks_for(rows * ROW_SUM_LANES, 64)), dim3(64), 0, s, (const uint32_t*)c->st_partials.p,
-                       (uint32_t)(W * P), (uint32_t)rows, (uint32_t*)c->rechk_pts.p);
+    Launch l(c, "k_static_row_sums");      // (rechk_pts is free while a prover runs: the verifier's re-check sums)
+    hipLaunchKernelGGL(k_static_row_sums, dim3(blocks_for(m.rows * ROW_SUM_LANES, 64)), dim3(64), 0, s, (const uint32_t*)c->st_partials.p,
+                       (uint32_t)(W * m.P), (uint32_t)m.rows, (uint32_t*)c->rechk_pts.p);
   }
   {
     Launch l(c, "k_encode_rows");
-    hipLaunchKernelGGL(k_encode_rows, dim3(blocks_for(rows, 64)), dim3(64), 0, s, (const uint32_t*)c->rechk_pts.p, (uint32_t)rows, d_out);
+    hipLaunchKernelGGL(k_encode_rows, dim3(blocks_for(m.rows, 64)), dim3(64), 0, s, (const uint32_t*)c->rechk_pts.p, (uint32_t)m.rows, d_out);
   }
   HIP_TRY(c, hipGetLastError());
   return ZKGPU_OK;
+}
+
+// one stage of a phase: the step -> its instantiation of k_pv_lanes (a lane per proof) or k_pv_wg (a workgroup per proof).
+// The stages of PV_CALL_STEPS are the instantiations there are; the profile names are "k_pv_lanes_1_1", "k_pv_wg_1_2", ...
+extern "C++" {      // (a template, inside the exports' extern "C")
+template <PvStepKind K, int PH, uint32_t ST>
+void pv_stage_launch_as(zkgpu_ctx* c, hipStream_t s, const char* name, const PvShape& sh, const PvPlan& P, const PvBatch& B, const uint32_t* pts, unsigned nb) {
+  if constexpr (K == PvStepKind::lanes) {
+    Launch l(c, name);
+    hipLaunchKernelGGL((k_pv_lanes<PH, ST>), dim3(blocks_for(nb, 64)), dim3(64), 0, s, sh, P, B, pts, nb);
+  } else if constexpr (K == PvStepKind::wg) {
+    Launch l(c, name);
+    hipLaunchKernelGGL((k_pv_wg<PH, ST>), dim3(nb), dim3(256), 0, s, sh, P, B, pts);
+  }
+}
+}
+void pv_stage_launch(zkgpu_ctx* c, hipStream_t s, const PvStep& st, const PvShape& sh, const PvPlan& P, const PvBatch& B, const uint32_t* pts, unsigned nb) {
+#define X(K, PH, ST) \
+  if (st.kind == PvStepKind::K && st.phase == PH && st.mask == ST) return pv_stage_launch_as<PvStepKind::K, PH, ST>(c, s, "k_pv_" #K "_" #PH "_" #ST, sh, P, B, pts, nb);
+  PV_CALL_STEPS(X)
+#undef X
 }
 
 // The TranscriptRng's draws -- one Keccak-f each, 3 + 2n of them per proof, a third of a proof's instructions in the wavefront
@@ -2066,8 +2084,8 @@ bool pv_rng_lanes_pay(const zkgpu_ctx* c, size_t batch_of_this_slice) {
   return batch_of_this_slice >= PV_RNG_LANES_FROM;
 }
 
-// Proves `batch` statements of one described system.  Host: the constant tables (once per call), the inputs' upload,
-// a queue of kernels; device: everything else.  values / blindings: batch x m x 32 bytes (any 256-bit values, reduced
+// Proves `batch` statements of one described system.  Host: the call's plan (prover_call_plan.hpp: everything settled before
+// the first launch), the constant tables (once per statement), the inputs' upload, a queue of kernels; device: everything else.  values / blindings: batch x m x 32 bytes (any 256-bit values, reduced
 // on the device), given: batch x n_given x 64, rng_seeds: batch x 32.  call_seed (a call without seeds, prover_draw.hpp): rng_seeds is NULL and blindings may be -- k_pv_draw writes those regions of the input area from the call's seed and the positions first + 0 .. batch - 1 in the CALL; cloak_tags: which tag table
 int prove_device(zkgpu_ctx* c, const zkgpu_pointset* ps, const PvHostPlan& hp, size_t batch, const uint8_t* values, const uint8_t* blindings,
                  const uint8_t* given, const uint8_t* rng_seeds, uint8_t* commitments, uint8_t* proofs, size_t proof_stride, size_t* proof_len, const uint8_t* call_seed = nullptr, uint64_t first = 0, bool cloak_tags = false) {
@@ -2078,152 +2096,101 @@ int prove_device(zkgpu_ctx* c, const zkgpu_pointset* ps, const PvHostPlan& hp, s
   DeviceGuard g(c->device);
   hipStream_t s = c->stream;
   const bool timing = getenv("ZKGPU_PROVER_TIMING") != nullptr;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t_start = now();
-  // constant tables: one blob
-  std::vector<uint32_t> blob;
-  auto put = [&blob](const std::vector<uint32_t>& v) { const size_t at = blob.size(); blob.insert(blob.end(), v.begin(), v.end()); while (blob.size() & 3) blob.push_back(0); return at; };
-  const size_t o_init = put(hp.init), o_mc = put(hp.mono_chal), o_mp = put(hp.mono_pow), o_co = put(hp.con_off), o_tk = put(hp.t_kind),
-               o_ti = put(hp.t_idx), o_tm = put(hp.t_mono), o_tc = put(hp.t_coef), o_md = put(hp.mult_def), o_gs = put(hp.given_slot),
-               o_to = put(hp.tgt_off), o_tinf = put(hp.term_info), o_pq = put(hp.prod_qm), o_pc = put(hp.prod_coef);
-  std::vector<uint32_t> labels((hp.chal_labels.size() + 3) / 4, 0);
-  memcpy(labels.data(), hp.chal_labels.data(), hp.chal_labels.size());
-  const size_t o_lab = put(labels), o_dr = call_seed ? put(cloak_tags ? pv_draw_table_cloak(sh.m / 2) : pv_draw_table_desc(sh.m)) : 0;
-  (void)put({sh.m, sh.n1, sh.n, sh.pn, sh.gens_capacity});   // part of the key the cached scaffolding goes by
-  if (blob != c->pv_plan_host) {        // the same statement as in the last call: the tables are already there
-    TRY(upload(c, c->pv_plan, blob.data(), blob.size() * 4));
-    c->pv_plan_host = blob;
+  const double t_start = now_seconds();
+  // 1. everything the call settles before its first launch
+  const PvCallPlan plan = plan_prover_call(hp, batch, ps->tbl_W, {call_seed != nullptr, cloak_tags, blindings != nullptr});
+  // 2. the constant tables: one blob (the same statement as in the last call: the tables are already there)
+  if (plan.blob != c->pv_plan_host) {
+    TRY(upload(c, c->pv_plan, plan.blob.data(), plan.blob.size() * 4));
+    c->pv_plan_host = plan.blob;
     c->pv_lay_batch = 0;
   }
   const uint32_t* base = (const uint32_t*)c->pv_plan.p;
-  PvPlan P;
-  P.init = base + o_init; P.chal_labels = (const uint8_t*)(base + o_lab); P.mono_chal = base + o_mc; P.mono_pow = base + o_mp;
-  P.con_off = base + o_co; P.t_kind = base + o_tk; P.t_idx = base + o_ti; P.t_mono = base + o_tm; P.t_coef = base + o_tc;
-  P.mult_def = base + o_md; P.given_slot = base + o_gs; P.tgt_off = base + o_to; P.term_info = base + o_tinf; P.prod_qm = base + o_pq;
-  P.prod_coef = base + o_pc;
-  // inputs: values | blindings | given | seeds
-  const size_t b_val = batch * sh.m * 32, b_giv = batch * (size_t)sh.n_given * 64, b_seed = batch * 32;
-  TRY(ensure(c, c->pv_in, 2 * b_val + b_giv + b_seed + 64));
+  const PvPlan P = plan.view(base);
+  // 3. inputs: values | blindings | given | seeds, uploaded or (a call without seeds) drawn where they lie
+  TRY(ensure(c, c->pv_in, plan.in.bytes));
   char* in = (char*)c->pv_in.p;
+  const size_t b_val = plan.in.blindings - plan.in.values, b_giv = plan.in.seeds - plan.in.given;
   if (b_val) {
-    HIP_TRY(c, hipMemcpyAsync(in, values, b_val, hipMemcpyHostToDevice, s));
-    if (blindings) HIP_TRY(c, hipMemcpyAsync(in + b_val, blindings, b_val, hipMemcpyHostToDevice, s));
+    HIP_TRY(c, hipMemcpyAsync(in + plan.in.values, values, b_val, hipMemcpyHostToDevice, s));
+    if (blindings) HIP_TRY(c, hipMemcpyAsync(in + plan.in.blindings, blindings, b_val, hipMemcpyHostToDevice, s));
   }
-  if (b_giv) HIP_TRY(c, hipMemcpyAsync(in + 2 * b_val, given, b_giv, hipMemcpyHostToDevice, s));
-  if (call_seed) TRY(pv_draw_launch(c, s, call_seed, first, batch, sh.m, !blindings, base + o_dr, in + b_val, in + 2 * b_val + b_giv)); else HIP_TRY(c, hipMemcpyAsync(in + 2 * b_val + b_giv, rng_seeds, b_seed, hipMemcpyHostToDevice, s));
-  // rows and their scaffolding (offsets and generator indices: kept on the device from call to call while statement and
-  // batch size stay the same)
-  const size_t cap = sh.gens_capacity;
-  const size_t row_len = (size_t)sh.pn + 1, n_ipa_rows = 2 * batch;
-  const size_t lay_rows[4] = {batch * sh.m, 3 * batch, 3 * batch, 5 * batch};
-  const size_t lay_terms[4] = {2 * batch * sh.m, batch * (size_t)sh.r1_terms, batch * (size_t)sh.r2_terms, 10 * batch};
-  size_t o_off[4], o_idx[4], o_ipa, lay_bytes = 0;
-  auto place = [&lay_bytes](size_t bytes) { const size_t at = lay_bytes; lay_bytes = (lay_bytes + bytes + 15) & ~(size_t)15; return at; };
-  for (int i = 0; i < 4; ++i) { o_off[i] = place((lay_rows[i] + 1) * 8); o_idx[i] = place(lay_terms[i] * 4); }
-  o_ipa = place((n_ipa_rows + 1) * 8);
+  if (b_giv) HIP_TRY(c, hipMemcpyAsync(in + plan.in.given, given, b_giv, hipMemcpyHostToDevice, s));
+  if (call_seed) TRY(pv_draw_launch(c, s, call_seed, first, batch, sh.m, plan.draw_blindings, base + plan.at.draw, in + plan.in.blindings, in + plan.in.seeds));
+  else HIP_TRY(c, hipMemcpyAsync(in + plan.in.seeds, rng_seeds, batch * 32, hipMemcpyHostToDevice, s));
+  // 4. the rows' scaffolding (offsets and generator indices: kept on the device from call to call while statement and batch
+  // size stay the same)
   if (c->pv_lay_batch != batch) {
-    const PvRows l0 = pv_rows_pairs(batch * sh.m), l1 = pv_rows_commit(batch, 0, sh.n1, cap, false),
-                 l2 = pv_rows_commit(batch, sh.n1, sh.n, cap, true), l3 = pv_rows_pairs(batch * 5);
-    const PvRows* lays[4] = {&l0, &l1, &l2, &l3};
-    std::vector<uint8_t> lay(lay_bytes, 0);
-    for (int i = 0; i < 4; ++i) {
-      if (lays[i]->offsets.size() != lay_rows[i] + 1 || lays[i]->index.size() != lay_terms[i]) { c->last_error = "prover: row scaffolding out of step"; return ZKGPU_EINVAL; }
-      memcpy(&lay[o_off[i]], lays[i]->offsets.data(), lays[i]->offsets.size() * 8);
-      memcpy(&lay[o_idx[i]], lays[i]->index.data(), lays[i]->index.size() * 4);
-    }
-    for (size_t r = 0; r <= n_ipa_rows; ++r) { const uint64_t v = r * row_len; memcpy(&lay[o_ipa + 8 * r], &v, 8); }
+    std::vector<uint8_t> lay(plan.lay_bytes);
+    if (!plan.fill_scaffolding(lay.data())) { c->last_error = "prover: row scaffolding out of step"; return ZKGPU_EINVAL; }
     TRY(upload(c, c->pv_lay, lay.data(), lay.size()));
     c->pv_lay_batch = batch;
   }
   const char* lb = (const char*)c->pv_lay.p;
-  TRY(ensure(c, c->pv_state, batch * (size_t)sh.state_words * 4));
-  TRY(ensure(c, c->pv_rows0, std::max<size_t>(batch * sh.m, 1) * 64));
-  TRY(ensure(c, c->pv_rows1, batch * (size_t)sh.r1_terms * 32));
-  TRY(ensure(c, c->pv_rows2, std::max<size_t>(batch * (size_t)sh.r2_terms, 1) * 32));
-  TRY(ensure(c, c->pv_rows3, batch * 5 * 64));
-  TRY(ensure(c, c->pv_pts, std::max<size_t>(batch * 5, batch * sh.m) * 32 + 64));
-  TRY(ensure(c, c->pv_com, std::max<size_t>(batch * sh.m, 1) * 32));
-  TRY(ensure(c, c->pv_ab, batch * 64));
-  TRY(ensure(c, c->pv_proofs, batch * (size_t)sh.proof_stride));
-  const size_t vec = (size_t)sh.pn * 32;
-  TRY(ensure(c, c->ipa_lv, batch * vec)); TRY(ensure(c, c->ipa_rv, batch * vec)); TRY(ensure(c, c->ipa_cg, batch * vec));
-  TRY(ensure(c, c->ipa_ch, batch * vec)); TRY(ensure(c, c->ipa_w, batch * 32)); TRY(ensure(c, c->ipa_u, batch * 64));
-  TRY(ensure(c, c->in_st_scalars, n_ipa_rows * row_len * 32));
-  TRY(ensure(c, c->in_st_index, n_ipa_rows * row_len * 4));
-  TRY(ensure(c, c->status, 64));
+  // 5. the workspace
+#define X(b) TRY(ensure(c, c->b, plan.ws.b));
+  PV_WORKSPACE(X)
+#undef X
   HIP_TRY(c, hipMemsetAsync(c->status.p, 0, 64, s));
   PvBatch B;
   B.state = (uint32_t*)c->pv_state.p;
-  B.values = (const uint32_t*)in; B.blindings = (const uint32_t*)(in + b_val); B.given = (const uint32_t*)(in + 2 * b_val);
-  B.rng_seed = (const uint32_t*)(in + 2 * b_val + b_giv);
+  B.values = (const uint32_t*)(in + plan.in.values); B.blindings = (const uint32_t*)(in + plan.in.blindings);
+  B.given = (const uint32_t*)(in + plan.in.given); B.rng_seed = (const uint32_t*)(in + plan.in.seeds);
   B.proofs = (uint8_t*)c->pv_proofs.p;
   B.rows0 = (uint32_t*)c->pv_rows0.p; B.rows1 = (uint32_t*)c->pv_rows1.p; B.rows2 = (uint32_t*)c->pv_rows2.p; B.rows3 = (uint32_t*)c->pv_rows3.p;
   B.ipa_lv = (uint32_t*)c->ipa_lv.p; B.ipa_rv = (uint32_t*)c->ipa_rv.p; B.ipa_cg = (uint32_t*)c->ipa_cg.p; B.ipa_ch = (uint32_t*)c->ipa_ch.p;
   B.ipa_w = (uint32_t*)c->ipa_w.p; B.ipa_u = (uint32_t*)c->ipa_u.p;
-  uint32_t* pts = (uint32_t*)c->pv_pts.p;
-  auto msm = [&](int which, const uint32_t* rows, uint32_t* out) {
-    return msm_ps_dev(c, ps, lay_rows[which], lay_terms[which], rows, (const uint32_t*)(lb + o_idx[which]),
-                      (const uint64_t*)(lb + o_off[which]), out, which == 1 || which == 2 ? 3u : 1u);
-  };
+  uint32_t* const rows[4] = {B.rows0, B.rows1, B.rows2, B.rows3};
+  uint32_t* const com = (uint32_t*)c->pv_com.p;       // the value commitments: phase 1 reads them, the caller gets them
+  uint32_t* const pts = (uint32_t*)c->pv_pts.p;       // the points of every later multiplication: the next phase reads them
   const unsigned nb = (unsigned)batch;
-  const double t_setup = now();
-  { Launch l(c, "k_pv_phase0"); hipLaunchKernelGGL(k_pv_phase0, dim3(nb), dim3(64), 0, s, sh, B); }
-  if (sh.m) TRY(msm(0, B.rows0, (uint32_t*)c->pv_com.p));
-  // a phase = its stages, each a launch: one lane per proof where a stage is one thread's work, a workgroup per proof elsewhere
-  const unsigned nbl = blocks_for(nb, 64);
-#define PV_LANES(PH, ST, pts_) { Launch l(c, "k_pv_lanes_" #PH "_" #ST); hipLaunchKernelGGL((k_pv_lanes<PH, ST>), dim3(nbl), dim3(64), 0, s, sh, P, B, (const uint32_t*)(pts_), nb); }
-#define PV_WG(PH, ST, pts_) { Launch l(c, "k_pv_wg_" #PH "_" #ST); hipLaunchKernelGGL((k_pv_wg<PH, ST>), dim3(nb), dim3(256), 0, s, sh, P, B, (const uint32_t*)(pts_)); }
-  PV_LANES(1, 1, c->pv_com.p) PV_WG(1, 2, c->pv_com.p) PV_LANES(1, 4, c->pv_com.p) PV_WG(1, 8, c->pv_com.p)
   // the TranscriptRng's draws: one wavefront per proof on the spread Keccak state (k_pv_rng, one lane per proof, is the
   // form the host emulation and the first device version ran; kept for comparison)
   static const int rng_env = [] { const char* e = getenv("ZKGPU_PV_RNG"); return e ? (e[0] == 'l' ? 1 : e[0] == 'c' ? 2 : 0) : 0; }();
   const bool rng_lanes = rng_env == 1 || (rng_env == 0 && pv_rng_lanes_pay(c, batch));
-  auto rng_launch = [&](uint32_t phase, uint32_t) {
-    if (rng_lanes) {
-      Launch l(c, "k_pv_rng");
-      hipLaunchKernelGGL(k_pv_rng, dim3(blocks_for(nb, 64)), dim3(64), 0, s, sh, B, nb, phase);
-    } else {
-      Launch l(c, "k_pv_rng_coop");
-      hipLaunchKernelGGL(k_pv_rng_coop, dim3(nb), dim3(64), 0, s, sh, B, nb, phase);
-    }
-  };
-  rng_launch(1u, sh.n1);
-  TRY(msm(1, B.rows1, pts));
-  PV_LANES(2, 1, pts)
-  if (sh.n > sh.n1) { PV_WG(2, 2, pts) PV_LANES(2, 4, pts) PV_WG(2, 8, pts) }
-  if (sh.n > sh.n1) rng_launch(2u, sh.n - sh.n1);
-  TRY(msm(2, B.rows2, pts));
-  PV_LANES(3, 1, pts) PV_WG(3, 2, pts) PV_LANES(3, 4, pts)
-  TRY(msm(3, B.rows3, pts));
-  PV_LANES(4, 1, pts) PV_WG(4, 2, pts)
-#undef PV_LANES
-#undef PV_WG
-  size_t len = sh.pn;
-  for (uint32_t round = 0; round <= sh.k; ++round) {
-    const bool last = round == sh.k;
-    {
-      Launch l(c, "k_ipa_round");
-      hipLaunchKernelGGL(k_ipa_round, dim3(nb), dim3(256), 0, s, B.ipa_lv, B.ipa_rv, B.ipa_cg, B.ipa_ch, (const uint32_t*)B.ipa_w,
-                         (const uint32_t*)B.ipa_u, sh.pn, (uint32_t)len, (uint32_t)cap, round > 0 ? 1u : 0u, last ? 0u : 1u,
-                         (uint32_t*)c->in_st_scalars.p, (uint32_t*)c->in_st_index.p, (uint32_t*)c->pv_ab.p);
-    }
-    if (last) break;
-    TRY(msm_ps_dev(c, ps, n_ipa_rows, (uint64_t)n_ipa_rows * row_len, (const uint32_t*)c->in_st_scalars.p, (const uint32_t*)c->in_st_index.p,
-                   (const uint64_t*)(lb + o_ipa), pts));
-    { Launch l(c, "k_pv_ipa_lanes"); hipLaunchKernelGGL(k_pv_ipa_lanes, dim3(blocks_for(nb, 64)), dim3(64), 0, s, sh, B, round, (const uint32_t*)pts, nb); }
-    len /= 2;
+  const double t_setup = now_seconds();
+  // 6. the steps.  A phase = its stages, each a launch: one lane per proof where a stage is one thread's work, a workgroup
+  // per proof elsewhere
+  for (const PvStep& st : plan.steps) switch (st.kind) {
+    case PvStepKind::phase0: { Launch l(c, "k_pv_phase0"); hipLaunchKernelGGL(k_pv_phase0, dim3(nb), dim3(64), 0, s, sh, B); } break;
+    case PvStepKind::msm: {
+      const PvMsm& m = plan.msm[st.phase];
+      TRY(msm_ps_dev(c, ps, m, rows[st.phase], (const uint32_t*)(lb + m.o_idx), (const uint64_t*)(lb + m.o_off), st.phase == 0 ? com : pts));
+    } break;
+    case PvStepKind::lanes: case PvStepKind::wg: pv_stage_launch(c, s, st, sh, P, B, st.phase == 1 ? com : pts, nb); break;
+    case PvStepKind::rng:
+      if (rng_lanes) { Launch l(c, "k_pv_rng"); hipLaunchKernelGGL(k_pv_rng, dim3(blocks_for(nb, 64)), dim3(64), 0, s, sh, B, nb, st.phase); }
+      else { Launch l(c, "k_pv_rng_coop"); hipLaunchKernelGGL(k_pv_rng_coop, dim3(nb), dim3(64), 0, s, sh, B, nb, st.phase); }
+      break;
+    case PvStepKind::ipa: {
+      size_t len = sh.pn;
+      for (uint32_t round = 0; round <= sh.k; ++round, len /= 2) {
+        const bool last = round == sh.k;
+        {
+          Launch l(c, "k_ipa_round");
+          hipLaunchKernelGGL(k_ipa_round, dim3(nb), dim3(256), 0, s, B.ipa_lv, B.ipa_rv, B.ipa_cg, B.ipa_ch, (const uint32_t*)B.ipa_w,
+                             (const uint32_t*)B.ipa_u, sh.pn, (uint32_t)len, sh.gens_capacity, round > 0 ? 1u : 0u, last ? 0u : 1u,
+                             (uint32_t*)c->in_st_scalars.p, (uint32_t*)c->in_st_index.p, (uint32_t*)c->pv_ab.p);
+        }
+        if (last) break;
+        const PvMsm& m = plan.msm[PV_MSM_IPA];
+        TRY(msm_ps_dev(c, ps, m, (const uint32_t*)c->in_st_scalars.p, (const uint32_t*)c->in_st_index.p, (const uint64_t*)(lb + m.o_off), pts));
+        { Launch l(c, "k_pv_ipa_lanes"); hipLaunchKernelGGL(k_pv_ipa_lanes, dim3(blocks_for(nb, 64)), dim3(64), 0, s, sh, B, round, (const uint32_t*)pts, nb); }
+      }
+    } break;
+    case PvStepKind::finish: { Launch l(c, "k_pv_finish"); hipLaunchKernelGGL(k_pv_finish, dim3(blocks_for(batch, 256)), dim3(256), 0, s, sh, B, (const uint32_t*)c->pv_ab.p, nb, (uint32_t*)c->status.p); } break;
   }
-  { Launch l(c, "k_pv_finish"); hipLaunchKernelGGL(k_pv_finish, dim3(blocks_for(batch, 256)), dim3(256), 0, s, sh, B, (const uint32_t*)c->pv_ab.p, nb, (uint32_t*)c->status.p); }
   HIP_TRY(c, hipGetLastError());
+  // 7. the results
   std::vector<uint8_t> h_proofs(batch * (size_t)sh.proof_stride);
   uint32_t st[2] = {0, 0};
   HIP_TRY(c, hipMemcpyAsync(h_proofs.data(), c->pv_proofs.p, h_proofs.size(), hipMemcpyDeviceToHost, s));
-  if (sh.m) HIP_TRY(c, hipMemcpyAsync(commitments, c->pv_com.p, batch * sh.m * 32, hipMemcpyDeviceToHost, s));
+  if (sh.m) HIP_TRY(c, hipMemcpyAsync(commitments, com, batch * sh.m * 32, hipMemcpyDeviceToHost, s));
   HIP_TRY(c, hipMemcpyAsync(st, c->status.p, 8, hipMemcpyDeviceToHost, s));
-  const double t_queued = now();
+  const double t_queued = now_seconds();
   HIP_TRY(c, hipStreamSynchronize(s));
   if (timing) fprintf(stderr, "device prover: setup + uploads %.1f ms, queueing %.1f ms, waiting for the device %.1f ms (%zu proofs)\n",
-                      (t_setup - t_start) * 1e3, (t_queued - t_setup) * 1e3, (now() - t_queued) * 1e3, batch);
+                      (t_setup - t_start) * 1e3, (t_queued - t_setup) * 1e3, (now_seconds() - t_queued) * 1e3, batch);
   if (c->profiling) prof_collect(c);
   if (st[0] & 1u) { c->last_error = "prover: inconsistent witness (a multiplier's defining constraint cannot be solved)"; return ZKGPU_EINVAL; }
   if (st[0] & 2u) { c->last_error = "prover: scalar out of range or TranscriptRng out of step"; return ZKGPU_EHIP; }
@@ -2255,7 +2222,6 @@ int prove_lockstep(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, int hos
   std::vector<uint32_t> idx;
   const bool timing = getenv("ZKGPU_PROVER_TIMING") != nullptr;
   double t_flat = 0, t_gpu = 0, t_step = 0;
-  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   for (int phase = 0;; ++phase) {
     bool any = false, bad = false;
     for (size_t i = 0; i < batch; ++i) { any |= !pr[i]->done(); bad |= pr[i]->failed(); }
@@ -2264,9 +2230,9 @@ int prove_lockstep(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, int hos
     if (pr[0]->at_ipa()) {
       // the inner-product argument of the whole batch: vectors and folds on the device (ipa_kernels.hpp), one
       // multiscalar-multiplication call per round on the tables, the three transcript messages per round on the host
-      const double t0 = now();
+      const double t0 = now_seconds();
       TRY(ipa_on_device(c, ps, pr, parallel));
-      if (timing) fprintf(stderr, "prover inner-product argument on the device: %.1f ms\n", (now() - t0) * 1e3);
+      if (timing) fprintf(stderr, "prover inner-product argument on the device: %.1f ms\n", (now_seconds() - t0) * 1e3);
       continue;
     }
     offs.assign(1, 0);
@@ -2275,7 +2241,7 @@ int prove_lockstep(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, int hos
       for (const MsmRow& r : rows[i]) offs.push_back(offs.back() + r.scalars.size());
       row_of[i + 1] = offs.size() - 1;
     }
-    const double t0 = now();
+    const double t0 = now_seconds();
     sc.resize(32 * offs.back());
     idx.resize(offs.back());
     parallel([&](size_t i) {
@@ -2285,11 +2251,11 @@ int prove_lockstep(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, int hos
     });
     const size_t n_rows = offs.size() - 1;
     pts.resize(32 * n_rows);
-    const double t1 = now();
+    const double t1 = now_seconds();
     TRY(zkgpu_msm_ps_batch(c, ps, n_rows, sc.data(), idx.data(), offs.data(), pts.data()));
-    const double t2 = now();
+    const double t2 = now_seconds();
     parallel([&](size_t i) { if (!pr[i]->done()) pr[i]->step(&pts[32 * row_of[i]], rows[i]); });
-    const double t3 = now();
+    const double t3 = now_seconds();
     t_flat += t1 - t0; t_gpu += t2 - t1; t_step += t3 - t2;
     if (timing) fprintf(stderr, "prover phase %d: %zu rows, %llu terms: flatten %.1f ms, msm %.1f ms, host step %.1f ms\n", phase,
                         n_rows, (unsigned long long)offs.back(), (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3);
@@ -2380,12 +2346,12 @@ int cloak_prove_whole(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t gens_capaci
   R1csDesc desc;
   std::vector<uint32_t> md;
   PvHostPlan hp;
-  const double t0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  const double t0 = now_seconds();
   try {
     PvCloakTrace::trace(n_in, n_out, desc, md);
     hp = pv_build(desc, md, gens_capacity);
   } catch (const std::exception& e) { c->last_error = e.what(); return ZKGPU_EINVAL; }
-  const double t1 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  const double t1 = now_seconds();
   const size_t m = 2 * nv;
   std::vector<uint8_t> vals(batch * m * 32), bl(call_seed ? 0 : batch * m * 32), giv(batch * (size_t)hp.sh.n_given * 64), rs(call_seed ? 0 : batch * 32);   // (call_seed, a call without seeds: blinding factors and rng seeds are drawn on the device, prove_device)
   std::atomic<bool> bad{false};
@@ -2406,7 +2372,7 @@ int cloak_prove_whole(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t gens_capaci
   if (bad) { c->last_error = "prover: the cloak witness does not fit the traced gadget"; return ZKGPU_EINVAL; }
   if (getenv("ZKGPU_PROVER_TIMING"))
     fprintf(stderr, "device prover: tracing the gadget + tables %.1f ms, blinding factors + witness queues %.1f ms\n", (t1 - t0) * 1e3,
-            (std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t1) * 1e3);
+            (now_seconds() - t1) * 1e3);
   return prove_device(c, ps, hp, batch, vals.data(), call_seed ? nullptr : bl.data(), giv.data(), call_seed ? nullptr : rs.data(), commitments, proofs, proof_stride, proof_len, call_seed, first, true);
 }
 
@@ -2451,6 +2417,28 @@ int r1cs_prove_whole(zkgpu_ctx* c, const zkgpu_pointset* ps, const zkgpu_r1cs_de
   });
   return prove_device(c, ps, hp, batch, values, blindings || call_seed ? blindings : bl.data(), given, call_seed ? nullptr : rs.data(), commitments, proofs, proof_stride, proof_len, call_seed, first, false);
 }
+
+// What the two exported prover calls share once their arguments are checked: the life of the call's seed (*seeds NULL: drawn),
+// the lockstep provers whole or the device prover in slices, outputs all zero after a failure, *proof_len.  com_bytes: of one
+// statement's commitments; prove(ctx, lo, hi, host_threads, call_seed, proof_len) proves statements [lo, hi) of the call on ctx
+// (lo: also the range's first position in the CALL, which a drawn seed is derived by)
+int prove_call(zkgpu_ctx* c, size_t batch, int host_threads, const uint8_t** seeds, uint8_t* commitments, size_t com_bytes, uint8_t* proofs,
+               size_t proof_stride, size_t* proof_len, const std::function<int(zkgpu_ctx*, size_t, size_t, int, const uint8_t*, size_t*)>& prove) {
+  std::lock_guard<std::recursive_mutex> lk(c->mu); PvCallSeed cs; std::atomic<size_t> len_out{0};
+  auto zero = [&] { memset(commitments, 0, com_bytes * batch); memset(proofs, 0, proof_stride * batch); };
+  if (!cs.begin(c, seeds, batch)) { zero(); return ZKGPU_EINVAL; }
+  if (c->prover_mode == 1)
+    return cs.closed(prove(c, 0, batch, host_threads, nullptr, proof_len), commitments, com_bytes * batch, proofs, proof_stride * batch, proof_len);
+  const int rc = run_sliced(c, batch, host_threads, [&](zkgpu_ctx* t, size_t lo, size_t hi, int ht) {
+    size_t pl = 0;
+    const int r = prove(t, lo, hi, ht, cs.for_device(c), &pl);
+    if (r == ZKGPU_OK) len_out = pl;
+    return r;
+  });
+  if (rc != ZKGPU_OK) { zero(); return rc; }
+  *proof_len = len_out;
+  return ZKGPU_OK;
+}
 }  // namespace
 
 int zkgpu_cloak_prove_batch(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t gens_capacity, size_t batch, uint32_t n_in,
@@ -2463,20 +2451,11 @@ int zkgpu_cloak_prove_batch(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t gens_
   if (!quantities || !flavors || ps->n < 2 + 2 * gens_capacity || n_in + n_out == 0) return ZKGPU_EINVAL;      // (seeds NULL: drawn, PvCallSeed)
   if (!ps->table) { c->last_error = "zkgpu_cloak_prove_batch needs zkgpu_pointset_build_tables first"; return ZKGPU_EINVAL; }
   const size_t nv = (size_t)n_in + n_out;
-  std::lock_guard<std::recursive_mutex> lk(c->mu); PvCallSeed cs; std::atomic<size_t> len_out{0};
-  if (!cs.begin(c, &seeds, batch)) { memset(commitments, 0, 64 * nv * batch); memset(proofs, 0, proof_stride * batch); return ZKGPU_EINVAL; }
-  if (c->prover_mode == 1)
-    return cs.closed(cloak_prove_whole(c, ps, gens_capacity, batch, n_in, n_out, quantities, flavors, seeds, host_threads, commitments, proofs, proof_stride, proof_len), commitments, 64 * nv * batch, proofs, proof_stride * batch, proof_len);
-  const int rc = run_sliced(c, batch, host_threads, [&](zkgpu_ctx* t, size_t lo, size_t hi, int ht) {
-    size_t pl = 0;
-    const int r = cloak_prove_whole(t, ps, gens_capacity, hi - lo, n_in, n_out, quantities + nv * lo, flavors + 32 * nv * lo, seeds ? seeds + 32 * lo : nullptr, ht,
-                                    commitments + 64 * nv * lo, proofs + proof_stride * lo, proof_stride, &pl, cs.for_device(c), lo);      // (lo: the slice's first position in the CALL)
-    if (r == ZKGPU_OK) len_out = pl;
-    return r;
+  return prove_call(c, batch, host_threads, &seeds, commitments, 64 * nv, proofs, proof_stride, proof_len,
+                    [&](zkgpu_ctx* t, size_t lo, size_t hi, int ht, const uint8_t* call_seed, size_t* pl) {
+    return cloak_prove_whole(t, ps, gens_capacity, hi - lo, n_in, n_out, quantities + nv * lo, flavors + 32 * nv * lo, seeds ? seeds + 32 * lo : nullptr, ht,
+                             commitments + 64 * nv * lo, proofs + proof_stride * lo, proof_stride, pl, call_seed, lo);
   });
-  if (rc != ZKGPU_OK) { memset(commitments, 0, 64 * nv * batch); memset(proofs, 0, proof_stride * batch); return rc; }
-  *proof_len = len_out;
-  return ZKGPU_OK;
 }
 
 int zkgpu_r1cs_prove_batch(zkgpu_ctx* c, const zkgpu_pointset* ps, const zkgpu_r1cs_desc* d, const uint32_t* mult_def,
@@ -2488,22 +2467,13 @@ int zkgpu_r1cs_prove_batch(zkgpu_ctx* c, const zkgpu_pointset* ps, const zkgpu_r
   if (batch == 0) return ZKGPU_OK;
   if (ps->n < 2 + 2 * gens_capacity || (d->n_commitments && !values) || (n_given && !given)) return ZKGPU_EINVAL;      // (seeds NULL: drawn, PvCallSeed)
   if (!ps->table) { c->last_error = "zkgpu_r1cs_prove_batch needs zkgpu_pointset_build_tables first"; return ZKGPU_EINVAL; }
-  std::lock_guard<std::recursive_mutex> lk(c->mu); PvCallSeed cs; std::atomic<size_t> len_out{0};
   const size_t m = d->n_commitments;
-  if (!cs.begin(c, &seeds, batch)) { memset(commitments, 0, 32 * m * batch); memset(proofs, 0, proof_stride * batch); return ZKGPU_EINVAL; }
-  if (c->prover_mode == 1)
-    return cs.closed(r1cs_prove_whole(c, ps, d, mult_def, gens_capacity, batch, values, blindings, given, n_given, seeds, host_threads, commitments, proofs, proof_stride, proof_len), commitments, 32 * m * batch, proofs, proof_stride * batch, proof_len);
-  const int rc = run_sliced(c, batch, host_threads, [&](zkgpu_ctx* t, size_t lo, size_t hi, int ht) {
-    size_t pl = 0;
-    const int r = r1cs_prove_whole(t, ps, d, mult_def, gens_capacity, hi - lo, values ? values + 32 * m * lo : nullptr,
-                                   blindings ? blindings + 32 * m * lo : nullptr, given ? given + 64 * n_given * lo : nullptr, n_given,
-                                   seeds ? seeds + 32 * lo : nullptr, ht, commitments + 32 * m * lo, proofs + proof_stride * lo, proof_stride, &pl, cs.for_device(c), lo);
-    if (r == ZKGPU_OK) len_out = pl;
-    return r;
+  return prove_call(c, batch, host_threads, &seeds, commitments, 32 * m, proofs, proof_stride, proof_len,
+                    [&](zkgpu_ctx* t, size_t lo, size_t hi, int ht, const uint8_t* call_seed, size_t* pl) {
+    return r1cs_prove_whole(t, ps, d, mult_def, gens_capacity, hi - lo, values ? values + 32 * m * lo : nullptr,
+                            blindings ? blindings + 32 * m * lo : nullptr, given ? given + 64 * n_given * lo : nullptr, n_given,
+                            seeds ? seeds + 32 * lo : nullptr, ht, commitments + 32 * m * lo, proofs + proof_stride * lo, proof_stride, pl, call_seed, lo);
   });
-  if (rc != ZKGPU_OK) { memset(commitments, 0, 32 * m * batch); memset(proofs, 0, proof_stride * batch); return rc; }
-  *proof_len = len_out;
-  return ZKGPU_OK;
 }
 
 int zkgpu_decode_check(zkgpu_ctx* c, const uint8_t* points, size_t n, uint8_t* ok) {

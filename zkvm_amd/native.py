@@ -612,6 +612,55 @@ class R1csDescription:
                                      k[4], k[5], k[6])
 
 
+PV_PLAN_TABLES = ("init", "mono_chal", "mono_pow", "con_off", "t_kind", "t_idx", "t_mono", "t_coef", "mult_def", "given_slot", "tgt_off",
+                  "term_info", "prod_qm", "prod_coef", "chal_labels", "draw")
+PV_WORKSPACE = ("pv_state", "pv_rows0", "pv_rows1", "pv_rows2", "pv_rows3", "pv_pts", "pv_com", "pv_ab", "pv_proofs", "ipa_lv", "ipa_rv",
+                "ipa_cg", "ipa_ch", "ipa_w", "ipa_u", "in_st_scalars", "in_st_index", "status", "digits", "st_partials", "rechk_pts")
+PV_STEP_KINDS = ("phase0", "msm", "lanes", "wg", "rng", "ipa", "finish")
+PV_SHAPE = ("m", "n1", "n", "pn", "k", "n_given", "r1_terms", "r2_terms", "state_words", "proof_stride", "gens_capacity")
+
+
+def prover_call_plan(batch: int, W: int, gens_capacity: int, desc: Optional["R1csDescription"] = None, mult_def: Optional[Sequence[int]] = None,
+                     cloak: Optional[Tuple[int, int]] = None, seeded: bool = False, blindings: bool = True) -> dict:
+    """What one device prover call settles before its first launch (csrc/prover_call_plan.hpp through libzkhost's
+    zkhost_prover_call_plan; no GPU needed) -- of the (n_in, n_out) cloak, or of a described system (mult_def None: every
+    multiplier given).  W: windows of the generator tables.  -> the plan's numbers by name ("in", "at", "msm", "ws": dicts /
+    a list of dicts; "shape": the statement shape it was made for), "steps" as (kind, phase, mask) triples, "blob" (words) and "lay" (the filled scaffolding bytes)."""
+    host = C.CDLL(os.path.join(HERE, "lib", "libzkhost.so"))
+    if cloak is None:
+        k = desc._keep                        # (the arrays themselves: a c_char_p read back from the struct stops at a zero byte)
+        head = (desc.label, desc.m, desc.n1, desc.n, len(desc.challenge_labels), k[0], len(desc.constraints), k[1], k[2], k[3], k[4], k[5], k[6],
+                None if mult_def is None else (C.c_uint32 * max(len(mult_def), 1))(*mult_def), 0, 0)
+    else:
+        head = (None, 0, 0, 0, 0, None, 0, None, None, None, None, None, None, None, cloak[0], cloak[1])
+    flags = (1 if seeded else 0) | (2 if cloak is not None else 0) | (4 if blindings else 0)
+    fn = host.zkhost_prover_call_plan
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_uint64),
+                   C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                   C.c_uint32, C.c_uint32, C.c_size_t, C.c_size_t, C.c_int, C.c_uint32,
+                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p]
+    tail = (gens_capacity, batch, W, flags)
+    nums = (C.c_uint64 * (10 + len(PV_PLAN_TABLES) + 30 + len(PV_WORKSPACE) + len(PV_SHAPE)))()
+    rc = fn(*head, *tail, nums, None, None, None)
+    if rc != 0:
+        raise ZkGpuError(EINVAL, "zkhost_prover_call_plan: %d" % rc)
+    n = list(nums)
+    steps, blob, lay = (C.c_uint32 * (3 * n[0]))(), (C.c_uint32 * max(n[1], 1))(), C.create_string_buffer(max(n[2], 1))
+    rc = fn(*head, *tail, nums, steps, blob, lay)
+    if rc != 0 or list(nums) != n:
+        raise ZkGpuError(EINVAL, "zkhost_prover_call_plan: %d" % rc)
+    at, msm, ws = 10, 10 + len(PV_PLAN_TABLES), 40 + len(PV_PLAN_TABLES)
+    shape = ws + len(PV_WORKSPACE)
+    return {"draw_blindings": bool(n[3]), "ipa_row_len": n[4], "lay_bytes": n[2],
+            "in": dict(zip(("values", "blindings", "given", "seeds", "bytes"), n[5:10])),
+            "at": dict(zip(PV_PLAN_TABLES, n[at:msm])),
+            "msm": [dict(zip(("rows", "terms", "P", "kinds", "o_off", "o_idx"), n[msm + 6 * i: msm + 6 * i + 6])) for i in range(5)],
+            "ws": dict(zip(PV_WORKSPACE, n[ws:shape])), "shape": dict(zip(PV_SHAPE, n[shape:])),
+            "steps": [(PV_STEP_KINDS[steps[3 * i]], steps[3 * i + 1], steps[3 * i + 2]) for i in range(n[0])],
+            "blob": list(blob)[: n[1]], "lay": lay.raw[: n[2]]}
+
+
 def shard_cuts(shapes: Sequence[Tuple[int, int]], world: int):
     """zkgpu_shard_cuts: contiguous shards of a block, balanced by multiscalar-multiplication terms (no GPU needed)."""
     lib = load_library()
