@@ -602,7 +602,7 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * stay on the host: they are known from the transaction's own bytes before anything reaches the device.  Opt-in. */
 #define ZKGPU_TXFORMAT_SIGN_ON_DEVICE 512   /* 0x200 */
 /* A third FLAG, or-ed to any valid value above but 0 (valid values of the call: 0, and {1, 2} x {0, 0x100, 0x300} x {0, 0x400};
- * alone, on a value that is invalid without it, or with any higher bit it is ZKGPU_EINVAL): the Ok side of upstream's
+ * alone, on a value that is invalid without it, or with any higher bit but those of the next flag it is ZKGPU_EINVAL): the Ok side of upstream's
  * Result<VerifiedTx, VMError> -- the TRANSACTION ID of every accepted transaction comes back with the verdicts.
  *
  *   !!  WITH THIS FLAG SET, THE `status` ARGUMENT OF zkgpu_tx_verify_batch AND zkgpu_tx_verify_wait POINTS AT  !!
@@ -617,8 +617,40 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * remembers it.  The accept bitmap is unchanged in every case.  Nothing is hashed for it: the IDs are the ones the
  * signature was checked against -- the host VM's, or with ZKGPU_TXFORMAT_HASH_ON_DEVICE the device's; all the flag adds on
  * the device is one copy of 32 bytes per transaction beside ZKGPU_TXFORMAT_SIGN_ON_DEVICE, which otherwise leaves them
- * there.  The IDs of the log's entries (contract IDs) do not come back: no argument can carry their number. */
+ * there.  The IDs of the log's entries (contract IDs) come back with the next flag. */
 #define ZKGPU_TXFORMAT_RETURN_IDS 1024   /* 0x400 */
+/* A fourth FLAG, only TOGETHER WITH ZKGPU_TXFORMAT_RETURN_IDS, and only with a window K in bits 16 .. 23 of the format
+ * (format | ZKGPU_TXFORMAT_RETURN_LOG | K << ZKGPU_TXFORMAT_LOG_SHIFT, 1 <= K <= 255): the second third of VerifiedTx -- the
+ * Input(id) / Output(id) entries of every accepted transaction's LOG, i.e. the contract IDs a node removes from and inserts
+ * into its UTXO set when it applies the block.  ZKGPU_EINVAL: the flag without ZKGPU_TXFORMAT_RETURN_IDS (0x801), the flag
+ * with K = 0, bits 16 .. 23 without the flag, any bit from 0x1000 to 0x8000, any bit from 24 up.
+ *
+ *   !!  WITH THIS FLAG SET, THE `status` ARGUMENT OF zkgpu_tx_verify_batch AND zkgpu_tx_verify_wait POINTS AT       !!
+ *   !!  batch * (33 + 1 + 33 * K) BYTES, NOT 33 * batch AND NOT batch.  A caller that sets the flag and passes      !!
+ *   !!  33 * batch bytes IS OVERRUN by batch * (1 + 33 * K): WITH K = 255 THAT IS 8416 BYTES PER TRANSACTION.       !!
+ *
+ * Bytes [0, batch) are the status bytes and [batch, 33 * batch) the transaction IDs, byte for byte what the same format
+ * writes without this flag.  Then follow `batch` log records of 1 + 33 * K bytes, in call order:
+ *     count:u8 | kind[K]:u8 | id[K][32]
+ * Beside status 0 and accept bit 1: count = the number of Input / Output entries of the transaction's log; kind[j]
+ * (ZKGPU_TXLOG_INPUT / ZKGPU_TXLOG_OUTPUT) and id[j] for j < count are those entries in the order the program logged them
+ * (the header entry is not listed); everything past `count` is zero.  An accepted transaction with MORE than K entries: count
+ * is the real number, saturated at 255, and every kind and ID byte is zero (bit, status byte and transaction ID are unchanged)
+ * -- the caller reads count > K and asks again with a wider window, or asks its own VM.  (count saturates: under K = 255 a
+ * count of 255 with kind[0] == 0 means "255 OR MORE entries, not listed" -- a listed entry never has kind 0, so a decoder
+ * treats count >= 1 with kind[0] == 0 as "did not fit" whatever K is.)  Everywhere else -- a rejected
+ * transaction whatever the reason, status 2, every transaction of a call that returns an error -- all 1 + 33 * K bytes are
+ * zero.  Fail-closed exactly as the IDs are: the area is zeroed before the call starts and again on any error; a record is
+ * written at the very end, only beside a set bit.  status == NULL stays legal.  A submitted call keeps the layout, K
+ * included, that was in force when zkgpu_tx_verify_submit QUEUED it; calls merged into one round keep one area each.  The
+ * accept bitmap is unchanged in every case.  Nothing is hashed for it: the contract IDs are those the transaction ID was
+ * hashed from -- the host VM's, or with ZKGPU_TXFORMAT_HASH_ON_DEVICE the device's, gathered there by one more launch per
+ * chunk and brought down by one more copy of 32 * K bytes per transaction.  No host fallback: an error of that launch or
+ * copy is an error of the call. */
+#define ZKGPU_TXFORMAT_RETURN_LOG 2048   /* 0x800; only together with ZKGPU_TXFORMAT_RETURN_IDS */
+#define ZKGPU_TXFORMAT_LOG_SHIFT 16      /* bits 16..23 of the format: K, the log entries kept per transaction, 1..255 */
+#define ZKGPU_TXLOG_INPUT 1
+#define ZKGPU_TXLOG_OUTPUT 2
 #define ZKGPU_TXSTATUS_ACCEPTED 0
 #define ZKGPU_TXSTATUS_REJECTED 1                 /* rejected, reason not available (V1 format, or any error path) */
 #define ZKGPU_TXSTATUS_OUTSIDE_SUBSET 2

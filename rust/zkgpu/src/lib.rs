@@ -32,7 +32,7 @@
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
 use std::ptr;
-use std::sync::atomic::{AtomicBool, Ordering};
+use std::sync::atomic::{AtomicBool, AtomicUsize, Ordering};
 
 use zkgpu_sys as sys;
 
@@ -171,6 +171,8 @@ pub struct TxCall<'v> {
     n: usize,
     /// submitted under `ZKGPU_TXFORMAT_RETURN_IDS`: the library writes 33 * n status bytes for this call, whatever the format says later
     ids: bool,
+    /// ... and under `ZKGPU_TXFORMAT_RETURN_LOG` with this window (0: no): `(33 + 1 + 33 * log_k) * n` bytes
+    log_k: usize,
     waited: bool,
     _blob: Vec<u8>,
     _offsets: Vec<u64>,
@@ -201,6 +203,26 @@ pub struct GpuVerifier {
     /// the transaction format set last carries `ZKGPU_TXFORMAT_RETURN_IDS`: the library then writes 33 bytes per
     /// transaction into the status array of a transaction call, and every call here sizes the array by this
     return_ids: AtomicBool,
+    /// ... and `ZKGPU_TXFORMAT_RETURN_LOG` with this window K (0: no): 33 + 1 + 33 K bytes per transaction
+    log_k: AtomicUsize,
+}
+
+/// One `Input(id)` / `Output(id)` entry of an accepted transaction's log: the contract a node removes from, or inserts into,
+/// its UTXO set when it applies the transaction (`VerifiedTx.log` of the reference, without the header entry).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum TxLogEntry {
+    Input([u8; 32]),
+    Output([u8; 32]),
+}
+
+/// The log entries `verify_txs_with_log` hands back beside an accepted transaction.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub enum TxLog {
+    /// in the order the program logged them
+    Entries(Vec<TxLogEntry>),
+    /// the transaction logs this many entries (saturated at 255: then "at least"), more than the window holds: ask again
+    /// with a wider window, or ask your own VM
+    MoreThanWindow(usize),
 }
 
 // the library serialises calls on a verifier with its own mutex, and hands out its error text as a per-thread copy made
@@ -254,7 +276,7 @@ impl GpuVerifier {
         match built {
             Ok((ps, v, warned)) => {
                 let warning = if warned { Some(text(unsafe { sys::zkgpu_verifier_last_error(v) })) } else { None };
-                Ok(GpuVerifier { ctx, gens: Generators { ps, capacity: gens_capacity }, v, warning, return_ids: AtomicBool::new(false) })
+                Ok(GpuVerifier { ctx, gens: Generators { ps, capacity: gens_capacity }, v, warning, return_ids: AtomicBool::new(false), log_k: AtomicUsize::new(0) })
             }
             Err(e) => {
                 unsafe { sys::zkgpu_destroy(ctx) };
@@ -349,6 +371,8 @@ impl GpuVerifier {
     fn set_tx_format(&self, format: c_int) -> Result<(), Error> {
         check(unsafe { sys::zkgpu_verifier_set_tx_format(self.v, format) }, self.err())?;
         self.return_ids.store(format & sys::ZKGPU_TXFORMAT_RETURN_IDS != 0, Ordering::SeqCst);
+        let k = if format & sys::ZKGPU_TXFORMAT_RETURN_LOG != 0 { ((format >> sys::ZKGPU_TXFORMAT_LOG_SHIFT) & 255) as usize } else { 0 };
+        self.log_k.store(k, Ordering::SeqCst);
         Ok(())
     }
 
@@ -388,9 +412,59 @@ impl GpuVerifier {
         self.set_tx_format(base | hash | sign | sys::ZKGPU_TXFORMAT_RETURN_IDS)
     }
 
-    /// status array of a call of `n` transactions: `n` bytes, or `33 * n` under `ZKGPU_TXFORMAT_RETURN_IDS`
-    fn tx_status_len(n: usize, ids: bool) -> usize {
-        if ids { 33 * n } else { n }
+    /// `enable_recollected_tx_format_returning_ids` with `ZKGPU_TXFORMAT_RETURN_LOG` and a window of `k` entries (1 ..= 255)
+    /// beside it: `verify_txs_with_log` then also hands back the `Input` / `Output` entries of every accepted transaction's
+    /// log, from which a shim fills `VerifiedTx.log` and a node applies the block to its UTXO set.  Same verdicts, same IDs.
+    pub fn enable_recollected_tx_format_returning_log(&self, k: usize, with_reasons: bool, hash_on_device: bool, sign_on_device: bool) -> Result<(), Error> {
+        if k == 0 || k > 255 {
+            return Err(Error::InvalidArgument("the log window is 1 ..= 255 entries".into()));
+        }
+        if sign_on_device && !hash_on_device {
+            return Err(Error::InvalidArgument("signing on the device needs hashing on the device".into()));
+        }
+        let base = if with_reasons { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS } else { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1 };
+        let hash = if hash_on_device { sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE } else { 0 };
+        let sign = if sign_on_device { sys::ZKGPU_TXFORMAT_SIGN_ON_DEVICE } else { 0 };
+        let log = sys::ZKGPU_TXFORMAT_RETURN_LOG | ((k as c_int) << sys::ZKGPU_TXFORMAT_LOG_SHIFT);
+        self.set_tx_format(base | hash | sign | sys::ZKGPU_TXFORMAT_RETURN_IDS | log)
+    }
+
+    /// status array of a call of `n` transactions: `n` bytes, `33 * n` under `ZKGPU_TXFORMAT_RETURN_IDS`, and
+    /// `(33 + 1 + 33 * log_k) * n` under `ZKGPU_TXFORMAT_RETURN_LOG` with window `log_k`
+    fn tx_status_len(n: usize, ids: bool, log_k: usize) -> usize {
+        if !ids {
+            n
+        } else if log_k == 0 {
+            33 * n
+        } else {
+            (33 + 1 + 33 * log_k) * n
+        }
+    }
+
+    /// the log records behind the ID area -> beside every `Accepted` its entries
+    fn tx_logs(n: usize, log_k: usize, verdicts: &[(TxVerdict, Option<[u8; 32]>)], status: &[u8]) -> Vec<Option<TxLog>> {
+        let per = 1 + 33 * log_k;
+        (0..n)
+            .map(|i| {
+                if log_k == 0 || verdicts[i].0 != TxVerdict::Accepted {
+                    return None;
+                }
+                let rec = &status[33 * n + per * i..33 * n + per * (i + 1)];
+                let count = rec[0] as usize;
+                // (count saturates at 255: a record that lists its entries has no kind byte of 0)
+                if count > log_k || (count > 0 && rec[1] == 0) {
+                    return Some(TxLog::MoreThanWindow(count));
+                }
+                let entries = (0..count)
+                    .map(|j| {
+                        let mut id = [0u8; 32];
+                        id.copy_from_slice(&rec[1 + log_k + 32 * j..1 + log_k + 32 * j + 32]);
+                        if rec[1 + j] as c_int == sys::ZKGPU_TXLOG_INPUT { TxLogEntry::Input(id) } else { TxLogEntry::Output(id) }
+                    })
+                    .collect();
+                Some(TxLog::Entries(entries))
+            })
+            .collect()
     }
 
     /// status bytes (+ the ID area, if the call had one) and bitmap -> a verdict per transaction, and beside `Accepted` its ID
@@ -419,6 +493,13 @@ impl GpuVerifier {
     /// `verify_txs`, and beside every `Accepted` the transaction ID -- `Some` only after
     /// `enable_recollected_tx_format_returning_ids`, `None` beside every other verdict: the `VerifiedTx.id` of the reference.
     pub fn verify_txs_with_ids(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<(TxVerdict, Option<[u8; 32]>)>, Error> {
+        Ok(self.verify_txs_with_log(txs, host_threads)?.into_iter().map(|(verdict, id, _)| (verdict, id)).collect())
+    }
+
+    /// `verify_txs_with_ids`, and beside every `Accepted` the `Input` / `Output` entries of its log -- `Some` only after
+    /// `enable_recollected_tx_format_returning_log`, `None` beside every other verdict: the `VerifiedTx.log` of the reference
+    /// without its header entry.
+    pub fn verify_txs_with_log(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<(TxVerdict, Option<[u8; 32]>, Option<TxLog>)>, Error> {
         let n = txs.len();
         if n == 0 {
             return Ok(Vec::new());
@@ -431,15 +512,18 @@ impl GpuVerifier {
             offs.push(blob.len() as u64);
         }
         let ids = self.return_ids.load(Ordering::SeqCst);
+        let log_k = if ids { self.log_k.load(Ordering::SeqCst) } else { 0 };
         let mut bitmap = vec![0u8; (n + 7) / 8];
-        let mut status = vec![1u8; Self::tx_status_len(n, ids)];
+        let mut status = vec![1u8; Self::tx_status_len(n, ids, log_k)];
         check(
             unsafe {
                 sys::zkgpu_tx_verify_batch(self.v, n, blob.as_ptr(), offs.as_ptr(), host_threads as c_int, bitmap.as_mut_ptr(), status.as_mut_ptr())
             },
             self.err(),
         )?;
-        Ok(Self::tx_verdicts_with_ids(n, ids, &bitmap, &status))
+        let verdicts = Self::tx_verdicts_with_ids(n, ids, &bitmap, &status);
+        let logs = Self::tx_logs(n, log_k, &verdicts, &status);
+        Ok(verdicts.into_iter().zip(logs).map(|((verdict, id), log)| (verdict, id, log)).collect())
     }
 
     /// `verify_txs` in two halves, callable from many threads at once (upstream's `Tx::verify` is pure and `&self`): the
@@ -459,9 +543,10 @@ impl GpuVerifier {
         }
         let mut id = 0u64;
         let ids = self.return_ids.load(Ordering::SeqCst); // (the layout of the call's status array is the one in force now)
+        let log_k = if ids { self.log_k.load(Ordering::SeqCst) } else { 0 };
         // (the heap buffers of `blob` and `offsets` do not move when the vectors are moved into the handle)
         check(unsafe { sys::zkgpu_tx_verify_submit(self.v, n, blob.as_ptr(), offsets.as_ptr(), host_threads as c_int, &mut id) }, self.err())?;
-        Ok(TxCall { verifier: self, id, n, ids, waited: false, _blob: blob, _offsets: offsets })
+        Ok(TxCall { verifier: self, id, n, ids, log_k, waited: false, _blob: blob, _offsets: offsets })
     }
 
     /// Blocks until the call's round is done: one verdict per transaction of THAT call.
@@ -477,7 +562,7 @@ impl GpuVerifier {
         }
         let n = call.n;
         let mut bitmap = vec![0u8; (n + 7) / 8];
-        let mut status = vec![1u8; Self::tx_status_len(n, call.ids)];
+        let mut status = vec![1u8; Self::tx_status_len(n, call.ids, call.log_k)];
         let rc = unsafe { sys::zkgpu_tx_verify_wait(self.v, call.id, bitmap.as_mut_ptr(), status.as_mut_ptr()) };
         call.waited = true; // (whatever it returned, the library is done with the call's bytes)
         check(rc, self.err())?;

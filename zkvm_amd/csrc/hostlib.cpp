@@ -1190,6 +1190,9 @@ class HostTxDevice : public TxDevice {
   // a caller that is handed the transaction IDs (ZKGPU_TXFORMAT_RETURN_IDS): said before the call is made
   bool ids() const override { return ids_; }
   void set_ids(bool on) { ids_ = on; }
+  // ... and the log's entries, at most k per transaction (ZKGPU_TXFORMAT_RETURN_LOG; only with ids)
+  size_t log_k() const override { return ids_ ? log_k_ : 0; }
+  void set_log_k(size_t k) { log_k_ = k; }
   size_t leaked() { std::lock_guard<std::mutex> lk(mu_); return staged_total_ - released_total_; }
 
  protected:
@@ -1221,6 +1224,7 @@ class HostTxDevice : public TxDevice {
   uint8_t base_[32];
   std::string err_;
   bool ids_ = false;
+  size_t log_k_ = 0;
 };
 }  // namespace
 
@@ -1388,6 +1392,17 @@ class HostHashingTxDevice : public HostTxDevice {
     s.th = std::thread([this, &s, us] {
       std::this_thread::sleep_for(std::chrono::microseconds(us));
       hash_tape_run_host(s.tape.block(), protos_, labels_, s.slots, s.ids);
+      // (the caller is handed the log: what k_tx_log_gather does, lane by lane, with the table the device would be sent)
+      const size_t K = log_k();
+      s.log_ok = true;
+      if (K && s.tape.n_tx()) {
+        std::vector<uint32_t> table;
+        s.log_ok = tx_log_table(s.tape.block(), table) && tx_log_lanes_fit(s.tape.n_tx(), K);
+        s.log.assign(8 * K * s.tape.n_tx(), 0xa5a5a5a5u);
+        for (uint32_t idx = 0; s.log_ok && idx < (uint32_t)(K * s.tape.n_tx()); ++idx)
+          tx_log_gather_lane(s.tape.block(), table.data(), s.slots.data(), s.log.data(), idx, (uint32_t)K);
+        if (s.log_ok) logged_ += tx_log_handed_back(s.tape.block(), table, K);
+      }
       s.done = true;
     });
     return 0;
@@ -1405,9 +1420,11 @@ class HostHashingTxDevice : public HostTxDevice {
   std::string last_error() override { return herr_.empty() ? HostTxDevice::last_error() : herr_; }
   uint64_t hashed() const { return hashed_; }
   uint64_t id_asks() const { return id_asks_; }           // collects that were given a host buffer for the IDs
+  const uint8_t* hash_log(int slot) override { return log_k() && h_[slot].log_ok ? (const uint8_t*)h_[slot].log.data() : nullptr; }
+  uint64_t logged() const { return logged_; }             // log entries the stand-in's gather handed back
 
  protected:
-  struct HashStage { TxHashTape tape; std::thread th; std::atomic<bool> done{true}; std::vector<uint32_t> slots, ids; };
+  struct HashStage { TxHashTape tape; std::thread th; std::atomic<bool> done{true}; std::vector<uint32_t> slots, ids, log; bool log_ok = true; };
   bool hash_failing() { return hash_fail_at_ >= 0 && hops_++ == hash_fail_at_; }
   HashStage h_[2];
   std::vector<uint32_t> protos_;
@@ -1416,6 +1433,7 @@ class HostHashingTxDevice : public HostTxDevice {
   const int hash_fail_at_;
   int hops_ = 0;
   uint64_t hashed_ = 0, id_asks_ = 0;
+  std::atomic<uint64_t> logged_{0};
   std::string herr_;
 };
 }  // namespace
@@ -1631,4 +1649,116 @@ extern "C" int zkhost_txcall_ids_selftest(int kind, int return_ids, size_t batch
   }
   std::memcpy(accept_bitmap, round_bits.data(), (batch + 7) / 8);
   return 0;
+}
+
+// ---- a call whose caller is also handed the LOG's entries (TxDevice::log_k: ZKGPU_TXFORMAT_RETURN_LOG with window K) on the CPU,
+// ---- over the same three stand-ins -- kind 0: the host's second pass fills the records; 1, 2: the hashing stage gathers the
+// ---- entries' contract IDs (tx_log_gather_lane, the kernel's code) and the call adds counts and kinds -- laid out and fail-closed
+// ---- as session.hpp does it.  split = 0: a lone call, status_a is batch * (33 + 1 + 33 K) bytes; split > 0 (a multiple of 8,
+// ---- < batch): two callers' pieces of one merged call, status_a split * (33 + 1 + 33 K) bytes and status_b (batch - split) *
+// ---- (33 + 1 + 33 k_b) with a window k_b of its own (0: K; the round's device gathers the wider of the two).  fail_at /
+// ---- fail_stage as zkhost_txcall_ids_selftest.  out[0] chunks, out[1] staged chunks never released, out[2] transactions the
+// ---- HOST's second pass hashed, out[3] IDs the stand-in's hashing stage produced, out[4] log entries its gather handed back,
+// ---- out[5] whether a failed call had left anything in an ID or record area before it was fail-closed (must be 0)
+extern "C" int zkhost_txcall_log_selftest(int kind, size_t K, size_t k_b, size_t batch, size_t split, const uint8_t* txs, const uint64_t* offs,
+                                          const uint8_t* proof_ok, int host_threads, size_t chunk, uint32_t delay_seed, int fail_at, int fail_stage,
+                                          int n_slots, uint8_t* accept_bitmap, uint8_t* status_a, uint8_t* status_b, uint64_t* out) {
+  for (int q = 0; q < 6; ++q) out[q] = 0;
+  if (kind < 0 || kind > 2 || fail_stage < 0 || fail_stage > kind || K < 1 || K > 255 || k_b > 255 || !status_a ||
+      (split && (split >= batch || split % 8 || !status_b))) return -1;
+  if (k_b == 0) k_b = K;
+  const int f0 = fail_stage == 0 ? fail_at : -1, f1 = fail_stage == 1 ? fail_at : -1, f2 = fail_stage == 2 ? fail_at : -1;
+  std::unique_ptr<HostTxDevice> dev;
+  if (kind == 0) dev.reset(new HostTxDevice(txs, offs, batch, proof_ok, delay_seed, f0));
+  else if (kind == 1) dev.reset(new HostHashingTxDevice(txs, offs, batch, proof_ok, delay_seed, f1, f0));
+  else dev.reset(new HostChainingTxDevice(txs, offs, batch, proof_ok, delay_seed, f2, f1, f0));
+  dev->set_ids(true);
+  dev->set_log_k(split ? std::max(K, k_b) : K);
+  const size_t na = split ? split : batch, nb = split ? batch - split : 0;
+  uint8_t* const ids_a = status_a + na;
+  uint8_t* const log_a = status_a + 33 * na;
+  uint8_t* const ids_b = nb ? status_b + nb : nullptr;
+  uint8_t* const log_b = nb ? status_b + 33 * nb : nullptr;
+  const size_t la = na * tx_log_record_bytes(K), lb = nb * tx_log_record_bytes(k_b);
+  std::memset(accept_bitmap, 0, (batch + 7) / 8);
+  std::memset(status_a, TX_INVALID, na);
+  std::memset(ids_a, 0, 32 * na + la);
+  if (nb) { std::memset(status_b, TX_INVALID, nb); std::memset(ids_b, 0, 32 * nb + lb); }
+  std::vector<uint8_t> round_bits((batch + 7) / 8 + 1, 0), round_status(split ? batch : 0, (uint8_t)TX_INVALID);
+  std::vector<TxStatement> store;
+  int rc;
+  {
+    std::unique_ptr<TxCall> call;
+    if (split == 0) {
+      call.reset(new TxCall(*dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, round_bits.data(), status_a, n_slots));
+    } else {
+      std::vector<TxCall::Piece> pieces{{txs, offs, na, ids_a, log_a, K}, {txs, offs + split, nb, ids_b, log_b, k_b}};
+      call.reset(new TxCall(*dev, store, (size_t)1 << 17, pieces, host_threads, chunk, round_bits.data(), round_status.data(), n_slots));
+    }
+    out[0] = call->n_chunks();
+    rc = call->run();
+    out[2] = call->n_host_hashed();
+  }
+  out[1] = dev->leaked();
+  if (kind >= 1) { out[3] = static_cast<HostHashingTxDevice*>(dev.get())->hashed(); out[4] = static_cast<HostHashingTxDevice*>(dev.get())->logged(); }
+  if (split) {
+    for (size_t i = 0; i < batch; ++i) {
+      uint8_t& to = i < split ? status_a[i] : status_b[i - split];
+      if (rc == 0) to = round_status[i]; else if (round_status[i] == TX_UNSUPPORTED) to = TX_UNSUPPORTED;
+    }
+  }
+  if (rc != 0) {
+    for (size_t i = 0; i < 32 * na + la; ++i) if (ids_a[i]) out[5] = 1;
+    for (size_t i = 0; nb && i < 32 * nb + lb; ++i) if (ids_b[i]) out[5] = 1;
+    if (split == 0) for (size_t i = 0; i < batch; ++i) if (status_a[i] != TX_UNSUPPORTED) status_a[i] = TX_INVALID;
+    std::memset(ids_a, 0, 32 * na + la);
+    if (nb) std::memset(ids_b, 0, 32 * nb + lb);
+    return rc;
+  }
+  std::memcpy(accept_bitmap, round_bits.data(), (batch + 7) / 8);
+  return 0;
+}
+
+// ---- tx_prepare_many_logged (tx_log.hpp) restates tx_prepare_many (zkvm_tx.hpp), which cannot be touched: the two second passes
+// ---- side by side over the same transactions in the same groups of eight, statement by statement -- status, reason text, header,
+// ---- transaction ID, arity, commitments, where the proof lies, the signature's scalars and points.  -> statements that differ
+// ---- (must be 0), -1 on bad arguments.  *lockstep_groups (may be NULL): groups of eight whose plans had one shape, i.e. that
+// ---- AVX-512 hashes in lockstep where the CPU has it -- so that a test knows it compared both ways of running the plans.
+extern "C" long long zkhost_tx_prepare_logged_compare(const uint8_t* txs, const uint64_t* offs, size_t batch, size_t K, uint64_t* lockstep_groups) {
+  if (!txs || !offs || K < 1 || K > 255) return -1;
+  long long differ = 0;
+  uint64_t same_shape_groups = 0;
+  std::vector<uint8_t> recs(8 * tx_log_record_bytes(K));
+  for (size_t first = 0; first < batch; first += 8) {
+    const size_t cnt = std::min<size_t>(8, batch - first);
+    const uint8_t* p[8];
+    size_t l[8];
+    for (size_t q = 0; q < cnt; ++q) { p[q] = txs + offs[first + q]; l[q] = (size_t)(offs[first + q + 1] - offs[first + q]); }
+    TxStatement a[8], b[8];
+    std::fill(recs.begin(), recs.end(), (uint8_t)0);
+    tx_prepare_many(p, l, a, cnt, true, ALL_PROTOS);
+    tx_prepare_many_logged(p, l, b, cnt, recs.data(), K);
+    bool one_shape = cnt >= 3;
+    TxPlan P0, P;
+    TxSlots out;
+    TxStatement s2;
+    for (size_t q = 0; q < cnt; ++q) {
+      const TxStatement &x = a[q], &y = b[q];
+      const bool same = x.status == y.status && std::strcmp(x.why, y.why) == 0 && x.version == y.version && x.mintime == y.mintime &&
+                        x.maxtime == y.maxtime && std::memcmp(x.txid, y.txid, 32) == 0 && x.n_in == y.n_in && x.n_out == y.n_out &&
+                        x.commitments.size() == y.commitments.size() && std::memcmp(x.commitments.data(), y.commitments.data(), x.commitments.size()) == 0 &&
+                        x.proof == y.proof && x.proof_len == y.proof_len && x.sig_scalars.size() == y.sig_scalars.size() &&
+                        std::memcmp(x.sig_scalars.data(), y.sig_scalars.data(), x.sig_scalars.size()) == 0 && x.sig_points.size() == y.sig_points.size() &&
+                        std::memcmp(x.sig_points.data(), y.sig_points.data(), x.sig_points.size()) == 0;
+      if (!same) ++differ;
+      // (a statement the VM does not accept has no record)
+      if (x.status != TX_OK) for (size_t i = 0; i < tx_log_record_bytes(K); ++i) if (recs[q * tx_log_record_bytes(K) + i]) { ++differ; break; }
+      (q == 0 ? P0 : P).only = 0xff;
+      tx_structure(p[q], l[q], s2, q == 0 ? P0 : P, out);
+      if (s2.status != TX_OK || (q > 0 && !P.same_shape(P0))) one_shape = false;
+    }
+    if (one_shape) ++same_shape_groups;
+  }
+  if (lockstep_groups) *lockstep_groups = same_shape_groups;
+  return differ;
 }

@@ -111,13 +111,26 @@ struct zkgpu_verifier {
     void *h_in = nullptr, *h_out = nullptr;
     size_t h_in_cap = 0, h_out_cap = 0, n_tx = 0;
     Buffer d_tape, d_slots, d_txid;
+    // ZKGPU_TXFORMAT_RETURN_LOG: the shapes' entry table on its way up, the gathered contract IDs (n_tx x K x 32 bytes) on
+    // their way down; entries the stage in flight hands back
+    void *h_tab = nullptr, *h_log = nullptr;
+    size_t h_tab_cap = 0, h_log_cap = 0;
+    uint64_t n_logged = 0;
+    bool logged = false, ids_marked = false;
+    hipEvent_t ev_ids = nullptr;                        // (a chain beside the flag: recorded behind k_tx_hash, what its challenge kernel waits for)
+    std::vector<uint32_t> log_table;
+    Buffer d_tab, d_log;
   };
   TxHashStage tx_hash[2];
   Buffer tx_hash_const;
   bool tx_sign_on_device = false;                       // the flag ZKGPU_TXFORMAT_SIGN_ON_DEVICE (only beside the one above)
-  // the flag ZKGPU_TXFORMAT_RETURN_IDS: the status argument of a call is 33 * batch bytes, the IDs of what was accepted behind
-  // the status bytes.  (Atomic: zkgpu_tx_verify_submit reads it without `mu`, which a round in flight holds.)
-  std::atomic<bool> tx_return_ids{false};
+  // The layout of a call's status argument, ONE word so that a call reads a pair the format had: bit 0 the flag
+  // ZKGPU_TXFORMAT_RETURN_IDS (33 * batch bytes, the IDs of what was accepted behind the status bytes), bits 8 .. 15 the window K
+  // of ZKGPU_TXFORMAT_RETURN_LOG (only beside bit 0; 0 without the flag: batch records of 1 + 33 K bytes behind the IDs).
+  // (Atomic: zkgpu_tx_verify_submit reads it without `mu`, which a round in flight holds.)
+  std::atomic<uint32_t> tx_layout{0};
+  static bool layout_ids(uint32_t layout) { return (layout & 1u) != 0; }
+  static size_t layout_log_k(uint32_t layout) { return (layout & 1u) ? (layout >> 8) & 255u : 0; }
   // what the signature's challenge needs beside its slot's signature context (tx_sig_rows.hpp): the rows' places on the tape,
   // the events that order it behind the slot's key stage and hashing stage; once per verifier, the script of the transcript
   struct TxSigStage { Buffer d_pos; hipEvent_t ev_keys = nullptr, ev_ids = nullptr; size_t rows = 0; };
@@ -154,6 +167,8 @@ struct zkgpu_verifier {
     std::vector<uint8_t> bits, status;
     bool return_ids = false;                            // the layout of its status argument, as the format said when it was SUBMITTED
     std::vector<uint8_t> txids;                         // ... then 32 bytes per transaction: zero but beside a set bit
+    size_t log_k = 0;                                   // ... and (only with return_ids) K of ZKGPU_TXFORMAT_RETURN_LOG when it was submitted
+    std::vector<uint8_t> txlog;                         // ... then a record of 1 + 33 K bytes per transaction, likewise
   };
   std::mutex tx_mu;
   std::condition_variable tx_cv;
@@ -396,7 +411,7 @@ int zkgpu_verifier_create(zkgpu_ctx* ctx, const zkgpu_pointset* ps, size_t gens_
   batches_in_flight = std::min(batches_in_flight, 1 + MAX_FORKS);
   zkgpu_verifier* v = new zkgpu_verifier();
   v->root = ctx; v->ps = ps; v->gens_capacity = gens_capacity;
-  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; ctx->tx_signed_on_device = 0; }
+  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; ctx->tx_signed_on_device = 0; ctx->tx_logged_on_device = 0; }
   v->lanes.push_back(ctx);
   v->lanes_requested = batches_in_flight;
   // A lane is worth having only if its light stream -- the latency-bound kernels of its batch: transcript, Horner chains,
@@ -477,7 +492,10 @@ void zkgpu_verifier_destroy(zkgpu_verifier* v) {
       if (hs.stream) { (void)hipStreamSynchronize(hs.stream); (void)hipStreamDestroy(hs.stream); }
       if (hs.h_in) (void)hipHostFree(hs.h_in);
       if (hs.h_out) (void)hipHostFree(hs.h_out);
-      for (Buffer* b : {&hs.d_tape, &hs.d_slots, &hs.d_txid}) if (b->p) (void)hipFree(b->p);
+      if (hs.h_tab) (void)hipHostFree(hs.h_tab);
+      if (hs.h_log) (void)hipHostFree(hs.h_log);
+      if (hs.ev_ids) (void)hipEventDestroy(hs.ev_ids);
+      for (Buffer* b : {&hs.d_tape, &hs.d_slots, &hs.d_txid, &hs.d_tab, &hs.d_log}) if (b->p) (void)hipFree(b->p);
     }
     if (v->tx_hash_const.p) (void)hipFree(v->tx_hash_const.p);
     for (auto& ss : v->tx_sig) {
@@ -1678,7 +1696,12 @@ int zkgpu_verifier_verify_sharded(zkgpu_verifier* v, zkgpu_comm* cm, size_t batc
 // (the verdicts stay with their tickets / runs) -- a synchronous call on a context with a batch in flight would
 // overwrite that batch's status words and pinned result buffer (and is refused by the context: refuse_if_pending).
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
-  const int base = format & ~(ZKGPU_TXFORMAT_HASH_ON_DEVICE | ZKGPU_TXFORMAT_SIGN_ON_DEVICE | ZKGPU_TXFORMAT_RETURN_IDS);     // (the flags go with a format: alone they name none)
+  // (ZKGPU_TXFORMAT_RETURN_LOG travels with its window K in bits 16 .. 23: both or neither, and only beside ZKGPU_TXFORMAT_RETURN_IDS)
+  const int log_k = (format >> ZKGPU_TXFORMAT_LOG_SHIFT) & 255;
+  const bool log = (format & ZKGPU_TXFORMAT_RETURN_LOG) != 0;
+  if (format < 0 || log != (log_k != 0) || (log && !(format & ZKGPU_TXFORMAT_RETURN_IDS))) return ZKGPU_EINVAL;
+  const int base = format & ~(ZKGPU_TXFORMAT_HASH_ON_DEVICE | ZKGPU_TXFORMAT_SIGN_ON_DEVICE | ZKGPU_TXFORMAT_RETURN_IDS | ZKGPU_TXFORMAT_RETURN_LOG |
+                              (255 << ZKGPU_TXFORMAT_LOG_SHIFT));     // (the flags go with a format: alone they name none)
   if (!v || (format != 0 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS)) return ZKGPU_EINVAL;
   // (the challenge reads the transaction ID where the hashing stage left it: no signing on the device without hashing there)
   if ((format & ZKGPU_TXFORMAT_SIGN_ON_DEVICE) && !(format & ZKGPU_TXFORMAT_HASH_ON_DEVICE)) return ZKGPU_EINVAL;
@@ -1686,7 +1709,7 @@ int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
   v->tx_format = base;
   v->tx_hash_on_device = (format & ZKGPU_TXFORMAT_HASH_ON_DEVICE) != 0;
   v->tx_sign_on_device = (format & ZKGPU_TXFORMAT_SIGN_ON_DEVICE) != 0;
-  v->tx_return_ids = (format & ZKGPU_TXFORMAT_RETURN_IDS) != 0;
+  v->tx_layout = ((format & ZKGPU_TXFORMAT_RETURN_IDS) ? 1u : 0u) | ((uint32_t)log_k << 8);
   return ZKGPU_OK;
 }
 
@@ -1769,8 +1792,13 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   if (status) memset(status, TX_INVALID, batch);
   // (ZKGPU_TXFORMAT_RETURN_IDS: `status` is 33 * batch bytes.  The ID area is zero from here on, whichever way the call
   // leaves; TxCall::verdicts writes into it beside the bits it sets, and an error zeroes it again below)
-  uint8_t* const txids = (status && v->tx_return_ids) ? status + batch : nullptr;
+  const uint32_t layout = v->tx_layout.load();
+  uint8_t* const txids = (status && zkgpu_verifier::layout_ids(layout)) ? status + batch : nullptr;
   if (txids) memset(txids, 0, 32 * batch);
+  // (ZKGPU_TXFORMAT_RETURN_LOG: ... and behind the IDs, batch records of 1 + 33 K bytes, zero in the same way)
+  const size_t log_k = txids ? zkgpu_verifier::layout_log_k(layout) : 0, log_bytes = log_k ? batch * zk::zkvm::tx_log_record_bytes(log_k) : 0;
+  uint8_t* const txlog = log_k ? status + 33 * batch : nullptr;
+  if (txlog) memset(txlog, 0, log_bytes);
   if (batch == 0) return ZKGPU_OK;
   if (!txs || !tx_offsets || batch >= (1ull << 31)) return ZKGPU_EINVAL;
   for (size_t i = 0; i < batch; ++i) if (tx_offsets[i + 1] < tx_offsets[i]) return ZKGPU_EINVAL;
@@ -1778,13 +1806,14 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   if (v->tx_format == 0) {                                        // no format enabled: nothing is inside the subset
     if (status) memset(status, TX_UNSUPPORTED, batch);
     if (txids) memset(txids, 0, 32 * batch);                      // (a format set meanwhile: the layout is the one the call began with)
+    if (txlog) memset(txlog, 0, log_bytes);
     return ZKGPU_OK;
   }
   TRY(tx_call_prepare(v));
   // (format 2 reads the same bytes and gives the same bits; what differs is what the status bytes say -- with no status
   // array there is nothing to say, and the call is the format-1 call)
   GpuTxDevice dev(v, 0, 0, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS && status != nullptr, v->tx_hash_on_device,
-                  v->tx_sign_on_device, txids != nullptr);
+                  v->tx_sign_on_device, txids != nullptr, log_k);
   int rc;
   try {
     TxCall call(dev, v->tx_statements, v->tx_statements_kept, batch, txs, tx_offsets, host_threads, v->tx_chunk, accept_bitmap, status);
@@ -1798,6 +1827,7 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
     memset(accept_bitmap, 0, (batch + 7) / 8);
     if (status) for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;     // (never a reason, never 0)
     if (txids) memset(txids, 0, 32 * batch);                      // (and never an ID)
+    if (txlog) memset(txlog, 0, log_bytes);                       // (nor a log entry)
   }
   return rc;
 }
@@ -1834,6 +1864,7 @@ void tx_round_distribute(TxRound& r) {
     p->bits.assign((p->batch + 7) / 8, 0);
     p->status.assign(p->batch, TX_INVALID);
     if (r.rc != ZKGPU_OK) std::fill(p->txids.begin(), p->txids.end(), (uint8_t)0);      // (a failed round: no ID either)
+    if (r.rc != ZKGPU_OK) std::fill(p->txlog.begin(), p->txlog.end(), (uint8_t)0);      // (nor a log entry)
     p->rc = r.rc;
     for (size_t i = 0; i < p->batch; ++i) {
       const size_t g = at + i;
@@ -1913,10 +1944,14 @@ void tx_engine_main(zkgpu_verifier* v) {
       TxRound& r = *fresh[set];
       int threads = 0;
       // (a call submitted under ZKGPU_TXFORMAT_RETURN_IDS has its own ID area, zero until verdicts() writes beside a set bit)
+      // (... and one submitted under ZKGPU_TXFORMAT_RETURN_LOG its own records, of its own window; the round's device gathers the widest)
       bool want_ids = false;
+      size_t want_log_k = 0;
       for (auto* p : r.calls) {
         if (p->return_ids) { p->txids.assign(32 * p->batch, 0); want_ids = true; }
-        r.pieces.push_back({p->txs, p->offsets, p->batch, p->return_ids ? p->txids.data() : nullptr});
+        if (p->return_ids && p->log_k) { p->txlog.assign(p->batch * tx_log_record_bytes(p->log_k), 0); want_log_k = std::max(want_log_k, p->log_k); }
+        r.pieces.push_back({p->txs, p->offsets, p->batch, p->return_ids ? p->txids.data() : nullptr, p->return_ids && p->log_k ? p->txlog.data() : nullptr,
+                            p->return_ids ? p->log_k : 0});
         threads = std::max(threads, p->host_threads);
       }
       r.bits.assign((r.total + 7) / 8 + 1, 0);
@@ -1928,7 +1963,7 @@ void tx_engine_main(zkgpu_verifier* v) {
         if (r.rc == ZKGPU_OK) {
           try {
             r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS, v->tx_hash_on_device,
-                                        v->tx_sign_on_device, want_ids));
+                                        v->tx_sign_on_device, want_ids, want_log_k));
             r.call.reset(new TxCall(*r.dev, set ? v->tx_statements_b : v->tx_statements, v->tx_statements_kept, r.pieces, threads, v->tx_chunk,
                                     r.bits.data(), r.status.data(), 1));
             r.call->set_on_news([&] { { std::lock_guard<std::mutex> nl(news_mu); news = true; } news_cv.notify_one(); });
@@ -1983,7 +2018,9 @@ int zkgpu_tx_verify_submit(zkgpu_verifier* v, size_t batch, const uint8_t* txs, 
   std::unique_ptr<zkgpu_verifier::TxPending> p(new zkgpu_verifier::TxPending());
   p->batch = batch; p->txs = txs; p->offsets = tx_offsets; p->host_threads = host_threads;
   p->arrived = std::chrono::steady_clock::now();
-  p->return_ids = v->tx_return_ids;                      // (the layout wait will write: the one in force now)
+  const uint32_t layout = v->tx_layout.load();           // (the layout wait will write: the one in force now)
+  p->return_ids = zkgpu_verifier::layout_ids(layout);
+  p->log_k = zkgpu_verifier::layout_log_k(layout);
   std::lock_guard<std::mutex> lk(v->tx_mu);
   if (v->tx_engine_quit) return ZKGPU_EINVAL;
   if (!v->tx_engine.joinable()) {
@@ -2012,6 +2049,11 @@ int zkgpu_tx_verify_wait(zkgpu_verifier* v, uint64_t call_id, uint8_t* accept_bi
   if (status && p->return_ids) {                         // (submitted under ZKGPU_TXFORMAT_RETURN_IDS: 33 * batch bytes)
     if (rc == ZKGPU_OK && p->txids.size() == 32 * p->batch) memcpy(status + p->batch, p->txids.data(), 32 * p->batch);
     else memset(status + p->batch, 0, 32 * p->batch);
+    if (p->log_k) {                                      // (... and under ZKGPU_TXFORMAT_RETURN_LOG: batch * (33 + 1 + 33 K))
+      const size_t log_bytes = p->batch * zk::zkvm::tx_log_record_bytes(p->log_k);
+      if (rc == ZKGPU_OK && p->txlog.size() == log_bytes) memcpy(status + 33 * p->batch, p->txlog.data(), log_bytes);
+      else memset(status + 33 * p->batch, 0, log_bytes);
+    }
   }
   v->tx_calls.erase(it);
   return rc;

@@ -47,12 +47,19 @@
 // bytes), written by verdicts() where it writes TX_OK and nowhere else, from the statement's txid: the one the VM's second
 // pass hashed for the signature, or the one the device's tape produced.  Nothing is hashed for it; all it adds is that a
 // device that chains copies its IDs down after all (hash_collect with a host buffer).
+// A fourth, only beside the third: TxDevice::log_k() (ZKGPU_TXFORMAT_RETURN_LOG) also hands the caller the Input / Output
+// entries of every accepted transaction's log (tx_log.hpp) -- a record of 1 + 33 K bytes each in an area of the caller's
+// (Piece::log), written by verdicts() where it writes the ID.  The records of the whole call are kept in a side array of the
+// call until then: the host's second pass fills them from the slots its plans wrote (tx_prepare_many_logged); a device that
+// hashes brings the entries' contract IDs down with the transaction IDs (hash_log) and the host adds counts and kinds from
+// the tape's shape table.  Nothing is hashed for it either, and the statements grow by nothing.
 // The calling thread's sub-steps (snapshot, queue_keys, queue_tape, proofs_turn, the collects, end_step) are the same whatever
 // the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run: step_host_signed()
 // and step_chained(), which say why.
 #pragma once
 #include "host_pool.hpp"
 #include "tx_hash_tape.hpp"
+#include "tx_log.hpp"
 #include "zkvm_tx.hpp"
 
 #include <atomic>
@@ -132,6 +139,12 @@ class TxDevice {
   // does the caller want the transaction IDs of what was accepted?  (A device that chains then brings its IDs down like one
   // that only hashes: hash_collect is given a host buffer.)
   virtual bool ids() const { return false; }
+  // ... and the log's entries, at most log_k() of them per transaction (0: no; only beside ids())?  A device that hashes then
+  // gathers the entries' contract IDs behind every tape: hash_log(slot), valid from a hash_collect that returned 0 until the
+  // slot's next hash_enqueue, is n_tx x log_k() x 32 bytes in the tape's order, entry j of a transaction whose shape logs
+  // count <= log_k() entries at [t][j], zeros elsewhere.
+  virtual size_t log_k() const { return 0; }
+  virtual const uint8_t* hash_log(int) { return nullptr; }
 };
 
 class TxCall {
@@ -144,22 +157,27 @@ class TxCall {
   // several callers' transactions as ONE call (zkgpu_tx_verify_submit: calls in flight are merged as tickets are): the
   // pieces in order, transaction i of the merged call = the i-th transaction counted through them
   // ids (only of a device with ids(); may be NULL): 32 * batch bytes of that caller's, zeroed by it, for the IDs of what is accepted
-  struct Piece { const uint8_t* txs; const uint64_t* tx_offsets; size_t batch; uint8_t* ids = nullptr; };
+  // log / log_k (only of a device with log_k() >= log_k; may be NULL): batch records of 1 + 33 * log_k bytes, zeroed likewise
+  struct Piece { const uint8_t* txs; const uint64_t* tx_offsets; size_t batch; uint8_t* ids = nullptr; uint8_t* log = nullptr; size_t log_k = 0; };
   // store: what the VM leaves per transaction, kept by the caller between calls (fresh memory costs a page fault per 4 KB);
   // at most `kept` entries of it are used, the rest of a longer call lives in the call.
-  // A lone call on a device with ids(): `status` points at 33 * batch bytes, the IDs behind the status bytes.
+  // A lone call on a device with ids(): `status` points at 33 * batch bytes, the IDs behind the status bytes; with log_k()
+  // = K as well, at batch * (33 + 1 + 33 K) bytes, the records behind the IDs.
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
-      : TxCall(dev, store, kept, std::vector<Piece>{Piece{txs, tx_offsets, batch, dev.ids() && status ? status + batch : nullptr}}, host_threads,
+      : TxCall(dev, store, kept, std::vector<Piece>{Piece{txs, tx_offsets, batch, dev.ids() && status ? status + batch : nullptr,
+                                                             dev.ids() && dev.log_k() && status ? status + 33 * batch : nullptr, dev.log_k()}}, host_threads,
                chunk_override, accept_bitmap, status, n_slots) {}
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
-        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), ids_(dev.ids() && any_ids(pieces)), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), ids_(dev.ids() && any_ids(pieces)), log_k_(ids_ && any_log(pieces, dev.log_k()) ? dev.log_k() : 0), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
     if (ids_) id_out_.reserve(batch_);
+    if (log_k_) { log_out_.reserve(batch_); log_rec_.assign(batch_ * tx_log_record_bytes(log_k_), 0); }
     for (const Piece& pc : pieces) {
       if (ids_) for (size_t i = 0; i < pc.batch; ++i) id_out_.push_back(pc.ids ? pc.ids + 32 * i : nullptr);
+      if (log_k_) for (size_t i = 0; i < pc.batch; ++i) log_out_.push_back({log_fits(pc, log_k_) ? pc.log + i * tx_log_record_bytes(pc.log_k) : nullptr, pc.log_k});
       for (size_t i = 0; i < pc.batch; ++i) { ptr_.push_back(pc.txs + pc.tx_offsets[i]); len_.push_back((size_t)(pc.tx_offsets[i + 1] - pc.tx_offsets[i])); }
     }
     plan(chunk_override, kept);
@@ -281,6 +299,9 @@ class TxCall {
 
   static size_t total_of(const std::vector<Piece>& pieces) { size_t n = 0; for (const Piece& p : pieces) n += p.batch; return n; }
   static bool any_ids(const std::vector<Piece>& pieces) { for (const Piece& p : pieces) if (p.ids && p.batch) return true; return false; }
+  // (a piece's window is at most the device's: the round's device is made for the widest of its calls)
+  static bool log_fits(const Piece& p, size_t k) { return p.log && p.ids && p.log_k >= 1 && p.log_k <= k; }
+  static bool any_log(const std::vector<Piece>& pieces, size_t k) { for (const Piece& p : pieces) if (log_fits(p, k) && p.batch) return true; return false; }
   static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
   void mark(const char* what, size_t i) const { if (timing_) fprintf(stderr, "    %7.3f ms  %s %zu\n", (now() - t00_) * 1e3, what, i); }
   TxStatement& statement(size_t i) { return i < store_.size() ? store_[i] : beyond_[i - store_.size()]; }
@@ -345,7 +366,11 @@ class TxCall {
   void vm_pass(Chunk& k, uint8_t only) {                // the VM over the chunk, hashing the jobs of `only` alone
     const double t0 = now();
     // (consecutive statements: the store's, or the overflow's -- a group of eight never straddles the two)
-    chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) { tx_prepare_many(p, l, &statement(k.lo + first), cnt, true, only); });
+    // (the second pass of a call whose caller is handed the log: the same, and the entries' slots into the call's records)
+    chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) {
+      if (log_k_ && only == ALL_PROTOS) tx_prepare_many_logged(p, l, &statement(k.lo + first), cnt, &log_rec_[(k.lo + first) * tx_log_record_bytes(log_k_)], log_k_);
+      else tx_prepare_many(p, l, &statement(k.lo + first), cnt, true, only);
+    });
     std::lock_guard<std::mutex> lk(hm_);
     (only == ALL_PROTOS ? t_vm_ : t_keys_host_) += now() - t0;
     if (only == ALL_PROTOS) n_host_hashed_ += k.n;
@@ -582,11 +607,23 @@ class TxCall {
       const int rc = dev_.hash_collect((int)(c % n_slots_), to_host ? hash_ids_.data() : nullptr);
       if (rc != OK) note(rc, dev_.last_error());
       else if (to_host) for (size_t t = 0; t < tape.n_tx(); ++t) memcpy(statement(k.lo + tape.position(t)).txid, &hash_ids_[32 * t], 32);
+      if (rc == OK && log_k_ && tape.n_tx()) log_collect(k, tape, dev_.hash_log((int)(c % n_slots_)));
       t_wait_ += now() - t0;
       mark("transaction IDs collected, chunk", c);
     }
     { std::lock_guard<std::mutex> lk(hm_); ids_upto_ = c + 1; }
     hcv_.notify_all();
+  }
+  // the records of a chunk whose tape is back: the IDs the device gathered, counts and kinds from the tape's shape table
+  void log_collect(const Chunk& k, const TxHashTape& tape, const uint8_t* gathered) {
+    if (!gathered || !tx_log_table(tape.block(), log_table_)) { note(EINVAL_, "the hashing stage brought no log entries back"); return; }
+    const HashTapeHead& h = tape.head();
+    for (size_t t = 0; t < tape.n_tx(); ++t) {
+      const uint32_t* sh = tx_log_shape(log_table_, (tape.block() + h.txs + 4 * t)[0]);
+      uint8_t* rec = &log_rec_[(k.lo + tape.position(t)) * tx_log_record_bytes(log_k_)];
+      memset(rec, 0, tx_log_record_bytes(log_k_));
+      tx_log_record(rec, log_k_, sh[0], [&](size_t j) { return std::make_pair(sh[1 + 2 * j], gathered + 32 * (t * log_k_ + j)); });
+    }
   }
   void proofs_collect(Chunk& k) {
     if (k.handle) {
@@ -811,6 +848,7 @@ class TxCall {
         accept_[i / 8] |= (uint8_t)(1u << (i % 8));
         if (status_) status_[i] = TX_OK;
         if (ids_ && id_out_[i]) memcpy(id_out_[i], statement(i).txid, 32);   // (here alone: an ID leaves only beside a set bit)
+        if (log_k_ && log_out_[i].first) tx_log_record_copy(log_out_[i].first, log_out_[i].second, &log_rec_[i * tx_log_record_bytes(log_k_)], log_k_);   // (and a record)
       }
     }
     if (reasons_) reasons_out();
@@ -863,6 +901,10 @@ class TxCall {
   const bool chains_;                                    // ... and forms the signature's challenge: a chunk's three stages are one chain on the device
   const bool ids_;                                       // the IDs of accepted transactions go out (the device says so, and a piece has room for them)
   std::vector<uint8_t*> id_out_;                         // ... per transaction of the call, where its 32 bytes go (NULL: its caller has no room)
+  const size_t log_k_;                                   // the log's entries go out too, at most so many per transaction (0: no)
+  std::vector<std::pair<uint8_t*, size_t>> log_out_;     // ... per transaction, where its record goes (NULL: no room) and its caller's window
+  std::vector<uint8_t> log_rec_;                         // ... the records of the whole call, window log_k_, until verdicts() hands them out
+  std::vector<uint32_t> log_table_;                      // (calling thread: the shape table of the tape being collected)
   const bool timing_;
   const double t00_;
   const size_t n_slots_;                                 // key / signature stages in flight at once (2; 1 when two calls share the stage contexts)

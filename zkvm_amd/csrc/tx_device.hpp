@@ -146,6 +146,7 @@ int const_upload(zkgpu_ctx* c, Buffer& kept, const void* a, size_t na, const voi
 // stages on aux_sigs[slot] (contexts of their own, each a pair of streams beside the lanes'), cloak proofs as blocks of
 // mixed shapes on the lanes, staged through the verifier's ring of pinned / device areas.  v->mu is held by the call.
 static_assert(zk::zkvm::TxCall::OK == ZKGPU_OK && zk::zkvm::TxCall::ENOMEM_ == ZKGPU_ENOMEM && zk::zkvm::TxCall::EINVAL_ == ZKGPU_EINVAL, "tx_call.hpp restates three status codes");
+static_assert(zk::zkvm::TXLOG_INPUT == ZKGPU_TXLOG_INPUT && zk::zkvm::TXLOG_OUTPUT == ZKGPU_TXLOG_OUTPUT, "tx_log.hpp restates the two entry kinds");
 class GpuTxDevice : public zk::zkvm::TxDevice {
  public:
   // slot_base / arena_base: which of the verifier's stage contexts and staging areas this call uses (a call alone: slots 0
@@ -155,13 +156,17 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   // chains: ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the signature's challenge comes from k_tx_sig_rows
   // ids: ZKGPU_TXFORMAT_RETURN_IDS -- the caller is handed the IDs of what it accepted; all it changes HERE is that a chained
   // stage copies its IDs down as an unchained one does (one copy on the hashing stream, no launch)
+  // log_k: ZKGPU_TXFORMAT_RETURN_LOG beside it -- K, the log entries kept per transaction (0: no).  Here: behind k_tx_hash, on
+  // its stream, k_tx_log_gather and one more copy down (hash_queue); a call without it queues exactly what it queued before
   explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false, bool hashes = false, bool chains = false,
-                       bool ids = false)
-      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes), chains_(hashes && chains), ids_(ids) {}
+                       bool ids = false, size_t log_k = 0)
+      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes), chains_(hashes && chains), ids_(ids), log_k_(ids ? log_k : 0) {}
   bool reasons() const override { return reasons_; }
   bool hashes() const override { return hashes_; }
   bool chains() const override { return chains_; }
   bool ids() const override { return ids_; }
+  size_t log_k() const override { return log_k_; }
+  const uint8_t* hash_log(int slot) override { return hashes_ && log_k_ ? (const uint8_t*)hash(slot).h_log : nullptr; }
   zk::zkvm::TxHashTape* hash_tape(int slot) override { return &hash(slot).tape; }
   // one copy up, one launch, one copy of the IDs down, on the stage's own high-priority stream
   int hash_enqueue(int slot, const zk::zkvm::TxHashTape& tape) override {
@@ -336,8 +341,12 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     TRY(upload(c, ss.d_pos, tape_pos, rows * 4));
     HIP_TRY(c, hipEventRecord(ss.ev_keys, key_stream));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, ss.ev_keys, 0));
-    HIP_TRY(c, hipEventRecord(ss.ev_ids, hs.stream));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, ss.ev_ids, 0));
+    if (hs.ids_marked) {                                 // (beside ZKGPU_TXFORMAT_RETURN_LOG: recorded behind k_tx_hash, before the gather -- hash_queue)
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, hs.ev_ids, 0));
+    } else {
+      HIP_TRY(c, hipEventRecord(ss.ev_ids, hs.stream));
+      HIP_TRY(c, hipStreamWaitEvent(c->stream, ss.ev_ids, 0));
+    }
     c->profiling = profiled;
     SigRowsView view{(const SigScript*)v_->tx_sig_const.p, (const uint32_t*)hs.d_txid.p, (const uint32_t*)ss.d_pos.p, (const uint32_t*)kc->values.p,
                      (const uint64_t*)c->in_offsets.p, (const uint32_t*)c->in_points.p, (uint32_t*)c->in_scalars.p, (uint32_t)rows};
@@ -386,13 +395,50 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     HIP_TRY(c, hipMemcpyAsync(hs.d_tape.p, hs.h_in, bytes, hipMemcpyHostToDevice, hs.stream));
     HashTapeView view{(const uint32_t*)hs.d_tape.p, (const uint32_t*)v_->tx_hash_const.p,
                       (const uint8_t*)v_->tx_hash_const.p + 4 * (size_t)N_PROTO * TAPE_PROTO_WORDS, (uint32_t*)hs.d_slots.p, (uint32_t*)hs.d_txid.p};
+    // (a profiled call: the stage's context takes the root's switch for the stage's launches alone, as a chained signature
+    // stage's does -- hash_wait hands what they recorded to the root's profile; nothing else ever runs profiled on this context)
+    bool profiled = false;
+    { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); profiled = v_->root->profiling; }
+    c->profiling = profiled;
     {
       Launch l(c, "k_tx_hash", hs.stream);
       hipLaunchKernelGGL(zk::k_tx_hash, dim3(h.n_lanes / 64), dim3(64), 0, hs.stream, view, h.n_lanes);
     }
+    c->profiling = false;
     HIP_TRY(c, hipGetLastError());
+    // (a chain beside ZKGPU_TXFORMAT_RETURN_LOG: its challenge kernel waits for the IDs, not for the gather and the copies queued
+    // below -- the event it waits for is recorded here; without the flag chain_queue records its own, as it always has)
+    hs.ids_marked = false;
+    if (chains_ && log_k_ && h.n_tx) {
+      if (!hs.ev_ids) HIP_TRY(c, hipEventCreateWithFlags(&hs.ev_ids, hipEventDisableTiming));
+      HIP_TRY(c, hipEventRecord(hs.ev_ids, hs.stream));
+      hs.ids_marked = true;
+    }
     // (a chain reads them on the device: they come down only for a caller that is handed them)
     if (!chains_ || ids_) HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));
+    // (the caller is handed the log: the contract IDs its entries name, gathered from the slots into n_tx x K x 32 dense bytes)
+    hs.logged = false;
+    if (log_k_ && h.n_tx) {
+      if (!tx_log_table(tape.block(), hs.log_table) || !tx_log_lanes_fit(h.n_tx, log_k_)) { c->last_error = "a log entry outside its transaction's slots"; return ZKGPU_EINVAL; }
+      const size_t tab_bytes = 4 * hs.log_table.size(), log_bytes = 32 * log_k_ * (size_t)h.n_tx;
+      TRY(pinned_grow(c, hs.h_tab, hs.h_tab_cap, tab_bytes));
+      TRY(pinned_grow(c, hs.h_log, hs.h_log_cap, log_bytes));
+      TRY(ensure(c, hs.d_tab, tab_bytes));
+      TRY(ensure(c, hs.d_log, log_bytes));
+      memcpy(hs.h_tab, hs.log_table.data(), tab_bytes);
+      HIP_TRY(c, hipMemcpyAsync(hs.d_tab.p, hs.h_tab, tab_bytes, hipMemcpyHostToDevice, hs.stream));
+      c->profiling = profiled;
+      {
+        Launch l(c, "k_tx_log_gather", hs.stream);
+        hipLaunchKernelGGL(zk::k_tx_log_gather, dim3(blocks_for((uint64_t)h.n_tx * log_k_, 64)), dim3(64), 0, hs.stream, (const uint32_t*)hs.d_tape.p,
+                           (const uint32_t*)hs.d_tab.p, (const uint32_t*)hs.d_slots.p, (uint32_t*)hs.d_log.p, h.n_tx, (uint32_t)log_k_);
+      }
+      c->profiling = false;
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipMemcpyAsync(hs.h_log, hs.d_log.p, log_bytes, hipMemcpyDeviceToHost, hs.stream));
+      hs.n_logged = tx_log_handed_back(tape.block(), hs.log_table, log_k_);
+      hs.logged = true;
+    }
     hs.n_tx = h.n_tx;
     return ZKGPU_OK;
   }
@@ -406,7 +452,8 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     if (n == 0) return ZKGPU_OK;
     HIP_TRY(c, hipStreamSynchronize(hs.stream));
     if (txids && (!chains_ || ids_)) memcpy(txids, hs.h_out, 32 * n);
-    { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_hashed_on_device += n; }
+    if (!c->ev_used.empty()) { prof_collect(c); profile_to_root(c); }     // (a profiled stage: its launches have run)
+    { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_hashed_on_device += n; if (hs.logged) v_->root->tx_logged_on_device += hs.n_logged; }
     return ZKGPU_OK;
   }
   // (an error's text: the context's, behind the name of the stage where a test or a caller tells stages by it)
@@ -417,6 +464,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   const int sb_;
   const size_t ab_;
   const bool reasons_, hashes_, chains_, ids_;
+  const size_t log_k_;
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];
   std::string err_;

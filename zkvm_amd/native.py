@@ -216,6 +216,9 @@ TXFORMAT_HASH_ON_DEVICE = 0x100        # a flag beside either format: the transa
 TXFORMAT_SIGN_ON_DEVICE = 0x200        # a second flag, only beside the first: the signature's challenge is formed there too
 TXFORMAT_RETURN_IDS = 0x400            # a third, beside any of those: the status array of a transaction call is 33 bytes per
                                        # transaction, the IDs of the accepted ones behind the status bytes
+TXFORMAT_RETURN_LOG = 0x800            # a fourth, only beside the third and with a window K << TXFORMAT_LOG_SHIFT (1 .. 255): behind
+TXFORMAT_LOG_SHIFT = 16                # the IDs, a record count | kind[K] | id[K][32] per transaction: its log's Input / Output entries
+TXLOG_INPUT, TXLOG_OUTPUT = 1, 2
 TXSTATUS_ACCEPTED, TXSTATUS_REJECTED, TXSTATUS_OUTSIDE_SUBSET = 0, 1, 2
 TXSTATUS_TX_INVALID, TXSTATUS_PROOF_FORMAT, TXSTATUS_PROOF_POINT, TXSTATUS_PROOF_EQUATION, TXSTATUS_KEY, TXSTATUS_SIGNATURE = 16, 17, 18, 19, 20, 21
 

@@ -327,6 +327,9 @@ class BlockVerifier:
     TXFORMAT_HASH_ON_DEVICE = 0x100        # a flag or-ed to either: contract IDs, anchors and the transaction ID hashed on the device
     TXFORMAT_SIGN_ON_DEVICE = 0x200        # a flag or-ed to a format WITH the one above: the signature's challenge formed on the device
     TXFORMAT_RETURN_IDS = 0x400            # a flag or-ed to any of those: the transaction ID of every accepted transaction comes back
+    TXFORMAT_RETURN_LOG = 0x800            # a flag only beside the one above, with a window K << TXFORMAT_LOG_SHIFT: the log's entries too
+    TXFORMAT_LOG_SHIFT = 16                # bits 16 .. 23 of the format: K, the log entries kept per transaction, 1 .. 255
+    TXLOG_INPUT, TXLOG_OUTPUT = 1, 2       # kind bytes of a log record (include/zkgpu.h: ZKGPU_TXLOG_*)
     # status bytes (include/zkgpu.h: ZKGPU_TXSTATUS_*); 16 .. 21 only with TXFORMAT_RECOLLECTED_V1_REASONS, lowest code first
     TXSTATUS_ACCEPTED = 0
     TXSTATUS_REJECTED = 1                  # rejected, no reason known (format 1, or any error)
@@ -340,7 +343,7 @@ class BlockVerifier:
 
     tx_errors = staticmethod(lambda status: tx_errors(status))    # (the module's helper, where the constants are)
 
-    def set_tx_format(self, fmt: int) -> None:
+    def set_tx_format(self, fmt: int, log_k: int = 0) -> None:
         """zkgpu_verifier_set_tx_format: the serialized-transaction format zkgpu_tx_verify_batch reads.  0 (the default):
         none -- every transaction is reported as outside the subset; TXFORMAT_RECOLLECTED_V1: the payment subset of
         DESIGN.md sec 4.5, an UNPINNED recollection of the ZkVM wire format (opt-in for exactly that reason);
@@ -349,22 +352,55 @@ class BlockVerifier:
         then also with TXFORMAT_SIGN_ON_DEVICE (same verdicts; the signature's challenge is formed on the device as well).
         Any of those may be or-ed with TXFORMAT_RETURN_IDS: same verdicts, and verify_txs / wait_txs called with ids=True also
         return the 32-byte transaction ID of every accepted transaction.  (The library then writes 33 bytes per transaction
-        into a call's status array; the arrays here are sized by what THIS method was given last, so set the format through it.)"""
+        into a call's status array; the arrays here are sized by what THIS method was given last, so set the format through it.)
+        A format with TXFORMAT_RETURN_IDS may also carry TXFORMAT_RETURN_LOG and a window K of 1 .. 255 in bits 16 .. 23 -- given
+        in `fmt` itself or as log_k=K, which sets both: verify_txs / wait_txs called with log=True then also return the Input /
+        Output entries of every accepted transaction's log (the library writes 33 + 1 + 33 K bytes per transaction)."""
+        if log_k:
+            if not 1 <= log_k <= 255:
+                raise ValueError("log_k is 1 .. 255")
+            if fmt & (self.TXFORMAT_RETURN_LOG | (255 << self.TXFORMAT_LOG_SHIFT)):
+                raise ValueError("log_k beside a format that already carries TXFORMAT_RETURN_LOG or a window")
+            fmt |= self.TXFORMAT_RETURN_LOG | (log_k << self.TXFORMAT_LOG_SHIFT)
         self._check(self.lib.zkgpu_verifier_set_tx_format(self.h, fmt))
         self._tx_return_ids = bool(fmt & self.TXFORMAT_RETURN_IDS)
+        self._tx_log_k = (fmt >> self.TXFORMAT_LOG_SHIFT) & 255 if fmt & self.TXFORMAT_RETURN_LOG else 0
 
     _tx_return_ids = False
+    _tx_log_k = 0
 
-    def _tx_result(self, bm, st, batch: int, has_ids: bool, ids: bool):
+    @staticmethod
+    def _tx_status_bytes(batch: int, has_ids: bool, log_k: int) -> int:
+        """bytes the library writes into a call's status array under that layout"""
+        return ((33 if has_ids else 1) + (1 + 33 * log_k if has_ids and log_k else 0)) * batch
+
+    def _tx_result(self, bm, st, batch: int, has_ids: bool, ids: bool, log_k: int = 0, log: bool = False):
         """(bitmap, status bytes) of a transaction call, and with ids=True the call's ID area: 32 bytes per transaction, the ID
-        beside status 0 and zeros everywhere else"""
-        out = (bm.raw[: (batch + 7) // 8], st.raw[:batch])
-        if not ids:
+        beside status 0 and zeros everywhere else; with log=True both, and the call's log records as a fourth element: per
+        transaction None (not accepted), a list of ("input" | "output", id) in log order, or -- accepted with more entries
+        than the window holds -- their number as an int"""
+        raw = st.raw
+        out = (bm.raw[: (batch + 7) // 8], raw[:batch])
+        if not (ids or log):
             return out
         if not has_ids:
             raise ValueError("ids=True needs a format with TXFORMAT_RETURN_IDS (set_tx_format)")
-        area = st.raw[batch: 33 * batch]
-        return out + ([area[32 * i: 32 * i + 32] for i in range(batch)],)
+        area = raw[batch: 33 * batch]
+        out += ([area[32 * i: 32 * i + 32] for i in range(batch)],)
+        if not log:
+            return out
+        if not log_k:
+            raise ValueError("log=True needs a format with TXFORMAT_RETURN_LOG (set_tx_format)")
+        per, names, logs = 1 + 33 * log_k, {self.TXLOG_INPUT: "input", self.TXLOG_OUTPUT: "output"}, []
+        for i in range(batch):
+            rec = raw[33 * batch + per * i: 33 * batch + per * (i + 1)]
+            if out[1][i] != self.TXSTATUS_ACCEPTED:
+                logs.append(None)
+            elif rec[0] > log_k or (rec[0] and rec[1] == 0):      # (more than the window holds; 255 saturates: no listed entry has kind 0)
+                logs.append(int(rec[0]))
+            else:
+                logs.append([(names.get(rec[1 + j], rec[1 + j]), rec[1 + log_k + 32 * j: 1 + log_k + 32 * j + 32]) for j in range(rec[0])])
+        return out + (logs,)
 
     def set_tx_chunk(self, transactions: int) -> None:
         """zkgpu_verifier_set_tx_chunk: transactions per chunk of the staged pipeline inside verify_txs (0 = automatic)"""
@@ -374,29 +410,34 @@ class BlockVerifier:
         """zkgpu_verifier_set_tx_statements_kept: how many transactions' VM results (700 B each) the verifier keeps between calls"""
         self._check(self.lib.zkgpu_verifier_set_tx_statements_kept(self.h, transactions))
 
-    def verify_txs(self, txs: Sequence[bytes], host_threads: int = 0, ids: bool = False):
+    def verify_txs(self, txs: Sequence[bytes], host_threads: int = 0, ids: bool = False, log: bool = False):
         """zkgpu_tx_verify_batch: serialized ZkVM transactions (payment subset) -> (accept bitmap, status bytes:
         0 accepted, 1 rejected, 2 outside the subset).  Inert until set_tx_format names a format.  With
         TXFORMAT_RECOLLECTED_V1_REASONS the bitmap is the same and a rejected transaction reads one of TXSTATUS_TX_INVALID ..
         TXSTATUS_SIGNATURE instead of 1 (the lowest code that applies; 1 for every transaction after an error): tx_errors(status)
         turns the bytes into upstream's error variants.  ids=True (only under a format with TXFORMAT_RETURN_IDS): -> (bitmap,
-        status bytes, ids) with ids[i] the transaction ID beside status 0 and 32 zero bytes beside everything else."""
-        return self.verify_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads, ids=ids)
+        status bytes, ids) with ids[i] the transaction ID beside status 0 and 32 zero bytes beside everything else.  log=True
+        (only under a format with TXFORMAT_RETURN_LOG): -> (bitmap, status bytes, ids, log) with log[i] None beside everything
+        but status 0, else the transaction's Input / Output log entries as a list of ("input" | "output", contract ID) in
+        the order the program logged them -- or, when there are more than the window K holds, their number as an int."""
+        return self.verify_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads, ids=ids, log=log)
 
-    def verify_txs_packed(self, blob: bytes, lengths, host_threads: int = 0, ids: bool = False):
+    def verify_txs_packed(self, blob: bytes, lengths, host_threads: int = 0, ids: bool = False, log: bool = False):
         """the same over one buffer of concatenated transactions and their lengths (same status bytes, reasons included)"""
         batch = len(lengths)
-        has_ids = self._tx_return_ids
+        has_ids, log_k = self._tx_return_ids, self._tx_log_k
         if ids and not has_ids:
             raise ValueError("ids=True needs a format with TXFORMAT_RETURN_IDS (set_tx_format)")
+        if log and not (has_ids and log_k):
+            raise ValueError("log=True needs a format with TXFORMAT_RETURN_LOG (set_tx_format)")
         offs = np.zeros(batch + 1, dtype=np.uint64)
         np.cumsum(lengths if isinstance(lengths, np.ndarray) and lengths.dtype == np.uint64 else np.asarray(lengths, dtype=np.uint64), out=offs[1:])
         if int(offs[-1]) != len(blob):
             raise ValueError("the lengths add up to %d bytes, the buffer holds %d" % (int(offs[-1]), len(blob)))
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
-        st = C.create_string_buffer(max((33 if has_ids else 1) * batch, 1))      # (with the flag the library writes 33 bytes per transaction)
+        st = C.create_string_buffer(max(self._tx_status_bytes(batch, has_ids, log_k), 1))      # (with the flags the library writes more than a byte per transaction)
         self._check(self.lib.zkgpu_tx_verify_batch(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, bm, st))
-        return self._tx_result(bm, st, batch, has_ids, ids)
+        return self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
 
     def submit_txs_packed(self, blob: bytes, lengths, host_threads: int = 0) -> int:
         """zkgpu_tx_verify_submit: the call is queued (calls in flight are merged into rounds); -> call id for wait_txs.  The
@@ -409,26 +450,30 @@ class BlockVerifier:
         cid = C.c_uint64(0)
         self._check(self.lib.zkgpu_tx_verify_submit(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, C.byref(cid)))
         # (the layout of the call's status array is the one in force when it was queued: remembered with the call)
-        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch, self._tx_return_ids)
+        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch, self._tx_return_ids, self._tx_log_k)
         return int(cid.value)
 
     def submit_txs(self, txs: Sequence[bytes], host_threads: int = 0) -> int:
         return self.submit_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads)
 
-    def wait_txs(self, call_id: int, ids: bool = False):
+    def wait_txs(self, call_id: int, ids: bool = False, log: bool = False):
         """zkgpu_tx_verify_wait -> (accept bitmap, status bytes) of that call; the status bytes are those verify_txs gives for
         the same transactions -- with TXFORMAT_RECOLLECTED_V1_REASONS the same reason codes, whatever round the call was merged into.
-        ids=True (the call was submitted under a format with TXFORMAT_RETURN_IDS): -> (bitmap, status bytes, ids) as verify_txs"""
-        _, _, batch, has_ids = self.__dict__["_tx_calls"][call_id]
+        ids=True (the call was submitted under a format with TXFORMAT_RETURN_IDS): -> (bitmap, status bytes, ids) as verify_txs;
+        log=True (... with TXFORMAT_RETURN_LOG): -> (bitmap, status bytes, ids, log) as verify_txs"""
+        queued = self.__dict__["_tx_calls"][call_id]
+        batch, has_ids, log_k = queued[2], queued[3], (queued[4] if len(queued) > 4 else 0)
         if ids and not has_ids:
             raise ValueError("ids=True: the call was not submitted under a format with TXFORMAT_RETURN_IDS")
+        if log and not (has_ids and log_k):
+            raise ValueError("log=True: the call was not submitted under a format with TXFORMAT_RETURN_LOG")
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
-        st = C.create_string_buffer(max((33 if has_ids else 1) * batch, 1))
+        st = C.create_string_buffer(max(self._tx_status_bytes(batch, has_ids, log_k), 1))
         try:
             self._check(self.lib.zkgpu_tx_verify_wait(self.h, call_id, bm, st))
         finally:
             del self.__dict__["_tx_calls"][call_id]
-        return self._tx_result(bm, st, batch, has_ids, ids)
+        return self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
 
     def tx_stats(self):
         """zkgpu_tx_verify_stats -> (rounds the engine has run, calls they held in all)"""
