@@ -152,6 +152,8 @@ int zkgpu_msm_ps_batch(zkgpu_ctx *ctx, const zkgpu_pointset *ps, size_t batch, c
  * Out: commitments batch x 64 (n_in + n_out) B (quantity, flavor per value); proofs batch x
  * proof_stride B, *proof_len bytes of each used (R1CSProof wire format, 1 + 32 (16 + 2k)).
  * (Replaces: spacesuit::cloak + bulletproofs r1cs::Prover::prove per transaction.)
+ * Every quantity is a u64, but the total of a flavor on one side may be 2^64 or more (2^63 + 2^63 -> 2^63 + 2^63 is a valid
+ * statement and gets a proof that verifies); a single quantity of 2^64 or more cannot be stated.
  *
  * seeds == NULL (recommended; also in zkgpu_r1cs_prove_batch): the library draws the call's randomness itself, as
  * upstream's r1cs::Prover does with thread_rng().  It takes ONE 32-byte call seed from getrandom(2) per call; statement i

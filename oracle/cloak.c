@@ -106,13 +106,13 @@ static int value_shuffle(r1cs_cs *cs, const cloak_value *x, const cloak_value *y
   return r1cs_specify_randomized_constraints(cs, value_shuffle_cb, ud);
 }
 
-static cloak_value allocate_value(r1cs_cs *cs, uint64_t q, const sc *f, int has) {
+/* q is a scalar: a run's total can pass 2^64 (q_val, a COMMITTED value's 64-bit quantity, stays 0 here: nothing reads it) */
+static cloak_value allocate_value(r1cs_cs *cs, const sc *q, const sc *f, int has) {
   cloak_value v;
   r1cs_var out[3];
-  sc qs; sc_from_u64(&qs, q);
-  sc fz; sc_from_u64(&fz, 0);
-  r1cs_allocate_multiplier(cs, &qs, has ? f : &fz, out);
-  v.q = out[0]; v.f = out[1]; v.q_val = q; v.f_val = has ? *f : fz; v.has_assignment = has;
+  sc z; sc_from_u64(&z, 0);
+  r1cs_allocate_multiplier(cs, has ? q : &z, has ? f : &z, out);
+  v.q = out[0]; v.f = out[1]; v.q_val = 0; v.f_val = has ? *f : z; v.has_assignment = has;
   return v;
 }
 
@@ -121,8 +121,8 @@ static int padded_shuffle(r1cs_cs *cs, const cloak_value *x, size_t kx, const cl
   cloak_value *xp = malloc(sizeof(cloak_value) * (k + 1)), *yp = malloc(sizeof(cloak_value) * (k + 1));
   sc zero; sc_from_u64(&zero, 0);
   int has = r1cs_is_prover(cs);
-  for (size_t i = 0; i < k; ++i) xp[i] = i < kx ? x[i] : allocate_value(cs, 0, &zero, has);
-  for (size_t i = 0; i < k; ++i) yp[i] = i < ky ? y[i] : allocate_value(cs, 0, &zero, has);
+  for (size_t i = 0; i < k; ++i) xp[i] = i < kx ? x[i] : allocate_value(cs, &zero, &zero, has);
+  for (size_t i = 0; i < k; ++i) yp[i] = i < ky ? y[i] : allocate_value(cs, &zero, &zero, has);
   int rc = value_shuffle(cs, xp, yp, k);
   free(xp); free(yp);
   return rc;
@@ -163,37 +163,37 @@ static int sc_cmp(const sc *a, const sc *b) {
   return 0;
 }
 
-/* k_mix: allocate `grouped` (the values ordered so equal flavors are adjacent) and
- * `merged` (one value per flavor run carrying the run's total, zeros elsewhere) and chain mixes. */
+/* k_mix: allocate `grouped` (the values ordered so equal flavors are adjacent) and `merged` (one value per flavor run carrying
+ * the run's total -- a sum of SCALARS: mix demands D.q = A.q + B.q mod l, and quantities below 2^64 can add up to more --, zeros elsewhere) and chain mixes. */
 static int k_mix(r1cs_cs *cs, const cloak_value *vals, size_t k, cloak_value *grouped, cloak_value *merged) {
   int has = r1cs_is_prover(cs);
   sc zero; sc_from_u64(&zero, 0);
   if (k == 0) return 0;
   if (k == 1) { grouped[0] = vals[0]; merged[0] = vals[0]; return 0; }
   /* witness: order by flavor (insertion sort, stable) */
-  uint64_t *gq = malloc(sizeof(uint64_t) * k), *mq = malloc(sizeof(uint64_t) * k), *dq = malloc(sizeof(uint64_t) * k);
+  sc *gq = malloc(sizeof(sc) * k), *mq = malloc(sizeof(sc) * k), *dq = malloc(sizeof(sc) * k);
   sc *gf = malloc(sizeof(sc) * k), *mf = malloc(sizeof(sc) * k), *df = malloc(sizeof(sc) * k);
-  for (size_t i = 0; i < k; ++i) { gq[i] = has ? vals[i].q_val : 0; gf[i] = has ? vals[i].f_val : zero; }
+  for (size_t i = 0; i < k; ++i) { sc_from_u64(&gq[i], has ? vals[i].q_val : 0); gf[i] = has ? vals[i].f_val : zero; }
   if (has) {
     for (size_t i = 1; i < k; ++i) {
-      uint64_t q = gq[i]; sc f = gf[i]; size_t j = i;
+      sc q = gq[i], f = gf[i]; size_t j = i;
       while (j > 0 && sc_cmp(&gf[j - 1], &f) > 0) { gq[j] = gq[j - 1]; gf[j] = gf[j - 1]; --j; }
       gq[j] = q; gf[j] = f;
     }
-    uint64_t aq = gq[0]; sc af = gf[0];
+    sc aq = gq[0], af = gf[0];
     for (size_t i = 1; i < k; ++i) {
-      if (sc_cmp(&af, &gf[i]) == 0) { mq[i - 1] = 0; mf[i - 1] = zero; aq += gq[i]; }
+      if (sc_cmp(&af, &gf[i]) == 0) { mq[i - 1] = zero; mf[i - 1] = zero; sc_add(&aq, &aq, &gq[i]); }
       else { mq[i - 1] = aq; mf[i - 1] = af; aq = gq[i]; af = gf[i]; }
       dq[i - 1] = aq; df[i - 1] = af;   /* running D after step i */
     }
     mq[k - 1] = aq; mf[k - 1] = af;
   } else {
-    for (size_t i = 0; i < k; ++i) { mq[i] = dq[i] = 0; mf[i] = df[i] = zero; }
+    for (size_t i = 0; i < k; ++i) { mq[i] = dq[i] = zero; mf[i] = df[i] = zero; }
   }
-  for (size_t i = 0; i < k; ++i) grouped[i] = allocate_value(cs, gq[i], &gf[i], has);
+  for (size_t i = 0; i < k; ++i) grouped[i] = allocate_value(cs, &gq[i], &gf[i], has);
   cloak_value *mid = malloc(sizeof(cloak_value) * k);
-  for (size_t i = 0; i + 2 < k; ++i) mid[i] = allocate_value(cs, dq[i], &df[i], has);
-  for (size_t i = 0; i < k; ++i) merged[i] = allocate_value(cs, mq[i], &mf[i], has);
+  for (size_t i = 0; i + 2 < k; ++i) mid[i] = allocate_value(cs, &dq[i], &df[i], has);
+  for (size_t i = 0; i < k; ++i) merged[i] = allocate_value(cs, &mq[i], &mf[i], has);
   for (size_t i = 0; i + 1 < k; ++i) {
     mix_ud *m = malloc(sizeof *m);
     m->A = i == 0 ? grouped[0] : mid[i - 1];

@@ -306,7 +306,8 @@ int zkhost_tape_challenges(uint32_t n_in, uint32_t n_out, const uint8_t* commitm
 
 namespace {
 // Reference evaluation of prover rows on the host (CPU tests only; the product evaluates them with
-// zkgpu_msm_ps_batch): bucket method, window 8, over decoded generator points.
+// zkgpu_msm_ps_batch): bucket method over decoded generator points, window 8 -- 4 for the rows of a few terms (value
+// commitments, T_i), where walking 255 buckets per window was nearly all of the work.
 void host_rows(const std::vector<ge>& gens, const std::vector<MsmRow>& rows, std::vector<uint8_t>& out) {
   out.assign(32 * rows.size(), 0);
   for (size_t r = 0; r < rows.size(); ++r) {
@@ -315,12 +316,13 @@ void host_rows(const std::vector<ge>& gens, const std::vector<MsmRow>& rows, std
     ge_identity(acc);
     std::vector<std::array<uint8_t, 32>> sb(row.scalars.size());
     for (size_t i = 0; i < sb.size(); ++i) row.scalars[i].to_bytes(sb[i].data());
-    for (int win = 31; win >= 0; --win) {
-      for (int d = 0; d < 8; ++d) ge_double(acc, acc);
-      std::vector<ge> bucket(256);
-      std::vector<char> used(256, 0);
+    const int c = sb.size() <= 16 ? 4 : 8, n_buckets = 1 << c;
+    for (int win = 256 / c - 1; win >= 0; --win) {
+      for (int d = 0; d < c; ++d) ge_double(acc, acc);
+      std::vector<ge> bucket(n_buckets);
+      std::vector<char> used(n_buckets, 0);
       for (size_t i = 0; i < sb.size(); ++i) {
-        const unsigned b = sb[i][win];
+        const unsigned b = c == 8 ? sb[i][win] : (sb[i][win >> 1] >> (4 * (win & 1))) & 15u;
         if (!b) continue;
         if (used[b]) ge_add(bucket[b], bucket[b], gens[row.index[i]]);
         else { bucket[b] = gens[row.index[i]]; used[b] = 1; }
@@ -328,7 +330,7 @@ void host_rows(const std::vector<ge>& gens, const std::vector<MsmRow>& rows, std
       ge run, sum;
       ge_identity(run);
       ge_identity(sum);
-      for (int b = 255; b >= 1; --b) {
+      for (int b = n_buckets - 1; b >= 1; --b) {
         if (used[b]) ge_add(run, run, bucket[b]);
         ge_add(sum, sum, run);
       }
@@ -630,6 +632,19 @@ int zkhost_prove_dev_cloak(uint32_t n_in, uint32_t n_out, const uint64_t* quanti
   }
   pv_cloak_given(n_in, n_out, quantities, flavors, given);
   return pv_emulate(d, md, values, blindings, given, seed, generators, gens_capacity, commitments, proof, proof_cap, proof_len_out);
+}
+
+// The witness queue of one cloak statement as the device prover receives it (pv_cloak_given): per first-phase allocation
+// its (left, right) assignment, 2 x 32 canonical bytes, in the gadget's allocation order.  -> the number of pairs; `out`
+// is written when `cap` pairs hold them all.
+size_t zkhost_cloak_given(uint32_t n_in, uint32_t n_out, const uint64_t* quantities, const uint8_t* flavors, uint8_t* out, size_t cap) {
+  std::vector<uint32_t> given;
+  pv_cloak_given(n_in, n_out, quantities, flavors, given);
+  const size_t pairs = given.size() / 16;
+  if (out && pairs <= cap)
+    for (size_t i = 0; i < given.size(); ++i)
+      for (int b = 0; b < 4; ++b) out[4 * i + b] = (uint8_t)(given[i] >> (8 * b));
+  return pairs;
 }
 
 int zkhost_prove_dev_r1cs(const char* label, uint32_t m, uint32_t n1, uint32_t n, uint32_t n_chal, const char* const* chal_labels,

@@ -96,8 +96,8 @@ class R1csProverCS : public ConstraintSystemT<Scalar> {
 
 namespace cloak {
 
-struct Amount {   // one value of the witness
-  uint64_t q;
+struct Amount {   // one value of the witness: a quantity (< 2^64), or the total of a run of equal flavors -- their sum as an
+  unsigned __int128 q;   // INTEGER, which can pass 2^64 (mix demands D.q = A.q + B.q over the scalars: a sum that wraps satisfies nothing)
   Scalar f;
 };
 
@@ -127,7 +127,7 @@ inline void k_mix_witness(const std::vector<Amount>& vals, std::deque<std::pair<
     d[i - 1] = acc;   // running D after step i
   }
   m[k - 1] = acc;
-  auto push = [&](const Amount& a) { out.emplace_back(Scalar::from_u64(a.q), a.f); };
+  auto push = [&](const Amount& a) { out.emplace_back(Scalar{{(uint64_t)a.q, (uint64_t)(a.q >> 64), 0, 0}}, a.f); };
   for (size_t i = 0; i < k; ++i) push(g[i]);
   for (size_t i = 0; i + 2 < k; ++i) push(d[i]);
   for (size_t i = 0; i < k; ++i) push(m[i]);
@@ -143,7 +143,7 @@ inline void gadget_witness(const std::vector<Amount>& in, const std::vector<Amou
   for (size_t i = 0; i < pad; ++i) q.emplace_back(Scalar::zero(), Scalar::zero());
   for (const Amount& o : out)
     for (int i = 0; i < 64; ++i) {
-      const uint64_t bit = (o.q >> i) & 1;
+      const uint64_t bit = (uint64_t)(o.q >> i) & 1;   // an output: below 2^64
       q.emplace_back(Scalar::from_u64(1 - bit), Scalar::from_u64(bit));
     }
 }
@@ -503,7 +503,7 @@ inline std::unique_ptr<R1csProver> cloak_prover(size_t n_in, size_t n_out, const
     std::memcpy(wide, flavors + 32 * i, 32);
     a.f = Scalar::from_wide(wide);
     amounts.push_back(a);
-    values.push_back(Scalar::from_u64(a.q)); blindings.push_back(R1csProver::derive_scalar(seed, "q_blinding", i));
+    values.push_back(Scalar::from_u64(quantities[i])); blindings.push_back(R1csProver::derive_scalar(seed, "q_blinding", i));
     values.push_back(a.f); blindings.push_back(R1csProver::derive_scalar(seed, "f_blinding", i));
   }
   auto synth = [amounts, n_in](R1csProverCS& cs, const std::vector<Var>& vars) {
