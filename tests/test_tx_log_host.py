@@ -109,8 +109,8 @@ def test_a_saturated_count_reads_as_a_number_not_as_entries():
 
 
 def test_the_logged_second_pass_leaves_the_statements_of_the_plain_one(host, oracle):
-    """tx_prepare_many_logged is a second copy of tx_prepare_many (whose file holds lines other documents cite and cannot be
-    touched): both over the same groups of eight, statement by statement -- groups of one shape (hashed in lockstep where the
+    """tx_prepare_many_logged and tx_prepare_many are two sets of parameters of one second pass (zkvm_tx.hpp: tx_run_group);
+    this guards what must not differ between them: both over the same groups of eight, statement by statement -- groups of one shape (hashed in lockstep where the
     CPU can) and mixed ones, with a truncated transaction and one outside the subset among them"""
     host.zkhost_tx_prepare_logged_compare.restype = C.c_longlong
     uniform = [wrapped(oracle, 2, 2, 2100 + k) for k in range(24)] + [wrapped(oracle, 3, 2, 2200 + k) for k in range(8)]

@@ -54,7 +54,7 @@ assert os.environ.get("ZKGPU_TEST_TX_FREE_HASHING") == "1" or not any(st)      #
 offs = np.zeros(len(lens) + 1, dtype=np.uint64)
 np.cumsum(np.asarray(lens, dtype=np.uint64), out=offs[1:])
 # (TX_BENCH_FORMAT may carry ZKGPU_TXFORMAT_RETURN_IDS / _RETURN_LOG | K << 16: the library then writes 33, or 33 + 1 + 33 K, bytes per transaction)
-bmb, stb = C.create_string_buffer((len(lens) + 7) // 8), C.create_string_buffer(bv._tx_status_bytes(len(lens), bv._tx_return_ids, bv._tx_log_k))
+bmb, stb = C.create_string_buffer((len(lens) + 7) // 8), C.create_string_buffer(bv._tx_status_bytes(len(lens), *bv._tx_layout))
 for _ in range(CALLS):
     t0 = time.perf_counter()
     rc = bv.lib.zkgpu_tx_verify_batch(bv.h, len(lens), blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), HT, bmb, stb)

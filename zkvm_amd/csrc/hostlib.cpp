@@ -1090,8 +1090,11 @@ bool add_terms(ge& acc, const uint8_t* sc, const uint8_t* pt, uint64_t lo, uint6
 
 class HostTxDevice : public TxDevice {
  public:
-  HostTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int fail_at)
-      : txs_(txs), offs_(offs), batch_(batch), proof_ok_(proof_ok), rng_(seed), fail_at_(fail_at) {
+  // format: of it the stand-ins read what the caller is handed (out: the IDs, the log's window); whether a stand-in hashes
+  // or chains is its class
+  HostTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int fail_at,
+               const TxFormat& format = TxFormat())
+      : txs_(txs), offs_(offs), batch_(batch), proof_ok_(proof_ok), rng_(seed), fail_at_(fail_at), out_(format.out) {
     ge B;
     B.X = fe_BASE_X(); B.Y = fe_BASE_Y(); B.Z = fe_one(); B.T = fe_BASE_T();
     encode_point(base_, B);
@@ -1202,12 +1205,10 @@ class HostTxDevice : public TxDevice {
     return 0;
   }
   std::string last_error() override { return err_.empty() ? "injected device fault" : err_; }
-  // a caller that is handed the transaction IDs (ZKGPU_TXFORMAT_RETURN_IDS): said before the call is made
-  bool ids() const override { return ids_; }
-  void set_ids(bool on) { ids_ = on; }
-  // ... and the log's entries, at most k per transaction (ZKGPU_TXFORMAT_RETURN_LOG; only with ids)
-  size_t log_k() const override { return ids_ ? log_k_ : 0; }
-  void set_log_k(size_t k) { log_k_ = k; }
+  // a caller that is handed the transaction IDs (ZKGPU_TXFORMAT_RETURN_IDS), and the log's entries, at most log_k() per
+  // transaction (ZKGPU_TXFORMAT_RETURN_LOG; only with ids)
+  bool ids() const override { return out_.ids; }
+  size_t log_k() const override { return out_.ids ? out_.log_k : 0; }
   size_t leaked() { std::lock_guard<std::mutex> lk(mu_); return staged_total_ - released_total_; }
 
  protected:
@@ -1238,8 +1239,7 @@ class HostTxDevice : public TxDevice {
   size_t staged_total_ = 0, released_total_ = 0;
   uint8_t base_[32];
   std::string err_;
-  bool ids_ = false;
-  size_t log_k_ = 0;
+  const TxOutLayout out_;
 };
 }  // namespace
 
@@ -1248,8 +1248,7 @@ class HostTxDevice : public TxDevice {
 namespace {
 int txcall_selftest(HostTxDevice& dev, size_t batch, const uint8_t* txs, const uint64_t* offs, int host_threads, size_t chunk, int n_slots,
                     uint8_t* accept_bitmap, uint8_t* status, size_t* n_chunks, size_t* n_sig_stages, size_t* leaked) {
-  std::memset(accept_bitmap, 0, (batch + 7) / 8);
-  std::memset(status, TX_INVALID, batch);
+  TxOutLayout().begin(accept_bitmap, status, batch);
   std::vector<TxStatement> store;
   int rc;
   {
@@ -1259,10 +1258,7 @@ int txcall_selftest(HostTxDevice& dev, size_t batch, const uint8_t* txs, const u
     rc = call.run();
   }
   *leaked = dev.leaked();
-  if (rc != 0) {
-    std::memset(accept_bitmap, 0, (batch + 7) / 8);
-    for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;
-  }
+  if (rc != 0) TxOutLayout().fail_closed(accept_bitmap, status, batch);
   return rc;
 }
 }  // namespace
@@ -1280,8 +1276,7 @@ extern "C" int zkhost_txcall_selftest(size_t batch, const uint8_t* txs, const ui
 extern "C" int zkhost_txcall_pair_selftest(size_t batch, size_t split, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok,
                                            int host_threads, size_t chunk, uint32_t delay_seed, uint8_t* accept_bitmap, uint8_t* status,
                                            size_t* leaked) {
-  std::memset(accept_bitmap, 0, (batch + 7) / 8);
-  std::memset(status, TX_INVALID, batch);
+  TxOutLayout().begin(accept_bitmap, status, batch);
   if (split == 0 || split >= batch || split % 8) return -1;
   std::vector<TxStatement> store[2];
   std::vector<uint8_t> bits[2] = {std::vector<uint8_t>((split + 7) / 8 + 1, 0), std::vector<uint8_t>((batch - split + 7) / 8 + 1, 0)};
@@ -1317,7 +1312,7 @@ extern "C" int zkhost_txcall_pair_selftest(size_t batch, size_t split, const uin
     leaked_all = dev0.leaked() + dev1.leaked();
   }
   *leaked = leaked_all;
-  if (rc_all != 0) return rc_all;
+  if (rc_all != 0) { TxOutLayout().fail_closed(accept_bitmap, status, batch); return rc_all; }
   for (size_t i = 0; i < split; ++i) if ((bits[0][i / 8] >> (i % 8)) & 1) accept_bitmap[i / 8] |= (uint8_t)(1u << (i % 8));
   for (size_t i = split; i < batch; ++i) { const size_t q = i - split; if ((bits[1][q / 8] >> (q % 8)) & 1) accept_bitmap[i / 8] |= (uint8_t)(1u << (i % 8)); }
   return 0;
@@ -1392,8 +1387,8 @@ namespace {
 class HostHashingTxDevice : public HostTxDevice {
  public:
   HostHashingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int hash_fail_at,
-                      int fail_at = -1)
-      : HostTxDevice(txs, offs, batch, proof_ok, seed, fail_at), hrng_(seed ^ 0x9e3779b9u), hash_fail_at_(hash_fail_at) { hash_tape_constants(protos_, labels_); }
+                      int fail_at = -1, const TxFormat& format = TxFormat())
+      : HostTxDevice(txs, offs, batch, proof_ok, seed, fail_at, format), hrng_(seed ^ 0x9e3779b9u), hash_fail_at_(hash_fail_at) { hash_tape_constants(protos_, labels_); }
   ~HostHashingTxDevice() override { for (auto& s : h_) if (s.th.joinable()) s.th.join(); }
   bool hashes() const override { return true; }
   TxHashTape* hash_tape(int slot) override { return &h_[slot].tape; }
@@ -1536,8 +1531,8 @@ namespace {
 class HostChainingTxDevice : public HostHashingTxDevice {
  public:
   HostChainingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int sig_fail_at,
-                       int hash_fail_at = -1, int fail_at = -1)
-      : HostHashingTxDevice(txs, offs, batch, proof_ok, seed, hash_fail_at, fail_at), crng_(seed ^ 0x51ed270bu), sig_fail_at_(sig_fail_at) { have_script_ = sig_script(script_); }
+                       int hash_fail_at = -1, int fail_at = -1, const TxFormat& format = TxFormat())
+      : HostHashingTxDevice(txs, offs, batch, proof_ok, seed, hash_fail_at, fail_at, format), crng_(seed ^ 0x51ed270bu), sig_fail_at_(sig_fail_at) { have_script_ = sig_script(script_); }
   bool chains() const override { return true; }
   int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc, const SigChain* chain) override {
     if (!chain) { cerr_ = "an unchained signature stage on a device that chains"; return -1; }
@@ -1602,140 +1597,145 @@ extern "C" int zkhost_txcall_chaining_selftest(size_t batch, const uint8_t* txs,
   return rc;
 }
 
-// ---- a call whose caller is handed the transaction IDs (TxDevice::ids: ZKGPU_TXFORMAT_RETURN_IDS) on the CPU, over any of the
-// ---- three stand-ins above -- kind 0: HostTxDevice, 1: hashing, 2: chaining -- laid out and fail-closed as session.hpp does it.
-// ---- split = 0: a lone call; status_a is 33 * batch bytes (batch when return_ids = 0), the IDs behind the status bytes.
-// ---- split > 0 (a multiple of 8, < batch): the transactions [0, split) and [split, batch) as two callers' pieces of ONE merged
-// ---- call, as a round of zkgpu_tx_verify_submit holds them: one bitmap and one status array for the round, handed out to
-// ---- status_a (33 * split bytes, or split) and status_b (33 * (batch - split), or batch - split), each with its own ID area.
-// ---- fail_at: the n-th operation of stage fail_stage fails (-1: none) -- 0 keys / proofs / unchained signatures, 1 the hashing
-// ---- stage, 2 the chained signature stage.  out[0] chunks, out[1] staged chunks never released, out[2] hash_collect calls
-// ---- that were given a host buffer, out[3] transactions whose ID the HOST's second pass hashed, out[4] IDs the stand-in's
-// ---- hashing stage produced, out[5] whether a failed call had left anything in an ID area before it was fail-closed (must be 0)
+// ---- a call whose caller is handed more than bits and status bytes -- the transaction IDs (TxDevice::ids: ZKGPU_TXFORMAT_RETURN_IDS),
+// ---- the log's entries (TxDevice::log_k: ZKGPU_TXFORMAT_RETURN_LOG) -- on the CPU, over any of the three stand-ins above, with the
+// ---- LIBRARY's own layout code (tx_out.hpp): begin, piece, the round's hand-out and the fail-closed clean-up are the functions
+// ---- session.hpp calls.  kind 0: HostTxDevice, 1: hashing, 2: chaining.  fail_at: the n-th operation of stage fail_stage fails
+// ---- (-1: none) -- 0 keys / proofs / unchained signatures, 1 the hashing stage, 2 the chained signature stage.
+namespace {
+std::unique_ptr<HostTxDevice> tx_stand_in(int kind, int fail_stage, int fail_at, const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok,
+                                          uint32_t delay_seed, const TxFormat& format) {
+  const int f0 = fail_stage == 0 ? fail_at : -1, f1 = fail_stage == 1 ? fail_at : -1, f2 = fail_stage == 2 ? fail_at : -1;
+  if (kind == 0) return std::unique_ptr<HostTxDevice>(new HostTxDevice(txs, offs, batch, proof_ok, delay_seed, f0, format));
+  if (kind == 1) return std::unique_ptr<HostTxDevice>(new HostHashingTxDevice(txs, offs, batch, proof_ok, delay_seed, f1, f0, format));
+  return std::unique_ptr<HostTxDevice>(new HostChainingTxDevice(txs, offs, batch, proof_ok, delay_seed, f2, f1, f0, format));
+}
+struct TxOutSelftest { size_t chunks = 0, leaked = 0, host_hashed = 0; uint64_t id_asks = 0, hashed = 0, logged = 0; bool dirty = false; };
+// split = 0: a lone call, status_a its whole status argument under layout la.  split > 0 (a multiple of 8, < batch): [0, split)
+// and [split, batch) as two callers' pieces of ONE merged call, as a round of zkgpu_tx_verify_submit holds them: one bitmap and
+// one status array for the round, handed out to status_a (la) and status_b (lb), each caller's bits to its part of accept_bitmap.
+// dirty: a failed call had left something behind a caller's status bytes before it was fail-closed (must not be).
+int tx_out_selftest(int kind, TxOutLayout la, TxOutLayout lb, size_t batch, size_t split, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok,
+                    int host_threads, size_t chunk, uint32_t delay_seed, int fail_at, int fail_stage, int n_slots, uint8_t* accept_bitmap,
+                    uint8_t* status_a, uint8_t* status_b, TxOutSelftest& t) {
+  if (kind < 0 || kind > 2 || fail_stage < 0 || fail_stage > kind || !status_a || (split && (split >= batch || split % 8 || !status_b))) return -1;
+  const size_t na = split ? split : batch, nb = split ? batch - split : 0;
+  TxFormat format;                                       // (the round's device brings back what the wider of its calls asks for)
+  format.out.ids = la.ids || (nb && lb.ids);
+  format.out.log_k = std::max(la.log_k, nb ? lb.log_k : 0);
+  const std::unique_ptr<HostTxDevice> dev = tx_stand_in(kind, fail_stage, fail_at, txs, offs, batch, proof_ok, delay_seed, format);
+  const TxHandOut to[2] = {{na, la, accept_bitmap, status_a}, {nb, lb, accept_bitmap + split / 8, status_b}};
+  for (const TxHandOut& h : to) if (h.batch) h.layout.begin(h.bits, h.area, h.batch);
+  std::vector<uint8_t> round_bits((batch + 7) / 8 + 1, 0), round_status(split ? batch : 0, (uint8_t)TX_INVALID);
+  std::vector<TxStatement> store;
+  int rc;
+  {
+    std::unique_ptr<TxCall> call;
+    if (split == 0) {
+      call.reset(new TxCall(*dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, round_bits.data(), status_a, n_slots));
+    } else {
+      std::vector<TxCall::Piece> pieces{la.piece(txs, offs, na, status_a), lb.piece(txs, offs + split, nb, status_b)};
+      call.reset(new TxCall(*dev, store, (size_t)1 << 17, pieces, host_threads, chunk, round_bits.data(), round_status.data(), n_slots));
+    }
+    t.chunks = call->n_chunks();
+    rc = call->run();
+    t.host_hashed = call->n_host_hashed();
+  }
+  t.leaked = dev->leaked();
+  if (kind >= 1) {
+    const HostHashingTxDevice& h = *static_cast<const HostHashingTxDevice*>(dev.get());
+    t.id_asks = h.id_asks(); t.hashed = h.hashed(); t.logged = h.logged();
+  }
+  for (const TxHandOut& h : to)
+    for (size_t i = h.batch; rc != 0 && i < h.layout.bytes(h.batch); ++i) if (h.area[i]) t.dirty = true;
+  if (split) {
+    tx_round_hand_out(round_bits.data(), round_status.data(), rc == 0, to, 2);
+  } else if (rc != 0) {
+    la.fail_closed(accept_bitmap, status_a, batch);
+  } else {
+    std::memcpy(accept_bitmap, round_bits.data(), (batch + 7) / 8);
+  }
+  return rc;
+}
+}  // namespace
+
+// ---- the transaction IDs: status_a / status_b are 33 bytes per transaction (1 when return_ids = 0).  out[0] chunks, out[1] staged
+// ---- chunks never released, out[2] hash_collect calls that were given a host buffer, out[3] transactions whose ID the HOST's second
+// ---- pass hashed, out[4] IDs the stand-in's hashing stage produced, out[5] the body's `dirty` (must be 0)
 extern "C" int zkhost_txcall_ids_selftest(int kind, int return_ids, size_t batch, size_t split, const uint8_t* txs, const uint64_t* offs,
                                           const uint8_t* proof_ok, int host_threads, size_t chunk, uint32_t delay_seed, int fail_at, int fail_stage,
                                           int n_slots, uint8_t* accept_bitmap, uint8_t* status_a, uint8_t* status_b, uint64_t* out) {
   for (int q = 0; q < 6; ++q) out[q] = 0;
-  if (kind < 0 || kind > 2 || fail_stage < 0 || fail_stage > kind || !status_a || (split && (split >= batch || split % 8 || !status_b))) return -1;
-  const int f0 = fail_stage == 0 ? fail_at : -1, f1 = fail_stage == 1 ? fail_at : -1, f2 = fail_stage == 2 ? fail_at : -1;
-  std::unique_ptr<HostTxDevice> dev;
-  if (kind == 0) dev.reset(new HostTxDevice(txs, offs, batch, proof_ok, delay_seed, f0));
-  else if (kind == 1) dev.reset(new HostHashingTxDevice(txs, offs, batch, proof_ok, delay_seed, f1, f0));
-  else dev.reset(new HostChainingTxDevice(txs, offs, batch, proof_ok, delay_seed, f2, f1, f0));
-  dev->set_ids(return_ids != 0);
-  const size_t na = split ? split : batch, nb = split ? batch - split : 0;
-  uint8_t* const ids_a = return_ids ? status_a + na : nullptr;
-  uint8_t* const ids_b = return_ids && nb ? status_b + nb : nullptr;
-  std::memset(accept_bitmap, 0, (batch + 7) / 8);
-  std::memset(status_a, TX_INVALID, na);
-  if (nb) std::memset(status_b, TX_INVALID, nb);
-  if (ids_a) std::memset(ids_a, 0, 32 * na);
-  if (ids_b) std::memset(ids_b, 0, 32 * nb);
-  std::vector<uint8_t> round_bits((batch + 7) / 8 + 1, 0), round_status(split ? batch : 0, (uint8_t)TX_INVALID);
-  std::vector<TxStatement> store;
-  int rc;
-  {
-    std::unique_ptr<TxCall> call;
-    if (split == 0) {
-      call.reset(new TxCall(*dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, round_bits.data(), status_a, n_slots));
-    } else {
-      std::vector<TxCall::Piece> pieces{{txs, offs, na, ids_a}, {txs, offs + split, nb, ids_b}};
-      call.reset(new TxCall(*dev, store, (size_t)1 << 17, pieces, host_threads, chunk, round_bits.data(), round_status.data(), n_slots));
-    }
-    out[0] = call->n_chunks();
-    rc = call->run();
-    out[3] = call->n_host_hashed();
-  }
-  out[1] = dev->leaked();
-  if (kind >= 1) { out[2] = static_cast<HostHashingTxDevice*>(dev.get())->id_asks(); out[4] = static_cast<HostHashingTxDevice*>(dev.get())->hashed(); }
-  if (split) {                                           // (tx_round_distribute: a failed round keeps "outside the subset" alone)
-    for (size_t i = 0; i < batch; ++i) {
-      uint8_t& to = i < split ? status_a[i] : status_b[i - split];
-      if (rc == 0) to = round_status[i]; else if (round_status[i] == TX_UNSUPPORTED) to = TX_UNSUPPORTED;
-    }
-  }
-  if (rc != 0) {
-    for (size_t i = 0; ids_a && i < 32 * na; ++i) if (ids_a[i]) out[5] = 1;
-    for (size_t i = 0; ids_b && i < 32 * nb; ++i) if (ids_b[i]) out[5] = 1;
-    if (split == 0) for (size_t i = 0; i < batch; ++i) if (status_a[i] != TX_UNSUPPORTED) status_a[i] = TX_INVALID;
-    if (ids_a) std::memset(ids_a, 0, 32 * na);
-    if (ids_b) std::memset(ids_b, 0, 32 * nb);
-    return rc;
-  }
-  std::memcpy(accept_bitmap, round_bits.data(), (batch + 7) / 8);
-  return 0;
+  TxOutLayout lay;
+  lay.ids = return_ids != 0;
+  TxOutSelftest t;
+  const int rc = tx_out_selftest(kind, lay, lay, batch, split, txs, offs, proof_ok, host_threads, chunk, delay_seed, fail_at, fail_stage, n_slots,
+                                 accept_bitmap, status_a, status_b, t);
+  out[0] = t.chunks; out[1] = t.leaked; out[2] = t.id_asks; out[3] = t.host_hashed; out[4] = t.hashed; out[5] = t.dirty;
+  return rc;
 }
 
-// ---- a call whose caller is also handed the LOG's entries (TxDevice::log_k: ZKGPU_TXFORMAT_RETURN_LOG with window K) on the CPU,
-// ---- over the same three stand-ins -- kind 0: the host's second pass fills the records; 1, 2: the hashing stage gathers the
-// ---- entries' contract IDs (tx_log_gather_lane, the kernel's code) and the call adds counts and kinds -- laid out and fail-closed
-// ---- as session.hpp does it.  split = 0: a lone call, status_a is batch * (33 + 1 + 33 K) bytes; split > 0 (a multiple of 8,
-// ---- < batch): two callers' pieces of one merged call, status_a split * (33 + 1 + 33 K) bytes and status_b (batch - split) *
-// ---- (33 + 1 + 33 k_b) with a window k_b of its own (0: K; the round's device gathers the wider of the two).  fail_at /
-// ---- fail_stage as zkhost_txcall_ids_selftest.  out[0] chunks, out[1] staged chunks never released, out[2] transactions the
-// ---- HOST's second pass hashed, out[3] IDs the stand-in's hashing stage produced, out[4] log entries its gather handed back,
-// ---- out[5] whether a failed call had left anything in an ID or record area before it was fail-closed (must be 0)
+// ---- ... and the log's entries with window K: kind 0, the host's second pass fills the records; 1, 2: the hashing stage gathers
+// ---- the entries' contract IDs (tx_log_gather_lane, the kernel's code) and the call adds counts and kinds.  status_a is 33 + 1 +
+// ---- 33 K bytes per transaction, status_b 33 + 1 + 33 k_b with a window of its own (0: K).  out[0] chunks, out[1] staged chunks
+// ---- never released, out[2] transactions the HOST's second pass hashed, out[3] IDs the stand-in's hashing stage produced, out[4]
+// ---- log entries its gather handed back, out[5] the body's `dirty` (must be 0)
 extern "C" int zkhost_txcall_log_selftest(int kind, size_t K, size_t k_b, size_t batch, size_t split, const uint8_t* txs, const uint64_t* offs,
                                           const uint8_t* proof_ok, int host_threads, size_t chunk, uint32_t delay_seed, int fail_at, int fail_stage,
                                           int n_slots, uint8_t* accept_bitmap, uint8_t* status_a, uint8_t* status_b, uint64_t* out) {
   for (int q = 0; q < 6; ++q) out[q] = 0;
-  if (kind < 0 || kind > 2 || fail_stage < 0 || fail_stage > kind || K < 1 || K > 255 || k_b > 255 || !status_a ||
-      (split && (split >= batch || split % 8 || !status_b))) return -1;
-  if (k_b == 0) k_b = K;
-  const int f0 = fail_stage == 0 ? fail_at : -1, f1 = fail_stage == 1 ? fail_at : -1, f2 = fail_stage == 2 ? fail_at : -1;
-  std::unique_ptr<HostTxDevice> dev;
-  if (kind == 0) dev.reset(new HostTxDevice(txs, offs, batch, proof_ok, delay_seed, f0));
-  else if (kind == 1) dev.reset(new HostHashingTxDevice(txs, offs, batch, proof_ok, delay_seed, f1, f0));
-  else dev.reset(new HostChainingTxDevice(txs, offs, batch, proof_ok, delay_seed, f2, f1, f0));
-  dev->set_ids(true);
-  dev->set_log_k(split ? std::max(K, k_b) : K);
-  const size_t na = split ? split : batch, nb = split ? batch - split : 0;
-  uint8_t* const ids_a = status_a + na;
-  uint8_t* const log_a = status_a + 33 * na;
-  uint8_t* const ids_b = nb ? status_b + nb : nullptr;
-  uint8_t* const log_b = nb ? status_b + 33 * nb : nullptr;
-  const size_t la = na * tx_log_record_bytes(K), lb = nb * tx_log_record_bytes(k_b);
-  std::memset(accept_bitmap, 0, (batch + 7) / 8);
-  std::memset(status_a, TX_INVALID, na);
-  std::memset(ids_a, 0, 32 * na + la);
-  if (nb) { std::memset(status_b, TX_INVALID, nb); std::memset(ids_b, 0, 32 * nb + lb); }
-  std::vector<uint8_t> round_bits((batch + 7) / 8 + 1, 0), round_status(split ? batch : 0, (uint8_t)TX_INVALID);
-  std::vector<TxStatement> store;
-  int rc;
-  {
-    std::unique_ptr<TxCall> call;
-    if (split == 0) {
-      call.reset(new TxCall(*dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, round_bits.data(), status_a, n_slots));
-    } else {
-      std::vector<TxCall::Piece> pieces{{txs, offs, na, ids_a, log_a, K}, {txs, offs + split, nb, ids_b, log_b, k_b}};
-      call.reset(new TxCall(*dev, store, (size_t)1 << 17, pieces, host_threads, chunk, round_bits.data(), round_status.data(), n_slots));
+  if (K < 1 || K > 255 || k_b > 255) return -1;
+  TxOutLayout la, lb;
+  la.ids = lb.ids = true;
+  la.log_k = K; lb.log_k = k_b ? k_b : K;
+  TxOutSelftest t;
+  const int rc = tx_out_selftest(kind, la, lb, batch, split, txs, offs, proof_ok, host_threads, chunk, delay_seed, fail_at, fail_stage, n_slots,
+                                 accept_bitmap, status_a, status_b, t);
+  out[0] = t.chunks; out[1] = t.leaked; out[2] = t.host_hashed; out[3] = t.hashed; out[4] = t.logged; out[5] = t.dirty;
+  return rc;
+}
+
+// ---- the layout header itself (tx_out.hpp), for the CPU test.  op 0: the format word in[0] -> out: valid, base, hash, sign, ids,
+// ---- K.  Ops 1 .. 4 take a layout in[0] = ids, in[1] = K and a batch in[2]: op 1 -> out: bytes(batch), the offsets of the status
+// ---- byte / ID / record of transaction in[3] and of a piece's ID / record areas (-1: not there), the piece's window; op 2 begin,
+// ---- 3 nothing-in-the-subset, 4 fail-closed over bitmap and area (either may be NULL).  op 5, a round's hand-out: in[0] calls,
+// ---- in[1] ok, then (ids, K, batch) per call; bitmap / area hold the ROUND's bits / status bytes, out_bits / out_area the
+// ---- calls' bitmaps ((batch + 7) / 8 bytes each) and areas one behind the other.  -> 0, -1 on bad arguments
+extern "C" int zkhost_tx_out_layout(int op, const int64_t* in, uint8_t* bitmap, uint8_t* area, uint8_t* out_bits, uint8_t* out_area, int64_t* out) {
+  if (!in || op < 0 || op > 5 || (op <= 1 && !out)) return -1;
+  const auto layout = [](const int64_t* q) { TxOutLayout l; l.ids = q[0] != 0; l.log_k = (size_t)q[1]; return l; };
+  if (op == 0) {
+    TxFormat f;
+    const int64_t r[6] = {TxFormat::of((int)in[0], &f), f.base, f.hash_on_device, f.sign_on_device, f.out.ids, (int64_t)f.out.log_k};
+    std::copy(r, r + 6, out);
+    return 0;
+  }
+  if (op == 5) {
+    std::vector<TxHandOut> to;
+    for (int64_t c = 0; c < in[0]; ++c) {
+      to.push_back({(size_t)in[4 + 3 * c], layout(in + 2 + 3 * c), out_bits, out_area});
+      out_bits += (to.back().batch + 7) / 8; out_area += to.back().layout.bytes(to.back().batch);
     }
-    out[0] = call->n_chunks();
-    rc = call->run();
-    out[2] = call->n_host_hashed();
+    tx_round_hand_out(bitmap, area, in[1] != 0, to.data(), to.size());
+    return 0;
   }
-  out[1] = dev->leaked();
-  if (kind >= 1) { out[3] = static_cast<HostHashingTxDevice*>(dev.get())->hashed(); out[4] = static_cast<HostHashingTxDevice*>(dev.get())->logged(); }
-  if (split) {
-    for (size_t i = 0; i < batch; ++i) {
-      uint8_t& to = i < split ? status_a[i] : status_b[i - split];
-      if (rc == 0) to = round_status[i]; else if (round_status[i] == TX_UNSUPPORTED) to = TX_UNSUPPORTED;
-    }
-  }
-  if (rc != 0) {
-    for (size_t i = 0; i < 32 * na + la; ++i) if (ids_a[i]) out[5] = 1;
-    for (size_t i = 0; nb && i < 32 * nb + lb; ++i) if (ids_b[i]) out[5] = 1;
-    if (split == 0) for (size_t i = 0; i < batch; ++i) if (status_a[i] != TX_UNSUPPORTED) status_a[i] = TX_INVALID;
-    std::memset(ids_a, 0, 32 * na + la);
-    if (nb) std::memset(ids_b, 0, 32 * nb + lb);
-    return rc;
-  }
-  std::memcpy(accept_bitmap, round_bits.data(), (batch + 7) / 8);
+  const TxOutLayout lay = layout(in);
+  const size_t batch = (size_t)in[2];
+  if (op == 2) lay.begin(bitmap, area, batch);
+  if (op == 3) lay.nothing_in_subset(area, batch);
+  if (op == 4) lay.fail_closed(bitmap, area, batch);
+  if (op != 1) return 0;
+  uint8_t* const base = (uint8_t*)(uintptr_t)4096;        // (offsets only: nothing is read or written)
+  const auto at = [&](const uint8_t* p) { return p ? (int64_t)(p - base) : (int64_t)-1; };
+  const TxPiece pc = lay.piece(nullptr, nullptr, batch, base);
+  const int64_t r[7] = {(int64_t)lay.bytes(batch), at(lay.status_of(base, (size_t)in[3])), at(lay.id_of(base, batch, (size_t)in[3])),
+                        at(lay.record_of(base, batch, (size_t)in[3])), at(pc.ids), at(pc.log), (int64_t)pc.log_k};
+  std::copy(r, r + 7, out);
   return 0;
 }
 
-// ---- tx_prepare_many_logged (tx_log.hpp) restates tx_prepare_many (zkvm_tx.hpp), which cannot be touched: the two second passes
-// ---- side by side over the same transactions in the same groups of eight, statement by statement -- status, reason text, header,
+// ---- tx_prepare_many_logged (tx_log.hpp) and tx_prepare_many (zkvm_tx.hpp) are two sets of parameters of ONE second pass
+// ---- (tx_run_group); what must not differ between them is guarded here: the two passes side by side over the same transactions in the same groups of eight, statement by statement -- status, reason text, header,
 // ---- transaction ID, arity, commitments, where the proof lies, the signature's scalars and points.  -> statements that differ
 // ---- (must be 0), -1 on bad arguments.  *lockstep_groups (may be NULL): groups of eight whose plans had one shape, i.e. that
 // ---- AVX-512 hashes in lockstep where the CPU has it -- so that a test knows it compared both ways of running the plans.

@@ -99,11 +99,14 @@ struct zkgpu_verifier {
   std::map<uint64_t, std::unique_ptr<BlockRun>> block_runs;
   uint64_t next_run = 1;
   int lanes_requested = 0, lanes_dropped = 0;           // lanes whose light stream shared a hardware queue with an earlier lane's were not kept
-  int tx_format = 0;                                    // zkgpu_verifier_set_tx_format: 0 = no serialized-transaction format enabled;
-                                                        // 1 and 2 read the same bytes, 2 writes a reason into the status bytes
-  bool tx_hash_on_device = false;                       // the format's flag ZKGPU_TXFORMAT_HASH_ON_DEVICE (tx_format keeps the low byte)
-  // its stage, per key / signature slot: a stream of its own (never behind the proofs), the tape's flattener, the tape on its
-  // way up (pinned, device), the slot memory, the IDs on their way down (device, pinned); and, once per verifier, the
+  // zkgpu_verifier_set_tx_format: the format word as it was given, VALIDATED (0 = no serialized-transaction format enabled).
+  // What it means -- base format, the two device switches, the layout of a call's status argument -- is tx_out.hpp's to say
+  // (TxFormat::of_valid, TxOutLayout); ONE word, so that whoever reads it reads a combination the format had.  (Atomic:
+  // zkgpu_tx_verify_batch reads the layout on entry and zkgpu_tx_verify_submit at submit time, both without `mu`, which a round
+  // in flight holds; the base format and the device switches are read by the call or round under `mu`.)
+  std::atomic<int> tx_format{0};
+  // the stage of ZKGPU_TXFORMAT_HASH_ON_DEVICE, per key / signature slot: a stream of its own (never behind the proofs), the
+  // tape's flattener, the tape on its way up (pinned, device), the slot memory, the IDs on their way down (device, pinned); and, once per verifier, the
   // protocols' initial transcripts and the label table.  Made at the first flagged call; grow-only.
   struct TxHashStage {
     hipStream_t stream = nullptr;
@@ -123,14 +126,6 @@ struct zkgpu_verifier {
   };
   TxHashStage tx_hash[2];
   Buffer tx_hash_const;
-  bool tx_sign_on_device = false;                       // the flag ZKGPU_TXFORMAT_SIGN_ON_DEVICE (only beside the one above)
-  // The layout of a call's status argument, ONE word so that a call reads a pair the format had: bit 0 the flag
-  // ZKGPU_TXFORMAT_RETURN_IDS (33 * batch bytes, the IDs of what was accepted behind the status bytes), bits 8 .. 15 the window K
-  // of ZKGPU_TXFORMAT_RETURN_LOG (only beside bit 0; 0 without the flag: batch records of 1 + 33 K bytes behind the IDs).
-  // (Atomic: zkgpu_tx_verify_submit reads it without `mu`, which a round in flight holds.)
-  std::atomic<uint32_t> tx_layout{0};
-  static bool layout_ids(uint32_t layout) { return (layout & 1u) != 0; }
-  static size_t layout_log_k(uint32_t layout) { return (layout & 1u) ? (layout >> 8) & 255u : 0; }
   // what the signature's challenge needs beside its slot's signature context (tx_sig_rows.hpp): the rows' places on the tape,
   // the events that order it behind the slot's key stage and hashing stage; once per verifier, the script of the transcript
   struct TxSigStage { Buffer d_pos; hipEvent_t ev_keys = nullptr, ev_ids = nullptr; size_t rows = 0; };
@@ -164,11 +159,8 @@ struct zkgpu_verifier {
     int host_threads = 0;
     int state = 0, rc = 0;                              // 0 queued, 1 in a round, 2 done
     std::chrono::steady_clock::time_point arrived;      // (the engine lets a small queue wait a little while a round is running)
-    std::vector<uint8_t> bits, status;
-    bool return_ids = false;                            // the layout of its status argument, as the format said when it was SUBMITTED
-    std::vector<uint8_t> txids;                         // ... then 32 bytes per transaction: zero but beside a set bit
-    size_t log_k = 0;                                   // ... and (only with return_ids) K of ZKGPU_TXFORMAT_RETURN_LOG when it was submitted
-    std::vector<uint8_t> txlog;                         // ... then a record of 1 + 33 K bytes per transaction, likewise
+    zk::zkvm::TxOutLayout layout;                       // of its status argument, as the format said when it was SUBMITTED
+    std::vector<uint8_t> bits, area;                    // its bitmap; its status argument, layout.bytes(batch), as wait will copy it out
   };
   std::mutex tx_mu;
   std::condition_variable tx_cv;
@@ -1695,21 +1687,16 @@ int zkgpu_verifier_verify_sharded(zkgpu_verifier* v, zkgpu_comm* cm, size_t batc
 // and blocks: the whole call holds the verifier's mutex, and whatever is in flight on the lanes is collected first
 // (the verdicts stay with their tickets / runs) -- a synchronous call on a context with a batch in flight would
 // overwrite that batch's status words and pinned result buffer (and is refused by the context: refuse_if_pending).
+static_assert(zk::zkvm::TXFORMAT_V1 == ZKGPU_TXFORMAT_RECOLLECTED_V1 && zk::zkvm::TXFORMAT_V1_REASONS == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS &&
+              zk::zkvm::TXFORMAT_HASH_ON_DEVICE == ZKGPU_TXFORMAT_HASH_ON_DEVICE && zk::zkvm::TXFORMAT_SIGN_ON_DEVICE == ZKGPU_TXFORMAT_SIGN_ON_DEVICE &&
+              zk::zkvm::TXFORMAT_RETURN_IDS == ZKGPU_TXFORMAT_RETURN_IDS && zk::zkvm::TXFORMAT_RETURN_LOG == ZKGPU_TXFORMAT_RETURN_LOG &&
+              zk::zkvm::TXFORMAT_LOG_SHIFT == ZKGPU_TXFORMAT_LOG_SHIFT && zk::zkvm::TXOUT_REJECTED == ZKGPU_TXSTATUS_REJECTED &&
+              zk::zkvm::TXOUT_OUTSIDE_SUBSET == ZKGPU_TXSTATUS_OUTSIDE_SUBSET, "tx_out.hpp restates the format's flags and two status bytes");
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
-  // (ZKGPU_TXFORMAT_RETURN_LOG travels with its window K in bits 16 .. 23: both or neither, and only beside ZKGPU_TXFORMAT_RETURN_IDS)
-  const int log_k = (format >> ZKGPU_TXFORMAT_LOG_SHIFT) & 255;
-  const bool log = (format & ZKGPU_TXFORMAT_RETURN_LOG) != 0;
-  if (format < 0 || log != (log_k != 0) || (log && !(format & ZKGPU_TXFORMAT_RETURN_IDS))) return ZKGPU_EINVAL;
-  const int base = format & ~(ZKGPU_TXFORMAT_HASH_ON_DEVICE | ZKGPU_TXFORMAT_SIGN_ON_DEVICE | ZKGPU_TXFORMAT_RETURN_IDS | ZKGPU_TXFORMAT_RETURN_LOG |
-                              (255 << ZKGPU_TXFORMAT_LOG_SHIFT));     // (the flags go with a format: alone they name none)
-  if (!v || (format != 0 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1 && base != ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS)) return ZKGPU_EINVAL;
-  // (the challenge reads the transaction ID where the hashing stage left it: no signing on the device without hashing there)
-  if ((format & ZKGPU_TXFORMAT_SIGN_ON_DEVICE) && !(format & ZKGPU_TXFORMAT_HASH_ON_DEVICE)) return ZKGPU_EINVAL;
+  zk::zkvm::TxFormat f;
+  if (!v || !zk::zkvm::TxFormat::of(format, &f)) return ZKGPU_EINVAL;     // (the rules: tx_out.hpp)
   std::lock_guard<std::mutex> lk(v->mu);
-  v->tx_format = base;
-  v->tx_hash_on_device = (format & ZKGPU_TXFORMAT_HASH_ON_DEVICE) != 0;
-  v->tx_sign_on_device = (format & ZKGPU_TXFORMAT_SIGN_ON_DEVICE) != 0;
-  v->tx_layout = ((format & ZKGPU_TXFORMAT_RETURN_IDS) ? 1u : 0u) | ((uint32_t)log_k << 8);
+  v->tx_format = format;
   return ZKGPU_OK;
 }
 
@@ -1788,32 +1775,25 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
                           uint8_t* accept_bitmap, uint8_t* status) {
   using namespace zk::zkvm;
   if (!v || !accept_bitmap) return ZKGPU_EINVAL;
-  memset(accept_bitmap, 0, (batch + 7) / 8);
-  if (status) memset(status, TX_INVALID, batch);
-  // (ZKGPU_TXFORMAT_RETURN_IDS: `status` is 33 * batch bytes.  The ID area is zero from here on, whichever way the call
-  // leaves; TxCall::verdicts writes into it beside the bits it sets, and an error zeroes it again below)
-  const uint32_t layout = v->tx_layout.load();
-  uint8_t* const txids = (status && zkgpu_verifier::layout_ids(layout)) ? status + batch : nullptr;
-  if (txids) memset(txids, 0, 32 * batch);
-  // (ZKGPU_TXFORMAT_RETURN_LOG: ... and behind the IDs, batch records of 1 + 33 K bytes, zero in the same way)
-  const size_t log_k = txids ? zkgpu_verifier::layout_log_k(layout) : 0, log_bytes = log_k ? batch * zk::zkvm::tx_log_record_bytes(log_k) : 0;
-  uint8_t* const txlog = log_k ? status + 33 * batch : nullptr;
-  if (txlog) memset(txlog, 0, log_bytes);
+  // (the layout of `status` is the one the format has on entry; it is "nothing accepted" from here on, whichever way the call
+  // leaves: TxCall::verdicts writes beside the bits it sets, and an error closes it again below)
+  const TxOutLayout out = TxFormat::of_valid(v->tx_format.load()).out;
+  out.begin(accept_bitmap, status, batch);
   if (batch == 0) return ZKGPU_OK;
   if (!txs || !tx_offsets || batch >= (1ull << 31)) return ZKGPU_EINVAL;
   for (size_t i = 0; i < batch; ++i) if (tx_offsets[i + 1] < tx_offsets[i]) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> vlk(v->mu);
-  if (v->tx_format == 0) {                                        // no format enabled: nothing is inside the subset
-    if (status) memset(status, TX_UNSUPPORTED, batch);
-    if (txids) memset(txids, 0, 32 * batch);                      // (a format set meanwhile: the layout is the one the call began with)
-    if (txlog) memset(txlog, 0, log_bytes);
+  // (format 2 reads the same bytes and gives the same bits; what differs is what the status bytes say -- with no status
+  // array there is nothing to say, and the call is the format-1 call.  A format set meanwhile: the layout stays the call's)
+  TxFormat format = TxFormat::of_valid(v->tx_format.load());
+  format.out = out;
+  if (!status) format = format.without_status();
+  if (format.base == 0) {                                         // no format enabled: nothing is inside the subset
+    out.nothing_in_subset(status, batch);
     return ZKGPU_OK;
   }
   TRY(tx_call_prepare(v));
-  // (format 2 reads the same bytes and gives the same bits; what differs is what the status bytes say -- with no status
-  // array there is nothing to say, and the call is the format-1 call)
-  GpuTxDevice dev(v, 0, 0, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS && status != nullptr, v->tx_hash_on_device,
-                  v->tx_sign_on_device, txids != nullptr, log_k);
+  GpuTxDevice dev(v, 0, 0, format);
   int rc;
   try {
     TxCall call(dev, v->tx_statements, v->tx_statements_kept, batch, txs, tx_offsets, host_threads, v->tx_chunk, accept_bitmap, status);
@@ -1823,12 +1803,7 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
     v->last_error = "out of host memory while planning the transaction call";
     rc = ZKGPU_ENOMEM;
   }
-  if (rc != ZKGPU_OK) {                                          // both outputs read "nothing accepted"
-    memset(accept_bitmap, 0, (batch + 7) / 8);
-    if (status) for (size_t i = 0; i < batch; ++i) if (status[i] != TX_UNSUPPORTED) status[i] = TX_INVALID;     // (never a reason, never 0)
-    if (txids) memset(txids, 0, 32 * batch);                      // (and never an ID)
-    if (txlog) memset(txlog, 0, log_bytes);                       // (nor a log entry)
-  }
+  if (rc != ZKGPU_OK) out.fail_closed(accept_bitmap, status, batch);
   return rc;
 }
 
@@ -1849,36 +1824,13 @@ constexpr std::chrono::microseconds TX_LINGER(300);
 struct TxRound {
   std::vector<zkgpu_verifier::TxPending*> calls;
   std::vector<zk::zkvm::TxCall::Piece> pieces;
+  std::vector<zk::zkvm::TxHandOut> hand_out;              // per call: its own bitmap and area
   std::vector<uint8_t> bits, status;
   std::unique_ptr<GpuTxDevice> dev;
   std::unique_ptr<zk::zkvm::TxCall> call;
   size_t total = 0;
   int rc = ZKGPU_OK;
 };
-
-// hands every call of a finished round its own bits (tx_mu held)
-void tx_round_distribute(TxRound& r) {
-  using namespace zk::zkvm;
-  size_t at = 0;
-  for (auto* p : r.calls) {
-    p->bits.assign((p->batch + 7) / 8, 0);
-    p->status.assign(p->batch, TX_INVALID);
-    if (r.rc != ZKGPU_OK) std::fill(p->txids.begin(), p->txids.end(), (uint8_t)0);      // (a failed round: no ID either)
-    if (r.rc != ZKGPU_OK) std::fill(p->txlog.begin(), p->txlog.end(), (uint8_t)0);      // (nor a log entry)
-    p->rc = r.rc;
-    for (size_t i = 0; i < p->batch; ++i) {
-      const size_t g = at + i;
-      if (r.rc == ZKGPU_OK) {
-        if ((r.bits[g / 8] >> (g % 8)) & 1) p->bits[i / 8] |= (uint8_t)(1u << (i % 8));
-        p->status[i] = r.status[g];
-      } else if (r.status[g] == TX_UNSUPPORTED) {
-        p->status[i] = TX_UNSUPPORTED;
-      }
-    }
-    at += p->batch;
-    p->state = 2;
-  }
-}
 
 // The engine: rounds of merged calls, driven by this one thread (TxCall::step never blocks; a round is finished only once
 // the device has settled).  It can keep TWO rounds in flight -- one key / signature stage slot and one set of staging areas
@@ -1943,27 +1895,29 @@ void tx_engine_main(zkgpu_verifier* v) {
       if (!fresh[set]) continue;
       TxRound& r = *fresh[set];
       int threads = 0;
-      // (a call submitted under ZKGPU_TXFORMAT_RETURN_IDS has its own ID area, zero until verdicts() writes beside a set bit)
-      // (... and one submitted under ZKGPU_TXFORMAT_RETURN_LOG its own records, of its own window; the round's device gathers the widest)
-      bool want_ids = false;
-      size_t want_log_k = 0;
+      // (every call has its own area, laid out as the format said when it was submitted and "nothing accepted" until verdicts()
+      // writes beside a set bit; the round's device brings back what the widest of them asks for)
+      TxFormat format = TxFormat::of_valid(v->tx_format.load());
+      format.out = TxOutLayout();
       for (auto* p : r.calls) {
-        if (p->return_ids) { p->txids.assign(32 * p->batch, 0); want_ids = true; }
-        if (p->return_ids && p->log_k) { p->txlog.assign(p->batch * tx_log_record_bytes(p->log_k), 0); want_log_k = std::max(want_log_k, p->log_k); }
-        r.pieces.push_back({p->txs, p->offsets, p->batch, p->return_ids ? p->txids.data() : nullptr, p->return_ids && p->log_k ? p->txlog.data() : nullptr,
-                            p->return_ids ? p->log_k : 0});
+        p->bits.resize((p->batch + 7) / 8);
+        p->area.resize(p->layout.bytes(p->batch));
+        p->layout.begin(p->bits.data(), p->area.data(), p->batch);
+        r.pieces.push_back(p->layout.piece(p->txs, p->offsets, p->batch, p->area.data()));
+        r.hand_out.push_back({p->batch, p->layout, p->bits.data(), p->area.data()});
+        format.out.ids |= p->layout.ids;
+        format.out.log_k = std::max(format.out.log_k, p->layout.log_k);
         threads = std::max(threads, p->host_threads);
       }
       r.bits.assign((r.total + 7) / 8 + 1, 0);
       r.status.assign(r.total, TX_INVALID);
-      if (v->tx_format == 0) {
+      if (format.base == 0) {
         std::fill(r.status.begin(), r.status.end(), (uint8_t)TX_UNSUPPORTED);       // no format enabled: nothing is inside the subset
       } else {
         r.rc = tx_call_prepare(v, !active[0] && !active[1]);
         if (r.rc == ZKGPU_OK) {
           try {
-            r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, v->tx_format == ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS, v->tx_hash_on_device,
-                                        v->tx_sign_on_device, want_ids, want_log_k));
+            r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, format));
             r.call.reset(new TxCall(*r.dev, set ? v->tx_statements_b : v->tx_statements, v->tx_statements_kept, r.pieces, threads, v->tx_chunk,
                                     r.bits.data(), r.status.data(), 1));
             r.call->set_on_news([&] { { std::lock_guard<std::mutex> nl(news_mu); news = true; } news_cv.notify_one(); });
@@ -1995,8 +1949,9 @@ void tx_engine_main(zkgpu_verifier* v) {
           r.call.reset();                                // (joins its staging thread: nothing calls on_news afterwards)
         }
         {
-          std::lock_guard<std::mutex> lk(v->tx_mu);
-          tx_round_distribute(r);
+          std::lock_guard<std::mutex> lk(v->tx_mu);        // every call its own bits and status bytes (tx_out.hpp)
+          tx_round_hand_out(r.bits.data(), r.status.data(), r.rc == ZKGPU_OK, r.hand_out.data(), r.hand_out.size());
+          for (auto* p : r.calls) { p->rc = r.rc; p->state = 2; }
         }
         v->tx_cv.notify_all();
         active[set].reset();
@@ -2018,9 +1973,7 @@ int zkgpu_tx_verify_submit(zkgpu_verifier* v, size_t batch, const uint8_t* txs, 
   std::unique_ptr<zkgpu_verifier::TxPending> p(new zkgpu_verifier::TxPending());
   p->batch = batch; p->txs = txs; p->offsets = tx_offsets; p->host_threads = host_threads;
   p->arrived = std::chrono::steady_clock::now();
-  const uint32_t layout = v->tx_layout.load();           // (the layout wait will write: the one in force now)
-  p->return_ids = zkgpu_verifier::layout_ids(layout);
-  p->log_k = zkgpu_verifier::layout_log_k(layout);
+  p->layout = zk::zkvm::TxFormat::of_valid(v->tx_format.load()).out;     // (the layout wait will write: the one in force now)
   std::lock_guard<std::mutex> lk(v->tx_mu);
   if (v->tx_engine_quit) return ZKGPU_EINVAL;
   if (!v->tx_engine.joinable()) {
@@ -2043,18 +1996,9 @@ int zkgpu_tx_verify_wait(zkgpu_verifier* v, uint64_t call_id, uint8_t* accept_bi
   zkgpu_verifier::TxPending* p = it->second.get();
   v->tx_cv.wait(lk, [&] { return p->state == 2; });
   const int rc = p->rc;
-  memset(accept_bitmap, 0, (p->batch + 7) / 8);
-  if (rc == ZKGPU_OK) memcpy(accept_bitmap, p->bits.data(), p->bits.size());
-  if (status) memcpy(status, p->status.data(), p->batch);
-  if (status && p->return_ids) {                         // (submitted under ZKGPU_TXFORMAT_RETURN_IDS: 33 * batch bytes)
-    if (rc == ZKGPU_OK && p->txids.size() == 32 * p->batch) memcpy(status + p->batch, p->txids.data(), 32 * p->batch);
-    else memset(status + p->batch, 0, 32 * p->batch);
-    if (p->log_k) {                                      // (... and under ZKGPU_TXFORMAT_RETURN_LOG: batch * (33 + 1 + 33 K))
-      const size_t log_bytes = p->batch * zk::zkvm::tx_log_record_bytes(p->log_k);
-      if (rc == ZKGPU_OK && p->txlog.size() == log_bytes) memcpy(status + 33 * p->batch, p->txlog.data(), log_bytes);
-      else memset(status + 33 * p->batch, 0, log_bytes);
-    }
-  }
+  // (its bitmap and its area are as the round handed them out: fail-closed already when the round failed)
+  memcpy(accept_bitmap, p->bits.data(), p->bits.size());
+  if (status) memcpy(status, p->area.data(), p->area.size());
   v->tx_calls.erase(it);
   return rc;
 }

@@ -42,17 +42,16 @@
 //     signature bits of a chunk are collected together, when its signature stage is through, and that is when its slot is
 //     free again (the IDs are not brought down: nothing on the host reads them).  A row whose key did not decode runs through
 //     all the same: its bit is ANDed with the key's.
-// A third switch changes nothing of the schedule: TxDevice::ids() (ZKGPU_TXFORMAT_RETURN_IDS) hands the caller the transaction
-// ID of every ACCEPTED transaction -- 32 bytes each in an area of the caller's (Piece::ids; of a lone call, behind its status
-// bytes), written by verdicts() where it writes TX_OK and nowhere else, from the statement's txid: the one the VM's second
-// pass hashed for the signature, or the one the device's tape produced.  Nothing is hashed for it; all it adds is that a
-// device that chains copies its IDs down after all (hash_collect with a host buffer).
-// A fourth, only beside the third: TxDevice::log_k() (ZKGPU_TXFORMAT_RETURN_LOG) also hands the caller the Input / Output
-// entries of every accepted transaction's log (tx_log.hpp) -- a record of 1 + 33 K bytes each in an area of the caller's
-// (Piece::log), written by verdicts() where it writes the ID.  The records of the whole call are kept in a side array of the
-// call until then: the host's second pass fills them from the slots its plans wrote (tx_prepare_many_logged); a device that
-// hashes brings the entries' contract IDs down with the transaction IDs (hash_log) and the host adds counts and kinds from
-// the tape's shape table.  Nothing is hashed for it either, and the statements grow by nothing.
+// What the caller is handed beside the bits changes nothing of the schedule, and its layout is tx_out.hpp's (TxOutLayout, TxPiece):
+//   TxDevice::ids() (ZKGPU_TXFORMAT_RETURN_IDS): the transaction ID of every ACCEPTED transaction, written by verdicts() where it
+//     writes TX_OK and nowhere else (Piece::ids), from the statement's txid: the one the VM's second pass hashed for the
+//     signature, or the one the device's tape produced.  Nothing is hashed for it; all it adds is that a device that chains
+//     copies its IDs down after all (hash_collect with a host buffer).
+//   TxDevice::log_k() (ZKGPU_TXFORMAT_RETURN_LOG, only beside ids()): also the Input / Output entries of every accepted
+//     transaction's log (tx_log.hpp), one record each (Piece::log), written by verdicts() where it writes the ID.  The records
+//     of the whole call are kept in a side array of the call until then: the host's second pass fills them from the slots its
+//     plans wrote (tx_prepare_many_logged); a device that hashes brings the entries' contract IDs down with the transaction IDs
+//     (hash_log) and the host adds counts and kinds from the tape's shape table.  Nothing is hashed for it either.
 // The calling thread's sub-steps (snapshot, queue_keys, queue_tape, proofs_turn, the collects, end_step) are the same whatever
 // the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run: step_host_signed()
 // and step_chained(), which say why.
@@ -60,6 +59,7 @@
 #include "host_pool.hpp"
 #include "tx_hash_tape.hpp"
 #include "tx_log.hpp"
+#include "tx_out.hpp"
 #include "zkvm_tx.hpp"
 
 #include <atomic>
@@ -155,18 +155,16 @@ class TxCall {
   enum : uint8_t { WHY_NONE = 1, WHY_TX_INVALID = 16, WHY_PROOF_FIRST = 17, WHY_KEY = 20, WHY_SIGNATURE = 21 };
 
   // several callers' transactions as ONE call (zkgpu_tx_verify_submit: calls in flight are merged as tickets are): the
-  // pieces in order, transaction i of the merged call = the i-th transaction counted through them
-  // ids (only of a device with ids(); may be NULL): 32 * batch bytes of that caller's, zeroed by it, for the IDs of what is accepted
-  // log / log_k (only of a device with log_k() >= log_k; may be NULL): batch records of 1 + 33 * log_k bytes, zeroed likewise
-  struct Piece { const uint8_t* txs; const uint64_t* tx_offsets; size_t batch; uint8_t* ids = nullptr; uint8_t* log = nullptr; size_t log_k = 0; };
+  // pieces in order, transaction i of the merged call = the i-th transaction counted through them.  ids / log are written only
+  // for a device with ids() / with log_k() >= the piece's log_k
+  using Piece = TxPiece;
+  static_assert(TX_INVALID == TXOUT_REJECTED && TX_UNSUPPORTED == TXOUT_OUTSIDE_SUBSET, "tx_out.hpp restates two status bytes");
   // store: what the VM leaves per transaction, kept by the caller between calls (fresh memory costs a page fault per 4 KB);
   // at most `kept` entries of it are used, the rest of a longer call lives in the call.
-  // A lone call on a device with ids(): `status` points at 33 * batch bytes, the IDs behind the status bytes; with log_k()
-  // = K as well, at batch * (33 + 1 + 33 K) bytes, the records behind the IDs.
+  // A lone call: `status` (may be NULL) is the caller's whole status argument, laid out as the device's ids() and log_k() say
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
-      : TxCall(dev, store, kept, std::vector<Piece>{Piece{txs, tx_offsets, batch, dev.ids() && status ? status + batch : nullptr,
-                                                             dev.ids() && dev.log_k() && status ? status + 33 * batch : nullptr, dev.log_k()}}, host_threads,
+      : TxCall(dev, store, kept, std::vector<Piece>{TxOutLayout{dev.ids(), dev.ids() ? dev.log_k() : 0}.piece(txs, tx_offsets, batch, status)}, host_threads,
                chunk_override, accept_bitmap, status, n_slots) {}
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)

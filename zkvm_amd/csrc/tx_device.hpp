@@ -151,16 +151,17 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
  public:
   // slot_base / arena_base: which of the verifier's stage contexts and staging areas this call uses (a call alone: slots 0
   // and 1, areas 0 .. RING - 1; two rounds in flight: one slot and one set of areas each)
-  // reasons: a format-2 call -- every stage also brings back one reason byte per row (tx_reason_kernels.hpp)
-  // hashes: the format's flag ZKGPU_TXFORMAT_HASH_ON_DEVICE -- the transaction IDs of every chunk come from k_tx_hash
-  // chains: ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the signature's challenge comes from k_tx_sig_rows
-  // ids: ZKGPU_TXFORMAT_RETURN_IDS -- the caller is handed the IDs of what it accepted; all it changes HERE is that a chained
-  // stage copies its IDs down as an unchained one does (one copy on the hashing stream, no launch)
-  // log_k: ZKGPU_TXFORMAT_RETURN_LOG beside it -- K, the log entries kept per transaction (0: no).  Here: behind k_tx_hash, on
-  // its stream, k_tx_log_gather and one more copy down (hash_queue); a call without it queues exactly what it queued before
-  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, bool reasons = false, bool hashes = false, bool chains = false,
-                       bool ids = false, size_t log_k = 0)
-      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(reasons), hashes_(hashes), chains_(hashes && chains), ids_(ids), log_k_(ids ? log_k : 0) {}
+  // format (tx_out.hpp: TxFormat, the verifier's format word decoded; of it the base format 0 never gets here):
+  //   reasons(): a format-2 call -- every stage also brings back one reason byte per row (tx_reason_kernels.hpp)
+  //   hash_on_device: ZKGPU_TXFORMAT_HASH_ON_DEVICE -- the transaction IDs of every chunk come from k_tx_hash
+  //   sign_on_device: ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the signature's challenge comes from k_tx_sig_rows
+  //   out.ids: ZKGPU_TXFORMAT_RETURN_IDS -- the caller is handed the IDs of what it accepted; all it changes HERE is that a chained
+  //     stage copies its IDs down as an unchained one does (one copy on the hashing stream, no launch)
+  //   out.log_k: ZKGPU_TXFORMAT_RETURN_LOG beside it -- K, the log entries kept per transaction (0: no).  Here: behind k_tx_hash, on
+  //     its stream, k_tx_log_gather and one more copy down (hash_queue); a call without it queues exactly what it queued before
+  explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, const zk::zkvm::TxFormat& format = zk::zkvm::TxFormat())
+      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(format.reasons()), hashes_(format.hash_on_device), chains_(format.hash_on_device && format.sign_on_device),
+        ids_(format.out.ids), log_k_(format.out.ids ? format.out.log_k : 0) {}
   bool reasons() const override { return reasons_; }
   bool hashes() const override { return hashes_; }
   bool chains() const override { return chains_; }

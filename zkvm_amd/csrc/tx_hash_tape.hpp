@@ -345,44 +345,14 @@ inline bool hash_tape_check(const uint32_t* b, size_t words) {
   return true;
 }
 
-// The second pass of a flagged call over up to eight transactions: parse, VM and the whole plan; the MuSig jobs run here
-// (in lockstep when the eight have one shape, as tx_prepare_many does), everything else of the plan goes to the tape as
-// transaction j0 + i of its chunk.  The statement's transaction ID reads zero until the device's has been collected.
+// The second pass of a flagged call over up to eight transactions (tx_run_group, zkvm_tx.hpp): parse, VM and the WHOLE plan;
+// the MuSig jobs alone run here, everything else of the plan goes to the tape as transaction j0 + i of its chunk.  The slot
+// memory is zeroed: the statement's transaction ID reads zero until the device's has been collected.
 // -> false: a plan the tape cannot hold (the call fails closed)
 inline bool tx_prepare_many_taped(const uint8_t* const* tx, const size_t* len, TxStatement* st, size_t count, TxHashTape& tape, size_t j0) {
-  static thread_local TxPlan plans[8];
-  static thread_local TxSlots outs[8];
-  static thread_local std::vector<uint8_t> slot_mem[8];
-  int live[8], n_live = 0;
-  for (size_t i = 0; i < count && i < 8; ++i) {
-    plans[i].only = 0xff;
-    tx_structure(tx[i], len[i], st[i], plans[i], outs[i]);
-    if (st[i].status != TX_OK) continue;
-    slot_mem[i].assign(32 * (size_t)plans[i].n_slots + 32, 0);
-    live[n_live++] = (int)i;
-  }
-  bool lockstep = false;
-#if ZK_HAVE_X8
-  lockstep = n_live >= 3 && x8_available();
-  for (int q = 1; lockstep && q < n_live; ++q) lockstep = plans[live[q]].same_shape(plans[live[0]]);
-  if (lockstep) {
-    static thread_local std::vector<uint8_t> spare[8];
-    const TxPlan* P[8];
-    uint8_t* S[8];
-    for (int l = 0; l < 8; ++l) {
-      if (l < n_live) { P[l] = &plans[live[l]]; S[l] = slot_mem[live[l]].data(); }
-      else { P[l] = &plans[live[0]]; spare[l].resize(slot_mem[live[0]].size()); S[l] = spare[l].data(); }
-    }
-    run_plans_x8(P, S, P_MUSIG);
-  }
-#endif
   bool ok = true;
-  for (int q = 0; q < n_live; ++q) {
-    const int i = live[q];
-    if (!lockstep) run_plan(plans[i], slot_mem[i].data(), P_MUSIG);
-    tx_finish_hashes(st[i], outs[i], slot_mem[i].data());
-    ok &= tape.add(j0 + (size_t)i, plans[i], outs[i].txid);
-  }
+  tx_run_group(tx, len, st, count, ALL_PROTOS, P_MUSIG, true, true,
+               [&](size_t i, const TxPlan& plan, const TxSlots& out, const uint8_t*) { ok &= tape.add(j0 + i, plan, out.txid); });
   return ok;
 }
 

@@ -19,12 +19,12 @@
 // under K = 255 tells "255 entries, listed" from "255 or more, not listed" (tx_log_listed).
 #pragma once
 #include "tx_hash_tape.hpp"
+#include "tx_out.hpp"     // tx_log_record_bytes: the size of a record is part of the layout
 
 namespace zk {
 namespace zkvm {
 
 constexpr uint32_t TXLOG_INPUT = 1, TXLOG_OUTPUT = 2;     // (ZKGPU_TXLOG_INPUT / _OUTPUT: tx_device.hpp asserts them)
-inline size_t tx_log_record_bytes(size_t K) { return 1 + 33 * K; }
 
 // ---- the table of a tape: words.  [0, n_shapes): where shape s's entries start; there: count, then count x (kind, slot)
 #if defined(__HIPCC__)
@@ -124,40 +124,11 @@ inline void tx_log_of_plan(const TxPlan& P, const uint8_t* slots, uint8_t* rec, 
 }
 
 // tx_prepare_many (zkvm_tx.hpp) with every protocol -- the host's second pass -- that also leaves every accepted transaction's
-// record at recs + i * (1 + 33 K).  Same statements, same hashing, in lockstep under the same conditions.
+// record at recs + i * (1 + 33 K), read off the zeroed slot memory its plan wrote.  Same statements, same hashing.
 inline void tx_prepare_many_logged(const uint8_t* const* tx, const size_t* len, TxStatement* st, size_t count, uint8_t* recs, size_t K) {
-  static thread_local TxPlan plans[8];
-  static thread_local TxSlots outs[8];
-  static thread_local std::vector<uint8_t> slot_mem[8];
-  int live[8], n_live = 0;
-  for (size_t i = 0; i < count && i < 8; ++i) {
-    plans[i].only = ALL_PROTOS;
-    tx_structure(tx[i], len[i], st[i], plans[i], outs[i]);
-    if (st[i].status != TX_OK) continue;
-    slot_mem[i].assign(32 * (size_t)plans[i].n_slots + 32, 0);
-    live[n_live++] = (int)i;
-  }
-  bool lockstep = false;
-#if ZK_HAVE_X8
-  lockstep = !tx_free_hashing_hook() && n_live >= 3 && x8_available();
-  for (int q = 1; lockstep && q < n_live; ++q) lockstep = plans[live[q]].same_shape(plans[live[0]]);
-  if (lockstep) {
-    static thread_local std::vector<uint8_t> spare[8];
-    const TxPlan* P[8];
-    uint8_t* S[8];
-    for (int l = 0; l < 8; ++l) {
-      if (l < n_live) { P[l] = &plans[live[l]]; S[l] = slot_mem[live[l]].data(); }
-      else { P[l] = &plans[live[0]]; spare[l].resize(slot_mem[live[0]].size()); S[l] = spare[l].data(); }
-    }
-    run_plans_x8(P, S, ALL_PROTOS);
-  }
-#endif
-  for (int q = 0; q < n_live; ++q) {
-    const int i = live[q];
-    if (!lockstep && !tx_free_hashing_hook()) run_plan(plans[i], slot_mem[i].data(), ALL_PROTOS);
-    tx_finish_hashes(st[i], outs[i], slot_mem[i].data());
-    tx_log_of_plan(plans[i], slot_mem[i].data(), recs + (size_t)i * tx_log_record_bytes(K), K);
-  }
+  tx_run_group(tx, len, st, count, ALL_PROTOS, ALL_PROTOS, true, true, [&](size_t i, const TxPlan& plan, const TxSlots&, const uint8_t* slots) {
+    tx_log_of_plan(plan, slots, recs + i * tx_log_record_bytes(K), K);
+  });
 }
 
 }  // namespace zkvm

@@ -1,0 +1,104 @@
+// tx_out.hpp -- what a transaction call hands its caller, laid out ONCE: the format word of zkgpu_verifier_set_tx_format decoded
+// and validated (TxFormat), the layout of a call's status argument as a value (TxOutLayout), and the hand-out of a merged round
+// to its calls (tx_round_hand_out).  Host-only, no HIP and no zkgpu.h (its constants are restated; session.hpp asserts them), so
+// that libzkgpu and libzkhost -- the CPU self-tests of hostlib.cpp -- compile the SAME code, like pipe_plan.hpp or msm_route.hpp.
+//
+// The status argument of a call over `batch` transactions:   status[batch] | id[batch][32] | record[batch][1 + 33 K]
+//   status: one byte per transaction (0 beside a set accept bit and nowhere else);
+//   id (ZKGPU_TXFORMAT_RETURN_IDS): the transaction ID of every ACCEPTED transaction, zeros elsewhere;
+//   record (ZKGPU_TXFORMAT_RETURN_LOG with window K, only beside the IDs): count | kind[K] | id[K][32] (tx_log.hpp), likewise.
+// Three moments write the whole of it -- begin, nothing_in_subset, fail_closed; in between TxCall::verdicts writes beside the
+// bits it sets, through a TxPiece.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+
+namespace zk {
+namespace zkvm {
+
+// (ZKGPU_TXFORMAT_*, ZKGPU_TXSTATUS_REJECTED / _OUTSIDE_SUBSET)
+constexpr int TXFORMAT_V1 = 1, TXFORMAT_V1_REASONS = 2, TXFORMAT_HASH_ON_DEVICE = 256, TXFORMAT_SIGN_ON_DEVICE = 512, TXFORMAT_RETURN_IDS = 1024,
+              TXFORMAT_RETURN_LOG = 2048, TXFORMAT_LOG_SHIFT = 16;
+constexpr uint8_t TXOUT_REJECTED = 1, TXOUT_OUTSIDE_SUBSET = 2;
+inline size_t tx_log_record_bytes(size_t K) { return 1 + 33 * K; }
+
+// One caller's transactions inside a call (TxCall::Piece).  ids (may be NULL): 32 * batch bytes of that caller's, zeroed by it,
+// for the IDs of what is accepted; log / log_k (may be NULL): batch records of 1 + 33 * log_k bytes, zeroed likewise
+struct TxPiece { const uint8_t* txs; const uint64_t* tx_offsets; size_t batch; uint8_t* ids = nullptr; uint8_t* log = nullptr; size_t log_k = 0; };
+
+struct TxOutLayout {
+  bool ids = false;                                       // the ID area is there
+  size_t log_k = 0;                                       // the window K of the records (0: no record area; only beside ids)
+
+  size_t bytes(size_t batch) const { return batch * (1 + (ids ? 32 : 0) + (log_k ? tx_log_record_bytes(log_k) : 0)); }
+  // where transaction i's status byte, ID and record lie in a caller's area of bytes(batch) (NULL: that part is not there)
+  uint8_t* status_of(uint8_t* area, size_t i) const { return area ? area + i : nullptr; }
+  uint8_t* id_of(uint8_t* area, size_t batch, size_t i) const { return area && ids ? area + batch + 32 * i : nullptr; }
+  uint8_t* record_of(uint8_t* area, size_t batch, size_t i) const { return area && log_k ? area + 33 * batch + i * tx_log_record_bytes(log_k) : nullptr; }
+  TxPiece piece(const uint8_t* txs, const uint64_t* tx_offsets, size_t batch, uint8_t* area) const {
+    return TxPiece{txs, tx_offsets, batch, id_of(area, batch, 0), record_of(area, batch, 0), log_k};
+  }
+
+  // a call begins: no bit set, every transaction "rejected", no ID, no record
+  void begin(uint8_t* bitmap, uint8_t* area, size_t batch) const { fill(bitmap, 0, (batch + 7) / 8); all(area, TXOUT_REJECTED, batch); }
+  // no format is enabled: every transaction of a call that has begun is outside the subset
+  void nothing_in_subset(uint8_t* area, size_t batch) const { all(area, TXOUT_OUTSIDE_SUBSET, batch); }
+  // a call that failed: "nothing accepted" -- never a reason, never 0, never an ID or a log entry; "outside the subset" stays
+  void fail_closed(uint8_t* bitmap, uint8_t* area, size_t batch) const {
+    fill(bitmap, 0, (batch + 7) / 8);
+    for (size_t i = 0; area && i < batch; ++i) if (area[i] != TXOUT_OUTSIDE_SUBSET) area[i] = TXOUT_REJECTED;
+    clear_behind_status(area, batch);
+  }
+
+ private:
+  static void fill(uint8_t* p, int byte, size_t n) { if (p && n) std::memset(p, byte, n); }
+  void clear_behind_status(uint8_t* area, size_t batch) const { if (area) fill(area + batch, 0, bytes(batch) - batch); }
+  void all(uint8_t* area, int status, size_t batch) const { fill(area, status, batch); clear_behind_status(area, batch); }
+};
+
+// The format word, decoded.  of(): false for a word zkgpu_verifier_set_tx_format refuses -- negative; the log flag without a
+// window K in bits 16 .. 23 or a window without the flag; the log without the IDs; signing on the device without hashing
+// there; flags (or any stray bit) without one of the two base formats.  0 alone is valid: no format enabled.
+struct TxFormat {
+  int base = 0;                                           // 0 none, 1, 2 (the same bytes and bits as 1; the status bytes carry a reason)
+  bool hash_on_device = false, sign_on_device = false;
+  TxOutLayout out;
+  static bool of(int word, TxFormat* f) {
+    const int log_k = (word >> TXFORMAT_LOG_SHIFT) & 255;
+    const bool log = (word & TXFORMAT_RETURN_LOG) != 0, ids = (word & TXFORMAT_RETURN_IDS) != 0;
+    const bool hash = (word & TXFORMAT_HASH_ON_DEVICE) != 0, sign = (word & TXFORMAT_SIGN_ON_DEVICE) != 0;
+    if (word < 0 || log != (log_k != 0) || (log && !ids) || (sign && !hash)) return false;
+    const int base = word & ~(TXFORMAT_HASH_ON_DEVICE | TXFORMAT_SIGN_ON_DEVICE | TXFORMAT_RETURN_IDS | TXFORMAT_RETURN_LOG | (255 << TXFORMAT_LOG_SHIFT));
+    if (word != 0 && base != TXFORMAT_V1 && base != TXFORMAT_V1_REASONS) return false;
+    f->base = base; f->hash_on_device = hash; f->sign_on_device = sign;
+    f->out.ids = ids; f->out.log_k = (size_t)log_k;
+    return true;
+  }
+  static TxFormat of_valid(int word) { TxFormat f; if (!of(word, &f)) f = TxFormat(); return f; }     // (of a word validated when it was stored)
+  bool reasons() const { return base == TXFORMAT_V1_REASONS; }
+  // the same for a caller that passed no status argument: nowhere to say a reason or to put an ID or a record -- the format-1 call
+  TxFormat without_status() const { TxFormat f = *this; f.base = reasons() ? TXFORMAT_V1 : base; f.out = TxOutLayout(); return f; }
+};
+
+// One call of a merged round (zkgpu_tx_verify_submit): its own bitmap ((batch + 7) / 8 bytes) and its own area of
+// layout.bytes(batch), whose ID and record parts the round's TxCall wrote through the call's TxPiece.  tx_round_hand_out gives
+// every call of a finished round its bits, re-based to its bit 0, and its status bytes out of the round's (the calls'
+// transactions in order); ok = false, a round that failed: every call is fail-closed.
+struct TxHandOut { size_t batch; TxOutLayout layout; uint8_t* bits; uint8_t* area; };
+inline void tx_round_hand_out(const uint8_t* round_bits, const uint8_t* round_status, bool ok, const TxHandOut* calls, size_t n_calls) {
+  size_t at = 0;
+  for (size_t c = 0; c < n_calls; ++c) {
+    const TxHandOut& to = calls[c];
+    if (to.batch) { std::memset(to.bits, 0, (to.batch + 7) / 8); std::memcpy(to.area, round_status + at, to.batch); }
+    if (!ok) to.layout.fail_closed(to.bits, to.area, to.batch);
+    for (size_t i = 0; ok && i < to.batch; ++i) {
+      const size_t g = at + i;
+      if ((round_bits[g / 8] >> (g % 8)) & 1) to.bits[i / 8] |= (uint8_t)(1u << (i % 8));
+    }
+    at += to.batch;
+  }
+}
+
+}  // namespace zkvm
+}  // namespace zk

@@ -516,53 +516,62 @@ inline void tx_finish_hashes(TxStatement& st, const TxSlots& out, const uint8_t*
   for (size_t i = 0; i < out.a.size(); ++i) std::memcpy(&st.sig_scalars[32 * (2 + i)], slots + 32 * (size_t)out.a[i], 32);
 }
 
-// Runs up to eight transactions: parse, VM, transaction ID, signature terms.  Transactions whose plans have one shape
-// (payments of the same arity and payload sizes, as a block mostly holds) are hashed in lockstep, eight Keccak states per
-// AVX-512 register; anything else -- other shapes side by side, a CPU without AVX-512 -- one at a time.  Same results.
-// only = P_MUSIG: the signature's key rows alone -- status, s, R, the keys X_i and their MuSig coefficients a_i are what the
-// statement holds afterwards (no transaction ID yet): the first pass of zkgpu_tx_verify_batch, which wants the aggregated
-// keys of a whole call on their way to the device before the rest of the hashing starts.
-inline void tx_prepare_many(const uint8_t* const* tx, const size_t* len, TxStatement* st, size_t count, bool allow_x8 = true,
-                            uint8_t only = ALL_PROTOS) {
-  static thread_local TxPlan plans[8];
-  static thread_local TxSlots outs[8];
-  static thread_local std::vector<uint8_t> slot_mem[8];
+// The second pass over a group of up to eight transactions, written down ONCE (the plain pass below, the taped one in
+// tx_hash_tape.hpp and the logged one in tx_log.hpp are its parameters): the structure pass -- parse, VM, the plan with the
+// jobs of plan_only kept (ALL_PROTOS: every job) --, the statements the VM accepted, their plans run on the host for the jobs of
+// host_only, tx_finish_hashes, then after(i, plan, its TxSlots, its slot memory) per accepted statement i in order.  Plans of one
+// shape (payments of the same arity and payload sizes, as a block mostly holds) are hashed in lockstep, eight Keccak states per
+// AVX-512 register, idle lanes repeating the first; anything else -- other shapes side by side, fewer than three, a CPU without
+// AVX-512, allow_x8 = false -- one at a time.  Same results.  zero_slots: the slot memory reads zero before the plans run (a
+// caller that sees slots the host does not write); false: it holds whatever the thread's last group left there.
+// In a -DZK_MEASURE_FREE_HASHING build with the hook on, whatever the host would have run here is skipped and every slot reads
+// zero -- uniformly, whichever of the three passes asks.
+struct TxGroupScratch { TxPlan plans[8]; TxSlots outs[8]; std::vector<uint8_t> slot_mem[8], spare[8]; };
+inline TxGroupScratch& tx_group_scratch() { static thread_local TxGroupScratch w; return w; }
+template <class After>
+inline void tx_run_group(const uint8_t* const* tx, const size_t* len, TxStatement* st, size_t count, uint8_t plan_only, uint8_t host_only,
+                         bool allow_x8, bool zero_slots, After after) {
+  TxGroupScratch& w = tx_group_scratch();
+  const bool skip = tx_free_hashing_hook();
   int live[8], n_live = 0;
   for (size_t i = 0; i < count && i < 8; ++i) {
-    plans[i].only = only;
-    tx_structure(tx[i], len[i], st[i], plans[i], outs[i]);
+    w.plans[i].only = plan_only;
+    tx_structure(tx[i], len[i], st[i], w.plans[i], w.outs[i]);
     if (st[i].status != TX_OK) continue;
-    slot_mem[i].resize(32 * (size_t)plans[i].n_slots + 32);
+    const size_t bytes = 32 * (size_t)w.plans[i].n_slots + 32;
+    if (zero_slots || skip) w.slot_mem[i].assign(bytes, 0); else w.slot_mem[i].resize(bytes);
     live[n_live++] = (int)i;
-  }
-  if (tx_free_hashing_hook()) {                 // (measurement hook: no hashing at all)
-    for (int q = 0; q < n_live; ++q) {
-      const int i = live[q];
-      std::fill(slot_mem[i].begin(), slot_mem[i].end(), (uint8_t)0);
-      tx_finish_hashes(st[i], outs[i], slot_mem[i].data());
-    }
-    return;
   }
   bool lockstep = false;
 #if ZK_HAVE_X8
-  lockstep = allow_x8 && n_live >= 3 && x8_available();
-  for (int q = 1; lockstep && q < n_live; ++q) lockstep = plans[live[q]].same_shape(plans[live[0]]);
+  lockstep = !skip && allow_x8 && n_live >= 3 && x8_available();
+  for (int q = 1; lockstep && q < n_live; ++q) lockstep = w.plans[live[q]].same_shape(w.plans[live[0]]);
   if (lockstep) {
-    static thread_local std::vector<uint8_t> spare[8];
     const TxPlan* P[8];
     uint8_t* S[8];
     for (int l = 0; l < 8; ++l) {
-      if (l < n_live) { P[l] = &plans[live[l]]; S[l] = slot_mem[live[l]].data(); }
-      else { P[l] = &plans[live[0]]; spare[l].resize(slot_mem[live[0]].size()); S[l] = spare[l].data(); }     // padding: lane 0's work again
+      if (l < n_live) { P[l] = &w.plans[live[l]]; S[l] = w.slot_mem[live[l]].data(); }
+      else { P[l] = &w.plans[live[0]]; w.spare[l].resize(w.slot_mem[live[0]].size()); S[l] = w.spare[l].data(); }     // padding: lane 0's work again
     }
-    run_plans_x8(P, S, only);
+    run_plans_x8(P, S, host_only);
   }
 #endif
   for (int q = 0; q < n_live; ++q) {
     const int i = live[q];
-    if (!lockstep) run_plan(plans[i], slot_mem[i].data(), only);
-    tx_finish_hashes(st[i], outs[i], slot_mem[i].data());     // (only = P_MUSIG: the transaction ID copied here is not one yet)
+    if (!lockstep && !skip) run_plan(w.plans[i], w.slot_mem[i].data(), host_only);
+    tx_finish_hashes(st[i], w.outs[i], w.slot_mem[i].data());
+    after((size_t)i, w.plans[i], w.outs[i], w.slot_mem[i].data());
   }
+}
+
+// Runs up to eight transactions: parse, VM, transaction ID, signature terms.
+// only = P_MUSIG: the signature's key rows alone -- status, s, R, the keys X_i and their MuSig coefficients a_i are what the
+// statement holds afterwards (no transaction ID yet: what tx_finish_hashes copied is not one): the first pass of
+// zkgpu_tx_verify_batch, which wants the aggregated keys of a whole call on their way to the device before the rest of the
+// hashing starts.
+inline void tx_prepare_many(const uint8_t* const* tx, const size_t* len, TxStatement* st, size_t count, bool allow_x8 = true,
+                            uint8_t only = ALL_PROTOS) {
+  tx_run_group(tx, len, st, count, only, only, allow_x8, false, [](size_t, const TxPlan&, const TxSlots&, const uint8_t*) {});
 }
 
 inline TxStatement tx_prepare(const uint8_t* tx, size_t len) {

@@ -18,7 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import numpy as np
 from dataclasses import dataclass
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 from .native import Context, PointSet, ZkGpuError
 
@@ -369,6 +369,17 @@ class BlockVerifier:
     _tx_return_ids = False
     _tx_log_k = 0
 
+    class _TxLayout(NamedTuple):
+        """the layout of a call's status array -- status[batch] | id[batch][32] | record[batch][1 + 33 K] -- as a value: what a
+        call reads when it is made or submitted.  _tx_status_bytes and _tx_result below are the one statement of it here
+        (the library's is csrc/tx_out.hpp)"""
+        has_ids: bool = False
+        log_k: int = 0
+
+    @property
+    def _tx_layout(self) -> "_TxLayout":
+        return self._TxLayout(self._tx_return_ids, self._tx_log_k)
+
     @staticmethod
     def _tx_status_bytes(batch: int, has_ids: bool, log_k: int) -> int:
         """bytes the library writes into a call's status array under that layout"""
@@ -425,7 +436,7 @@ class BlockVerifier:
     def verify_txs_packed(self, blob: bytes, lengths, host_threads: int = 0, ids: bool = False, log: bool = False):
         """the same over one buffer of concatenated transactions and their lengths (same status bytes, reasons included)"""
         batch = len(lengths)
-        has_ids, log_k = self._tx_return_ids, self._tx_log_k
+        has_ids, log_k = self._tx_layout
         if ids and not has_ids:
             raise ValueError("ids=True needs a format with TXFORMAT_RETURN_IDS (set_tx_format)")
         if log and not (has_ids and log_k):
@@ -450,7 +461,7 @@ class BlockVerifier:
         cid = C.c_uint64(0)
         self._check(self.lib.zkgpu_tx_verify_submit(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, C.byref(cid)))
         # (the layout of the call's status array is the one in force when it was queued: remembered with the call)
-        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch, self._tx_return_ids, self._tx_log_k)
+        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch) + self._tx_layout
         return int(cid.value)
 
     def submit_txs(self, txs: Sequence[bytes], host_threads: int = 0) -> int:
@@ -462,7 +473,7 @@ class BlockVerifier:
         ids=True (the call was submitted under a format with TXFORMAT_RETURN_IDS): -> (bitmap, status bytes, ids) as verify_txs;
         log=True (... with TXFORMAT_RETURN_LOG): -> (bitmap, status bytes, ids, log) as verify_txs"""
         queued = self.__dict__["_tx_calls"][call_id]
-        batch, has_ids, log_k = queued[2], queued[3], (queued[4] if len(queued) > 4 else 0)
+        batch, (has_ids, log_k) = queued[2], self._TxLayout(*queued[3:])
         if ids and not has_ids:
             raise ValueError("ids=True: the call was not submitted under a format with TXFORMAT_RETURN_IDS")
         if log and not (has_ids and log_k):
