@@ -156,7 +156,7 @@ def _benched_sets(ctx, oracle, n_steps, batch, compare=2):
 def test_device_tickets_merged_into_two_device_batches_fail_closed_at_every_runtime_call(ctx, oracle):
     """(a) twenty 1024-transaction tickets queued by ONE zkgpu_verifier_submit_many_dev, merged into two device batches of
     10 240 on a five-lane verifier (bench.py's arrangement): the merge kernel, the three pieces of each device batch
-    (front / decoding / back: session.hpp flush_backs and its back-half failure branch), the waits."""
+    (front / decoding / back: session.hpp OwedBacks::flush and its back-half failure branch), the waits."""
     from zkvm_amd.verifier import BlockVerifier, BulletproofGens
     n_steps, batch = 20, 1024
     sets, n_in, n_out, plen = _benched_sets(ctx, oracle, n_steps, batch)

@@ -217,6 +217,7 @@ void ticket_collect(zkgpu_verifier* v, int lane);
 int ticket_dispatch(zkgpu_verifier* v, bool force);
 int host_dispatch(zkgpu_verifier* v, zkgpu_host_batch* must);
 void collect_oldest(zkgpu_verifier* v);
+int free_ticket_lane(zkgpu_verifier* v);
 
 // ---- RCCL, bound on first use -------------------------------------------------------------
 struct RcclApi {
@@ -878,8 +879,8 @@ int zkgpu_verifier_verify(zkgpu_verifier* v, size_t batch, const uint32_t* n_in,
 namespace {
 
 // ---- reason bytes (tx_reason_kernels.hpp) ---------------------------------------------------------------------------------
-// Queued behind a whole-proof batch's bitmap fold on the same stream, by pipe_enqueue, when the context was asked for them
-// (zkgpu_ctx::want_reasons: set by ticket_dispatch for a device batch that holds a format-2 transaction call's statements):
+// Queued behind a whole-proof batch's bitmap fold on the same stream, by pipe_back, when the batch was begun with
+// WholeProofOpts::want_reasons (ticket_dispatch: a device batch that holds a format-2 transaction call's statements):
 // one launch and one copy to the pinned result buffer, behind the bitmap's -- the event the collector waits for covers both.
 static_assert(TXR_ACCEPTED == ZKGPU_TXSTATUS_ACCEPTED && TXR_REJECTED == ZKGPU_TXSTATUS_REJECTED && TXR_TX_INVALID == ZKGPU_TXSTATUS_TX_INVALID &&
               TXR_PROOF_FORMAT == ZKGPU_TXSTATUS_PROOF_FORMAT && TXR_PROOF_POINT == ZKGPU_TXSTATUS_PROOF_POINT &&
@@ -925,11 +926,13 @@ int tx_reasons_parked(zkgpu_ctx* c, const uint32_t* d_wellformed, size_t B, int 
 
 // the reason bytes of the batch zkgpu_verify_wait has just collected on this context (bitmap: what it gave); the context
 // forgets that it was asked.  A batch that never reached the device (a proof length no plan serves: every bit is zero)
-// reads PROOF_FORMAT; a byte that disagrees with its bit is never handed on: "rejected" alone.
+// reads PROOF_FORMAT; a byte that disagrees with its bit is never handed on: "rejected" alone.  out NULL (nobody asked, or
+// the batch failed): the context forgets, nothing is read.
 void tx_reasons_take(zkgpu_ctx* c, size_t B, const uint8_t* bitmap, uint8_t* out) {
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   const int src = c->reasons_src;
   c->reasons_src = 0; c->want_reasons = false;
+  if (!out) return;
   if (src == 1) memcpy(out, (const char*)c->pinned + (B + 7) / 8 + 64, B);
   else if (src == 2 && c->sync_reasons.size() == B) memcpy(out, c->sync_reasons.data(), B);
   else memset(out, ZKGPU_TXSTATUS_PROOF_FORMAT, B);
@@ -939,10 +942,35 @@ void tx_reasons_take(zkgpu_ctx* c, size_t B, const uint8_t* bitmap, uint8_t* out
   }
 }
 
-void ticket_collect(zkgpu_verifier* v, int lane) {       // v->mu held
-  std::vector<zkgpu_request*> members;
+// the lane is free again (v->mu held) -> members: the requests of the batch it ran
+void lane_release(zkgpu_verifier* v, int lane, std::vector<zkgpu_request*>& members) {
+  members.clear();
   members.swap(v->running[(size_t)lane]);
   for (auto it = v->busy.begin(); it != v->busy.end(); ++it) if (*it == lane) { v->busy.erase(it); break; }
+}
+
+// the request is done without verdicts (v->mu held): rc -- OK: every proof is Err -- and all bits zero.  to_run: a block's
+// request also answers to its run here and is gone; a ticket is found by whoever waits for it.
+void request_fail(zkgpu_verifier* v, zkgpu_request* r, int rc, bool to_run = false) {
+  r->state = 2; r->rc = rc; r->form = nullptr; r->bits.assign((r->batch + 7) / 8, 0);
+  if (to_run && r->run) block_request_done(v, r);
+}
+
+// a new ticket, registered under its id (v->mu held); with device inputs it is queued for ticket_dispatch as well
+zkgpu_request* ticket_new(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, size_t batch, size_t proof_len,
+                          const void* d_com = nullptr, const void* d_proofs = nullptr, const void* d_r = nullptr) {
+  zkgpu_request* r = new zkgpu_request();
+  r->id = v->next_id++;
+  r->n_in = n_in; r->n_out = n_out; r->batch = batch; r->proof_len = proof_len;
+  r->d_com = d_com; r->d_proofs = d_proofs; r->d_r = d_r;
+  v->requests[r->id] = r;
+  if (d_com) v->queue.push_back(r);
+  return r;
+}
+
+void ticket_collect(zkgpu_verifier* v, int lane) {       // v->mu held
+  std::vector<zkgpu_request*> members;
+  lane_release(v, lane, members);
   if (members.empty()) return;
   size_t total = 0;
   for (auto* r : members) total += r->batch;
@@ -951,8 +979,7 @@ void ticket_collect(zkgpu_verifier* v, int lane) {       // v->mu held
   if (rc != ZKGPU_OK) v->last_error = zkgpu_last_error(v->lanes[(size_t)lane]);
   std::vector<uint8_t> big_why;                          // (only for a device batch that holds statements of a format-2 transaction call)
   for (auto* r : members) if (r->reasons) { big_why.assign(total, (uint8_t)ZKGPU_TXSTATUS_REJECTED); break; }
-  if (!big_why.empty() && rc == ZKGPU_OK) tx_reasons_take(v->lanes[(size_t)lane], total, big.data(), big_why.data());
-  { zkgpu_ctx* L = v->lanes[(size_t)lane]; std::lock_guard<std::recursive_mutex> lk(L->mu); L->want_reasons = false; L->reasons_src = 0; }
+  tx_reasons_take(v->lanes[(size_t)lane], total, big.data(), !big_why.empty() && rc == ZKGPU_OK ? big_why.data() : nullptr);
   if ((size_t)lane < v->lane_stage.size() && v->lane_stage[(size_t)lane] >= 0) {      // a batch formed from host memory: its twin is free
     v->host_stages[(size_t)v->lane_stage[(size_t)lane]].taken = false;
     v->lane_stage[(size_t)lane] = -1;
@@ -971,196 +998,221 @@ void ticket_collect(zkgpu_verifier* v, int lane) {       // v->mu held
   }
 }
 
-// launches the batches at the head of the queue that share its shape; force: even below the merge target, and
-// if no lane is free the oldest one in flight is collected first
-int ticket_dispatch(zkgpu_verifier* v, bool force) {       // v->mu held
-  // Device batches that leave in one call are queued piece by piece (zkgpu_ctx::enqueue_phase): every batch's light front, then
-  // every batch's point decoding, then the rest of each -- the second batch's transcript and decoding then run beside the
-  // first's.  `fronts`: batches whose later pieces are still owed.
-  struct Front { int lane; zkgpu_cloak_plan* plan; size_t total, proof_len; const void *com, *proofs, *r; };
+// ---- ticket_dispatch and its steps (v->mu held throughout) ---------------------------------------------------------------
+// What is still to leave of the cut decided for one shape, and the tickets that leave as one device batch with where their
+// inputs lie: in place for a lone ticket, else gathered into the lane's merge buffers.
+struct TicketCut { size_t owed = 0; uint64_t shape[3] = {0, 0, 0}; };
+struct TicketBatch {
+  std::vector<zkgpu_request*> pick;
+  size_t total = 0;
+  const void *com = nullptr, *proofs = nullptr, *r = nullptr;
+  hipEvent_t after = nullptr;          // a lone batch of a block whose copy to HBM is still queued on the copy stream
+  bool drew = false;                   // tickets that brought no r got theirs from `seed`
+  uint8_t seed[32] = {0};
+  std::string err;                     // what went wrong in a step here (empty: the lane's own last error says it)
+};
+
+// Device batches whose front is queued and whose middle and back are still owed: batches that leave in one call get every
+// front, then every middle, then the backs (why: PipeCall, zkgpu.hip)
+struct OwedBacks {
+  struct Front { int lane; PipeCall call; };
+  zkgpu_verifier* v;
   std::vector<Front> fronts;
-  auto flush_backs = [&]() {
-    std::vector<int> mid_rc(fronts.size(), ZKGPU_OK);
+  void flush() {
+    std::vector<int> rcs(fronts.size(), ZKGPU_OK);
     for (size_t i = 0; i < fronts.size(); ++i) {        // every batch's chip-filling decoding, then every batch's rest
-      const Front& f = fronts[i];
-      zkgpu_ctx* L = v->lanes[(size_t)f.lane];
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_MID; }
-      mid_rc[i] = zkgpu_cloak_verify_submit_dev(L, v->ps, f.plan, f.total, f.com, f.proofs, f.proof_len, f.r);
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; }
+      zkgpu_ctx* L = v->lanes[(size_t)fronts[i].lane];
+      std::lock_guard<std::recursive_mutex> lk(L->mu);
+      DeviceGuard g(L->device);
+      rcs[i] = pipe_mid(fronts[i].call);
+      if (rcs[i] == ZKGPU_OK) rcs[i] = pipe_piece_queued(L);
     }
     for (size_t i = 0; i < fronts.size(); ++i) {
-      const Front& f = fronts[i];
-      zkgpu_ctx* L = v->lanes[(size_t)f.lane];
-      int rc = mid_rc[i];
-      if (rc == ZKGPU_OK) {
-        { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_BACK; }
-        rc = zkgpu_cloak_verify_submit_dev(L, v->ps, f.plan, f.total, f.com, f.proofs, f.proof_len, f.r);
+      const int lane = fronts[i].lane;
+      zkgpu_ctx* L = v->lanes[(size_t)lane];
+      if (rcs[i] == ZKGPU_OK) {
+        std::lock_guard<std::recursive_mutex> lk(L->mu);
+        DeviceGuard g(L->device);
+        rcs[i] = pipe_back(fronts[i].call);
       }
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; L->awaiting_back = false; if (rc != ZKGPU_OK) L->want_reasons = false; }
-      if (rc != ZKGPU_OK) {
-        // the back half could not be queued (a launch failed): what the front half queued is waited for, and the batch's
-        // requests fail with the error -- nothing is left in flight on the lane
-        v->last_error = zkgpu_last_error(L);
-        quiesce_after_fault(L);
-        std::vector<zkgpu_request*> members;
-        members.swap(v->running[(size_t)f.lane]);
-        for (auto it = v->busy.begin(); it != v->busy.end(); ++it) if (*it == f.lane) { v->busy.erase(it); break; }
-        for (zkgpu_request* r : members) {
-          r->state = 2; r->rc = rc; r->bits.assign((r->batch + 7) / 8, 0);
-          if (r->run) block_request_done(v, r);
-        }
-      }
+      if (rcs[i] == ZKGPU_OK) continue;
+      // the back half could not be queued (a launch failed): what the front half queued is waited for, and the batch's
+      // requests fail with the error -- nothing is left in flight on the lane
+      v->last_error = zkgpu_last_error(L);
+      tx_reasons_take(L, 0, nullptr, nullptr);
+      quiesce_after_fault(L);
+      std::vector<zkgpu_request*> members;
+      lane_release(v, lane, members);
+      for (zkgpu_request* r : members) request_fail(v, r, rcs[i], /*to_run=*/true);
     }
     fronts.clear();
-  };
-  struct FlushAtExit { decltype(flush_backs)& f; ~FlushAtExit() { f(); } } flush_at_exit{flush_backs};
-  size_t owed = 0;                                      // device batches still to leave of the cut decided for the head's shape
-  uint64_t owed_shape[3] = {0, 0, 0};
+  }
+  ~OwedBacks() { flush(); }
+};
+
+// Step 1, the tickets of the head's shape that leave next.  Everything queued of the head's shape, T transactions, leaves in
+// round(T / target) device batches of EQUAL size (to the ticket): 20 tickets of 1024 at a target of 10 240 are two batches of
+// ten as before, but 16 are two of eight (not ten and six), 24 two of twelve, 37 four of ten, nine, nine, nine.  What a run of
+// any length then pays is the one tail behind its last batch, not a short straggler batch as well (`value`
+// used to peak where the step count was a multiple of the target).  Tickets that trickle in one by one leave at the target,
+// as they always did.  false: below the target and nobody forces them out.
+bool ticket_choose(zkgpu_verifier* v, bool force, TicketCut& cut, TicketBatch& b) {
+  const zkgpu_request* head = v->queue.front();
+  auto like_head = [&](const zkgpu_request* r) { return r->n_in == head->n_in && r->n_out == head->n_out && r->proof_len == head->proof_len; };
+  const size_t target = head->run ? v->block_merge : v->merge_target;
+  size_t queued = 0;
+  for (zkgpu_request* r : v->queue) if (like_head(r)) queued += r->batch;
+  // the cut is decided ONCE for what is queued, and every part of it leaves in this call (`owed`): two parts of 8192 must not
+  // turn into one now and one when somebody waits (the second would start after the first had finished -- measured, 16 steps)
+  const bool same_cut = cut.owed > 0 && cut.shape[0] == head->n_in && cut.shape[1] == head->n_out && cut.shape[2] == head->proof_len;
+  if (!same_cut) {
+    if (queued < target && !force) return false;
+    cut.owed = zk::ticket_parts(queued, target);            // (ticket_cut.hpp: the policy, also driven by the CPU tests)
+    cut.shape[0] = head->n_in; cut.shape[1] = head->n_out; cut.shape[2] = head->proof_len;
+  }
+  const size_t quota = zk::ticket_quota(queued, cut.owed);
+  for (zkgpu_request* r : v->queue) {
+    if (!like_head(r)) continue;
+    b.pick.push_back(r);
+    b.total += r->batch;
+    if (b.total >= quota) break;
+  }
+  return true;
+}
+
+// Step 2, the inputs: a lone ticket is read in place.  Several are gathered side by side into the lane's merge buffers, behind
+// the copies of blocks that are still on their way to HBM (whoever reads their inputs waits for them) -- plan NULL: no plan
+// serves them, nothing will read them.  One gather launch per 16 tickets (commitments and randomness as 16-byte vectors;
+// buffers that are not 16-byte aligned go through plain copies).
+int ticket_gather(zkgpu_ctx* L, const zkgpu_cloak_plan* plan, size_t proof_len, TicketBatch& b) {
+  const std::vector<zkgpu_request*>& pick = b.pick;
+  b.com = pick[0]->d_com; b.proofs = pick[0]->d_proofs; b.r = pick[0]->d_r;
+  if (pick.size() == 1) { b.after = pick[0]->ready; return ZKGPU_OK; }
+  std::lock_guard<std::recursive_mutex> lk(L->mu);
+  DeviceGuard g(L->device);
+  hipEvent_t seen = nullptr;
+  for (zkgpu_request* r : pick)
+    if (r->ready && r->ready != seen) { seen = r->ready; if (hipStreamWaitEvent(L->stream_l, r->ready, 0) != hipSuccess) { b.err = "hipStreamWaitEvent (block copy)"; return ZKGPU_EHIP; } }
+  if (!plan) return ZKGPU_OK;
+  const size_t wcom = (size_t)plan->dev.sh.m * 32;
+  TRY(ensure(L, L->coal_com, b.total * wcom));
+  TRY(ensure(L, L->coal_proofs, b.total * proof_len + 16));   // (k_merge_inputs writes whole words)
+  TRY(ensure(L, L->coal_r, b.total * 64));
+  size_t off = 0, at = 0;
+  while (at < pick.size()) {
+    MergeSources ms;
+    ms.n = 0;
+    bool aligned = true;
+    const size_t base = off;
+    while (at < pick.size() && ms.n < 16) {
+      zkgpu_request* r = pick[at];
+      aligned = aligned && ((uintptr_t)r->d_com % 16 == 0) && ((uintptr_t)r->d_r % 16 == 0);     // (no r: NULL, drawn in step 3)
+      ms.com[ms.n] = (const uint4*)r->d_com; ms.proofs[ms.n] = (const uint8_t*)r->d_proofs; ms.r[ms.n] = (const uint4*)r->d_r;
+      ms.first[ms.n] = (uint32_t)(off - base);
+      off += r->batch;
+      ++ms.n; ++at;
+    }
+    ms.first[ms.n] = (uint32_t)(off - base);
+    if (aligned && (base * proof_len) % 4 == 0) {
+      const uint32_t span = ms.first[ms.n];
+      hipLaunchKernelGGL(k_merge_inputs, dim3(std::min<unsigned>(blocks_for((uint64_t)span * (proof_len / 4 + 1), 256), 1024u)), dim3(256), 0, L->stream_l, ms,
+                         (uint32_t)(wcom / 16), (uint32_t)proof_len, (uint4*)((char*)L->coal_com.p + base * wcom),
+                         (uint8_t*)L->coal_proofs.p + base * proof_len, (uint4*)((char*)L->coal_r.p + base * 64));
+      if (hipGetLastError() != hipSuccess) { b.err = "k_merge_inputs"; return ZKGPU_EHIP; }
+    } else {
+      size_t o2 = base;
+      for (uint32_t k = 0; k < ms.n; ++k) {
+        const size_t nb = ms.first[k + 1] - ms.first[k];
+        hipError_t e = hipMemcpyAsync((char*)L->coal_com.p + o2 * wcom, ms.com[k], nb * wcom, hipMemcpyDeviceToDevice, L->stream_l);
+        if (e == hipSuccess) e = hipMemcpyAsync((char*)L->coal_proofs.p + o2 * proof_len, ms.proofs[k], nb * proof_len, hipMemcpyDeviceToDevice, L->stream_l);
+        if (e == hipSuccess && ms.r[k]) e = hipMemcpyAsync((char*)L->coal_r.p + o2 * 64, ms.r[k], nb * 64, hipMemcpyDeviceToDevice, L->stream_l);
+        if (e != hipSuccess) { b.err = hipGetErrorString(e); return ZKGPU_EHIP; }
+        o2 += nb;
+      }
+    }
+  }
+  b.com = L->coal_com.p; b.proofs = L->coal_proofs.p; b.r = L->coal_r.p;
+  return ZKGPU_OK;
+}
+
+// Step 3: tickets that brought no verifier randomness (d_r NULL) get it here, once per DEVICE batch: one seed from the OS, and
+// statement i of the device batch gets r(seed, i) (draw_r.hpp) in the lane's coal_r -- also a lone unmerged ticket, so that
+// nothing of the caller's is aliased.  Tickets with an r of their own keep their bytes.  No seed: the batch fails.
+int ticket_draw_r(zkgpu_ctx* L, TicketBatch& b) {
+  if (!os_random(b.seed, sizeof b.seed)) { b.err = "getrandom failed"; return ZKGPU_EINVAL; }
+  std::lock_guard<std::recursive_mutex> lk(L->mu);
+  DeviceGuard g(L->device);
+  TRY(ensure(L, L->coal_r, b.total * 64));
+  size_t off = 0;
+  for (size_t at = 0; at < b.pick.size();) {      // one launch per run of neighbouring tickets without r
+    if (b.pick[at]->d_r) { off += b.pick[at]->batch; ++at; continue; }
+    const size_t first = off;
+    while (at < b.pick.size() && !b.pick[at]->d_r) { off += b.pick[at]->batch; ++at; }
+    TRY(draw_r_launch(L, L->stream_l, b.seed, first, (uint32_t)(off - first), (char*)L->coal_r.p + first * 64));
+  }
+  b.r = L->coal_r.p;
+  b.drew = true;
+  return ZKGPU_OK;
+}
+
+// Step 4: the batch begins on the lane, and its front is queued when the pipeline takes it -- middle and back are then owed
+int ticket_begin_front(zkgpu_verifier* v, int lane, zkgpu_cloak_plan* plan, size_t proof_len, const TicketBatch& b, OwedBacks& owed) {
+  zkgpu_ctx* L = v->lanes[(size_t)lane];
+  WholeProofOpts opts;
+  opts.after = b.after;
+  for (const zkgpu_request* r : b.pick) opts.want_reasons = opts.want_reasons || r->reasons;   // statements of a format-2 transaction call among them
+  opts.r_seed = b.drew ? b.seed : nullptr;
+  OwedBacks::Front f{lane, PipeCall()};
+  std::lock_guard<std::recursive_mutex> lk(L->mu);
+  DeviceGuard g(L->device);
+  TRY(whole_proof_begin(L, v->ps, plan, b.total, (const uint32_t*)b.com, (const uint8_t*)b.proofs, (const uint32_t*)b.r, proof_len, opts, f.call));
+  if (f.call.how != PipeCall::PIPED) return ZKGPU_OK;
+  int rc = pipe_front(f.call);
+  if (rc == ZKGPU_OK) rc = pipe_piece_queued(L);
+  if (rc == ZKGPU_OK) owed.fronts.push_back(f); else tx_reasons_take(L, 0, nullptr, nullptr);
+  return rc;
+}
+
+// Step 5: the tickets leave the queue, in flight on the lane -- or done at once: failed with rc, or (OK, no plan) every proof Err
+void ticket_settle(zkgpu_verifier* v, int lane, bool in_flight, int rc, const TicketBatch& b) {
+  size_t off = 0;
+  for (zkgpu_request* r : b.pick) {
+    for (auto it = v->queue.begin(); it != v->queue.end(); ++it) if (*it == r) { v->queue.erase(it); break; }
+    r->bit_off = off; off += r->batch;
+    if (in_flight) { r->state = 1; r->lane = lane; }
+  }
+  if (in_flight) { v->running[(size_t)lane] = b.pick; v->busy.push_back(lane); return; }
+  if (rc != ZKGPU_OK) quiesce_after_fault(v->lanes[(size_t)lane]);      // (merge copies, a front half: nothing of it stays in flight on a lane that reads as free)
+  for (zkgpu_request* r : b.pick) request_fail(v, r, rc, /*to_run=*/true);     // (a block's batches answer to their run, at once)
+}
+
+// launches the batches at the head of the queue that share its shape; force: even below the merge target, and
+// if no lane is free the oldest one in flight is collected first
+int ticket_dispatch(zkgpu_verifier* v, bool force) {
+  OwedBacks owed{v, {}};                                // (flushed when this returns)
+  TicketCut cut;
   while (!v->queue.empty()) {
-    zkgpu_request* head = v->queue.front();
-    // Everything queued of the head's shape, T transactions, leaves in round(T / target) device batches of EQUAL size (to the
-    // ticket): 20 tickets of 1024 at a target of 10 240 are two batches of ten as before, but 16 are two of eight (not ten and
-    // six), 24 two of twelve, 37 four of ten, nine, nine, nine.  What a run of any length then pays is the one tail behind its
-    // last batch, not a short straggler batch as well (`value` used to peak where the step count was a
-    // multiple of the target).  Tickets that trickle in one by one leave at the target, as they always did.
-    const size_t target = head->run ? v->block_merge : v->merge_target;
-    size_t queued = 0;
-    for (zkgpu_request* r : v->queue)
-      if (r->n_in == head->n_in && r->n_out == head->n_out && r->proof_len == head->proof_len) queued += r->batch;
-    // the cut is decided ONCE for what is queued, and every part of it leaves in this call (`owed`): two parts of 8192 must not
-    // turn into one now and one when somebody waits (the second would start after the first had finished -- measured, 16 steps)
-    const bool same_cut = owed > 0 && owed_shape[0] == head->n_in && owed_shape[1] == head->n_out && owed_shape[2] == head->proof_len;
-    if (!same_cut) {
-      if (queued < target && !force) return ZKGPU_OK;
-      owed = zk::ticket_parts(queued, target);            // (ticket_cut.hpp: the policy, also driven by the CPU tests)
-      owed_shape[0] = head->n_in; owed_shape[1] = head->n_out; owed_shape[2] = head->proof_len;
-    }
-    const size_t quota = zk::ticket_quota(queued, owed);
-    std::vector<zkgpu_request*> pick;
-    size_t total = 0;
-    for (zkgpu_request* r : v->queue) {
-      if (r->n_in != head->n_in || r->n_out != head->n_out || r->proof_len != head->proof_len) continue;
-      pick.push_back(r);
-      total += r->batch;
-      if (total >= quota) break;
-    }
-    int lane = -1;
-    for (size_t i = 0; i < v->lanes.size(); ++i) if (v->running[i].empty()) { lane = (int)i; break; }
+    const zkgpu_request* head = v->queue.front();
+    TicketBatch b;
+    if (!ticket_choose(v, force, cut, b)) return ZKGPU_OK;
+    const int lane = free_ticket_lane(v);
     if (lane < 0) {
       if (!force) return ZKGPU_OK;
-      flush_backs();                                    // (a lane that is waited for must have its whole batch queued)
+      owed.flush();                                     // (a lane that is waited for must have its whole batch queued)
       collect_oldest(v);
       continue;
     }
-    --owed;
+    --cut.owed;
     zkgpu_ctx* L = v->lanes[(size_t)lane];
+    const size_t proof_len = head->proof_len;
     int rc = ZKGPU_OK;
-    std::string plan_err;
-    zkgpu_cloak_plan* plan = verifier_plan(v, head->n_in, head->n_out, &rc, &plan_err);   // rc != OK: no plan THIS time -> the tickets fail with it
-    if (rc != ZKGPU_OK) v->last_error = plan_err;                                          // (v->mu held)
-    const void *p_com = pick[0]->d_com, *p_proofs = pick[0]->d_proofs, *p_r = pick[0]->d_r;
-    // Tickets that brought no verifier randomness (d_r NULL) get it here, once per DEVICE batch: one seed from the OS, and
-    // statement i of the device batch gets r(seed, i) (draw_r.hpp) in the lane's coal_r -- also a lone unmerged ticket, so that
-    // nothing of the caller's is aliased.  Tickets with an r of their own keep their bytes.  No seed: the batch fails.
-    bool draw = false;
-    for (zkgpu_request* r : pick) draw = draw || !r->d_r;
-    uint8_t seed[32] = {0};
-    const bool runs = rc == ZKGPU_OK && plan && proof_len_fits(plan->dev.sh, head->proof_len);
-    if (runs && draw && !os_random(seed, sizeof seed)) {
-      std::lock_guard<std::recursive_mutex> lk(L->mu);
-      L->last_error = "getrandom failed";
-      rc = ZKGPU_EINVAL;
-    }
-    // batches of blocks whose copy to HBM is still queued on the copy stream: whoever reads their inputs waits for it
-    if (pick.size() == 1) {
-      if (pick[0]->ready) { std::lock_guard<std::recursive_mutex> lk(L->mu); L->dep_event = pick[0]->ready; }
-    } else {
-      std::lock_guard<std::recursive_mutex> lk(L->mu);
-      DeviceGuard g(L->device);
-      hipEvent_t seen = nullptr;
-      for (zkgpu_request* r : pick)
-        if (r->ready && r->ready != seen) { seen = r->ready; if (hipStreamWaitEvent(L->stream_l, r->ready, 0) != hipSuccess && rc == ZKGPU_OK) { L->last_error = "hipStreamWaitEvent (block copy)"; rc = ZKGPU_EHIP; } }
-    }
-    if (rc == ZKGPU_OK && plan && proof_len_fits(plan->dev.sh, head->proof_len) && pick.size() > 1) {
-      std::lock_guard<std::recursive_mutex> lk(L->mu);
-      DeviceGuard g(L->device);
-      const size_t wcom = (size_t)plan->dev.sh.m * 32;
-      rc = ensure(L, L->coal_com, total * wcom);
-      if (rc == ZKGPU_OK) rc = ensure(L, L->coal_proofs, total * head->proof_len + 16);   // (k_merge_inputs writes whole words)
-      if (rc == ZKGPU_OK) rc = ensure(L, L->coal_r, total * 64);
-      // one gather launch per 16 queued batches (commitments and randomness as 16-byte vectors; buffers that are not
-      // 16-byte aligned go through plain copies)
-      size_t off = 0, at = 0;
-      while (rc == ZKGPU_OK && at < pick.size()) {
-        MergeSources ms;
-        ms.n = 0;
-        bool aligned = true;
-        const size_t base = off;
-        while (at < pick.size() && ms.n < 16) {
-          zkgpu_request* r = pick[at];
-          aligned = aligned && ((uintptr_t)r->d_com % 16 == 0) && ((uintptr_t)r->d_r % 16 == 0);     // (no r: NULL, drawn below)
-          ms.com[ms.n] = (const uint4*)r->d_com; ms.proofs[ms.n] = (const uint8_t*)r->d_proofs; ms.r[ms.n] = (const uint4*)r->d_r;
-          ms.first[ms.n] = (uint32_t)(off - base);
-          off += r->batch;
-          ++ms.n; ++at;
-        }
-        ms.first[ms.n] = (uint32_t)(off - base);
-        if (aligned && (base * head->proof_len) % 4 == 0) {
-          const uint32_t span = ms.first[ms.n];
-          hipLaunchKernelGGL(k_merge_inputs, dim3(std::min<unsigned>(blocks_for((uint64_t)span * (head->proof_len / 4 + 1), 256), 1024u)), dim3(256), 0, L->stream_l, ms,
-                             (uint32_t)(wcom / 16), (uint32_t)head->proof_len, (uint4*)((char*)L->coal_com.p + base * wcom),
-                             (uint8_t*)L->coal_proofs.p + base * head->proof_len, (uint4*)((char*)L->coal_r.p + base * 64));
-          if (hipGetLastError() != hipSuccess) { L->last_error = "k_merge_inputs"; rc = ZKGPU_EHIP; }
-        } else {
-          size_t o2 = base;
-          for (uint32_t k = 0; k < ms.n && rc == ZKGPU_OK; ++k) {
-            const size_t nb = ms.first[k + 1] - ms.first[k];
-            hipError_t e = hipMemcpyAsync((char*)L->coal_com.p + o2 * wcom, ms.com[k], nb * wcom, hipMemcpyDeviceToDevice, L->stream_l);
-            if (e == hipSuccess) e = hipMemcpyAsync((char*)L->coal_proofs.p + o2 * head->proof_len, ms.proofs[k], nb * head->proof_len, hipMemcpyDeviceToDevice, L->stream_l);
-            if (e == hipSuccess && ms.r[k]) e = hipMemcpyAsync((char*)L->coal_r.p + o2 * 64, ms.r[k], nb * 64, hipMemcpyDeviceToDevice, L->stream_l);
-            if (e != hipSuccess) { L->last_error = hipGetErrorString(e); rc = ZKGPU_EHIP; }
-            o2 += nb;
-          }
-        }
-      }
-      p_com = L->coal_com.p; p_proofs = L->coal_proofs.p; p_r = L->coal_r.p;
-    }
-    if (rc == ZKGPU_OK && runs && draw) {
-      std::lock_guard<std::recursive_mutex> lk(L->mu);
-      DeviceGuard g(L->device);
-      rc = ensure(L, L->coal_r, total * 64);
-      size_t off = 0;
-      for (size_t at = 0; at < pick.size() && rc == ZKGPU_OK;) {      // one launch per run of neighbouring tickets without r
-        if (pick[at]->d_r) { off += pick[at]->batch; ++at; continue; }
-        const size_t first = off;
-        while (at < pick.size() && !pick[at]->d_r) { off += pick[at]->batch; ++at; }
-        rc = draw_r_launch(L, L->stream_l, seed, first, (uint32_t)(off - first), (char*)L->coal_r.p + first * 64);
-      }
-      p_r = L->coal_r.p;
-    }
-    bool front_only = false;
-    if (rc == ZKGPU_OK && plan) {
-      bool why = false;                                   // statements of a format-2 transaction call among them: the batch also says why
-      for (zkgpu_request* r : pick) why = why || r->reasons;
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_FRONT; L->awaiting_back = false; L->want_reasons = why; L->reasons_src = 0; }
-      rc = zkgpu_cloak_verify_submit_dev(L, v->ps, plan, total, p_com, p_proofs, head->proof_len, p_r);
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->enqueue_phase = zkgpu_ctx::ENQ_ALL; front_only = rc == ZKGPU_OK && L->awaiting_back; if (rc != ZKGPU_OK) L->want_reasons = false; if (draw) memcpy(L->r_seed, seed, sizeof seed); }
-      if (front_only) fronts.push_back(Front{lane, plan, total, head->proof_len, p_com, p_proofs, p_r});
-    }
-    size_t off = 0;
-    for (zkgpu_request* r : pick) {
-      for (auto it = v->queue.begin(); it != v->queue.end(); ++it) if (*it == r) { v->queue.erase(it); break; }
-      r->bit_off = off; off += r->batch;
-      if (rc == ZKGPU_OK && plan) { r->state = 1; r->lane = lane; }
-      else { r->state = 2; r->rc = rc; r->bits.assign((r->batch + 7) / 8, 0); }   // rc OK and no plan: every proof is Err
-    }
-    if (rc == ZKGPU_OK && plan) { v->running[(size_t)lane] = pick; v->busy.push_back(lane); }
-    else {
-      if (rc != ZKGPU_OK && plan) v->last_error = zkgpu_last_error(L);
-      if (rc != ZKGPU_OK) quiesce_after_fault(L);          // (merge copies, a front half: nothing of it stays in flight on a lane that reads as free)
-      { std::lock_guard<std::recursive_mutex> lk(L->mu); L->dep_event = nullptr; }
-      for (zkgpu_request* r : pick) if (r->run) block_request_done(v, r);     // (a block's batches answer to their run, at once)
-    }
+    zkgpu_cloak_plan* plan = verifier_plan(v, head->n_in, head->n_out, &rc, &b.err);   // rc != OK: no plan THIS time -> the tickets fail with it
+    const bool runs = rc == ZKGPU_OK && plan && proof_len_fits(plan->dev.sh, proof_len);
+    if (rc == ZKGPU_OK) rc = ticket_gather(L, runs ? plan : nullptr, proof_len, b);
+    if (rc == ZKGPU_OK && runs) for (const zkgpu_request* r : b.pick) if (!r->d_r) { rc = ticket_draw_r(L, b); break; }
+    if (rc == ZKGPU_OK && plan) rc = ticket_begin_front(v, lane, plan, proof_len, b, owed);
+    if (rc != ZKGPU_OK) v->last_error = b.err.empty() ? zkgpu_last_error(L) : b.err;
+    ticket_settle(v, lane, rc == ZKGPU_OK && plan, rc, b);
   }
   return ZKGPU_OK;
 }
@@ -1175,6 +1227,19 @@ int free_ticket_lane(zkgpu_verifier* v) {
   return -1;
 }
 
+// the area and its twin in HBM freed and allocated anew for `bytes` (the device is current) -> NULL, or which allocation
+// failed: the area is then empty
+const char* host_stage_grow(zkgpu_verifier::HostStage& hs, size_t bytes) {
+  if (hs.pin) (void)hipHostFree(hs.pin);
+  if (hs.dev) (void)hipFree(hs.dev);
+  hs.pin = hs.dev = nullptr; hs.cap = 0;
+  const size_t want = bytes + bytes / 8 + 4096;
+  if (hipHostMalloc(&hs.pin, want, hipHostMallocDefault) != hipSuccess) { hs.pin = nullptr; return "hipHostMalloc (ticket staging)"; }
+  if (hipMalloc(&hs.dev, want) != hipSuccess) { (void)hipHostFree(hs.pin); hs.pin = hs.dev = nullptr; return "hipMalloc (ticket staging twin)"; }
+  hs.cap = want;
+  return nullptr;
+}
+
 // a staging area nobody forms a batch in; its last copy to the device is waited for (long done in practice).  -1: none
 int host_stage_acquire(zkgpu_verifier* v, size_t bytes, int* rc) {
   *rc = ZKGPU_OK;
@@ -1186,26 +1251,14 @@ int host_stage_acquire(zkgpu_verifier* v, size_t bytes, int* rc) {
     zkgpu_verifier::HostStage& hs = v->host_stages[i];
     if (hs.taken || hs.cap >= bytes) continue;
     DeviceGuard g(v->root->device);
-    if (hs.pin) (void)hipHostFree(hs.pin);
-    if (hs.dev) (void)hipFree(hs.dev);
-    hs.pin = hs.dev = nullptr; hs.cap = 0;
-    const size_t want = bytes + bytes / 8 + 4096;
-    if (hipHostMalloc(&hs.pin, want, hipHostMallocDefault) != hipSuccess) { hs.pin = nullptr; continue; }     // (tried again when it is handed out)
-    if (hipMalloc(&hs.dev, want) != hipSuccess) { (void)hipHostFree(hs.pin); hs.pin = hs.dev = nullptr; continue; }
-    hs.cap = want;
+    (void)host_stage_grow(hs, bytes);      // (failed: tried again when the area is handed out)
   }
   for (size_t i = 0; i < v->host_stages.size(); ++i) {
     zkgpu_verifier::HostStage& hs = v->host_stages[i];
     if (hs.taken) continue;                // (a free area has no copy in flight: its last batch has been collected)
     DeviceGuard g(v->root->device);
     if (hs.cap < bytes) {
-      if (hs.pin) (void)hipHostFree(hs.pin);
-      if (hs.dev) (void)hipFree(hs.dev);
-      hs.pin = hs.dev = nullptr; hs.cap = 0;
-      const size_t want = bytes + bytes / 8 + 4096;
-      if (hipHostMalloc(&hs.pin, want, hipHostMallocDefault) != hipSuccess) { hs.pin = nullptr; v->last_error = "hipHostMalloc (ticket staging)"; *rc = ZKGPU_ENOMEM; return -1; }
-      if (hipMalloc(&hs.dev, want) != hipSuccess) { (void)hipHostFree(hs.pin); hs.pin = hs.dev = nullptr; v->last_error = "hipMalloc (ticket staging twin)"; *rc = ZKGPU_ENOMEM; return -1; }
-      hs.cap = want;
+      if (const char* failed = host_stage_grow(hs, bytes)) { v->last_error = failed; *rc = ZKGPU_ENOMEM; return -1; }
     }
     if (!hs.copied && hipEventCreateWithFlags(&hs.copied, hipEventDisableTiming) != hipSuccess) { v->last_error = "hipEventCreate (ticket staging)"; *rc = ZKGPU_EHIP; return -1; }
     if (!v->copy_stream && hipStreamCreateWithFlags(&v->copy_stream, hipStreamNonBlocking) != hipSuccess) { v->last_error = "hipStreamCreate (ticket staging)"; *rc = ZKGPU_EHIP; return -1; }
@@ -1216,7 +1269,7 @@ int host_stage_acquire(zkgpu_verifier* v, size_t bytes, int* rc) {
 }
 
 void host_batch_fail(zkgpu_verifier* v, zkgpu_host_batch* F, int rc) {      // every member done, with rc (OK: all bits zero)
-  for (zkgpu_request* r : F->members) { r->state = 2; r->rc = rc; r->form = nullptr; r->bits.assign((r->batch + 7) / 8, 0); }
+  for (zkgpu_request* r : F->members) request_fail(v, r, rc);
   if (F->stage >= 0) {
     zkgpu_verifier::HostStage& hs = v->host_stages[(size_t)F->stage];
     quiesce_after_fault(v->root);      // (copies of staged tickets may still be queued, kernels of a half-queued batch may still read the twin)
@@ -1230,11 +1283,16 @@ int host_launch(zkgpu_verifier* v, zkgpu_host_batch* F, int lane) {
   zkgpu_ctx* L = v->lanes[(size_t)lane];
   zkgpu_verifier::HostStage& hs = v->host_stages[(size_t)F->stage];
   const char* d = (const char*)hs.dev;
-  { std::lock_guard<std::recursive_mutex> lk(L->mu); L->dep_event = hs.copied; }
-  const int rc = zkgpu_cloak_verify_submit_dev(L, v->ps, F->plan, F->total, d, d + F->o_proofs, F->proof_len, d + F->o_r);
+  WholeProofOpts opts;
+  opts.after = hs.copied;
+  int rc;
+  {
+    std::lock_guard<std::recursive_mutex> lk(L->mu);
+    DeviceGuard g(L->device);
+    rc = whole_proof_enqueue(L, v->ps, F->plan, F->total, (const uint32_t*)d, (const uint8_t*)d + F->o_proofs, (const uint32_t*)(d + F->o_r), F->proof_len, opts);
+  }
   if (rc != ZKGPU_OK) {
     v->last_error = zkgpu_last_error(L);
-    { std::lock_guard<std::recursive_mutex> lk(L->mu); L->dep_event = nullptr; }
     host_batch_fail(v, F, rc);
     return rc;
   }
@@ -1297,17 +1355,14 @@ void staged_copy(const CopySpan* spans, int count) {
 // one ticket from host memory: copied into the batch being formed for its shape (a new one when that is full)
 int host_submit_one(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, size_t batch, const uint8_t* com, const uint8_t* proofs,
                     size_t proof_len, const uint8_t* r_bytes, uint64_t* ticket) {
-  zkgpu_request* r = new zkgpu_request();
-  r->id = v->next_id++;
-  r->n_in = n_in; r->n_out = n_out; r->batch = batch; r->proof_len = proof_len;
-  v->requests[r->id] = r;
+  zkgpu_request* r = ticket_new(v, n_in, n_out, batch, proof_len);
   *ticket = r->id;
   int rc = ZKGPU_OK;
   std::string plan_err;
   zkgpu_cloak_plan* plan = verifier_plan(v, n_in, n_out, &rc, &plan_err);
   if (rc != ZKGPU_OK) v->last_error = plan_err;
   if (rc != ZKGPU_OK || !plan || !proof_len_fits(plan->dev.sh, proof_len)) {   // no plan THIS time: the ticket fails with rc; a shape or
-    r->state = 2; r->rc = rc; r->bits.assign((batch + 7) / 8, 0);             // length the reference rejects: every proof is Err
+    request_fail(v, r, rc);                                                    // length the reference rejects: every proof is Err
     return ZKGPU_OK;
   }
   const size_t wcom = (size_t)plan->dev.sh.m * 32;
@@ -1319,7 +1374,7 @@ int host_submit_one(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, size_t bat
     auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_proofs = align(cap_tx * wcom), o_r = align(o_proofs + cap_tx * proof_len + 16), bytes = o_r + cap_tx * 64;
     const int st = host_stage_acquire(v, bytes, &rc);
-    if (rc != ZKGPU_OK) { r->state = 2; r->rc = rc; r->bits.assign((batch + 7) / 8, 0); return ZKGPU_OK; }
+    if (rc != ZKGPU_OK) { request_fail(v, r, rc); return ZKGPU_OK; }
     if (st < 0) {                         // every area holds a batch that waits: the oldest goes out now (a lane is made free for it)
       (void)host_dispatch(v, v->forming.front().get());
       continue;
@@ -1339,7 +1394,7 @@ int host_submit_one(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, size_t bat
   }
   if (!r_bytes) {                                // verifier randomness: SHAKE256 of 32 bytes from the OS and the ticket number
     uint8_t seed[40] = {0};
-    if (!os_random(seed, 32)) { r->state = 2; r->rc = ZKGPU_EINVAL; r->bits.assign((batch + 7) / 8, 0); v->last_error = "getrandom failed"; return ZKGPU_OK; }
+    if (!os_random(seed, 32)) { request_fail(v, r, ZKGPU_EINVAL); v->last_error = "getrandom failed"; return ZKGPU_OK; }
     for (int q = 0; q < 8; ++q) seed[32 + q] = (uint8_t)(r->id >> (8 * q));
     Sponge sp = shake256_sponge();
     sp.absorb(seed, 40);
@@ -1357,7 +1412,7 @@ int host_submit_one(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, size_t bat
     if (e != hipSuccess) {
       v->last_error = std::string("ticket staging copy: ") + hipGetErrorString(e);
       quiesce_after_fault(v->root);
-      r->state = 2; r->rc = ZKGPU_EHIP; r->bits.assign((batch + 7) / 8, 0);
+      request_fail(v, r, ZKGPU_EHIP);
       return ZKGPU_OK;
     }
   }
@@ -1409,11 +1464,12 @@ int zkgpu_verifier_reserve(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, siz
   const size_t proof_len = 1 + 4 * (size_t)plan->dev.sh.proof_words;
   const size_t wcom = (size_t)plan->dev.sh.m * 32;
   for (zkgpu_ctx* L : v->lanes) {
-    rc = cloak_reserve(L, v->ps, plan, transactions, proof_len);
-    if (rc == ZKGPU_OK) {
+    {
       std::lock_guard<std::recursive_mutex> llk(L->mu);
       DeviceGuard g(L->device);
-      rc = ensure(L, L->coal_com, transactions * wcom);
+      PipeCall sized;                                                    // (what a batch of that size would be: not kept)
+      rc = L->pending ? ZKGPU_EINVAL : whole_proof_workspace(L, v->ps, plan, transactions, sized);
+      if (rc == ZKGPU_OK) rc = ensure(L, L->coal_com, transactions * wcom);
       if (rc == ZKGPU_OK) rc = ensure(L, L->coal_proofs, transactions * proof_len + 16);
       if (rc == ZKGPU_OK) rc = ensure(L, L->coal_r, transactions * 64);
     }
@@ -1433,13 +1489,7 @@ int zkgpu_verifier_submit_dev(zkgpu_verifier* v, uint32_t n_in, uint32_t n_out, 
                               const void* d_proofs, size_t proof_len, const void* d_r, uint64_t* ticket) {
   if (!v || !ticket || batch == 0 || batch >= (1ull << 24) || !d_commitments || !d_proofs) return ZKGPU_EINVAL;     // (d_r NULL: drawn per device batch, ticket_dispatch)
   std::lock_guard<std::mutex> lk(v->mu);
-  zkgpu_request* r = new zkgpu_request();
-  r->id = v->next_id++;
-  r->n_in = n_in; r->n_out = n_out; r->batch = batch; r->proof_len = proof_len;
-  r->d_com = d_commitments; r->d_proofs = d_proofs; r->d_r = d_r;
-  v->requests[r->id] = r;
-  v->queue.push_back(r);
-  *ticket = r->id;
+  *ticket = ticket_new(v, n_in, n_out, batch, proof_len, d_commitments, d_proofs, d_r)->id;
   return ticket_dispatch(v, false);
 }
 
@@ -1450,15 +1500,8 @@ int zkgpu_verifier_submit_many_dev(zkgpu_verifier* v, uint32_t n_in, uint32_t n_
   if (!v || !tickets || !d_commitments || !d_proofs || batch_each == 0 || batch_each >= (1ull << 24)) return ZKGPU_EINVAL;
   for (size_t i = 0; i < count; ++i) if (!d_commitments[i] || !d_proofs[i]) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> lk(v->mu);
-  for (size_t i = 0; i < count; ++i) {
-    zkgpu_request* r = new zkgpu_request();
-    r->id = v->next_id++;
-    r->n_in = n_in; r->n_out = n_out; r->batch = batch_each; r->proof_len = proof_len;
-    r->d_com = d_commitments[i]; r->d_proofs = d_proofs[i]; r->d_r = d_r ? d_r[i] : nullptr;       // (d_r or d_r[i] NULL: drawn per device batch)
-    v->requests[r->id] = r;
-    v->queue.push_back(r);
-    tickets[i] = r->id;
-  }
+  for (size_t i = 0; i < count; ++i)       // (d_r or d_r[i] NULL: drawn per device batch)
+    tickets[i] = ticket_new(v, n_in, n_out, batch_each, proof_len, d_commitments[i], d_proofs[i], d_r ? d_r[i] : nullptr)->id;
   return ticket_dispatch(v, false);
 }
 

@@ -102,19 +102,8 @@ struct zkgpu_ctx {
   // signature stages of zkgpu_tx_verify_batch can run beside the host's work on the next chunk (session.hpp)
   struct SplitOp { int kind = 0; size_t batch = 0; bool values = false; hipStream_t stream = nullptr; } split;
   int pair_overlaps = -1;          // root contexts: do stream and stream2 run side by side (streams_overlap at creation; -1 not probed)
-  hipEvent_t dep_event = nullptr;  // the next whole-proof submit on this context waits for it first (its inputs are still being copied)
-  bool reserve_only = false;       // zkgpu_verifier_reserve: the next whole-proof enqueue sizes the workspace and launches nothing
-  // A whole-proof batch queued in three pieces (session.hpp, ticket_dispatch: several device batches leaving together).  FRONT =
-  // the light kernels that need the proof bytes alone -- unpack, the transcript replay; MID = the proof points' decoding and
-  // tables (chip-filling); BACK = everything that waits for the transcript.  The verifier queues the FRONT of every batch,
-  // then the MID of every batch, then the BACKs, so that the second batch's transcript and decoding run beside the first's
-  // instead of 0.6 ms later, when the host has finished queueing the first batch's ~45 launches
-  // (profiles/archive/r04am_timeline.txt).  The same call is made once per piece with the same arguments.
-  enum { ENQ_ALL = 0, ENQ_FRONT = 1, ENQ_MID = 2, ENQ_BACK = 3 };
-  int enqueue_phase = ENQ_ALL;
-  bool awaiting_back = false;      // an ENQ_FRONT call really queued a front half (shapes outside the pipeline run whole, at once)
   std::vector<uint8_t> sync_result, sync_reasons; // result of a submit that had to run synchronously | its reason bytes (tx_reasons_parked)
-  bool sync_result_valid = false, want_reasons = false;   // | the whole-proof batches of this context also say WHY (tx_reason_kernels.hpp)
+  bool sync_result_valid = false, want_reasons = false;   // | the whole-proof batch in flight also says WHY (tx_reason_kernels.hpp; WholeProofOpts)
   int sync_rc = 0, reasons_src = 0;   // | where the reason bytes of the batch in flight are: 0 nowhere, 1 pinned result buffer, 2 sync_reasons
   std::recursive_mutex mu;
   std::string last_error;
@@ -128,7 +117,7 @@ struct zkgpu_ctx {
   Buffer grp_ws, grp_wf, grp_dyn;             // window sums of the groups, their flags, the groups' proof-point sums
   Buffer grp_fail, grp_fail_sum, rechk_pts;   // failed groups: list | located candidate, their sums S1; sums of the re-checked transactions
   // the batch in flight, kept for the (never expected) ungrouped re-run when a located transaction does not explain its group; mixed: a zkgpu_r1cs_verify_mixed call, with its groups of two or more and the statements in them
-  struct LastBatch { bool valid = false, has_prep = false; const zkgpu_pointset* ps = nullptr; std::vector<uint8_t> job, prep; bool mixed = false; uint64_t mx_groups = 0, mx_stmts = 0; } last;
+  struct LastBatch { bool valid = false; std::vector<uint8_t> call; bool mixed = false; uint64_t mx_groups = 0, mx_stmts = 0; } last;   // (call: the PipeCall, as bytes)
   bool force_unresolved = false;   // test hook: take that re-run path
   uint64_t regroup_fallbacks = 0, mx_stats[4] = {0, 0, 0, 0};   // | zkgpu_debug_read "mixed_groups": the mixed call finished last
   int group_size = 16;             // transactions per group check (1 = every transaction on its own)
@@ -962,28 +951,42 @@ int pipe_workspace(zkgpu_ctx* c, const PipePlan& p) {
   return small_window_workspace(c, p.small, /*with_tables=*/true);
 }
 
-int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const PrepLaunch* prep) {
-  static_assert(std::is_trivially_copyable<Job>::value && std::is_trivially_copyable<PrepLaunch>::value, "kept as bytes");
-  {
-    std::vector<uint8_t> jb(sizeof(Job)), pb(prep ? sizeof(PrepLaunch) : 0);     // (job may alias c->last: copy first)
-    memcpy(jb.data(), &job, sizeof(Job));
-    if (prep) memcpy(pb.data(), prep, sizeof(PrepLaunch));
-    c->last.job.swap(jb); c->last.prep.swap(pb);
-    c->last.ps = ps; c->last.has_prep = prep != nullptr; c->last.valid = true; c->last.mixed = false;
-  }
-  const size_t B = job.n_msm;
-  hipStream_t L = c->stream_l, H1 = c->serial ? L : c->stream, H2 = c->serial ? L : c->stream2, H3s = c->serial ? L : c->stream3;
-  const uint32_t ns = prep ? prep->plan.sh.n_static : 0;
-  const PipePlan pp = plan_pipe(PipeShape{job.n_msm, job.n_dyn, job.n_static, ps->tbl_W, prep != nullptr, ns},
-                                PipeKnobs{c->group_size, c->locate_mode, c->locate_parts, c->forced_parts, c->want_reasons});
-  const int W = ps->tbl_W, P = pp.P, Pg = pp.Pg, Pf = pp.Pf, Pl = pp.Pl;
-  const uint32_t group = pp.group, n_groups = pp.n_groups, grp_rows = pp.grp_rows;
-  const bool locate = pp.locate, spec = pp.spec;
-  TRY(pipe_workspace(c, pp));
-  if (c->reserve_only) return ZKGPU_OK;                 // (the workspace now fits a batch of this shape and size: nothing is launched)
-  const int phase = prep ? c->enqueue_phase : (int)zkgpu_ctx::ENQ_ALL;        // (two halves: whole proofs only)
-  // ---- front: what needs the proof bytes alone, on the light stream
-  if (phase == zkgpu_ctx::ENQ_ALL || phase == zkgpu_ctx::ENQ_FRONT) {
+// One batch on its way into the pipeline, as a value.  It is queued in three pieces -- pipe_front, pipe_mid, pipe_back, in
+// that order, under c->mu -- which a caller with several batches interleaves (session.hpp, ticket_dispatch: every front, every
+// middle, then the backs: the second batch's transcript and decoding run beside the first's instead of 0.6 ms later, when
+// the host has finished queueing the first batch's ~45 launches, profiles/archive/r04am_timeline.txt).
+struct PipeCall {
+  zkgpu_ctx* c = nullptr;
+  const zkgpu_pointset* ps = nullptr;
+  enum How { PARKED, SYNC, PIPED } how = PARKED;   // all-zero bits parked, nothing ran | ran here and now, result parked | the three pieces are owed
+  Job job;
+  PrepLaunch prep;                                 // whole proofs only (has_prep)
+  bool has_prep = false;
+  PipePlan pp;
+};
+
+PipePlan pipe_geometry(const zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, bool whole_proofs, uint32_t n_static_each) {
+  return plan_pipe(PipeShape{job.n_msm, job.n_dyn, job.n_static, ps->tbl_W, whole_proofs, n_static_each},
+                   PipeKnobs{c->group_size, c->locate_mode, c->locate_parts, c->forced_parts, c->want_reasons});
+}
+
+// the batch in flight, kept for pipe_wait's ungrouped re-run
+void pipe_remember(const PipeCall& k) {
+  static_assert(std::is_trivially_copyable<PipeCall>::value, "kept as bytes");
+  k.c->last.call.assign((const uint8_t*)&k, (const uint8_t*)(&k + 1));
+  k.c->last.valid = true; k.c->last.mixed = false;
+}
+
+// A front or a middle piece queued on its own ends with this: its launches' error, if any, belongs to this batch
+int pipe_piece_queued(zkgpu_ctx* c) { HIP_TRY(c, hipGetLastError()); return ZKGPU_OK; }
+
+// ---- front: what needs the proof bytes alone, on the light stream
+int pipe_front(const PipeCall& k) {
+  zkgpu_ctx* c = k.c;
+  const PrepLaunch* prep = k.has_prep ? &k.prep : nullptr;
+  const size_t B = k.job.n_msm;
+  hipStream_t L = c->stream_l;
+  const uint32_t group = k.pp.group;
   batch_init_launch(c, L, B, /*with_wellformed=*/prep != nullptr);
   if (prep) {
     const PrepPlan& d = prep->plan; const PrepShape& sh = d.sh;
@@ -1012,27 +1015,45 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
     }
   }
   HIP_TRY(c, hipEventRecord(c->ev_t, L));
+  return ZKGPU_OK;
+}
+
+// ---- mid: the proof points' decoding and tables, chip-filling (whole proofs only)
+int pipe_mid(const PipeCall& k) {
+  if (!k.has_prep) return ZKGPU_OK;
+  zkgpu_ctx* c = k.c;
+  const PrepLaunch* prep = &k.prep;
+  const size_t B = k.job.n_msm;
+  hipStream_t H1 = c->serial ? c->stream_l : c->stream;
+  // the proof-specific points need the proof bytes only: gather, decompress and build their small tables on the shared
+  // stream while the transcript is replayed.  Queued AFTER the transcript: k_points_tables takes every register of the chip
+  // (255 per lane, two wavefronts per SIMD), and a light kernel queued behind it waits for one of its wavefronts to retire
+  // -- ~0.6 ms (measured: the next batch's 30 us merge copy took 0.59 ms there, profiles/archive/r04an_timeline.txt)
+  const PrepShape& sh = prep->plan.sh;
+  HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_u, 0));
+  {
+    Launch l(c, "k_points_tables", H1);
+    hipLaunchKernelGGL(k_points_tables, dim3(blocks_for((uint64_t)B * sh.n_dyn, 256)), dim3(256), 0, H1, sh,
+                       prep->d_com, (const uint32_t*)c->prep_pw.p, (uint32_t)B, (uint32_t*)c->small_tbl.p,
+                       (uint32_t*)c->msm_fail.p, (unsigned long long*)((char*)c->status.p + 8));
   }
-  if (phase == zkgpu_ctx::ENQ_FRONT) { HIP_TRY(c, hipGetLastError()); c->awaiting_back = true; return ZKGPU_OK; }
-  // ---- mid: the proof points' decoding and tables, chip-filling
-  if (prep && (phase == zkgpu_ctx::ENQ_ALL || phase == zkgpu_ctx::ENQ_MID)) {
-    // the proof-specific points need the proof bytes only: gather, decompress and build their small tables on the shared
-    // stream while the transcript is replayed.  Queued AFTER the transcript: k_points_tables takes every register of the chip
-    // (255 per lane, two wavefronts per SIMD), and a light kernel queued behind it waits for one of its wavefronts to retire
-    // -- ~0.6 ms (measured: the next batch's 30 us merge copy took 0.59 ms there, profiles/archive/r04an_timeline.txt)
-    const PrepShape& sh = prep->plan.sh;
-    HIP_TRY(c, hipStreamWaitEvent(H1, c->ev_u, 0));
-    {
-      Launch l(c, "k_points_tables", H1);
-      hipLaunchKernelGGL(k_points_tables, dim3(blocks_for((uint64_t)B * sh.n_dyn, 256)), dim3(256), 0, H1, sh,
-                         prep->d_com, (const uint32_t*)c->prep_pw.p, (uint32_t)B, (uint32_t*)c->small_tbl.p,
-                         (uint32_t*)c->msm_fail.p, (unsigned long long*)((char*)c->status.p + 8));
-    }
-    HIP_TRY(c, hipEventRecord(c->ev_dig, H1));      // msm_fail is final: the group sums leave such transactions out
-  }
-  if (phase == zkgpu_ctx::ENQ_MID) { HIP_TRY(c, hipGetLastError()); return ZKGPU_OK; }
-  // ---- back: everything that waits for the transcript
-  c->awaiting_back = false;
+  HIP_TRY(c, hipEventRecord(c->ev_dig, H1));      // msm_fail is final: the group sums leave such transactions out
+  return ZKGPU_OK;
+}
+
+// ---- back: everything that waits for the transcript
+int pipe_back(const PipeCall& k) {
+  zkgpu_ctx* c = k.c;
+  const zkgpu_pointset* ps = k.ps;
+  const Job& job = k.job;
+  const PrepLaunch* prep = k.has_prep ? &k.prep : nullptr;
+  const PipePlan& pp = k.pp;
+  const size_t B = job.n_msm;
+  hipStream_t L = c->stream_l, H1 = c->serial ? L : c->stream, H2 = c->serial ? L : c->stream2, H3s = c->serial ? L : c->stream3;
+  const uint32_t ns = prep ? prep->plan.sh.n_static : 0;
+  const int W = ps->tbl_W, P = pp.P, Pg = pp.Pg, Pf = pp.Pf, Pl = pp.Pl;
+  const uint32_t group = pp.group, n_groups = pp.n_groups, grp_rows = pp.grp_rows;
+  const bool locate = pp.locate, spec = pp.spec;
   if (prep) {
     HIP_TRY(c, hipStreamWaitEvent(H3s, c->ev_t, 0));
     TRY(prepare_launch(c, H3s, *prep, (uint32_t)B, /*with_points=*/false));
@@ -1138,6 +1159,20 @@ int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const P
   return ZKGPU_OK;
 }
 
+int pipe_pieces(const PipeCall& k) { TRY(pipe_front(k)); TRY(pipe_mid(k)); return pipe_back(k); }
+
+// The one-call form: a batch the pipeline takes (pipe_eligible), begun and queued whole.  The rows-only submit, the mixed
+// call's statements checked alone and pipe_wait's ungrouped re-run.  (job may alias c->last: the call holds copies.)
+int pipe_enqueue(zkgpu_ctx* c, const Job& job, const zkgpu_pointset* ps, const PrepLaunch* prep) {
+  PipeCall k;
+  k.c = c; k.ps = ps; k.how = PipeCall::PIPED; k.job = job; k.has_prep = prep != nullptr;
+  if (prep) k.prep = *prep;
+  pipe_remember(k);
+  k.pp = pipe_geometry(c, k.job, ps, k.has_prep, prep ? prep->plan.sh.n_static : 0);
+  TRY(pipe_workspace(c, k.pp));
+  return pipe_pieces(k);
+}
+
 // a submit whose shape the pipeline does not cover has already run synchronously: park its result
 void park_sync_result(zkgpu_ctx* c, int rc, const uint8_t* bitmap, size_t batch) {
   c->sync_result.assign(bitmap, bitmap + (batch + 7) / 8);
@@ -1178,13 +1213,11 @@ int pipe_wait(zkgpu_ctx* c, uint8_t* accept_bitmap) {
   if (!mixed && (st & 4u) && c->last.valid && c->group_size > 1) {
     // a located transaction did not account for its group's sum (probability ~2^-248, or the test hook): verdicts
     // must not rest on it -- run the same batch again with every transaction checked on its own
-    Job job;
-    PrepLaunch prep;
-    memcpy(&job, c->last.job.data(), sizeof job);
-    if (c->last.has_prep) memcpy(&prep, c->last.prep.data(), sizeof prep);
+    PipeCall k;
+    memcpy(&k, c->last.call.data(), sizeof k);
     const int saved = c->group_size;
     c->group_size = 1;
-    const int rc = pipe_enqueue(c, job, c->last.ps, c->last.has_prep ? &prep : nullptr);
+    const int rc = pipe_enqueue(c, k.job, k.ps, k.has_prep ? &k.prep : nullptr);
     c->group_size = saved;
     c->pending = false;
     ++c->regroup_fallbacks;
@@ -2803,85 +2836,34 @@ int zkgpu_cloak_plan_layout(const zkgpu_cloak_plan* p, uint32_t out[8]) {
 // replay (one lane per transaction), scalar preparation (one workgroup per transaction),
 // then the multiscalar multiplications.  All `batch` statements have the plan's shape.
 namespace {
-int draw_r_if_none(zkgpu_ctx* c, uint32_t B, const uint32_t** d_r);      // (below: d_r NULL -> drawn.)  Shared body: d_com / d_proofs / d_r are device pointers
-int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
-                             const uint32_t* d_com, const uint8_t* d_proofs, const uint32_t* d_r, size_t proof_len);
-int cloak_verify_gpu_body(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
-                          const uint32_t* d_com, const uint8_t* d_proofs, const uint32_t* d_r, size_t proof_len,
-                          uint8_t* accept_bitmap);
-}  // namespace
+int draw_r_if_none(zkgpu_ctx* c, uint32_t B, const uint32_t** d_r, const uint8_t* caller_seed);      // (below)
 
-// Asynchronous form of zkgpu_cloak_verify_batch_gpu (inputs in host memory; they may be reused as
-// soon as this returns); zkgpu_verify_wait collects the bitmap.
-int zkgpu_cloak_verify_submit(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
-                              const uint8_t* commitments, const uint8_t* proofs, size_t proof_len,
-                              const uint8_t* r_bytes) {
-  if (!c || !ps || !plan || plan->device != c->device || ps->ctx->device != c->device) return ZKGPU_EINVAL;
-  if (batch == 0 || !commitments || !proofs || batch >= (1ull << 24)) return ZKGPU_EINVAL;
+// What the caller of a whole-proof batch may ask for beside its inputs (d_com / d_proofs / d_r: device pointers)
+struct WholeProofOpts {
+  hipEvent_t after = nullptr;        // the inputs are still on their way to HBM on another stream: the light stream waits for this first
+  bool want_reasons = false;         // the batch also says WHY (tx_reason_kernels.hpp): tx_reasons_take reads it once the batch is collected
+  const uint8_t* r_seed = nullptr;   // the caller drew d_r itself (draw_r_launch) from these 32 bytes: what the hook "r_seed" then reads
+};
+
+// the argument checks the four exports below share
+bool whole_proof_args_ok(const zkgpu_ctx* c, const zkgpu_pointset* ps, const zkgpu_cloak_plan* plan) {
+  return c && ps && plan && plan->device == c->device && ps->ctx->device == c->device;
+}
+
+// a proof length the plan does not serve: every proof is Err -- all-zero bits are parked, there is nothing to queue
+bool park_if_unserved(zkgpu_ctx* c, const zkgpu_cloak_plan* plan, size_t batch, size_t proof_len) {
+  if (proof_len_fits(plan->dev.sh, proof_len)) return false;
+  std::vector<uint8_t> z((batch + 7) / 8, 0);
+  park_sync_result(c, ZKGPU_OK, z.data(), batch);
+  return true;
+}
+
+// Every buffer a whole-proof batch of `batch` statements of the plan's shape needs on this context, in the order the fault
+// tests count on, and the plan's cached offset and index rows.  Launches nothing: zkgpu_verifier_reserve calls it as it is.
+// -> k: the job over that workspace, PIPED with its geometry or SYNC (no generator tables, forced window width, many proof points)
+int whole_proof_workspace(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch, PipeCall& k) {
   const PrepShape& sh = plan->dev.sh;
-  {
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (c->pending) return ZKGPU_EINVAL;
-    if (!proof_len_fits(sh, proof_len)) {     // wrong length for this statement: every proof is Err
-      std::vector<uint8_t> z((batch + 7) / 8, 0);
-      park_sync_result(c, ZKGPU_OK, z.data(), batch);
-      return ZKGPU_OK;
-    }
-    DeviceGuard g(c->device);
-    const StageSpan in[] = {{commitments, batch * sh.m * 32, &c->prep_com}, {proofs, batch * proof_len, &c->prep_proofs},
-                            {r_bytes, batch * 64, &c->prep_r}};
-    TRY(stage_inputs(c, in));
-  }
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  return cloak_verify_gpu_enqueue(c, ps, plan, batch, (const uint32_t*)c->prep_com.p, (const uint8_t*)c->prep_proofs.p,
-                                  (const uint32_t*)c->prep_r.p, proof_len);
-}
-
-int zkgpu_cloak_verify_batch_gpu(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
-                                 const uint8_t* commitments, const uint8_t* proofs, size_t proof_len,
-                                 const uint8_t* r_bytes, uint8_t* accept_bitmap) {
-  if (!c || !ps || !plan || plan->device != c->device || ps->ctx->device != c->device || !accept_bitmap) return ZKGPU_EINVAL;
-  memset(accept_bitmap, 0, (batch + 7) / 8);
-  if (batch == 0) return ZKGPU_OK;
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  TRY(zkgpu_cloak_verify_submit(c, ps, plan, batch, commitments, proofs, proof_len, r_bytes));
-  DeviceGuard g(c->device);
-  int rc = pipe_wait(c, accept_bitmap);
-  if (rc != ZKGPU_OK) memset(accept_bitmap, 0, (batch + 7) / 8);
-  return rc;
-}
-
-// Inputs already resident in HBM (what bench.py times): d_commitments = batch x 64 (n_in + n_out)
-// bytes, d_proofs = batch x proof_len bytes, d_r = batch x 64 bytes of verifier randomness.
-int zkgpu_cloak_verify_batch_gpu_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
-                                     const void* d_commitments, const void* d_proofs, size_t proof_len,
-                                     const void* d_r, uint8_t* accept_bitmap) {
-  if (!c || !ps || !plan || plan->device != c->device || ps->ctx->device != c->device || !accept_bitmap) return ZKGPU_EINVAL;
-  memset(accept_bitmap, 0, (batch + 7) / 8);
-  if (batch == 0) return ZKGPU_OK;
-  if (!d_commitments || !d_proofs || batch >= (1ull << 24)) return ZKGPU_EINVAL;       // (d_r NULL: drawn here, cloak_verify_gpu_enqueue)
-  if (!proof_len_fits(plan->dev.sh, proof_len)) return ZKGPU_OK;
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  return cloak_verify_gpu_body(c, ps, plan, batch, (const uint32_t*)d_commitments, (const uint8_t*)d_proofs,
-                               (const uint32_t*)d_r, proof_len, accept_bitmap);
-}
-
-namespace {
-// Enqueues (pipeline) or runs (shapes the pipeline does not cover) the verification of one batch;
-// the result is collected by pipe_wait.
-int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
-                             const uint32_t* d_com, const uint8_t* d_proofs, const uint32_t* d_r, size_t proof_len) {
-  if (ps->n < 2 + 2 * plan->gens_capacity) return ZKGPU_EINVAL;
-  if (c->pending) { c->last_error = "a submitted batch is still waiting for zkgpu_verify_wait"; return ZKGPU_EINVAL; }
-  if (c->dep_event) {            // inputs on their way to HBM on another stream (session.hpp, staged transactions)
-    const hipEvent_t ev = c->dep_event;
-    c->dep_event = nullptr;
-    HIP_TRY(c, hipStreamWaitEvent(c->stream_l, ev, 0));
-  }
-  const PrepShape& sh = plan->dev.sh;
-  const uint32_t B = (uint32_t)batch; TRY(draw_r_if_none(c, B, &d_r));      // (d_r NULL: drawn into c->r_draw, on the light stream)
+  const uint32_t B = (uint32_t)batch;
   TRY(ensure(c, c->prep_pw, (size_t)B * sh.proof_words * 4));
   TRY(ensure(c, c->prep_ch, (size_t)B * sh.n_ch_ext * 32));
   if (plan->large) TRY(ensure(c, c->prep_large, lp_ws_bytes(lp_layout(sh).slots, B)));
@@ -2893,8 +2875,8 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
     TRY(ensure(c, c->prep_absorb, (size_t)B * plan->dev.n_seg * 25 * 8));
     TRY(ensure(c, c->prep_raw, (size_t)B * sh.n_ch * 64));
   }
-  const uint64_t *d_dyn_off, *d_st_off;
-  const uint32_t* d_st_index;
+  Job& job = k.job;
+  job = Job();
   {
     std::lock_guard<std::mutex> plk(plan->mu);
     if (plan->cached_batch < batch + 1) {      // rows a launch indexes: with locate mode 3, 2 * ceil(batch / group) -- batch + 1 for groups of two over an odd batch
@@ -2922,83 +2904,130 @@ int cloak_verify_gpu_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak
       plan->d_dyn_off = nd; plan->d_st_off = ns; plan->d_st_index = ni;
       plan->cached_batch = nb;
     }
-    d_dyn_off = plan->d_dyn_off; d_st_off = plan->d_st_off; d_st_index = plan->d_st_index;
+    job.d_dyn_offsets = plan->d_dyn_off; job.d_st_offsets = plan->d_st_off; job.d_st_index = plan->d_st_index;
   }
-  Job job;
   job.d_dyn_scalars = (const uint32_t*)c->prep_dyn_sc.p;
   job.d_dyn_points = (const uint32_t*)c->prep_dyn_pt.p;
-  job.d_dyn_offsets = d_dyn_off;
   job.n_dyn = (uint64_t)B * sh.n_dyn;
   job.d_st_scalars = (const uint32_t*)c->prep_st_sc.p;
-  job.d_st_index = d_st_index;
-  job.d_st_offsets = d_st_off;
   job.n_static = (uint64_t)B * sh.n_static;
   job.d_static_rows = ps->rows;
   job.n_msm = B;
   job.d_wellformed = (const uint32_t*)c->prep_wf.p;   // folded into the accept bitmap on the device
-  const PrepLaunch pl = {plan->dev, plan->lds_bytes, plan->large, d_com, d_proofs, d_r, proof_len};
-  if (pipe_eligible(c, ps, job.n_msm, job.n_dyn, job.n_static)) return pipe_enqueue(c, job, ps, &pl);
-  // general shapes (no generator tables, forced window width, many proof points): one stream, synchronous
-  hipStream_t s = c->stream;
-  TRY(ensure(c, c->recoded, std::max<uint64_t>(job.n_dyn, 1) * 32));
-  if (c->reserve_only) return ZKGPU_OK;
-  HIP_TRY(c, hipStreamSynchronize(c->stream_l));      // uploads, if any, were queued on the light stream
-  HIP_TRY(c, hipMemsetAsync(c->prep_wf.p, 0xff, (size_t)B * 4, s));
-  proof_unpack_launch(c, s, pl, B);
-  transcript_launch(c, s, pl, B, /*grouped=*/false);
-  TRY(prepare_launch(c, s, pl, B, /*with_points=*/true));
-  HIP_TRY(c, hipGetLastError());
-  return tx_reasons_parked(c, job.d_wellformed, B, run_sync_and_park(c, job, ps));
+  k.c = c; k.ps = ps; k.has_prep = true;
+  if (pipe_eligible(c, ps, job.n_msm, job.n_dyn, job.n_static)) {
+    k.how = PipeCall::PIPED;
+    k.pp = pipe_geometry(c, job, ps, /*whole_proofs=*/true, sh.n_static);
+    return pipe_workspace(c, k.pp);
+  }
+  k.how = PipeCall::SYNC;
+  return ensure(c, c->recoded, std::max<uint64_t>(job.n_dyn, 1) * 32);
 }
 
-int cloak_verify_gpu_body(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
-                          const uint32_t* d_com, const uint8_t* d_proofs, const uint32_t* d_r, size_t proof_len,
-                          uint8_t* accept_bitmap) {
-  TRY(cloak_verify_gpu_enqueue(c, ps, plan, batch, d_com, d_proofs, d_r, proof_len));
+// Begins the verification of one batch (c->mu held): checks, the wait for opts.after, the draw of r when the caller brought
+// none, the workspace; the batch's job, launch arguments and geometry are settled here, once.  -> k.how: PARKED or SYNC --
+// zkgpu_verify_wait finds the result -- or PIPED: pipe_front, pipe_mid and pipe_back are owed, in that order.
+int whole_proof_begin(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch, const uint32_t* d_com,
+                      const uint8_t* d_proofs, const uint32_t* d_r, size_t proof_len, const WholeProofOpts& opts, PipeCall& k) {
+  if (c->pending) { c->last_error = "a submitted batch is still waiting for zkgpu_verify_wait"; return ZKGPU_EINVAL; }
+  c->want_reasons = opts.want_reasons; c->reasons_src = 0;
+  const int rc = [&]() -> int {
+    if (park_if_unserved(c, plan, batch, proof_len)) return ZKGPU_OK;
+    if (ps->n < 2 + 2 * plan->gens_capacity) return ZKGPU_EINVAL;
+    if (opts.after) HIP_TRY(c, hipStreamWaitEvent(c->stream_l, opts.after, 0));
+    const uint32_t B = (uint32_t)batch;
+    TRY(draw_r_if_none(c, B, &d_r, opts.r_seed));      // (d_r NULL: drawn into c->r_draw, on the light stream)
+    TRY(whole_proof_workspace(c, ps, plan, batch, k));
+    k.prep = PrepLaunch{plan->dev, plan->lds_bytes, plan->large, d_com, d_proofs, d_r, proof_len};
+    if (k.how == PipeCall::PIPED) { pipe_remember(k); return ZKGPU_OK; }
+    hipStream_t s = c->stream;
+    HIP_TRY(c, hipStreamSynchronize(c->stream_l));      // uploads, if any, were queued on the light stream
+    HIP_TRY(c, hipMemsetAsync(c->prep_wf.p, 0xff, (size_t)B * 4, s));
+    proof_unpack_launch(c, s, k.prep, B);
+    transcript_launch(c, s, k.prep, B, /*grouped=*/false);
+    TRY(prepare_launch(c, s, k.prep, B, /*with_points=*/true));
+    HIP_TRY(c, hipGetLastError());
+    return tx_reasons_parked(c, k.job.d_wellformed, B, run_sync_and_park(c, k.job, ps));
+  }();
+  if (rc != ZKGPU_OK) c->want_reasons = false;
+  return rc;
+}
+
+// begin and the three pieces in one go (c->mu held): what the four exports do, and a batch formed from host-memory tickets
+// (session.hpp, host_launch); zkgpu_verify_wait / pipe_wait collects
+int whole_proof_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch, const uint32_t* d_com,
+                        const uint8_t* d_proofs, const uint32_t* d_r, size_t proof_len, const WholeProofOpts& opts = WholeProofOpts()) {
+  PipeCall k;
+  TRY(whole_proof_begin(c, ps, plan, batch, d_com, d_proofs, d_r, proof_len, opts, k));
+  return k.how == PipeCall::PIPED ? pipe_pieces(k) : ZKGPU_OK;
+}
+
+int pipe_wait_or_zero(zkgpu_ctx* c, size_t batch, uint8_t* accept_bitmap) {
   int rc = pipe_wait(c, accept_bitmap);
   if (rc != ZKGPU_OK) memset(accept_bitmap, 0, (batch + 7) / 8);
   return rc;
 }
 }  // namespace
 
+// Asynchronous form of zkgpu_cloak_verify_batch_gpu (inputs in host memory; they may be reused as
+// soon as this returns); zkgpu_verify_wait collects the bitmap.
+int zkgpu_cloak_verify_submit(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
+                              const uint8_t* commitments, const uint8_t* proofs, size_t proof_len,
+                              const uint8_t* r_bytes) {
+  if (!whole_proof_args_ok(c, ps, plan)) return ZKGPU_EINVAL;
+  if (batch == 0 || !commitments || !proofs || batch >= (1ull << 24)) return ZKGPU_EINVAL;
+  const PrepShape& sh = plan->dev.sh;
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  if (c->pending) return ZKGPU_EINVAL;
+  if (park_if_unserved(c, plan, batch, proof_len)) return ZKGPU_OK;     // (before anything is staged)
+  DeviceGuard g(c->device);
+  const StageSpan in[] = {{commitments, batch * sh.m * 32, &c->prep_com}, {proofs, batch * proof_len, &c->prep_proofs},
+                          {r_bytes, batch * 64, &c->prep_r}};
+  TRY(stage_inputs(c, in));
+  return whole_proof_enqueue(c, ps, plan, batch, (const uint32_t*)c->prep_com.p, (const uint8_t*)c->prep_proofs.p,
+                             (const uint32_t*)c->prep_r.p, proof_len);
+}
+
+int zkgpu_cloak_verify_batch_gpu(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
+                                 const uint8_t* commitments, const uint8_t* proofs, size_t proof_len,
+                                 const uint8_t* r_bytes, uint8_t* accept_bitmap) {
+  if (!whole_proof_args_ok(c, ps, plan) || !accept_bitmap) return ZKGPU_EINVAL;
+  memset(accept_bitmap, 0, (batch + 7) / 8);
+  if (batch == 0) return ZKGPU_OK;
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  TRY(zkgpu_cloak_verify_submit(c, ps, plan, batch, commitments, proofs, proof_len, r_bytes));
+  DeviceGuard g(c->device);
+  return pipe_wait_or_zero(c, batch, accept_bitmap);
+}
+
+// Inputs already resident in HBM (what bench.py times): d_commitments = batch x 64 (n_in + n_out)
+// bytes, d_proofs = batch x proof_len bytes, d_r = batch x 64 bytes of verifier randomness (NULL: drawn here).
+int zkgpu_cloak_verify_batch_gpu_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
+                                     const void* d_commitments, const void* d_proofs, size_t proof_len,
+                                     const void* d_r, uint8_t* accept_bitmap) {
+  if (!whole_proof_args_ok(c, ps, plan) || !accept_bitmap) return ZKGPU_EINVAL;
+  memset(accept_bitmap, 0, (batch + 7) / 8);
+  if (batch == 0) return ZKGPU_OK;
+  if (!d_commitments || !d_proofs || batch >= (1ull << 24)) return ZKGPU_EINVAL;
+  if (!proof_len_fits(plan->dev.sh, proof_len)) return ZKGPU_OK;
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  TRY(whole_proof_enqueue(c, ps, plan, batch, (const uint32_t*)d_commitments, (const uint8_t*)d_proofs, (const uint32_t*)d_r, proof_len));
+  return pipe_wait_or_zero(c, batch, accept_bitmap);
+}
+
 // Asynchronous form: enqueue the verification of one batch (inputs resident in HBM, as for
 // zkgpu_cloak_verify_batch_gpu_dev) and return; zkgpu_verify_wait(ctx, bitmap) collects the result.
 // One batch may be pending per context; fork contexts (zkgpu_ctx_fork) to keep several in flight.
 int zkgpu_cloak_verify_submit_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch,
                                   const void* d_commitments, const void* d_proofs, size_t proof_len, const void* d_r) {
-  if (!c || !ps || !plan || plan->device != c->device || ps->ctx->device != c->device) return ZKGPU_EINVAL;
+  if (!whole_proof_args_ok(c, ps, plan)) return ZKGPU_EINVAL;
   if (batch == 0 || !d_commitments || !d_proofs || batch >= (1ull << 24)) return ZKGPU_EINVAL;
-  {
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    if (c->pending) return ZKGPU_EINVAL;
-    if (!proof_len_fits(plan->dev.sh, proof_len)) {     // wrong length for this statement: every proof is Err
-      std::vector<uint8_t> z((batch + 7) / 8, 0);
-      c->dep_event = nullptr;
-      park_sync_result(c, ZKGPU_OK, z.data(), batch);
-      return ZKGPU_OK;
-    }
-  }
-  std::lock_guard<std::recursive_mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  return cloak_verify_gpu_enqueue(c, ps, plan, batch, (const uint32_t*)d_commitments, (const uint8_t*)d_proofs,
-                                  (const uint32_t*)d_r, proof_len);
-}
-
-namespace {
-// sizes the context's workspace for a whole-proof batch of `batch` statements of the plan's shape without launching anything
-// (every buffer the pipeline would need: the ensure() calls of the enqueue path, run dry)
-int cloak_reserve(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* plan, size_t batch, size_t proof_len) {
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   if (c->pending) return ZKGPU_EINVAL;
   DeviceGuard g(c->device);
-  c->reserve_only = true;
-  static const uint32_t dummy[4] = {0, 0, 0, 0};        // (never dereferenced: nothing is launched)
-  const int rc = cloak_verify_gpu_enqueue(c, ps, plan, batch, dummy, (const uint8_t*)dummy, dummy, proof_len);
-  c->reserve_only = false;
-  c->last.valid = false;
-  return rc;
+  return whole_proof_enqueue(c, ps, plan, batch, (const uint32_t*)d_commitments, (const uint8_t*)d_proofs, (const uint32_t*)d_r, proof_len);
 }
-}  // namespace
 
 int zkgpu_verify_batch_ps_submit_dev(zkgpu_ctx* c, const zkgpu_pointset* ps, size_t batch, const void* d_dyn_scalars,
                                      const void* d_dyn_points, const void* d_dyn_offsets, size_t n_dyn,
@@ -3326,22 +3355,19 @@ int draw_r_launch(zkgpu_ctx* c, hipStream_t s, const uint8_t seed[32], uint64_t 
   return ZKGPU_OK;
 }
 
-// Verifier randomness of a whole-proof batch (cloak_verify_gpu_enqueue): the caller's, or (*d_r NULL) drawn here -- 32 bytes from
-// the OS per batch, expanded on the device into a buffer of this context's own that lives until the batch has been collected
-// (the failed groups' re-check and the ungrouped re-run of pipe_wait read it again).  Queued on the light stream, whose
-// kernels read r first.  A batch queued in pieces (enqueue_phase) draws with its first piece; the later ones find the same
-// bytes.  reserve_only: the buffer is sized, nothing is launched.  No randomness from the OS: the batch fails.
-int draw_r_if_none(zkgpu_ctx* c, uint32_t B, const uint32_t** d_r) {
-  const bool draws = !c->reserve_only && (c->enqueue_phase == zkgpu_ctx::ENQ_ALL || c->enqueue_phase == zkgpu_ctx::ENQ_FRONT);
+// Verifier randomness of a whole-proof batch (whole_proof_begin, once per batch): the caller's, or (*d_r NULL) drawn here -- 32
+// bytes from the OS per batch, expanded on the device into a buffer of this context's own that lives until the batch has been
+// collected (the failed groups' re-check and the ungrouped re-run of pipe_wait read it again).  Queued on the light stream,
+// whose kernels read r first.  No randomness from the OS: the batch fails.  caller_seed: the caller's r was itself drawn
+// from that seed (a lane's coal_r: session.hpp), else NULL; c->r_seed reads the seed of either draw, zero for an r brought along.
+int draw_r_if_none(zkgpu_ctx* c, uint32_t B, const uint32_t** d_r, const uint8_t* caller_seed) {
   if (*d_r) {
-    if (draws) memset(c->r_seed, 0, sizeof c->r_seed);
+    if (caller_seed) memcpy(c->r_seed, caller_seed, sizeof c->r_seed); else memset(c->r_seed, 0, sizeof c->r_seed);
     return ZKGPU_OK;
   }
   TRY(ensure(c, c->r_draw, (size_t)B * 64));
-  if (draws) {
-    if (!os_random(c->r_seed, sizeof c->r_seed)) { memset(c->r_seed, 0, sizeof c->r_seed); c->last_error = "getrandom failed"; return ZKGPU_EINVAL; }
-    TRY(draw_r_launch(c, c->stream_l, c->r_seed, 0, B, c->r_draw.p));
-  }
+  if (!os_random(c->r_seed, sizeof c->r_seed)) { memset(c->r_seed, 0, sizeof c->r_seed); c->last_error = "getrandom failed"; return ZKGPU_EINVAL; }
+  TRY(draw_r_launch(c, c->stream_l, c->r_seed, 0, B, c->r_draw.p));
   *d_r = (const uint32_t*)c->r_draw.p;
   return ZKGPU_OK;
 }
@@ -3626,7 +3652,7 @@ int mixed_enqueue(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_plan* cons
     c->last.mixed = true; c->last.mx_groups = c->last.mx_stmts = 0;
     return ZKGPU_OK;
   }
-  // general shapes (no generator tables, forced window width): synchronous, as cloak_verify_gpu_enqueue
+  // general shapes (no generator tables, forced window width): synchronous, as whole_proof_begin
   HIP_TRY(c, hipStreamSynchronize(L));
   TRY(run_sync_and_park(c, job, ps));
   memset(c->mx_stats, 0, sizeof c->mx_stats);        // (the call has run: no groups on this route)
@@ -3653,9 +3679,7 @@ int zkgpu_r1cs_verify_mixed(zkgpu_ctx* c, const zkgpu_pointset* ps, zkgpu_cloak_
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   DeviceGuard g(c->device);
   TRY(mixed_enqueue(c, ps, plans, n_plans, batch, plan_index, commitments, proofs, proof_offsets, r_bytes));
-  const int rc = pipe_wait(c, accept_bitmap);
-  if (rc != ZKGPU_OK) memset(accept_bitmap, 0, (batch + 7) / 8);
-  return rc;
+  return pipe_wait_or_zero(c, batch, accept_bitmap);
 }
 
 // Test hook zkgpu_debug_read: the context's DECODE counters, or an intermediate buffer (debug_read_buffers)
