@@ -625,7 +625,7 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * (format | ZKGPU_TXFORMAT_RETURN_LOG | K << ZKGPU_TXFORMAT_LOG_SHIFT, 1 <= K <= 255): the second third of VerifiedTx -- the
  * Input(id) / Output(id) entries of every accepted transaction's LOG, i.e. the contract IDs a node removes from and inserts
  * into its UTXO set when it applies the block.  ZKGPU_EINVAL: the flag without ZKGPU_TXFORMAT_RETURN_IDS (0x801), the flag
- * with K = 0, bits 16 .. 23 without the flag, any bit from 0x1000 to 0x8000, any bit from 24 up.
+ * with K = 0, bits 16 .. 23 without the flag, 0x1000, 0x4000, 0x8000, any bit from 24 up (0x2000 is the next flag).
  *
  *   !!  WITH THIS FLAG SET, THE `status` ARGUMENT OF zkgpu_tx_verify_batch AND zkgpu_tx_verify_wait POINTS AT       !!
  *   !!  batch * (33 + 1 + 33 * K) BYTES, NOT 33 * batch AND NOT batch.  A caller that sets the flag and passes      !!
@@ -651,11 +651,42 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * copy is an error of the call. */
 #define ZKGPU_TXFORMAT_RETURN_LOG 2048   /* 0x800; only together with ZKGPU_TXFORMAT_RETURN_IDS */
 #define ZKGPU_TXFORMAT_LOG_SHIFT 16      /* bits 16..23 of the format: K, the log entries kept per transaction, 1..255 */
+/* A fifth FLAG, only TOGETHER WITH ZKGPU_TXFORMAT_RETURN_IDS and never beside ZKGPU_TXFORMAT_SIGN_ON_DEVICE (valid: {1, 2} x
+ * {0, 0x100} x 0x400 x {0, 0x800 | K << 16} x 0x2000; ZKGPU_EINVAL: alone, beside format 0, without 0x400, beside 0x200): the
+ * FIRST HALF of upstream's Tx::verify alone -- Tx::precompute(), which runs the VM and yields the header, the transaction ID
+ * and the log with nothing cryptographic checked.  A node uses it to drop transactions it already knows, to check a block's
+ * transaction root against its header and to order a mempool BEFORE it pays for verification.
+ *
+ *   !!  WITH THIS FLAG SET THE CALL VERIFIES NOTHING.  THE ACCEPT BITMAP IS WRITTEN AND IS ALL ZERO.  STATUS 3         !!
+ *   !!  (ZKGPU_TXSTATUS_PRECOMPUTED) IS NOT A VERDICT: A TRANSACTION WITH A FORGED SIGNATURE, AN UNDECODABLE KEY, A    !!
+ *   !!  CORRUPT PROOF OR A COMMITMENT THAT IS NO POINT READS 3 WITH ITS ID LIKE A VALID ONE.  NEVER TREAT 3 AS 0.      !!
+ *
+ * The call reads the same bytes, and `status` is laid out exactly as ZKGPU_TXFORMAT_RETURN_IDS (and ZKGPU_TXFORMAT_RETURN_LOG
+ * with its K) lay it out: batch status bytes, 32 * batch bytes of IDs, then the log records.  Status bytes under the flag:
+ *   3   the VM ran to the end; beside it stand the transaction ID and, with 0x800, the log record (count, kinds, IDs and the
+ *       "more than K entries" rule as documented there).  NOT examined: the signature equation, the keys' encodings, the proof
+ *       bytes, the commitments' encodings.  For every transaction the same format WITHOUT this flag accepts, the ID and the
+ *       record are byte for byte what that call writes beside status 0; a transaction that call rejects with 17 .. 21 still
+ *       reads 3 here.
+ *   2   outside the subset, as always.
+ *   1 (format 1) / 16 (format 2), and 21 for a signature scalar s that is not canonical: what the host VM alone finds,
+ *       reported exactly as a verifying call of the same base format reports it.  17 .. 20 never appear; 0 is never written.
+ * Beside anything but 3 the ID and the record are zero.  Fail-closed: the areas are zeroed before the call starts and again on
+ * any error; after an error every transaction inside the subset reads 1 and no ID and no record is written.  status == NULL
+ * stays legal: the call then only zeroes the bitmap.  On the device nothing runs but the hashing stage, and only beside
+ * ZKGPU_TXFORMAT_HASH_ON_DEVICE (one tape up, one hashing launch, the log's gather when a log is asked for, the copies down);
+ * without that flag the device is not touched.  A submitted precompute-only call keeps what it was QUEUED under -- the flag,
+ * the base format (1 or 2: which codes it reports) and ZKGPU_TXFORMAT_HASH_ON_DEVICE, like its layout -- whatever the format
+ * says when its round starts; a round never holds precompute-only and verifying calls together, nor precompute-only calls
+ * queued under different base formats or hashing switches.  (A submitted VERIFYING call keeps its layout alone, as it always
+ * has: base format and device switches are those in force when its round starts.) */
+#define ZKGPU_TXFORMAT_PRECOMPUTE_ONLY 8192   /* 0x2000; only together with ZKGPU_TXFORMAT_RETURN_IDS, never with ..._SIGN_ON_DEVICE */
 #define ZKGPU_TXLOG_INPUT 1
 #define ZKGPU_TXLOG_OUTPUT 2
 #define ZKGPU_TXSTATUS_ACCEPTED 0
 #define ZKGPU_TXSTATUS_REJECTED 1                 /* rejected, reason not available (V1 format, or any error path) */
 #define ZKGPU_TXSTATUS_OUTSIDE_SUBSET 2
+#define ZKGPU_TXSTATUS_PRECOMPUTED 3              /* ZKGPU_TXFORMAT_PRECOMPUTE_ONLY alone: the VM ran to the end, ID and log computed, NOTHING verified */
 #define ZKGPU_TXSTATUS_TX_INVALID 16              /* the transaction itself: wire format, time bounds, program / VM error (host) */
 #define ZKGPU_TXSTATUS_PROOF_FORMAT 17            /* R1CSProof malformed: length, version byte, non-canonical scalar, forbidden identity */
 #define ZKGPU_TXSTATUS_PROOF_POINT 18             /* a commitment or proof point is not a ristretto255 encoding */

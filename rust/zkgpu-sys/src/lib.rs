@@ -28,11 +28,13 @@ pub const ZKGPU_TXFORMAT_SIGN_ON_DEVICE: c_int = 512;
 pub const ZKGPU_TXFORMAT_RETURN_IDS: c_int = 1024;
 pub const ZKGPU_TXFORMAT_RETURN_LOG: c_int = 2048;
 pub const ZKGPU_TXFORMAT_LOG_SHIFT: c_int = 16;
+pub const ZKGPU_TXFORMAT_PRECOMPUTE_ONLY: c_int = 8192;
 pub const ZKGPU_TXLOG_INPUT: c_int = 1;
 pub const ZKGPU_TXLOG_OUTPUT: c_int = 2;
 pub const ZKGPU_TXSTATUS_ACCEPTED: c_int = 0;
 pub const ZKGPU_TXSTATUS_REJECTED: c_int = 1;
 pub const ZKGPU_TXSTATUS_OUTSIDE_SUBSET: c_int = 2;
+pub const ZKGPU_TXSTATUS_PRECOMPUTED: c_int = 3;
 pub const ZKGPU_TXSTATUS_TX_INVALID: c_int = 16;
 pub const ZKGPU_TXSTATUS_PROOF_FORMAT: c_int = 17;
 pub const ZKGPU_TXSTATUS_PROOF_POINT: c_int = 18;

@@ -205,6 +205,8 @@ pub struct GpuVerifier {
     return_ids: AtomicBool,
     /// ... and `ZKGPU_TXFORMAT_RETURN_LOG` with this window K (0: no): 33 + 1 + 33 K bytes per transaction
     log_k: AtomicUsize,
+    /// ... and `ZKGPU_TXFORMAT_PRECOMPUTE_ONLY`: calls verify nothing, and only `precompute` makes them
+    precompute_only: AtomicBool,
 }
 
 /// One `Input(id)` / `Output(id)` entry of an accepted transaction's log: the contract a node removes from, or inserts into,
@@ -213,6 +215,19 @@ pub struct GpuVerifier {
 pub enum TxLogEntry {
     Input([u8; 32]),
     Output([u8; 32]),
+}
+
+/// What `precompute` says of one transaction: the reference's `Tx::precompute()` -- the VM has run, NOTHING is verified.
+#[derive(Clone, Debug, PartialEq, Eq)]
+pub enum PrecomputedTx {
+    /// The VM ran to the end: the transaction ID and, if the format asks for the log, its `Input` / `Output` entries.
+    /// NOT a verdict and never a `VerifiedTx`: the signature, the keys, the proof and the commitments were not looked at.
+    Computed { id: [u8; 32], log: Option<TxLog> },
+    /// outside the payment subset: the caller's own VM must run it
+    OutsideSubset,
+    /// what the host VM alone finds -- the wire format, the time bounds, the program, a signature scalar that is not
+    /// canonical -- with the reason if the format carries reasons
+    Invalid(Option<TxReject>),
 }
 
 /// The log entries `verify_txs_with_log` hands back beside an accepted transaction.
@@ -276,7 +291,7 @@ impl GpuVerifier {
         match built {
             Ok((ps, v, warned)) => {
                 let warning = if warned { Some(text(unsafe { sys::zkgpu_verifier_last_error(v) })) } else { None };
-                Ok(GpuVerifier { ctx, gens: Generators { ps, capacity: gens_capacity }, v, warning, return_ids: AtomicBool::new(false), log_k: AtomicUsize::new(0) })
+                Ok(GpuVerifier { ctx, gens: Generators { ps, capacity: gens_capacity }, v, warning, return_ids: AtomicBool::new(false), log_k: AtomicUsize::new(0), precompute_only: AtomicBool::new(false) })
             }
             Err(e) => {
                 unsafe { sys::zkgpu_destroy(ctx) };
@@ -373,6 +388,7 @@ impl GpuVerifier {
         self.return_ids.store(format & sys::ZKGPU_TXFORMAT_RETURN_IDS != 0, Ordering::SeqCst);
         let k = if format & sys::ZKGPU_TXFORMAT_RETURN_LOG != 0 { ((format >> sys::ZKGPU_TXFORMAT_LOG_SHIFT) & 255) as usize } else { 0 };
         self.log_k.store(k, Ordering::SeqCst);
+        self.precompute_only.store(format & sys::ZKGPU_TXFORMAT_PRECOMPUTE_ONLY != 0, Ordering::SeqCst);
         Ok(())
     }
 
@@ -429,6 +445,63 @@ impl GpuVerifier {
         self.set_tx_format(base | hash | sign | sys::ZKGPU_TXFORMAT_RETURN_IDS | log)
     }
 
+    /// `ZKGPU_TXFORMAT_PRECOMPUTE_ONLY` beside `ZKGPU_TXFORMAT_RETURN_IDS` (and, `k` > 0, `ZKGPU_TXFORMAT_RETURN_LOG` with that
+    /// window): from here on the verifier's transaction calls VERIFY NOTHING and are made through `precompute`, the
+    /// reference's `Tx::precompute()`; `verify_txs` and `submit_txs` refuse until a verifying format is enabled again.
+    /// `hash_on_device`: the IDs are hashed on the device (the only device work such a call has).
+    pub fn enable_recollected_tx_format_precompute_only(&self, k: usize, with_reasons: bool, hash_on_device: bool) -> Result<(), Error> {
+        if k > 255 {
+            return Err(Error::InvalidArgument("the log window is 0 (no log) or 1 ..= 255 entries".into()));
+        }
+        let base = if with_reasons { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS } else { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1 };
+        let hash = if hash_on_device { sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE } else { 0 };
+        let log = if k > 0 { sys::ZKGPU_TXFORMAT_RETURN_LOG | ((k as c_int) << sys::ZKGPU_TXFORMAT_LOG_SHIFT) } else { 0 };
+        self.set_tx_format(base | hash | sys::ZKGPU_TXFORMAT_RETURN_IDS | log | sys::ZKGPU_TXFORMAT_PRECOMPUTE_ONLY)
+    }
+
+    /// The reference's `Tx::precompute()` over `Tx::encode()` bytes, after `enable_recollected_tx_format_precompute_only`:
+    /// per transaction its ID and log, with NOTHING verified.  A node drops what it already knows, checks a block's
+    /// transaction root and orders its mempool with these, and only then pays for `verify_txs` under a verifying format.
+    /// `PrecomputedTx::Computed` must never be turned into a `VerifiedTx`.
+    pub fn precompute(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<PrecomputedTx>, Error> {
+        if !self.precompute_only.load(Ordering::SeqCst) {
+            return Err(Error::InvalidArgument("precompute: enable_recollected_tx_format_precompute_only first".into()));
+        }
+        let n = txs.len();
+        if n == 0 {
+            return Ok(Vec::new());
+        }
+        let mut blob = Vec::with_capacity(txs.iter().map(|t| t.len()).sum());
+        let mut offs = Vec::with_capacity(n + 1);
+        offs.push(0u64);
+        for t in txs {
+            blob.extend_from_slice(t);
+            offs.push(blob.len() as u64);
+        }
+        let log_k = self.log_k.load(Ordering::SeqCst);
+        let mut bitmap = vec![0u8; (n + 7) / 8];
+        let mut status = vec![1u8; Self::tx_status_len(n, true, log_k)];
+        check(
+            unsafe {
+                sys::zkgpu_tx_verify_batch(self.v, n, blob.as_ptr(), offs.as_ptr(), host_threads as c_int, bitmap.as_mut_ptr(), status.as_mut_ptr())
+            },
+            self.err(),
+        )?;
+        let per = 1 + 33 * log_k;
+        Ok((0..n)
+            .map(|i| match status[i] as c_int {
+                sys::ZKGPU_TXSTATUS_PRECOMPUTED => {
+                    let mut id = [0u8; 32];
+                    id.copy_from_slice(&status[n + 32 * i..n + 32 * i + 32]);
+                    let log = if log_k == 0 { None } else { Some(Self::tx_log_of(&status[33 * n + per * i..33 * n + per * (i + 1)], log_k)) };
+                    PrecomputedTx::Computed { id, log }
+                }
+                sys::ZKGPU_TXSTATUS_OUTSIDE_SUBSET => PrecomputedTx::OutsideSubset,
+                _ => PrecomputedTx::Invalid(TxReject::from_status(status[i])),
+            })
+            .collect())
+    }
+
     /// status array of a call of `n` transactions: `n` bytes, `33 * n` under `ZKGPU_TXFORMAT_RETURN_IDS`, and
     /// `(33 + 1 + 33 * log_k) * n` under `ZKGPU_TXFORMAT_RETURN_LOG` with window `log_k`
     fn tx_status_len(n: usize, ids: bool, log_k: usize) -> usize {
@@ -449,22 +522,26 @@ impl GpuVerifier {
                 if log_k == 0 || verdicts[i].0 != TxVerdict::Accepted {
                     return None;
                 }
-                let rec = &status[33 * n + per * i..33 * n + per * (i + 1)];
-                let count = rec[0] as usize;
-                // (count saturates at 255: a record that lists its entries has no kind byte of 0)
-                if count > log_k || (count > 0 && rec[1] == 0) {
-                    return Some(TxLog::MoreThanWindow(count));
-                }
-                let entries = (0..count)
-                    .map(|j| {
-                        let mut id = [0u8; 32];
-                        id.copy_from_slice(&rec[1 + log_k + 32 * j..1 + log_k + 32 * j + 32]);
-                        if rec[1 + j] as c_int == sys::ZKGPU_TXLOG_INPUT { TxLogEntry::Input(id) } else { TxLogEntry::Output(id) }
-                    })
-                    .collect();
-                Some(TxLog::Entries(entries))
+                Some(Self::tx_log_of(&status[33 * n + per * i..33 * n + per * (i + 1)], log_k))
             })
             .collect()
+    }
+
+    /// one log record of window `log_k` (count | kind[K] | id[K][32]) that stands beside an ID
+    fn tx_log_of(rec: &[u8], log_k: usize) -> TxLog {
+        let count = rec[0] as usize;
+        // (count saturates at 255: a record that lists its entries has no kind byte of 0)
+        if count > log_k || (count > 0 && rec[1] == 0) {
+            return TxLog::MoreThanWindow(count);
+        }
+        let entries = (0..count)
+            .map(|j| {
+                let mut id = [0u8; 32];
+                id.copy_from_slice(&rec[1 + log_k + 32 * j..1 + log_k + 32 * j + 32]);
+                if rec[1 + j] as c_int == sys::ZKGPU_TXLOG_INPUT { TxLogEntry::Input(id) } else { TxLogEntry::Output(id) }
+            })
+            .collect();
+        TxLog::Entries(entries)
     }
 
     /// status bytes (+ the ID area, if the call had one) and bitmap -> a verdict per transaction, and beside `Accepted` its ID
@@ -500,6 +577,9 @@ impl GpuVerifier {
     /// `enable_recollected_tx_format_returning_log`, `None` beside every other verdict: the `VerifiedTx.log` of the reference
     /// without its header entry.
     pub fn verify_txs_with_log(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<(TxVerdict, Option<[u8; 32]>, Option<TxLog>)>, Error> {
+        if self.precompute_only.load(Ordering::SeqCst) {
+            return Err(Error::InvalidArgument("verify_txs: the format in force is precompute-only, nothing would be verified".into()));
+        }
         let n = txs.len();
         if n == 0 {
             return Ok(Vec::new());
@@ -530,6 +610,9 @@ impl GpuVerifier {
     /// call is queued and this returns; an engine thread of the verifier merges whatever is queued into rounds (dynamic
     /// batching), so that eight threads handing over 1024 transactions each see the rate of calls of several thousand.
     pub fn submit_txs(&self, txs: &[&[u8]], host_threads: i32) -> Result<TxCall<'_>, Error> {
+        if self.precompute_only.load(Ordering::SeqCst) {
+            return Err(Error::InvalidArgument("submit_txs: the format in force is precompute-only, nothing would be verified".into()));
+        }
         let n = txs.len();
         if n == 0 {
             return Err(Error::InvalidArgument("submit_txs: no transactions".into()));

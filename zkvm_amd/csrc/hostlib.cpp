@@ -1696,7 +1696,7 @@ extern "C" int zkhost_txcall_log_selftest(int kind, size_t K, size_t k_b, size_t
 }
 
 // ---- the layout header itself (tx_out.hpp), for the CPU test.  op 0: the format word in[0] -> out: valid, base, hash, sign, ids,
-// ---- K.  Ops 1 .. 4 take a layout in[0] = ids, in[1] = K and a batch in[2]: op 1 -> out: bytes(batch), the offsets of the status
+// ---- K, precompute-only.  Ops 1 .. 4 take a layout in[0] = ids, in[1] = K and a batch in[2]: op 1 -> out: bytes(batch), the offsets of the status
 // ---- byte / ID / record of transaction in[3] and of a piece's ID / record areas (-1: not there), the piece's window; op 2 begin,
 // ---- 3 nothing-in-the-subset, 4 fail-closed over bitmap and area (either may be NULL).  op 5, a round's hand-out: in[0] calls,
 // ---- in[1] ok, then (ids, K, batch) per call; bitmap / area hold the ROUND's bits / status bytes, out_bits / out_area the
@@ -1706,8 +1706,8 @@ extern "C" int zkhost_tx_out_layout(int op, const int64_t* in, uint8_t* bitmap, 
   const auto layout = [](const int64_t* q) { TxOutLayout l; l.ids = q[0] != 0; l.log_k = (size_t)q[1]; return l; };
   if (op == 0) {
     TxFormat f;
-    const int64_t r[6] = {TxFormat::of((int)in[0], &f), f.base, f.hash_on_device, f.sign_on_device, f.out.ids, (int64_t)f.out.log_k};
-    std::copy(r, r + 6, out);
+    const int64_t r[7] = {TxFormat::of((int)in[0], &f), f.base, f.hash_on_device, f.sign_on_device, f.out.ids, (int64_t)f.out.log_k, f.precompute_only};
+    std::copy(r, r + 7, out);
     return 0;
   }
   if (op == 5) {
@@ -1776,4 +1776,108 @@ extern "C" long long zkhost_tx_prepare_logged_compare(const uint8_t* txs, const 
   }
   if (lockstep_groups) *lockstep_groups = same_shape_groups;
   return differ;
+}
+
+// ---- the hash tape walked by dependency level (tx_hash_levels.hpp) on the CPU: `count` transactions as ONE chunk the way a
+// ---- precompute-only call tapes it (no job run on the host), the side table, and the level interpreter -- the function
+// ---- k_tx_hash_levels runs per lane -- level by level and lane by lane with `lanes` lanes per transaction, beside tx_hash_run
+// ---- over the same block.  Out: status per transaction; the block and the table (words; sizes[0], sizes[1]: how many, sizes[2]:
+// ---- slots); per transaction (zero where not on the tape) the ID the level walk left and the one tx_hash_run left;
+// ---- sizes[3]: slot words on which the two differ (must be 0).
+// ---- -> transactions on the tape, or -1 a plan the tape cannot hold, -2 the block fails hash_tape_check, -3 an output too small,
+// ---- -4 no side table
+#include "tx_hash_levels.hpp"
+extern "C" long long zkhost_tx_hash_levels(const uint8_t* txs, const uint64_t* offs, size_t count, int threads, uint32_t lanes, uint8_t* status,
+                                           uint32_t* block, size_t block_cap, uint32_t* table, size_t table_cap, uint64_t* sizes,
+                                           uint8_t* txid_levels, uint8_t* txid_run) {
+  using namespace zk::zkvm;
+  TxHashTape tape;
+  std::vector<TxStatement> st(count);
+  std::atomic<int> bad{0};
+  tape.reset(count);
+  tx_groups_of_eight(count, threads, [&](size_t i) { return std::make_pair(txs + offs[i], (size_t)(offs[i + 1] - offs[i])); },
+                     [&](const uint8_t** p, const size_t* l, size_t first, size_t n) {
+                       if (!tx_prepare_many_taped(p, l, &st[first], n, tape, first, NO_PROTO)) bad = 1;
+                     });
+  for (size_t i = 0; i < count; ++i) status[i] = (uint8_t)st[i].status;
+  std::memset(txid_levels, 0, 32 * count); std::memset(txid_run, 0, 32 * count);
+  for (int q = 0; q < 4; ++q) sizes[q] = 0;
+  if (bad) return -1;
+  tape.finish(threads);
+  const HashTapeHead& h = tape.head();
+  if (!hash_tape_check(tape.block(), h.words)) return -2;
+  std::vector<uint32_t> tab, protos, sl, ids, lsl, lids;
+  std::vector<uint8_t> labels;
+  if (!tx_hash_levels_table(tape.block(), tab)) return -4;
+  sizes[0] = h.words; sizes[1] = tab.size(); sizes[2] = h.n_slots;
+  if (h.words > block_cap || tab.size() > table_cap) return -3;
+  std::memcpy(block, tape.block(), 4 * (size_t)h.words);
+  std::memcpy(table, tab.data(), 4 * tab.size());
+  hash_tape_constants(protos, labels);
+  hash_tape_run_host(tape.block(), protos, labels, sl, ids);
+  if (!hash_tape_run_levels_host(tape.block(), protos, labels, lanes, lsl, lids)) return -4;
+  for (size_t w = 0; w < sl.size(); ++w) sizes[3] += sl[w] != lsl[w];
+  for (size_t t = 0; t < tape.n_tx(); ++t) {
+    std::memcpy(txid_levels + 32 * tape.position(t), &lids[8 * t], 32);
+    std::memcpy(txid_run + 32 * tape.position(t), &ids[8 * t], 32);
+  }
+  return (long long)tape.n_tx();
+}
+
+// ---- a PRECOMPUTE-ONLY call (TxDevice::precompute: ZKGPU_TXFORMAT_PRECOMPUTE_ONLY) on the CPU: TxCall over a stand-in that
+// ---- hashes (hashing = 1: the tapes interpreted as above, hash_fail_at as there) or not, with reasons (format 2) or without, the
+// ---- caller handed IDs and, K > 0, the log -- and that COUNTS every key, proof and signature operation it is asked for: there
+// ---- must be none.  status is laid out by tx_out.hpp (33 + (K ? 1 + 33 K : 0) bytes per transaction), begun and fail-closed as
+// ---- session.hpp does it.  out[0] chunks, out[1] key / proof / signature operations asked for (must be 0), out[2] transactions
+// ---- the host's pass hashed, out[3] IDs the stand-in's hashing stage produced, out[4] transactions that left with
+// ---- PRECOMPUTED, out[5] something lay behind the status bytes of a failed call before it was fail-closed (must be 0)
+namespace {
+class HostPrecomputeTxDevice : public HostHashingTxDevice {
+ public:
+  HostPrecomputeTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, uint32_t seed, bool hashing, bool reasons, int hash_fail_at, const TxFormat& format)
+      : HostHashingTxDevice(txs, offs, batch, nullptr, seed, hash_fail_at, -1, format), hashing_(hashing), reasons_(reasons) {}
+  bool precompute() const override { return true; }
+  bool hashes() const override { return hashing_; }
+  bool reasons() const override { return reasons_; }
+  int keys_enqueue(int, const uint8_t*, const uint8_t*, const uint64_t*, size_t) override { return asked(); }
+  int keys_collect(int, uint8_t*, uint8_t*, uint8_t*) override { return asked(); }
+  int proofs_stage(size_t, size_t, const TxProofSource*, int, void**, std::string*) override { return asked(); }
+  int proofs_start(size_t, void*) override { return asked(); }
+  int proofs_finish(void*, uint8_t*, uint8_t*) override { return asked(); }
+  void proofs_release(void*) override { (void)asked(); }
+  int sigs_enqueue(int, size_t, const uint8_t*, const uint8_t*, const uint64_t*, const uint8_t*, const SigChain*) override { return asked(); }
+  int sigs_collect(int, uint8_t*, uint8_t*) override { return asked(); }
+  uint64_t stage_ops() const { return stage_ops_; }
+
+ private:
+  int asked() { ++stage_ops_; return -1; }
+  const bool hashing_, reasons_;
+  std::atomic<uint64_t> stage_ops_{0};
+};
+}  // namespace
+
+extern "C" int zkhost_txcall_precompute_selftest(int hashing, int reasons, size_t K, size_t batch, const uint8_t* txs, const uint64_t* offs, int host_threads,
+                                                 size_t chunk, uint32_t delay_seed, int hash_fail_at, int n_slots, uint8_t* accept_bitmap, uint8_t* status,
+                                                 uint64_t* out) {
+  for (int q = 0; q < 6; ++q) out[q] = 0;
+  if (K > 255 || !status || !accept_bitmap) return -1;
+  TxFormat format;
+  format.base = reasons ? TXFORMAT_V1_REASONS : TXFORMAT_V1;
+  format.hash_on_device = hashing != 0; format.precompute_only = true;
+  format.out.ids = true; format.out.log_k = K;
+  HostPrecomputeTxDevice dev(txs, offs, batch, delay_seed, hashing != 0, reasons != 0, hash_fail_at, format);
+  format.out.begin(accept_bitmap, status, batch);
+  std::vector<TxStatement> store;
+  int rc;
+  {
+    TxCall call(dev, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, accept_bitmap, status, n_slots);
+    out[0] = call.n_chunks();
+    rc = call.run();
+    out[2] = call.n_host_hashed();
+    out[4] = rc == 0 ? call.n_precomputed() : 0;
+  }
+  out[1] = dev.stage_ops(); out[3] = dev.hashed();
+  for (size_t i = batch; rc != 0 && i < format.out.bytes(batch); ++i) if (status[i]) out[5] = 1;
+  if (rc != 0) format.out.fail_closed(accept_bitmap, status, batch);
+  return rc;
 }

@@ -15,6 +15,7 @@
 #include "comm_frame.hpp"
 #include "tx_call.hpp"
 #include "tx_hash_kernels.hpp"
+#include "tx_hash_levels.hpp"
 #include "tx_sig_rows.hpp"
 #include "zkvm_tx.hpp"
 
@@ -123,6 +124,11 @@ struct zkgpu_verifier {
     hipEvent_t ev_ids = nullptr;                        // (a chain beside the flag: recorded behind k_tx_hash, what its challenge kernel waits for)
     std::vector<uint32_t> log_table;
     Buffer d_tab, d_log;
+    // a precompute-only call whose tape is walked by dependency level (tx_hash_levels.hpp): the side table on its way up
+    void* h_levels = nullptr;
+    size_t h_levels_cap = 0;
+    std::vector<uint32_t> levels_table;
+    Buffer d_levels;
   };
   TxHashStage tx_hash[2];
   Buffer tx_hash_const;
@@ -160,6 +166,10 @@ struct zkgpu_verifier {
     int state = 0, rc = 0;                              // 0 queued, 1 in a round, 2 done
     std::chrono::steady_clock::time_point arrived;      // (the engine lets a small queue wait a little while a round is running)
     zk::zkvm::TxOutLayout layout;                       // of its status argument, as the format said when it was SUBMITTED
+    // ... and its KIND: 0 a verifying call (base format and device switches are the round's, read when it starts, as they always
+    // were); a precompute-only call: ZKGPU_TXFORMAT_PRECOMPUTE_ONLY | the base format | ZKGPU_TXFORMAT_HASH_ON_DEVICE as the
+    // format said them when it was submitted.  A round holds calls of ONE kind and, precompute-only, runs under it
+    int kind = 0;
     std::vector<uint8_t> bits, area;                    // its bitmap; its status argument, layout.bytes(batch), as wait will copy it out
   };
   std::mutex tx_mu;
@@ -404,7 +414,7 @@ int zkgpu_verifier_create(zkgpu_ctx* ctx, const zkgpu_pointset* ps, size_t gens_
   batches_in_flight = std::min(batches_in_flight, 1 + MAX_FORKS);
   zkgpu_verifier* v = new zkgpu_verifier();
   v->root = ctx; v->ps = ps; v->gens_capacity = gens_capacity;
-  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; ctx->tx_signed_on_device = 0; ctx->tx_logged_on_device = 0; }
+  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; ctx->tx_signed_on_device = 0; ctx->tx_logged_on_device = 0; ctx->tx_precomputed = 0; }
   v->lanes.push_back(ctx);
   v->lanes_requested = batches_in_flight;
   // A lane is worth having only if its light stream -- the latency-bound kernels of its batch: transcript, Horner chains,
@@ -487,8 +497,9 @@ void zkgpu_verifier_destroy(zkgpu_verifier* v) {
       if (hs.h_out) (void)hipHostFree(hs.h_out);
       if (hs.h_tab) (void)hipHostFree(hs.h_tab);
       if (hs.h_log) (void)hipHostFree(hs.h_log);
+      if (hs.h_levels) (void)hipHostFree(hs.h_levels);
       if (hs.ev_ids) (void)hipEventDestroy(hs.ev_ids);
-      for (Buffer* b : {&hs.d_tape, &hs.d_slots, &hs.d_txid, &hs.d_tab, &hs.d_log}) if (b->p) (void)hipFree(b->p);
+      for (Buffer* b : {&hs.d_tape, &hs.d_slots, &hs.d_txid, &hs.d_tab, &hs.d_log, &hs.d_levels}) if (b->p) (void)hipFree(b->p);
     }
     if (v->tx_hash_const.p) (void)hipFree(v->tx_hash_const.p);
     for (auto& ss : v->tx_sig) {
@@ -1734,7 +1745,8 @@ static_assert(zk::zkvm::TXFORMAT_V1 == ZKGPU_TXFORMAT_RECOLLECTED_V1 && zk::zkvm
               zk::zkvm::TXFORMAT_HASH_ON_DEVICE == ZKGPU_TXFORMAT_HASH_ON_DEVICE && zk::zkvm::TXFORMAT_SIGN_ON_DEVICE == ZKGPU_TXFORMAT_SIGN_ON_DEVICE &&
               zk::zkvm::TXFORMAT_RETURN_IDS == ZKGPU_TXFORMAT_RETURN_IDS && zk::zkvm::TXFORMAT_RETURN_LOG == ZKGPU_TXFORMAT_RETURN_LOG &&
               zk::zkvm::TXFORMAT_LOG_SHIFT == ZKGPU_TXFORMAT_LOG_SHIFT && zk::zkvm::TXOUT_REJECTED == ZKGPU_TXSTATUS_REJECTED &&
-              zk::zkvm::TXOUT_OUTSIDE_SUBSET == ZKGPU_TXSTATUS_OUTSIDE_SUBSET, "tx_out.hpp restates the format's flags and two status bytes");
+              zk::zkvm::TXOUT_OUTSIDE_SUBSET == ZKGPU_TXSTATUS_OUTSIDE_SUBSET && zk::zkvm::TXFORMAT_PRECOMPUTE_ONLY == ZKGPU_TXFORMAT_PRECOMPUTE_ONLY &&
+              zk::zkvm::TXOUT_PRECOMPUTED == ZKGPU_TXSTATUS_PRECOMPUTED, "tx_out.hpp restates the format's flags and three status bytes");
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
   zk::zkvm::TxFormat f;
   if (!v || !zk::zkvm::TxFormat::of(format, &f)) return ZKGPU_EINVAL;     // (the rules: tx_out.hpp)
@@ -1810,6 +1822,13 @@ int tx_call_prepare(zkgpu_verifier* v, bool collect_lanes = true) {
   return ZKGPU_OK;
 }
 
+// transactions that left a precompute-only call with status 3, counted on the root context ("tx_precomputed")
+void tx_precomputed_count(zkgpu_verifier* v, size_t n) {
+  if (n == 0) return;
+  std::lock_guard<std::recursive_mutex> rl(v->root->mu);
+  v->root->tx_precomputed += n;
+}
+
 }  // namespace
 
 // The scheduling of a call -- chunks, stages, the staging thread and the calling thread -- is csrc/tx_call.hpp (TxCall); the
@@ -1835,13 +1854,17 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
     out.nothing_in_subset(status, batch);
     return ZKGPU_OK;
   }
-  TRY(tx_call_prepare(v));
+  // (ZKGPU_TXFORMAT_PRECOMPUTE_ONLY: nothing is verified, so no bit is ever set, and without a status argument there is nowhere to
+  // put what the call computes.  The stage contexts are made only for a call whose device hashes: its stream and buffers hang on one)
+  if (format.precompute_only && !status) return ZKGPU_OK;
+  if (!format.precompute_only || format.hash_on_device) TRY(tx_call_prepare(v));
   GpuTxDevice dev(v, 0, 0, format);
   int rc;
   try {
     TxCall call(dev, v->tx_statements, v->tx_statements_kept, batch, txs, tx_offsets, host_threads, v->tx_chunk, accept_bitmap, status);
     rc = call.run();
     if (rc != ZKGPU_OK) v->last_error = call.error_text();
+    else tx_precomputed_count(v, call.n_precomputed());
   } catch (const std::bad_alloc&) {
     v->last_error = "out of host memory while planning the transaction call";
     rc = ZKGPU_ENOMEM;
@@ -1923,7 +1946,9 @@ void tx_engine_main(zkgpu_verifier* v) {
         }
         fresh[set].reset(new TxRound());
         TxRound& r = *fresh[set];
-        while (!v->tx_queue.empty() && (r.calls.empty() || r.total + v->tx_queue.front()->batch <= v->tx_merge_max)) {
+        // (a round holds calls of ONE kind: a precompute-only call never shares a round with a verifying one)
+        while (!v->tx_queue.empty() && (r.calls.empty() || (r.total + v->tx_queue.front()->batch <= v->tx_merge_max &&
+                                                            v->tx_queue.front()->kind == r.calls.front()->kind))) {
           r.calls.push_back(v->tx_queue.front());
           r.total += r.calls.back()->batch;
           r.calls.back()->state = 1;
@@ -1942,6 +1967,11 @@ void tx_engine_main(zkgpu_verifier* v) {
       // writes beside a set bit; the round's device brings back what the widest of them asks for)
       TxFormat format = TxFormat::of_valid(v->tx_format.load());
       format.out = TxOutLayout();
+      // (the kind is the calls', as the layout is: a precompute-only round runs under the base format and the hashing switch its
+      // calls were queued under, whatever the format says by now, and never chains)
+      const int kind = r.calls.front()->kind;
+      format.precompute_only = kind != 0;
+      if (kind) { format.base = kind & 3; format.hash_on_device = (kind & TXFORMAT_HASH_ON_DEVICE) != 0; format.sign_on_device = false; }
       for (auto* p : r.calls) {
         p->bits.resize((p->batch + 7) / 8);
         p->area.resize(p->layout.bytes(p->batch));
@@ -1957,7 +1987,7 @@ void tx_engine_main(zkgpu_verifier* v) {
       if (format.base == 0) {
         std::fill(r.status.begin(), r.status.end(), (uint8_t)TX_UNSUPPORTED);       // no format enabled: nothing is inside the subset
       } else {
-        r.rc = tx_call_prepare(v, !active[0] && !active[1]);
+        r.rc = (!format.precompute_only || format.hash_on_device) ? tx_call_prepare(v, !active[0] && !active[1]) : ZKGPU_OK;
         if (r.rc == ZKGPU_OK) {
           try {
             r.dev.reset(new GpuTxDevice(v, set, (size_t)set * TxCall::RING, format));
@@ -1989,6 +2019,7 @@ void tx_engine_main(zkgpu_verifier* v) {
           const int rc = r.call->finish();
           if (r.rc == ZKGPU_OK) r.rc = rc;
           if (rc != ZKGPU_OK) v->last_error = r.call->error_text();
+          else tx_precomputed_count(v, r.call->n_precomputed());
           r.call.reset();                                // (joins its staging thread: nothing calls on_news afterwards)
         }
         {
@@ -2016,7 +2047,9 @@ int zkgpu_tx_verify_submit(zkgpu_verifier* v, size_t batch, const uint8_t* txs, 
   std::unique_ptr<zkgpu_verifier::TxPending> p(new zkgpu_verifier::TxPending());
   p->batch = batch; p->txs = txs; p->offsets = tx_offsets; p->host_threads = host_threads;
   p->arrived = std::chrono::steady_clock::now();
-  p->layout = zk::zkvm::TxFormat::of_valid(v->tx_format.load()).out;     // (the layout wait will write: the one in force now)
+  const zk::zkvm::TxFormat submitted = zk::zkvm::TxFormat::of_valid(v->tx_format.load());
+  p->layout = submitted.out;                             // (the layout wait will write: the one in force now; so with the call's kind)
+  if (submitted.precompute_only) p->kind = zk::zkvm::TXFORMAT_PRECOMPUTE_ONLY | submitted.base | (submitted.hash_on_device ? zk::zkvm::TXFORMAT_HASH_ON_DEVICE : 0);
   std::lock_guard<std::mutex> lk(v->tx_mu);
   if (v->tx_engine_quit) return ZKGPU_EINVAL;
   if (!v->tx_engine.joinable()) {

@@ -52,9 +52,15 @@
 //     of the whole call are kept in a side array of the call until then: the host's second pass fills them from the slots its
 //     plans wrote (tx_prepare_many_logged); a device that hashes brings the entries' contract IDs down with the transaction IDs
 //     (hash_log) and the host adds counts and kinds from the tape's shape table.  Nothing is hashed for it either.
+//   TxDevice::precompute() (ZKGPU_TXFORMAT_PRECOMPUTE_ONLY, only beside ids() and never beside chains()): the call VERIFIES NOTHING.
+//     The staging thread makes ONE pass per chunk -- the VM and the plans of what the ID and the log need, run on the host or,
+//     on a device that hashes, written to the chunk's tape with no job run at all -- and the calling thread queues and
+//     collects tapes (step_precompute: the first two sub-steps of step_host_signed) or, without such a device, only waits for
+//     the staging thread.  No key stage, no proofs, no signature stage is planned, staged or queued.  verdicts() sets no bit
+//     and writes PRECOMPUTED (3), never 0, beside the ID and the record of every transaction the VM ran to the end.
 // The calling thread's sub-steps (snapshot, queue_keys, queue_tape, proofs_turn, the collects, end_step) are the same whatever
-// the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run: step_host_signed()
-// and step_chained(), which say why.
+// the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run: step_host_signed(),
+// step_chained() and step_precompute(), which say why.
 #pragma once
 #include "host_pool.hpp"
 #include "tx_hash_tape.hpp"
@@ -145,6 +151,9 @@ class TxDevice {
   // count <= log_k() entries at [t][j], zeros elsewhere.
   virtual size_t log_k() const { return 0; }
   virtual const uint8_t* hash_log(int) { return nullptr; }
+  // is the call a precompute-only one: the VM, the IDs and the log, nothing verified?  (Only of a device with ids() that does
+  // not chain.)  Such a call asks for nothing above but the hash_* functions, and those only of a device that hashes.
+  virtual bool precompute() const { return false; }
 };
 
 class TxCall {
@@ -153,6 +162,7 @@ class TxCall {
   enum : int { OK = 0, EINVAL_ = -1, ENOMEM_ = -4 };     // (ZKGPU_OK / _EINVAL / _ENOMEM: this header does not see zkgpu.h)
   // status bytes of a call with reasons (ZKGPU_TXSTATUS_*, restated for the same reason; session.hpp asserts them)
   enum : uint8_t { WHY_NONE = 1, WHY_TX_INVALID = 16, WHY_PROOF_FIRST = 17, WHY_KEY = 20, WHY_SIGNATURE = 21 };
+  static constexpr uint8_t PRECOMPUTED = TXOUT_PRECOMPUTED;     // what a precompute-only call writes where a verifying one decides between 0 and a reason
 
   // several callers' transactions as ONE call (zkgpu_tx_verify_submit: calls in flight are merged as tickets are): the
   // pieces in order, transaction i of the merged call = the i-th transaction counted through them.  ids / log are written only
@@ -169,7 +179,7 @@ class TxCall {
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
-        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), ids_(dev.ids() && any_ids(pieces)), log_k_(ids_ && any_log(pieces, dev.log_k()) ? dev.log_k() : 0), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), precompute_(dev.precompute() && dev.ids() && !chains_), ids_(dev.ids() && any_ids(pieces)), log_k_(ids_ && any_log(pieces, dev.log_k()) ? dev.log_k() : 0), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
     if (ids_) id_out_.reserve(batch_);
     if (log_k_) { log_out_.reserve(batch_); log_rec_.assign(batch_ * tx_log_record_bytes(log_k_), 0); }
@@ -267,6 +277,8 @@ class TxCall {
   size_t n_sig_stages_planned() const { return sig_plan_.size(); }
   // transactions whose second pass ran on the host with every protocol -- the transaction ID's among them (0 on a device that hashes)
   size_t n_host_hashed() { std::lock_guard<std::mutex> lk(hm_); return n_host_hashed_; }
+  // (after finish() returned OK) transactions that left a precompute-only call with PRECOMPUTED
+  size_t n_precomputed() const { return n_precomputed_; }
 
  private:
   struct Chunk {
@@ -334,6 +346,7 @@ class TxCall {
       if (c == n && c - first > 1) { sig_plan_.push_back({first, c - 1}); sig_plan_.push_back({c - 1, c}); }
       else sig_plan_.push_back({first, c});
     }
+    if (precompute_) { sig_plan_.clear(); all_sigs_made_ = true; }     // (no signature is looked at)
     if (chains_) {                                       // one stage per chunk, all of them there from the start: chain_rows_[c] publishes c's rows
       sig_plan_.clear();
       for (size_t c = 0; c < n; ++c) { sig_plan_.push_back({c, c + 1}); sig_stages_.emplace_back(new SigStage()); sig_stages_[c]->first = c; sig_stages_[c]->last = c + 1; }
@@ -374,17 +387,27 @@ class TxCall {
     if (only == ALL_PROTOS) n_host_hashed_ += k.n;
   }
   // the second pass of a chunk on a device that hashes: the plans into the slot's tape, the MuSig jobs alone on the host
-  void vm_pass_taped(Chunk& k, TxHashTape& tape) {
+  void vm_pass_taped(Chunk& k, TxHashTape& tape, uint8_t host_only = P_MUSIG) {
     const double t0 = now();
     std::atomic<int> bad{0};
     tape.reset(k.n);
     chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) {
-      if (!tx_prepare_many_taped(p, l, &statement(k.lo + first), cnt, tape, first)) bad = 1;
+      if (!tx_prepare_many_taped(p, l, &statement(k.lo + first), cnt, tape, first, host_only)) bad = 1;
     });
     tape.finish(threads_);
     std::lock_guard<std::mutex> lk(hm_);
     if (bad) tape_failed_ = true;
     t_vm_ += now() - t0;
+  }
+  // the one pass of a precompute-only call over a chunk whose plans the host runs: IDs into the statements, records into log_rec_
+  void vm_pass_ids(Chunk& k) {
+    const double t0 = now();
+    chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) {
+      tx_precompute_many(p, l, &statement(k.lo + first), cnt, log_k_ ? &log_rec_[(k.lo + first) * tx_log_record_bytes(log_k_)] : nullptr, log_k_);
+    });
+    std::lock_guard<std::mutex> lk(hm_);
+    t_vm_ += now() - t0;
+    n_host_hashed_ += k.n;
   }
   void scan(Chunk& k, Segment& sg) {                    // which transactions the VM accepts
     sg.g_lo = k.g0 = live_all_.size();
@@ -509,7 +532,26 @@ class TxCall {
       news();
     }
   }
+  // A precompute-only call: one pass per chunk and nothing else.  On a device that hashes the pass writes the chunk's tape (its
+  // slot is free once chunk ci - n_slots has been collected) and runs no job; otherwise it runs what the IDs and the log need.
+  void staging_precompute() {
+    for (size_t ci = 0; ci < chunks_.size(); ++ci) {
+      Chunk& k = *chunks_[ci];
+      if (hashes_) {
+        std::unique_lock<std::mutex> lk(hm_);
+        hcv_.wait(lk, [&] { return quit_ || ids_upto_ + n_slots_ > ci; });
+        if (quit_) return;
+      }
+      if (hashes_) vm_pass_taped(k, *dev_.hash_tape((int)(ci % n_slots_)), NO_PROTO); else vm_pass_ids(k);
+      scan(k, seg_[ci]);
+      std::lock_guard<std::mutex> lk(hm_);
+      if (quit_) return;
+      if (hashes_) tape_ready_[ci] = 1; else hashed_upto_ = ids_upto_ = ci + 1;
+      news();
+    }
+  }
   void staging_main() {
+    if (precompute_) { staging_precompute(); return; }
     for (const Span& run : runs_) {                     // a run of chunks: keys and proofs of each on their way, then their IDs
       for (size_t ci = run.first; ci < run.last; ++ci) {
         Chunk& k = *chunks_[ci];
@@ -657,12 +699,13 @@ class TxCall {
     bool rows = false, staged = false, ring_free = true, tape = false, sig_rows = false;     // of next_key_ / next_stage_ (and its ring slot) / next_hash_ / next_sig_ (chained)
     bool sigs_all = false;                                                                   // every signature stage of the call is made,
     size_t sig_avail = 0;                                                                    // so many of them so far
+    size_t ids_upto = 0;                                                                     // chunks whose IDs are in the statements (read by step_precompute alone)
   };
   bool snapshot(Ready& r) {                              // false: the staging thread has failed, and the call is over
     const size_t n = chunks_.size();
     std::lock_guard<std::mutex> lk(hm_);
     if (stager_failed_) { note(ENOMEM_, "out of host memory while staging the transactions"); finished_ = true; return false; }
-    r.sig_avail = n_sig_stages_; r.sigs_all = all_sigs_made_;
+    r.sig_avail = n_sig_stages_; r.sigs_all = all_sigs_made_; r.ids_upto = ids_upto_;
     if (next_key_ < n) r.rows = key_rows_[next_key_] != 0;
     if (next_stage_ < n) r.staged = staged_[next_stage_] != 0;
     if (next_stage_ >= RING) r.ring_free = arena_free_[next_stage_ - RING] != 0;
@@ -795,13 +838,27 @@ class TxCall {
     }
     return end_step(progress);
   }
+  // A precompute-only call: the tapes and nothing else, in the order of step_host_signed() -- a chunk's tape goes out when the
+  // staging thread has written it and its slot is free, the IDs that are back are collected.  Without a device that hashes there
+  // is nothing to queue: the call is through when the staging thread has passed the last chunk.
+  bool step_precompute(const Ready& r) {
+    const size_t n = chunks_.size();
+    if (hashes_ ? next_hcollect_ == n : r.ids_upto == n) { finished_ = true; return true; }
+    if (!hashes_) return end_step(false);
+    bool progress = queue_tape(r, next_hcollect_ + n_slots_ > next_hash_);
+    if (rc_ == OK && next_hcollect_ < next_hash_ && (!hash_pending_[next_hcollect_] || dev_.hash_done((int)(next_hcollect_ % n_slots_)))) {
+      hash_collect(next_hcollect_++);
+      progress = true;
+    }
+    return end_step(progress);
+  }
  public:
   bool step() {
     if (finished_) return false;
     if (rc_ != OK) { finished_ = true; return true; }
     Ready r;
     if (!snapshot(r)) return true;
-    return chains_ ? step_chained(r) : step_host_signed(r);
+    return precompute_ ? step_precompute(r) : chains_ ? step_chained(r) : step_host_signed(r);
   }
  private:
   // chunk c's signature stage behind its key stage and its tape (both queued, or empty like the stage itself)
@@ -832,7 +889,24 @@ class TxCall {
       if (!seen_pdone_[c] && k.handle && k.started && dev_.proofs_done(k.handle)) { seen_pdone_[c] = 1; mark("proofs done on the device, chunk", c); }
     }
   }
+  // what a precompute-only call writes: no bit; PRECOMPUTED, the ID and the record of every transaction the VM ran to the end;
+  // beside the others what the host VM alone finds, as a verifying call of the same base format says it
+  void precomputed_out() {
+    for (const auto& kp : chunks_) {
+      const Chunk& k = *kp;
+      for (size_t j = 0; j < k.live.size(); ++j) {
+        const size_t i = k.lo + k.live[j];
+        if (status_) status_[i] = PRECOMPUTED;
+        if (ids_ && id_out_[i]) memcpy(id_out_[i], statement(i).txid, 32);
+        if (log_k_ && log_out_[i].first) tx_log_record_copy(log_out_[i].first, log_out_[i].second, &log_rec_[i * tx_log_record_bytes(log_k_)], log_k_);
+        ++n_precomputed_;
+      }
+    }
+    for (size_t i = 0; reasons_ && i < batch_; ++i)
+      if (statement(i).status == TX_INVALID) status_[i] = host_reason(statement(i));
+  }
   void verdicts() {
+    if (precompute_) { precomputed_out(); return; }
     std::vector<uint8_t> sig_ok(live_all_.size(), 0);
     // (key_ok_ matters for a chained stage alone, whose rows include those with an undecodable key; an unchained stage's
     // `keyed` holds only rows whose keys decoded, and the test is always true there)
@@ -897,6 +971,7 @@ class TxCall {
   const bool reasons_;                                   // the device brings back reason bytes, and there is a status array to write them to
   const bool hashes_;                                    // the device hashes the transaction IDs (tapes instead of the host's second-pass hashing)
   const bool chains_;                                    // ... and forms the signature's challenge: a chunk's three stages are one chain on the device
+  const bool precompute_;                                // nothing is verified: one pass, the tapes, and PRECOMPUTED beside IDs and records (no keys, proofs or signatures)
   const bool ids_;                                       // the IDs of accepted transactions go out (the device says so, and a piece has room for them)
   std::vector<uint8_t*> id_out_;                         // ... per transaction of the call, where its 32 bytes go (NULL: its caller has no room)
   const size_t log_k_;                                   // the log's entries go out too, at most so many per transaction (0: no)
@@ -925,7 +1000,7 @@ class TxCall {
   size_t ids_upto_ = 0;
   bool tape_failed_ = false;
   std::vector<std::unique_ptr<SigStage>> sig_stages_;
-  size_t n_sig_stages_ = 0, sig_next_ = 0, hashed_upto_ = 0, n_host_hashed_ = 0;
+  size_t n_sig_stages_ = 0, sig_next_ = 0, hashed_upto_ = 0, n_host_hashed_ = 0, n_precomputed_ = 0;
   bool all_sigs_made_ = false, quit_ = false, stager_failed_ = false;
   double t_keys_host_ = 0, t_sig_host_ = 0, t_stage_host_ = 0, t_vm_ = 0;
   // written by the staging thread BEFORE the flag that publishes them (key_rows_ / staged_ / n_sig_stages_), read by the

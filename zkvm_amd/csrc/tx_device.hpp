@@ -159,9 +159,17 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   //     stage copies its IDs down as an unchained one does (one copy on the hashing stream, no launch)
   //   out.log_k: ZKGPU_TXFORMAT_RETURN_LOG beside it -- K, the log entries kept per transaction (0: no).  Here: behind k_tx_hash, on
   //     its stream, k_tx_log_gather and one more copy down (hash_queue); a call without it queues exactly what it queued before
+  //   precompute_only: ZKGPU_TXFORMAT_PRECOMPUTE_ONLY -- the call asks for the hashing stage alone (tx_call.hpp), and that stage
+  //     walks the tape by dependency level (tx_hash_levels.hpp: k_tx_hash_levels) because that kernel, timed alone on the tapes of
+  //     1024 and of 8192 payments, was faster in every process than k_tx_hash in any (median 250 / 255 us against a minimum of
+  //     359 / 360 us: DESIGN.md sec 4.5, profiles/r14a_tx_precompute.txt); ZKGPU_TX_HASH_LEVELS=0 / 1 picks the kernel for the
+  //     tests and for measuring.  A verifying call's stage never does: its launches are as they were
+  static constexpr bool TX_HASH_LEVELS_SERVE = true;
   explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, const zk::zkvm::TxFormat& format = zk::zkvm::TxFormat())
       : v_(v), sb_(slot_base), ab_(arena_base), reasons_(format.reasons()), hashes_(format.hash_on_device), chains_(format.hash_on_device && format.sign_on_device),
-        ids_(format.out.ids), log_k_(format.out.ids ? format.out.log_k : 0) {}
+        ids_(format.out.ids), precompute_(format.precompute_only && format.out.ids && !chains_), levels_(precompute_ && levels_asked()),
+        log_k_(format.out.ids ? format.out.log_k : 0) {}
+  bool precompute() const override { return precompute_; }
   bool reasons() const override { return reasons_; }
   bool hashes() const override { return hashes_; }
   bool chains() const override { return chains_; }
@@ -401,7 +409,9 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     bool profiled = false;
     { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); profiled = v_->root->profiling; }
     c->profiling = profiled;
-    {
+    if (levels_) {
+      TRY(levels_queue(c, hs, tape, view));
+    } else {
       Launch l(c, "k_tx_hash", hs.stream);
       hipLaunchKernelGGL(zk::k_tx_hash, dim3(h.n_lanes / 64), dim3(64), 0, hs.stream, view, h.n_lanes);
     }
@@ -443,6 +453,32 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     hs.n_tx = h.n_tx;
     return ZKGPU_OK;
   }
+  static bool levels_asked() {
+    const char* e = getenv("ZKGPU_TX_HASH_LEVELS");
+    return e && (e[0] == '0' || e[0] == '1') ? e[0] == '1' : TX_HASH_LEVELS_SERVE;
+  }
+  // the tape by dependency level: its side table up beside it, then k_tx_hash_levels -- 4 lanes per entry of the lane table, 16
+  // entries per block (c->mu held, the device set, c->profiling as the launch wants it; after an error the switch is off again)
+  int levels_queue(zkgpu_ctx* c, zkgpu_verifier::TxHashStage& hs, const zk::zkvm::TxHashTape& tape, const zk::zkvm::HashTapeView& view) {
+    using namespace zk::zkvm;
+    const HashTapeHead& h = tape.head();
+    auto queue = [&]() -> int {
+      if (!tx_hash_levels_table(tape.block(), hs.levels_table)) { c->last_error = "the tape's jobs have no order by levels"; return ZKGPU_EINVAL; }
+      const size_t tab_bytes = 4 * hs.levels_table.size();
+      TRY(pinned_grow(c, hs.h_levels, hs.h_levels_cap, tab_bytes));
+      TRY(ensure(c, hs.d_levels, tab_bytes));
+      memcpy(hs.h_levels, hs.levels_table.data(), tab_bytes);
+      HIP_TRY(c, hipMemcpyAsync(hs.d_levels.p, hs.h_levels, tab_bytes, hipMemcpyHostToDevice, hs.stream));
+      const HashLevelsView lv{(const uint32_t*)hs.d_levels.p, (uint32_t)hs.levels_table.size()};
+      if (h.n_lanes == 0) return ZKGPU_OK;
+      Launch l(c, "k_tx_hash_levels", hs.stream);
+      hipLaunchKernelGGL(zk::k_tx_hash_levels, dim3(h.n_lanes / (64 / TAPE_LEVEL_LANES)), dim3(64), 0, hs.stream, view, lv, h.n_lanes);
+      return ZKGPU_OK;
+    };
+    const int rc = queue();
+    if (rc != ZKGPU_OK) c->profiling = false;
+    return rc;
+  }
   int hash_wait(int slot, uint8_t* txids) {
     zkgpu_ctx* c = keys(slot);
     zkgpu_verifier::TxHashStage& hs = hash(slot);
@@ -465,6 +501,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   const int sb_;
   const size_t ab_;
   const bool reasons_, hashes_, chains_, ids_;
+  const bool precompute_, levels_;                       // a precompute-only call | ... whose tapes are walked by level
   const size_t log_k_;
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];

@@ -7,7 +7,8 @@
 // words in LDS (word i of lane l at st[i * 64 + l]: no bank conflicts, and byte positions index memory, not registers), as
 // k_transcript does (prep_kernels.hpp); the permutation is merlin_dev.hpp's, in registers.  Idle lanes return before they
 // touch memory other than their word of the lane table.  Slots live in global memory, 32 bytes each; the root's 32 bytes are
-// also written to the dense txid[] array, which is all that is copied back.
+// also written to the dense txid[] array, which is all that is copied back.  (The same tape walked by dependency level, four
+// lanes per transaction: k_tx_hash_levels, tx_hash_levels.hpp -- the hashing stage of a precompute-only call.)
 //
 // k_tx_log_gather (ZKGPU_TXFORMAT_RETURN_LOG; tx_log.hpp): behind k_tx_hash on the same stream, one lane per (transaction of
 // the tape, window position j < K), 64 lanes per block.  A lane reads its transaction's shape and slot base from the tape's

@@ -1,6 +1,7 @@
 // tx_hash_tape.hpp -- the hash plans of a chunk of transactions (zkvm_tx.hpp: TxPlan) flattened into ONE block of words a
 // kernel can index blindly, and the interpreter that runs it: tx_hash_run, one function for the host and the device
-// (tx_hash_kernels.hpp: k_tx_hash runs it one lane per transaction; the CPU tests and libzkhost run the same code).
+// (tx_hash_kernels.hpp: k_tx_hash runs it one lane per transaction; the CPU tests and libzkhost run the same code).  The block
+// read another way -- its jobs by dependency level, several lanes per transaction -- is tx_hash_levels.hpp's.
 //
 // With ZKGPU_TXFORMAT_HASH_ON_DEVICE the second pass of a transaction call (tx_call.hpp) writes the plans of its chunk but
 // runs none of the jobs of P_CONTRACTID, P_RATCHET and P_TXID on the host: they come here.  P_MUSIG and P_SIGNTX stay on the
@@ -349,9 +350,11 @@ inline bool hash_tape_check(const uint32_t* b, size_t words) {
 // the MuSig jobs alone run here, everything else of the plan goes to the tape as transaction j0 + i of its chunk.  The slot
 // memory is zeroed: the statement's transaction ID reads zero until the device's has been collected.
 // -> false: a plan the tape cannot hold (the call fails closed)
-inline bool tx_prepare_many_taped(const uint8_t* const* tx, const size_t* len, TxStatement* st, size_t count, TxHashTape& tape, size_t j0) {
+// host_only = NO_PROTO (a precompute-only call): not even the MuSig jobs run -- nothing of the signature is looked at
+inline bool tx_prepare_many_taped(const uint8_t* const* tx, const size_t* len, TxStatement* st, size_t count, TxHashTape& tape, size_t j0,
+                                  uint8_t host_only = P_MUSIG) {
   bool ok = true;
-  tx_run_group(tx, len, st, count, ALL_PROTOS, P_MUSIG, true, true,
+  tx_run_group(tx, len, st, count, ALL_PROTOS, host_only, true, true,
                [&](size_t i, const TxPlan& plan, const TxSlots& out, const uint8_t*) { ok &= tape.add(j0 + i, plan, out.txid); });
   return ok;
 }

@@ -131,5 +131,16 @@ inline void tx_prepare_many_logged(const uint8_t* const* tx, const size_t* len, 
   });
 }
 
+// The one pass of a precompute-only call (ZKGPU_TXFORMAT_PRECOMPUTE_ONLY) whose host hashes: the same structure pass, the plans
+// run for what the transaction ID and the log need and nothing else (ID_PROTOS: no MuSig coefficient is hashed, the statement's
+// signature scalars are not what a verifying call would find there), the records as above when recs is not NULL.
+static_assert(P_CONTRACTID < P_MUSIG && P_RATCHET < P_MUSIG && P_TXID < P_MUSIG && P_SIGNTX > P_MUSIG,
+              "ID_PROTOS (zkvm_tx.hpp: run_plan) takes every protocol below P_MUSIG: the three the ID and the log are hashed from, and no other");
+inline void tx_precompute_many(const uint8_t* const* tx, const size_t* len, TxStatement* st, size_t count, uint8_t* recs, size_t K) {
+  tx_run_group(tx, len, st, count, ALL_PROTOS, ID_PROTOS, true, true, [&](size_t i, const TxPlan& plan, const TxSlots&, const uint8_t* slots) {
+    if (recs) tx_log_of_plan(plan, slots, recs + i * tx_log_record_bytes(K), K);
+  });
+}
+
 }  // namespace zkvm
 }  // namespace zk

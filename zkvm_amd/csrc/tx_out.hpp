@@ -17,10 +17,10 @@
 namespace zk {
 namespace zkvm {
 
-// (ZKGPU_TXFORMAT_*, ZKGPU_TXSTATUS_REJECTED / _OUTSIDE_SUBSET)
+// (ZKGPU_TXFORMAT_*, ZKGPU_TXSTATUS_REJECTED / _OUTSIDE_SUBSET / _PRECOMPUTED)
 constexpr int TXFORMAT_V1 = 1, TXFORMAT_V1_REASONS = 2, TXFORMAT_HASH_ON_DEVICE = 256, TXFORMAT_SIGN_ON_DEVICE = 512, TXFORMAT_RETURN_IDS = 1024,
-              TXFORMAT_RETURN_LOG = 2048, TXFORMAT_LOG_SHIFT = 16;
-constexpr uint8_t TXOUT_REJECTED = 1, TXOUT_OUTSIDE_SUBSET = 2;
+              TXFORMAT_RETURN_LOG = 2048, TXFORMAT_PRECOMPUTE_ONLY = 8192, TXFORMAT_LOG_SHIFT = 16;
+constexpr uint8_t TXOUT_REJECTED = 1, TXOUT_OUTSIDE_SUBSET = 2, TXOUT_PRECOMPUTED = 3;
 inline size_t tx_log_record_bytes(size_t K) { return 1 + 33 * K; }
 
 // One caller's transactions inside a call (TxCall::Piece).  ids (may be NULL): 32 * batch bytes of that caller's, zeroed by it,
@@ -59,19 +59,22 @@ struct TxOutLayout {
 
 // The format word, decoded.  of(): false for a word zkgpu_verifier_set_tx_format refuses -- negative; the log flag without a
 // window K in bits 16 .. 23 or a window without the flag; the log without the IDs; signing on the device without hashing
-// there; flags (or any stray bit) without one of the two base formats.  0 alone is valid: no format enabled.
+// there; flags (or any stray bit) without one of the two base formats; precompute-only without the IDs (it has nothing else
+// to hand out) or beside signing on the device (it checks no signature).  0 alone is valid: no format enabled.
 struct TxFormat {
   int base = 0;                                           // 0 none, 1, 2 (the same bytes and bits as 1; the status bytes carry a reason)
   bool hash_on_device = false, sign_on_device = false;
+  bool precompute_only = false;                           // the VM, the ID and the log alone: nothing is verified, nothing accepted (status 3)
   TxOutLayout out;
   static bool of(int word, TxFormat* f) {
     const int log_k = (word >> TXFORMAT_LOG_SHIFT) & 255;
     const bool log = (word & TXFORMAT_RETURN_LOG) != 0, ids = (word & TXFORMAT_RETURN_IDS) != 0;
     const bool hash = (word & TXFORMAT_HASH_ON_DEVICE) != 0, sign = (word & TXFORMAT_SIGN_ON_DEVICE) != 0;
-    if (word < 0 || log != (log_k != 0) || (log && !ids) || (sign && !hash)) return false;
-    const int base = word & ~(TXFORMAT_HASH_ON_DEVICE | TXFORMAT_SIGN_ON_DEVICE | TXFORMAT_RETURN_IDS | TXFORMAT_RETURN_LOG | (255 << TXFORMAT_LOG_SHIFT));
+    const bool pre = (word & TXFORMAT_PRECOMPUTE_ONLY) != 0;
+    if (word < 0 || log != (log_k != 0) || (log && !ids) || (sign && !hash) || (pre && (!ids || sign))) return false;
+    const int base = word & ~(TXFORMAT_HASH_ON_DEVICE | TXFORMAT_SIGN_ON_DEVICE | TXFORMAT_RETURN_IDS | TXFORMAT_RETURN_LOG | TXFORMAT_PRECOMPUTE_ONLY | (255 << TXFORMAT_LOG_SHIFT));
     if (word != 0 && base != TXFORMAT_V1 && base != TXFORMAT_V1_REASONS) return false;
-    f->base = base; f->hash_on_device = hash; f->sign_on_device = sign;
+    f->base = base; f->hash_on_device = hash; f->sign_on_device = sign; f->precompute_only = pre;
     f->out.ids = ids; f->out.log_k = (size_t)log_k;
     return true;
   }

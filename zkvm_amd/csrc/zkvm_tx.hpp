@@ -179,11 +179,11 @@ inline const uint8_t* piece_bytes(const TxPlan& P, const HashPiece& h, const uin
 // slots: 32 bytes per slot.  One transaction.  only != ALL_PROTOS: just the jobs of that protocol (they must not read slots
 // of the others: true of P_MUSIG, whose inputs are keys and counters).
 constexpr uint8_t ALL_PROTOS = 0xff;
-constexpr uint8_t NO_PROTO = 0xfe;      // (as `only`: no job at all -- the VM's stack machine alone)
+constexpr uint8_t NO_PROTO = 0xfe, ID_PROTOS = 0xfd;     // (as `only`: no job at all -- the VM's stack machine alone | run_plan alone: every job but P_MUSIG's, what the transaction ID and the log need)
 inline void run_plan(const TxPlan& P, uint8_t* slots, uint8_t only = ALL_PROTOS) {
   static thread_local std::vector<uint8_t> msg;
   for (const HashJob& j : P.jobs) {
-    if (only != ALL_PROTOS && j.proto != only) continue;
+    if (only != ALL_PROTOS && j.proto != only && !(only == ID_PROTOS && j.proto < P_MUSIG)) continue;
     Transcript t = proto_transcript(j.proto);
     for (uint32_t q = j.first; q < j.first + j.count;) {
       const HashPiece& h = P.pieces[q];
@@ -208,7 +208,7 @@ ZK_X8 inline void run_plans_x8(const TxPlan* const P[8], uint8_t* const slots[8]
   const TxPlan& P0 = *P[0];
   for (size_t ji = 0; ji < P0.jobs.size(); ++ji) {
     const HashJob& j = P0.jobs[ji];
-    if (only != ALL_PROTOS && j.proto != only) continue;
+    if (only != ALL_PROTOS && j.proto != only && !(only == ID_PROTOS && j.proto < P_MUSIG)) continue;
     TranscriptX8 t(proto_transcript(j.proto));
     for (uint32_t q = j.first; q < j.first + j.count; ++q) {
       const HashPiece& h = P0.pieces[q];

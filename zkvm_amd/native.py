@@ -218,6 +218,8 @@ TXFORMAT_RETURN_IDS = 0x400            # a third, beside any of those: the statu
                                        # transaction, the IDs of the accepted ones behind the status bytes
 TXFORMAT_RETURN_LOG = 0x800            # a fourth, only beside the third and with a window K << TXFORMAT_LOG_SHIFT (1 .. 255): behind
 TXFORMAT_LOG_SHIFT = 16                # the IDs, a record count | kind[K] | id[K][32] per transaction: its log's Input / Output entries
+TXFORMAT_PRECOMPUTE_ONLY = 0x2000      # a fifth, only beside the third and never beside the second: the VM, the IDs and the log ALONE -- nothing is verified,
+TXSTATUS_PRECOMPUTED = 3               # no bit is set, and a transaction the VM ran to the end reads 3 beside its ID and record: NOT a verdict
 TXLOG_INPUT, TXLOG_OUTPUT = 1, 2
 TXSTATUS_ACCEPTED, TXSTATUS_REJECTED, TXSTATUS_OUTSIDE_SUBSET = 0, 1, 2
 TXSTATUS_TX_INVALID, TXSTATUS_PROOF_FORMAT, TXSTATUS_PROOF_POINT, TXSTATUS_PROOF_EQUATION, TXSTATUS_KEY, TXSTATUS_SIGNATURE = 16, 17, 18, 19, 20, 21

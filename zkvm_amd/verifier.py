@@ -329,11 +329,13 @@ class BlockVerifier:
     TXFORMAT_RETURN_IDS = 0x400            # a flag or-ed to any of those: the transaction ID of every accepted transaction comes back
     TXFORMAT_RETURN_LOG = 0x800            # a flag only beside the one above, with a window K << TXFORMAT_LOG_SHIFT: the log's entries too
     TXFORMAT_LOG_SHIFT = 16                # bits 16 .. 23 of the format: K, the log entries kept per transaction, 1 .. 255
+    TXFORMAT_PRECOMPUTE_ONLY = 0x2000      # a flag only beside TXFORMAT_RETURN_IDS, never beside TXFORMAT_SIGN_ON_DEVICE: NOTHING is verified (precompute_txs)
     TXLOG_INPUT, TXLOG_OUTPUT = 1, 2       # kind bytes of a log record (include/zkgpu.h: ZKGPU_TXLOG_*)
     # status bytes (include/zkgpu.h: ZKGPU_TXSTATUS_*); 16 .. 21 only with TXFORMAT_RECOLLECTED_V1_REASONS, lowest code first
     TXSTATUS_ACCEPTED = 0
     TXSTATUS_REJECTED = 1                  # rejected, no reason known (format 1, or any error)
     TXSTATUS_OUTSIDE_SUBSET = 2
+    TXSTATUS_PRECOMPUTED = 3               # only under TXFORMAT_PRECOMPUTE_ONLY: the VM ran to the end, ID and log computed -- NOT a verdict
     TXSTATUS_TX_INVALID = 16
     TXSTATUS_PROOF_FORMAT = 17
     TXSTATUS_PROOF_POINT = 18
@@ -355,7 +357,10 @@ class BlockVerifier:
         into a call's status array; the arrays here are sized by what THIS method was given last, so set the format through it.)
         A format with TXFORMAT_RETURN_IDS may also carry TXFORMAT_RETURN_LOG and a window K of 1 .. 255 in bits 16 .. 23 -- given
         in `fmt` itself or as log_k=K, which sets both: verify_txs / wait_txs called with log=True then also return the Input /
-        Output entries of every accepted transaction's log (the library writes 33 + 1 + 33 K bytes per transaction)."""
+        Output entries of every accepted transaction's log (the library writes 33 + 1 + 33 K bytes per transaction).
+        A format with TXFORMAT_RETURN_IDS and without TXFORMAT_SIGN_ON_DEVICE may carry TXFORMAT_PRECOMPUTE_ONLY: the calls
+        then VERIFY NOTHING -- upstream's Tx::precompute alone -- and are made through precompute_txs / submit_txs and
+        wait_precomputed; verify_txs and wait_txs refuse, so that a status of 3 is never read as a verdict."""
         if log_k:
             if not 1 <= log_k <= 255:
                 raise ValueError("log_k is 1 .. 255")
@@ -365,9 +370,11 @@ class BlockVerifier:
         self._check(self.lib.zkgpu_verifier_set_tx_format(self.h, fmt))
         self._tx_return_ids = bool(fmt & self.TXFORMAT_RETURN_IDS)
         self._tx_log_k = (fmt >> self.TXFORMAT_LOG_SHIFT) & 255 if fmt & self.TXFORMAT_RETURN_LOG else 0
+        self._tx_precompute = bool(fmt & self.TXFORMAT_PRECOMPUTE_ONLY)
 
     _tx_return_ids = False
     _tx_log_k = 0
+    _tx_precompute = False
 
     class _TxLayout(NamedTuple):
         """the layout of a call's status array -- status[batch] | id[batch][32] | record[batch][1 + 33 K] -- as a value: what a
@@ -385,11 +392,12 @@ class BlockVerifier:
         """bytes the library writes into a call's status array under that layout"""
         return ((33 if has_ids else 1) + (1 + 33 * log_k if has_ids and log_k else 0)) * batch
 
-    def _tx_result(self, bm, st, batch: int, has_ids: bool, ids: bool, log_k: int = 0, log: bool = False):
+    def _tx_result(self, bm, st, batch: int, has_ids: bool, ids: bool, log_k: int = 0, log: bool = False, beside: int = 0):
         """(bitmap, status bytes) of a transaction call, and with ids=True the call's ID area: 32 bytes per transaction, the ID
         beside status 0 and zeros everywhere else; with log=True both, and the call's log records as a fourth element: per
         transaction None (not accepted), a list of ("input" | "output", id) in log order, or -- accepted with more entries
-        than the window holds -- their number as an int"""
+        than the window holds -- their number as an int.  beside: the status byte a record stands beside (TXSTATUS_ACCEPTED; a
+        precompute-only call: TXSTATUS_PRECOMPUTED)"""
         raw = st.raw
         out = (bm.raw[: (batch + 7) // 8], raw[:batch])
         if not (ids or log):
@@ -405,7 +413,7 @@ class BlockVerifier:
         per, names, logs = 1 + 33 * log_k, {self.TXLOG_INPUT: "input", self.TXLOG_OUTPUT: "output"}, []
         for i in range(batch):
             rec = raw[33 * batch + per * i: 33 * batch + per * (i + 1)]
-            if out[1][i] != self.TXSTATUS_ACCEPTED:
+            if out[1][i] != beside:
                 logs.append(None)
             elif rec[0] > log_k or (rec[0] and rec[1] == 0):      # (more than the window holds; 255 saturates: no listed entry has kind 0)
                 logs.append(int(rec[0]))
@@ -437,10 +445,19 @@ class BlockVerifier:
         """the same over one buffer of concatenated transactions and their lengths (same status bytes, reasons included)"""
         batch = len(lengths)
         has_ids, log_k = self._tx_layout
+        if self._tx_precompute:
+            raise ValueError("the format carries TXFORMAT_PRECOMPUTE_ONLY: nothing would be verified (precompute_txs)")
         if ids and not has_ids:
             raise ValueError("ids=True needs a format with TXFORMAT_RETURN_IDS (set_tx_format)")
         if log and not (has_ids and log_k):
             raise ValueError("log=True needs a format with TXFORMAT_RETURN_LOG (set_tx_format)")
+        bm, st = self._tx_call(blob, lengths, host_threads)
+        return self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
+
+    def _tx_call(self, blob: bytes, lengths, host_threads: int):
+        """zkgpu_tx_verify_batch under the layout in force -> (bitmap buffer, status buffer)"""
+        batch = len(lengths)
+        has_ids, log_k = self._tx_layout
         offs = np.zeros(batch + 1, dtype=np.uint64)
         np.cumsum(lengths if isinstance(lengths, np.ndarray) and lengths.dtype == np.uint64 else np.asarray(lengths, dtype=np.uint64), out=offs[1:])
         if int(offs[-1]) != len(blob):
@@ -448,7 +465,40 @@ class BlockVerifier:
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
         st = C.create_string_buffer(max(self._tx_status_bytes(batch, has_ids, log_k), 1))      # (with the flags the library writes more than a byte per transaction)
         self._check(self.lib.zkgpu_tx_verify_batch(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, bm, st))
-        return self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
+        return bm, st
+
+    def _precomputed(self, bm, st, batch: int, log_k: int):
+        if any(bm.raw[: (batch + 7) // 8]):
+            raise ZkGpuError("a precompute-only call set an accept bit")
+        out = self._tx_result(bm, st, batch, True, True, log_k, bool(log_k), beside=self.TXSTATUS_PRECOMPUTED)
+        return out[1], out[2], (out[3] if log_k else None)
+
+    def precompute_txs(self, txs: Sequence[bytes], host_threads: int = 0):
+        """upstream's Tx::precompute over serialized transactions, under a format with TXFORMAT_PRECOMPUTE_ONLY: the VM runs, NOTHING
+        is verified.  -> (status bytes, ids, logs).  status[i] is TXSTATUS_PRECOMPUTED (3) where the VM ran to the end -- beside
+        it ids[i] is the transaction ID and, under TXFORMAT_RETURN_LOG, logs[i] the Input / Output entries as verify_txs lists
+        them (or their number, when the window is too small) --, 2 outside the subset, otherwise what the host VM alone finds
+        (1, or 16 / 21 with reasons), with ids[i] 32 zero bytes and logs[i] None.  logs is None without TXFORMAT_RETURN_LOG.
+        A 3 is NOT a verdict: signature, keys, proof and commitments were not looked at -- never treat it as accepted."""
+        if not (self._tx_precompute and self._tx_return_ids):
+            raise ValueError("precompute_txs needs a format with TXFORMAT_PRECOMPUTE_ONLY (set_tx_format)")
+        bm, st = self._tx_call(b"".join(txs), [len(t) for t in txs], host_threads)
+        return self._precomputed(bm, st, len(txs), self._tx_log_k)
+
+    def wait_precomputed(self, call_id: int):
+        """zkgpu_tx_verify_wait for a call submitted under a format with TXFORMAT_PRECOMPUTE_ONLY -> (status bytes, ids, logs) as
+        precompute_txs"""
+        queued = self.__dict__["_tx_calls"][call_id]
+        if not (len(queued) > 5 and queued[5]):
+            raise ValueError("the call was not submitted under a format with TXFORMAT_PRECOMPUTE_ONLY")
+        batch, log_k = queued[2], queued[4]
+        bm = C.create_string_buffer(max((batch + 7) // 8, 1))
+        st = C.create_string_buffer(max(self._tx_status_bytes(batch, True, log_k), 1))
+        try:
+            self._check(self.lib.zkgpu_tx_verify_wait(self.h, call_id, bm, st))
+        finally:
+            del self.__dict__["_tx_calls"][call_id]
+        return self._precomputed(bm, st, batch, log_k)
 
     def submit_txs_packed(self, blob: bytes, lengths, host_threads: int = 0) -> int:
         """zkgpu_tx_verify_submit: the call is queued (calls in flight are merged into rounds); -> call id for wait_txs.  The
@@ -461,7 +511,7 @@ class BlockVerifier:
         cid = C.c_uint64(0)
         self._check(self.lib.zkgpu_tx_verify_submit(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, C.byref(cid)))
         # (the layout of the call's status array is the one in force when it was queued: remembered with the call)
-        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch) + self._tx_layout
+        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch) + self._tx_layout + (self._tx_precompute,)
         return int(cid.value)
 
     def submit_txs(self, txs: Sequence[bytes], host_threads: int = 0) -> int:
@@ -473,7 +523,9 @@ class BlockVerifier:
         ids=True (the call was submitted under a format with TXFORMAT_RETURN_IDS): -> (bitmap, status bytes, ids) as verify_txs;
         log=True (... with TXFORMAT_RETURN_LOG): -> (bitmap, status bytes, ids, log) as verify_txs"""
         queued = self.__dict__["_tx_calls"][call_id]
-        batch, (has_ids, log_k) = queued[2], self._TxLayout(*queued[3:])
+        batch, (has_ids, log_k) = queued[2], self._TxLayout(*queued[3:5])
+        if len(queued) > 5 and queued[5]:
+            raise ValueError("the call was submitted under TXFORMAT_PRECOMPUTE_ONLY: nothing was verified (wait_precomputed)")
         if ids and not has_ids:
             raise ValueError("ids=True: the call was not submitted under a format with TXFORMAT_RETURN_IDS")
         if log and not (has_ids and log_k):
