@@ -681,6 +681,37 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * queued under different base formats or hashing switches.  (A submitted VERIFYING call keeps its layout alone, as it always
  * has: base format and device switches are those in force when its round starts.) */
 #define ZKGPU_TXFORMAT_PRECOMPUTE_ONLY 8192   /* 0x2000; only together with ZKGPU_TXFORMAT_RETURN_IDS, never with ..._SIGN_ON_DEVICE */
+/* A third BASE FORMAT (3 stays invalid): the SECOND HALF of upstream's Tx::verify alone -- PrecomputedTx::verify -- for a
+ * caller that ran ITS OWN VM (Tx::precompute()) and hands over what that VM left, not serialized transactions.  `txs` /
+ * `tx_offsets` are then a CSR of RECORDS.  The framing is THIS LIBRARY'S OWN, not a recollection of anything upstream; of the
+ * unpinned rows (oracle/UNPINNED.md) the format depends on the tx.musig / tx.signtx / tx.schnorr ones alone.  Little endian:
+ *
+ *   txid:32 | R:32 s:32 | k:u32 keys[k]:32 each | n_in:u32 n_out:u32 | commitments: 64*(n_in+n_out) | p:u32 R1CSProof[p]
+ *
+ * keys: the verification keys in the order the program's signtx instructions met them; commitments: (quantity, flavor) per
+ * value, inputs first -- what the cloak instruction left.
+ *
+ *   !!  THE LIBRARY CANNOT KNOW WHETHER txid BELONGS TO ANYTHING.  IT IS THE MESSAGE THE SIGNATURE IS CHECKED OVER, NO     !!
+ *   !!  MORE: A RECORD WHOSE txid WAS NOT COMPUTED BY THE CALLER'S OWN VM FROM THE TRANSACTION IT STANDS FOR IS ACCEPTED   !!
+ *   !!  IF THE SIGNATURE AND THE PROOF FIT IT.  NOTHING OF THE TRANSACTION'S PROGRAM, HEADER OR LOG IS SEEN OR CHECKED.    !!
+ *
+ * Accept bit = every key decodes AND s B = R + c X AND the cloak proof verifies, with X = sum a_i X_i, a_i and c formed as
+ * the transaction formats form them.  Status bytes are ALWAYS the reason codes of format 2 (there is no reasonless twin):
+ *   0        accepted (beside a set bit and nowhere else)
+ *   16       the record is malformed: its fields overrun it or do not fill it, or k = 0
+ *   21       s is not canonical (found on the host before the rest of the record is looked at), R does not decode, or the
+ *            equation fails
+ *   20       a key does not decode
+ *   17..19   from the proof, as in format 2
+ *   2        what the library cannot serve and the caller's own verifier must: n_in or n_out of 0 or above 64, k above 64
+ * For the bytes a record carries, bit and status are those format 2 writes for the transaction the record was taken from.
+ * Fail-closed as format 2 is; status == NULL stays legal.  Valid words: 4, and 4 | ZKGPU_TXFORMAT_SIGN_ON_DEVICE (0x204) --
+ * for this base alone the flag is legal without ZKGPU_TXFORMAT_HASH_ON_DEVICE, because the ID arrives in the record and
+ * there is nothing to hash for it: with it NO transcript of the call runs on the host (the MuSig coefficients a_i and the
+ * challenge c are formed on the device; verdicts are the same, and there is no host fallback).  ZKGPU_EINVAL: base 4 beside
+ * 0x100, 0x400, 0x800 or any window, or 0x2000.  A submitted statements call keeps what it was QUEUED under (the base and
+ * 0x200); a round never holds statements calls and transaction calls together, nor calls queued under 4 and under 0x204. */
+#define ZKGPU_TXFORMAT_STATEMENTS_V1 4
 #define ZKGPU_TXLOG_INPUT 1
 #define ZKGPU_TXLOG_OUTPUT 2
 #define ZKGPU_TXSTATUS_ACCEPTED 0

@@ -502,6 +502,41 @@ impl GpuVerifier {
             .collect())
     }
 
+    /// One record of `ZKGPU_TXFORMAT_STATEMENTS_V1` (the framing is this library's own; `include/zkgpu.h`): what the reference's
+    /// `Tx::precompute()` leaves of a transaction -- its ID, the signature `(R, s)`, the verification keys in the order the
+    /// program's `signtx` instructions met them, the cloak's arity and `(quantity, flavor)` commitments, inputs first, and the
+    /// proof bytes.  The library cannot know whether `txid` belongs to anything: it is the message the signature is checked over.
+    pub fn pack_statement(txid: &[u8; 32], r: &[u8; 32], s: &[u8; 32], keys: &[[u8; 32]], n_in: u32, n_out: u32, commitments: &[u8], proof: &[u8]) -> Result<Vec<u8>, Error> {
+        if commitments.len() != 64 * (n_in as usize + n_out as usize) || keys.len() > u32::MAX as usize || proof.len() > u32::MAX as usize {
+            return Err(Error::InvalidArgument("pack_statement: 64 bytes of commitments per value; counts fit 32 bits".into()));
+        }
+        let mut rec = Vec::with_capacity(112 + 32 * keys.len() + commitments.len() + proof.len());
+        rec.extend_from_slice(txid);
+        rec.extend_from_slice(r);
+        rec.extend_from_slice(s);
+        rec.extend_from_slice(&(keys.len() as u32).to_le_bytes());
+        for k in keys {
+            rec.extend_from_slice(k);
+        }
+        rec.extend_from_slice(&n_in.to_le_bytes());
+        rec.extend_from_slice(&n_out.to_le_bytes());
+        rec.extend_from_slice(commitments);
+        rec.extend_from_slice(&(proof.len() as u32).to_le_bytes());
+        rec.extend_from_slice(proof);
+        Ok(rec)
+    }
+
+    /// The reference's `PrecomputedTx::verify` behind the CALLER'S OWN VM: `records` are `pack_statement` records of what
+    /// `Tx::precompute()` left; per record MuSig key aggregation, the Schnorr equation over its `txid` and the cloak proof.
+    /// Sets the format to `ZKGPU_TXFORMAT_STATEMENTS_V1` (`on_device`: beside `ZKGPU_TXFORMAT_SIGN_ON_DEVICE` -- the MuSig
+    /// coefficients and the challenge are formed on the device, same verdicts).  Verdicts always carry a reason:
+    /// `RejectedBecause(TxReject)`; `OutsideSubset`: more keys or values than the library serves.
+    pub fn verify_precomputed(&self, records: &[&[u8]], host_threads: i32, on_device: bool) -> Result<Vec<TxVerdict>, Error> {
+        let sign = if on_device { sys::ZKGPU_TXFORMAT_SIGN_ON_DEVICE } else { 0 };
+        self.set_tx_format(sys::ZKGPU_TXFORMAT_STATEMENTS_V1 | sign)?;
+        self.verify_txs(records, host_threads)
+    }
+
     /// status array of a call of `n` transactions: `n` bytes, `33 * n` under `ZKGPU_TXFORMAT_RETURN_IDS`, and
     /// `(33 + 1 + 33 * log_k) * n` under `ZKGPU_TXFORMAT_RETURN_LOG` with window `log_k`
     fn tx_status_len(n: usize, ids: bool, log_k: usize) -> usize {

@@ -1881,3 +1881,208 @@ extern "C" int zkhost_txcall_precompute_selftest(int hashing, int reasons, size_
   if (rc != 0) format.out.fail_closed(accept_bitmap, status, batch);
   return rc;
 }
+
+// ---- records of what the caller's own VM left (tx_statements.hpp; ZKGPU_TXFORMAT_STATEMENTS_V1) on the CPU ---------------------
+#include "tx_musig_rows.hpp"
+#include "tx_statements.hpp"
+
+// ---- the parser alone.  -> the statement's status (0 ok, 1 invalid, 2 unsupported); out_u32: n_in, n_out, terms, proof offset in
+// ---- the record, proof length; why: the reason text (up to 63 bytes, NUL-terminated); txid 32 bytes; commitments (cap_com bytes
+// ---- of room), scalars / points (cap_terms * 32 bytes of room each): copied as far as they fit
+extern "C" int zkhost_tx_statement_parse(const uint8_t* rec, size_t len, uint32_t* out_u32, char* why, uint8_t* txid, uint8_t* commitments, size_t cap_com,
+                                         uint8_t* scalars, uint8_t* points, size_t cap_terms) {
+  TxStatement st;
+  tx_statement_parse(rec, len, st);
+  out_u32[0] = st.n_in; out_u32[1] = st.n_out; out_u32[2] = (uint32_t)(st.sig_scalars.size() / 32);
+  out_u32[3] = st.proof ? (uint32_t)(st.proof - rec) : 0; out_u32[4] = (uint32_t)st.proof_len;
+  std::strncpy(why, st.why, 63); why[63] = 0;
+  std::memcpy(txid, st.txid, 32);
+  std::memcpy(commitments, st.commitments.data(), std::min(cap_com, st.commitments.size()));
+  std::memcpy(scalars, st.sig_scalars.data(), std::min(32 * cap_terms, st.sig_scalars.size()));
+  std::memcpy(points, st.sig_points.data(), std::min(32 * cap_terms, st.sig_points.size()));
+  return (int)st.status;
+}
+
+// ---- the records of a group of up to eight with the host's MuSig jobs run (lockstep != 0: eight-wide where the CPU can): per
+// ---- record its status and, at scalars + 32 * 66 * i, its terms' scalars (s, -1, a_0 ..)
+extern "C" void zkhost_tx_statements_group(const uint8_t* recs, const uint64_t* offs, size_t count, int lockstep, uint8_t* status, uint8_t* scalars) {
+  const uint8_t* p[8];
+  size_t l[8];
+  TxStatement st[8];
+  count = std::min<size_t>(count, 8);
+  for (size_t q = 0; q < count; ++q) { p[q] = recs + offs[q]; l[q] = (size_t)(offs[q + 1] - offs[q]); }
+  tx_statements_many(p, l, st, count, true, lockstep != 0);
+  for (size_t q = 0; q < count; ++q) {
+    status[q] = (uint8_t)st[q].status;
+    std::memcpy(scalars + 32 * 66 * q, st[q].sig_scalars.data(), st[q].sig_scalars.size());
+  }
+}
+
+// ---- musig_row, the function k_musig_rows runs per lane, over every row: scalars (32 bytes per term, in and out -- the key
+// ---- terms are written), points, offsets (rows + 1), skip.  trace[3]: where the sponge's rate boundary fell (tx_musig_rows.hpp).
+// ---- -> 0, -1: no script / bad arguments
+extern "C" int zkhost_musig_rows(uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t rows, uint32_t skip, uint32_t* trace) {
+  MusigScript sc;
+  if (!musig_script(sc) || !scalars || !points || !offsets || rows >= (1u << 31)) return -1;
+  for (size_t r = 0; r < rows; ++r) if (offsets[r + 1] < offsets[r] + skip + 1) return -1;
+  const size_t n = (size_t)offsets[rows];
+  std::vector<uint32_t> sw(8 * n + 8), pw(8 * n + 8);
+  std::memcpy(sw.data(), scalars, 32 * n);
+  std::memcpy(pw.data(), points, 32 * n);
+  uint32_t tr[3] = {0, 0, 0};
+  const MusigRowsView v{&sc, offsets, pw.data(), sw.data(), (uint32_t)rows, skip, tr};
+  musig_rows_run_host(v);
+  std::memcpy(scalars, sw.data(), 32 * n);
+  if (trace) std::memcpy(trace, tr, sizeof tr);
+  return 0;
+}
+
+// ---- the recipe the device's script is recorded from (tx_musig_jobs) against what the VM's plan holds for one serialized
+// ---- transaction: job for job and piece for piece -- protocol, labels, kinds, lengths, immediates, the bytes of the keys, the
+// ---- challenge's label and length.  -> the number of MuSig jobs compared (= the keys), -1: they differ, -2: the VM rejects it
+extern "C" long long zkhost_musig_recipe_compare(const uint8_t* tx, size_t len) {
+  TxStatement st;
+  TxPlan P;
+  TxSlots out;
+  P.only = 0xff;
+  tx_structure(tx, len, st, P, out);
+  if (st.status != TX_OK) return -2;
+  const size_t k = st.sig_points.size() / 32 - 2;
+  std::vector<const uint8_t*> keys(k);
+  for (size_t j = 0; j < k; ++j) keys[j] = &st.sig_points[32 * (2 + j)];
+  MusigRecorder rec;
+  std::vector<uint32_t> slots;
+  tx_musig_jobs(rec, keys.data(), k, slots);
+  size_t at = 0;
+  for (const HashJob& j : P.jobs) {
+    if (j.proto != P_MUSIG) continue;
+    if (at >= rec.jobs.size()) return -1;
+    const MusigRecorder::Job& r = rec.jobs[at++];
+    if (r.proto != j.proto || r.chal_label != j.chal_label || r.out_len != j.out_len || r.pieces.size() != j.count) return -1;
+    for (uint32_t q = 0; q < j.count; ++q) {
+      const HashPiece& h = P.pieces[j.first + q];
+      const MusigRecorder::Piece& rp = r.pieces[q];
+      if (h.label != rp.label || h.len != rp.len || h.msg_len != rp.len || (h.kind == HashPiece::Imm) != rp.imm || h.kind == HashPiece::Slot) return -1;
+      uint8_t imm[8];
+      for (int b = 0; b < 8; ++b) imm[b] = (uint8_t)(rp.value >> (8 * b));
+      if (std::memcmp(piece_bytes(P, h, nullptr), rp.imm ? imm : rp.p, h.len) != 0) return -1;
+    }
+  }
+  return at == rec.jobs.size() && at == k ? (long long)at : -1;
+}
+
+// ---- the scheduling of a statements call (TxCall::step_statements) on the CPU: the stand-in of zkhost_txcall_selftest that
+// ---- says statements(), refuses every hashing operation, and -- on_device -- forms the coefficients itself: a key stage that
+// ---- arrives as points alone (musig_row with skip 0, then the stage), a signature stage that arrives as a chain with the host's
+// ---- IDs (musig_row with skip 1, tx_sig_row over those IDs once the slot's key stage is through, then the equations).
+namespace {
+class HostStatementsTxDevice : public HostTxDevice {
+ public:
+  HostStatementsTxDevice(const uint8_t* recs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int fail_at, bool on_device, bool reasons)
+      : HostTxDevice(recs, offs, batch, proof_ok, seed, fail_at), on_device_(on_device), reasons_(reasons), srng_(seed ^ 0x3c6ef372u) {
+    have_scripts_ = musig_script(musig_) && sig_script(script_);
+  }
+  bool statements() const override { return true; }
+  bool forms_musig() const override { return on_device_; }
+  bool reasons() const override { return reasons_; }
+  TxHashTape* hash_tape(int) override { ++hash_asks_; return nullptr; }
+  int hash_enqueue(int, const TxHashTape&) override { ++hash_asks_; return -1; }
+  int hash_collect(int, uint8_t*) override { ++hash_asks_; return -1; }
+  int keys_enqueue(int slot, const uint8_t* sc, const uint8_t* pt, const uint64_t* off, size_t rows) override {
+    if (on_device_) { err_ = "a key stage with scalars on a device that forms them"; return -1; }
+    return HostTxDevice::keys_enqueue(slot, sc, pt, off, rows);
+  }
+  int keys_enqueue_formed(int slot, const uint8_t* pt, const uint64_t* off, size_t rows) override {
+    if (!on_device_ || !have_scripts_) { err_ = "a key stage without scalars on a device that does not form them"; return -1; }
+    std::vector<uint8_t>& sc = formed_[slot];
+    sc.assign(32 * off[rows], 0);
+    if (zkhost_musig_rows(sc.data(), pt, off, rows, 0, nullptr) != 0) { err_ = "a key row without a key"; return -1; }
+    return HostTxDevice::keys_enqueue(slot, sc.data(), pt, off, rows);
+  }
+  int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values, uint8_t* why) override {
+    const int rc = HostTxDevice::keys_collect(slot, ok_bits, values, why);
+    if (rc == 0 && why) for (size_t r = 0; 32 * r < keys_[slot].values.size(); ++r) why[r] = ((ok_bits[r / 8] >> (r % 8)) & 1) ? 0 : TxCall::WHY_KEY;
+    return rc;
+  }
+  int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t* why) override {
+    const size_t n = ((Proofs*)handle)->src.size();
+    const int rc = HostTxDevice::proofs_finish(handle, accept_bits, why);
+    if (rc == 0 && why) for (size_t r = 0; r < n; ++r) why[r] = ((accept_bits[r / 8] >> (r % 8)) & 1) ? 0 : (uint8_t)(TxCall::WHY_PROOF_FIRST + 2);
+    return rc;
+  }
+  int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc, const SigChain* chain) override {
+    sig_rows_[slot] = rows;
+    if (!on_device_) return HostTxDevice::sigs_enqueue(slot, rows, dsc, dpt, doff, bsc, chain);
+    if (!chain || !chain->txids || !have_scripts_) { err_ = "a signature stage of a device that forms the coefficients without the host's IDs"; return -1; }
+    if (failing()) return -3;
+    Stage& s = sigs_[slot];
+    Stage& ks = keys_[chain->key_slot];
+    if (s.th.joinable()) { err_ = "signature slot reused before it was collected"; return -1; }
+    if (!ks.th.joinable() || ks.values.size() != 32 * rows) { err_ = "a chained signature stage without its key stage in flight"; return -1; }
+    s.done = false;
+    s.ok.assign((rows + 7) / 8 + 1, 0);
+    s.values.assign(dsc, dsc + 32 * doff[rows]);
+    const uint8_t* ids = chain->txids;
+    const unsigned us = (unsigned)(srng_() % 400);
+    s.th = std::thread([=, &s, &ks] {
+      std::this_thread::sleep_for(std::chrono::microseconds(us));
+      (void)zkhost_musig_rows(s.values.data(), dpt, doff, rows, 1, nullptr);
+      while (!ks.done) std::this_thread::sleep_for(std::chrono::microseconds(20));
+      std::vector<uint32_t> sc(s.values.size() / 4 + 8), pt(8 * doff[rows] + 8), agg(8 * rows + 8), idw(8 * rows + 8), pos(rows);
+      std::memcpy(sc.data(), s.values.data(), s.values.size());
+      std::memcpy(pt.data(), dpt, 32 * doff[rows]);
+      std::memcpy(agg.data(), ks.values.data(), 32 * rows);
+      std::memcpy(idw.data(), ids, 32 * rows);
+      for (size_t r = 0; r < rows; ++r) pos[r] = (uint32_t)r;
+      SigRowsView v{&script_, idw.data(), pos.data(), agg.data(), doff, pt.data(), sc.data(), (uint32_t)rows};
+      sig_rows_run_host(v);
+      std::memcpy(s.values.data(), sc.data(), s.values.size());
+      sig_rows_check(s, rows, s.values.data(), dpt, doff, bsc);
+      formed_rows_ += rows;
+      s.done = true;
+    });
+    return 0;
+  }
+  int sigs_collect(int slot, uint8_t* bits, uint8_t* why) override {
+    const int rc = HostTxDevice::sigs_collect(slot, bits, why);
+    if (rc == 0 && why) for (size_t r = 0; r < sig_rows_[slot]; ++r) why[r] = ((bits[r / 8] >> (r % 8)) & 1) ? 0 : TxCall::WHY_SIGNATURE;
+    return rc;
+  }
+  uint64_t hash_asks() const { return hash_asks_; }
+  uint64_t formed_rows() const { return formed_rows_; }
+
+ private:
+  const bool on_device_, reasons_;
+  std::mt19937 srng_;
+  MusigScript musig_;
+  SigScript script_;
+  bool have_scripts_ = false;
+  std::vector<uint8_t> formed_[2];
+  size_t sig_rows_[2] = {0, 0};
+  std::atomic<uint64_t> hash_asks_{0}, formed_rows_{0};
+};
+}  // namespace
+
+// One statements call over the stand-in, fail-closed in both outputs (status: one byte per record; may be NULL).  on_device: the
+// stand-in forms a_i and c (0x204) or the host's transcripts do (4).  out[0] chunks, out[1] staged chunks never released, out[2]
+// hashing operations asked for (must be 0), out[3] records whose second pass the host hashed (must be 0), out[4] signature rows
+// whose coefficients the stand-in formed
+extern "C" int zkhost_txcall_statements_selftest(int on_device, int reasons, size_t batch, const uint8_t* recs, const uint64_t* offs, const uint8_t* proof_ok,
+                                                 int host_threads, size_t chunk, uint32_t delay_seed, int fail_at, int n_slots, uint8_t* accept_bitmap,
+                                                 uint8_t* status, uint64_t* out) {
+  for (int q = 0; q < 5; ++q) out[q] = 0;
+  if (!accept_bitmap || !recs || !offs || !proof_ok) return -1;
+  HostStatementsTxDevice dev(recs, offs, batch, proof_ok, delay_seed, fail_at, on_device != 0, reasons != 0);
+  TxOutLayout().begin(accept_bitmap, status, batch);
+  std::vector<TxStatement> store;
+  int rc;
+  {
+    TxCall call(dev, store, (size_t)1 << 17, batch, recs, offs, host_threads, chunk, accept_bitmap, status, n_slots);
+    out[0] = call.n_chunks();
+    rc = call.run();
+    out[3] = call.n_host_hashed();
+  }
+  out[1] = dev.leaked(); out[2] = dev.hash_asks(); out[4] = dev.formed_rows();
+  if (rc != 0) TxOutLayout().fail_closed(accept_bitmap, status, batch);
+  return rc;
+}

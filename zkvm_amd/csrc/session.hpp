@@ -17,6 +17,7 @@
 #include "tx_hash_kernels.hpp"
 #include "tx_hash_levels.hpp"
 #include "tx_sig_rows.hpp"
+#include "tx_musig_rows.hpp"
 #include "zkvm_tx.hpp"
 
 #include <deque>
@@ -134,9 +135,12 @@ struct zkgpu_verifier {
   Buffer tx_hash_const;
   // what the signature's challenge needs beside its slot's signature context (tx_sig_rows.hpp): the rows' places on the tape,
   // the events that order it behind the slot's key stage and hashing stage; once per verifier, the script of the transcript
-  struct TxSigStage { Buffer d_pos; hipEvent_t ev_keys = nullptr, ev_ids = nullptr; size_t rows = 0; };
+  // (d_ids, h_pos: a statements call whose device forms a_i and c -- the rows' IDs as the host uploaded them, and the identity
+  // that stands for their places on a tape; tx_musig_const: the script of the key-aggregation transcripts, tx_musig_rows.hpp)
+  struct TxSigStage { Buffer d_pos; hipEvent_t ev_keys = nullptr, ev_ids = nullptr; size_t rows = 0; Buffer d_ids; std::vector<uint32_t> h_pos; };
   TxSigStage tx_sig[2];
   Buffer tx_sig_const;
+  Buffer tx_musig_const;
   // zkgpu_tx_verify_batch: two contexts of their own for the key and the signature stages (each a pair of streams beside
   // the lanes'), and a ring of staging areas (pinned host + device, grow-only) for the cloak statements of the chunks in
   // flight -- nothing on that path allocates or frees device memory once the sizes have been seen (hipFree synchronises)
@@ -169,8 +173,12 @@ struct zkgpu_verifier {
     // ... and its KIND: 0 a verifying call (base format and device switches are the round's, read when it starts, as they always
     // were); a precompute-only call: ZKGPU_TXFORMAT_PRECOMPUTE_ONLY | the base format | ZKGPU_TXFORMAT_HASH_ON_DEVICE as the
     // format said them when it was submitted.  A round holds calls of ONE kind and, precompute-only, runs under it
-    int kind = 0;
-    std::vector<uint8_t> bits, area;                    // its bitmap; its status argument, layout.bytes(batch), as wait will copy it out
+    // a statements call (ZKGPU_TXFORMAT_STATEMENTS_V1): the word it was submitted under, 4 or 4 | ZKGPU_TXFORMAT_SIGN_ON_DEVICE -- a
+    // round never holds statements calls beside transaction calls, nor calls queued under the one word beside the other's.
+    // word: the whole format word at submit time (read for a verifying call only when the statements format is in force by
+    // the time its round starts)
+    int kind = 0, word = 0;
+    std::vector<uint8_t> bits, area;                   // its bitmap; its status argument, layout.bytes(batch), as wait will copy it out
   };
   std::mutex tx_mu;
   std::condition_variable tx_cv;
@@ -414,7 +422,7 @@ int zkgpu_verifier_create(zkgpu_ctx* ctx, const zkgpu_pointset* ps, size_t gens_
   batches_in_flight = std::min(batches_in_flight, 1 + MAX_FORKS);
   zkgpu_verifier* v = new zkgpu_verifier();
   v->root = ctx; v->ps = ps; v->gens_capacity = gens_capacity;
-  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; ctx->tx_signed_on_device = 0; ctx->tx_logged_on_device = 0; ctx->tx_precomputed = 0; }
+  { std::lock_guard<std::recursive_mutex> clk(ctx->mu); ctx->tx_hashed_on_device = 0; ctx->tx_signed_on_device = 0; ctx->tx_logged_on_device = 0; ctx->tx_precomputed = 0; ctx->tx_musig_on_device = 0; }
   v->lanes.push_back(ctx);
   v->lanes_requested = batches_in_flight;
   // A lane is worth having only if its light stream -- the latency-bound kernels of its batch: transcript, Horner chains,
@@ -506,8 +514,10 @@ void zkgpu_verifier_destroy(zkgpu_verifier* v) {
       if (ss.ev_keys) (void)hipEventDestroy(ss.ev_keys);
       if (ss.ev_ids) (void)hipEventDestroy(ss.ev_ids);
       if (ss.d_pos.p) (void)hipFree(ss.d_pos.p);
+      if (ss.d_ids.p) (void)hipFree(ss.d_ids.p);
     }
     if (v->tx_sig_const.p) (void)hipFree(v->tx_sig_const.p);
+    if (v->tx_musig_const.p) (void)hipFree(v->tx_musig_const.p);
   }
   for (auto& kv : v->plans) if (kv.second) zkgpu_cloak_plan_destroy(kv.second);
   delete v;
@@ -1746,7 +1756,8 @@ static_assert(zk::zkvm::TXFORMAT_V1 == ZKGPU_TXFORMAT_RECOLLECTED_V1 && zk::zkvm
               zk::zkvm::TXFORMAT_RETURN_IDS == ZKGPU_TXFORMAT_RETURN_IDS && zk::zkvm::TXFORMAT_RETURN_LOG == ZKGPU_TXFORMAT_RETURN_LOG &&
               zk::zkvm::TXFORMAT_LOG_SHIFT == ZKGPU_TXFORMAT_LOG_SHIFT && zk::zkvm::TXOUT_REJECTED == ZKGPU_TXSTATUS_REJECTED &&
               zk::zkvm::TXOUT_OUTSIDE_SUBSET == ZKGPU_TXSTATUS_OUTSIDE_SUBSET && zk::zkvm::TXFORMAT_PRECOMPUTE_ONLY == ZKGPU_TXFORMAT_PRECOMPUTE_ONLY &&
-              zk::zkvm::TXOUT_PRECOMPUTED == ZKGPU_TXSTATUS_PRECOMPUTED, "tx_out.hpp restates the format's flags and three status bytes");
+              zk::zkvm::TXOUT_PRECOMPUTED == ZKGPU_TXSTATUS_PRECOMPUTED && zk::zkvm::TXFORMAT_STATEMENTS_V1 == ZKGPU_TXFORMAT_STATEMENTS_V1,
+              "tx_out.hpp restates the format's flags and three status bytes");
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
   zk::zkvm::TxFormat f;
   if (!v || !zk::zkvm::TxFormat::of(format, &f)) return ZKGPU_EINVAL;     // (the rules: tx_out.hpp)
@@ -1969,9 +1980,15 @@ void tx_engine_main(zkgpu_verifier* v) {
       format.out = TxOutLayout();
       // (the kind is the calls', as the layout is: a precompute-only round runs under the base format and the hashing switch its
       // calls were queued under, whatever the format says by now, and never chains)
+      // (a statements round likewise runs under what its calls were QUEUED under -- the base and the signing switch; and a round of
+      // transaction calls that finds the statements format in force by now runs under the word its first call was queued under:
+      // its bytes are transactions, whatever the format says meanwhile)
       const int kind = r.calls.front()->kind;
-      format.precompute_only = kind != 0;
-      if (kind) { format.base = kind & 3; format.hash_on_device = (kind & TXFORMAT_HASH_ON_DEVICE) != 0; format.sign_on_device = false; }
+      const bool kind_statements = kind != 0 && (kind & TXFORMAT_PRECOMPUTE_ONLY) == 0;
+      if (kind == 0 && format.statements()) { format = TxFormat::of_valid(r.calls.front()->word); format.out = TxOutLayout(); }
+      format.precompute_only = kind != 0 && !kind_statements;
+      if (kind_statements) { format = TxFormat::of_valid(kind); format.out = TxOutLayout(); }
+      else if (kind) { format.base = kind & 3; format.hash_on_device = (kind & TXFORMAT_HASH_ON_DEVICE) != 0; format.sign_on_device = false; }
       for (auto* p : r.calls) {
         p->bits.resize((p->batch + 7) / 8);
         p->area.resize(p->layout.bytes(p->batch));
@@ -2047,9 +2064,12 @@ int zkgpu_tx_verify_submit(zkgpu_verifier* v, size_t batch, const uint8_t* txs, 
   std::unique_ptr<zkgpu_verifier::TxPending> p(new zkgpu_verifier::TxPending());
   p->batch = batch; p->txs = txs; p->offsets = tx_offsets; p->host_threads = host_threads;
   p->arrived = std::chrono::steady_clock::now();
-  const zk::zkvm::TxFormat submitted = zk::zkvm::TxFormat::of_valid(v->tx_format.load());
+  const int word_now = v->tx_format.load();
+  const zk::zkvm::TxFormat submitted = zk::zkvm::TxFormat::of_valid(word_now);
   p->layout = submitted.out;                             // (the layout wait will write: the one in force now; so with the call's kind)
   if (submitted.precompute_only) p->kind = zk::zkvm::TXFORMAT_PRECOMPUTE_ONLY | submitted.base | (submitted.hash_on_device ? zk::zkvm::TXFORMAT_HASH_ON_DEVICE : 0);
+  if (submitted.statements()) p->kind = zk::zkvm::TXFORMAT_STATEMENTS_V1 | (submitted.sign_on_device ? zk::zkvm::TXFORMAT_SIGN_ON_DEVICE : 0);
+  p->word = word_now;
   std::lock_guard<std::mutex> lk(v->tx_mu);
   if (v->tx_engine_quit) return ZKGPU_EINVAL;
   if (!v->tx_engine.joinable()) {

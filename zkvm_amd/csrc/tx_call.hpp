@@ -58,14 +58,21 @@
 //     collects tapes (step_precompute: the first two sub-steps of step_host_signed) or, without such a device, only waits for
 //     the staging thread.  No key stage, no proofs, no signature stage is planned, staged or queued.  verdicts() sets no bit
 //     and writes PRECOMPUTED (3), never 0, beside the ID and the record of every transaction the VM ran to the end.
-// The calling thread's sub-steps (snapshot, queue_keys, queue_tape, proofs_turn, the collects, end_step) are the same whatever
-// the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run: step_host_signed(),
-// step_chained() and step_precompute(), which say why.
+//   TxDevice::statements() (ZKGPU_TXFORMAT_STATEMENTS_V1): the pieces hold RECORDS of what the caller's own VM left
+//     (tx_statements.hpp), not transactions.  The staging thread makes ONE pass per chunk -- the records parsed, the MuSig jobs run
+//     on the host -- and no tape is ever written; the ID arrived in the record, so a chunk's signature rows wait for its keys
+//     alone.  With TxDevice::forms_musig() (ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it) no transcript runs on the host at all: a key
+//     stage goes out as points and offsets (keys_enqueue_formed), a chunk's signature stage right behind it as a chain whose IDs
+//     the host uploads (SigChain::txids), and both are collected together.  verdicts() is the verifying call's.
+// The calling thread's sub-steps (snapshot, queue_keys, queue_tape, proofs_turn, keys_turn, sigs_turn, the collects, end_step)
+// are the same whatever the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run:
+// step_host_signed(), step_chained(), step_precompute() and step_statements(), which say why.
 #pragma once
 #include "host_pool.hpp"
 #include "tx_hash_tape.hpp"
 #include "tx_log.hpp"
 #include "tx_out.hpp"
+#include "tx_statements.hpp"
 #include "zkvm_tx.hpp"
 
 #include <atomic>
@@ -88,7 +95,9 @@ namespace zkvm {
 struct TxProofSource { uint32_t n_in, n_out; const uint8_t* com; const uint8_t* proof; uint64_t proof_len; };
 // What a signature stage of a device that chains waits for ON THE DEVICE: the key stage queued last in key_slot (its row r holds
 // the aggregated key of row r) and the tape queued last in hash_slot (tape_pos[r]: which of its transactions row r signs).
-struct SigChain { int key_slot, hash_slot; const uint32_t* tape_pos; };
+// txids (a statements call whose device forms the coefficients: TxDevice::forms_musig): THE IDS COME FROM THE HOST -- 32 bytes
+// per row, uploaded with the rows; there is no hash slot (hash_slot and tape_pos are not read: a row's ID is its own)
+struct SigChain { int key_slot, hash_slot; const uint32_t* tape_pos; const uint8_t* txids = nullptr; };
 
 // f(p, l, first, cnt) for every group of eight of `count` transactions -- the groups the VM hashes in lockstep -- with p[q],
 // l[q] = where(first + q): where transaction first + q lies and how long it is
@@ -154,6 +163,14 @@ class TxDevice {
   // is the call a precompute-only one: the VM, the IDs and the log, nothing verified?  (Only of a device with ids() that does
   // not chain.)  Such a call asks for nothing above but the hash_* functions, and those only of a device that hashes.
   virtual bool precompute() const { return false; }
+  // is the call one over RECORDS of what the caller's own VM left (ZKGPU_TXFORMAT_STATEMENTS_V1: tx_statements.hpp)?  Such a
+  // call asks for keys, proofs and signatures alone: nothing is hashed for an ID, no tape is written.
+  virtual bool statements() const { return false; }
+  // ... and does the device form the MuSig coefficients a_i and the challenge c itself (ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside
+  // it)?  Then a key stage arrives as points and offsets alone (keys_enqueue_formed: the device writes the scalars), and a
+  // signature stage as a chain whose IDs come from the host (SigChain::txids), its key terms' scalars unset.
+  virtual bool forms_musig() const { return false; }
+  virtual int keys_enqueue_formed(int, const uint8_t*, const uint64_t*, size_t) { return -1; }
 };
 
 class TxCall {
@@ -179,7 +196,8 @@ class TxCall {
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
-        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes()), chains_(dev.hashes() && dev.chains()), precompute_(dev.precompute() && dev.ids() && !chains_), ids_(dev.ids() && any_ids(pieces)), log_k_(ids_ && any_log(pieces, dev.log_k()) ? dev.log_k() : 0), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes() && !dev.statements()), chains_(hashes_ && dev.chains()), precompute_(dev.precompute() && dev.ids() && !chains_ && !dev.statements()),
+        statements_(dev.statements()), musig_dev_(statements_ && dev.forms_musig()), ids_(dev.ids() && any_ids(pieces)), log_k_(ids_ && any_log(pieces, dev.log_k()) ? dev.log_k() : 0), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
     if (ids_) id_out_.reserve(batch_);
     if (log_k_) { log_out_.reserve(batch_); log_rec_.assign(batch_ * tx_log_record_bytes(log_k_), 0); }
@@ -303,6 +321,7 @@ class TxCall {
     std::vector<uint64_t> soff;
     std::vector<uint8_t> ssc, spt, sst, bits, why;
     std::vector<uint32_t> pos;                           // (a device that chains) per row, its transaction on the chunk's tape
+    std::vector<uint8_t> ids;                            // (a statements call whose device forms a_i and c) per row, its 32-byte ID
     bool pending = false;
   };
   struct Span { size_t first, last; };
@@ -347,7 +366,7 @@ class TxCall {
       else sig_plan_.push_back({first, c});
     }
     if (precompute_) { sig_plan_.clear(); all_sigs_made_ = true; }     // (no signature is looked at)
-    if (chains_) {                                       // one stage per chunk, all of them there from the start: chain_rows_[c] publishes c's rows
+    if (chains_ || musig_dev_) {                         // one stage per chunk, all of them there from the start: chain_rows_[c] publishes c's rows
       sig_plan_.clear();
       for (size_t c = 0; c < n; ++c) { sig_plan_.push_back({c, c + 1}); sig_stages_.emplace_back(new SigStage()); sig_stages_[c]->first = c; sig_stages_[c]->last = c + 1; }
       n_sig_stages_ = sig_next_ = n; all_sigs_made_ = true;
@@ -470,6 +489,10 @@ class TxCall {
     sg.keyed.resize(k.live.size());
     for (size_t q = 0; q < k.live.size(); ++q) sg.keyed[q] = k.g0 + q;
     lay_rows(sg, [&](size_t q) -> TxStatement& { return statement(k.lo + k.live[q]); }, [](size_t, size_t) {});
+    if (musig_dev_) {                                    // (the IDs the records brought go up with the rows)
+      sg.ids.resize(32 * k.live.size());
+      for (size_t q = 0; q < k.live.size(); ++q) memcpy(&sg.ids[32 * q], statement(k.lo + k.live[q]).txid, 32);
+    }
     std::lock_guard<std::mutex> lk(hm_);
     t_sig_host_ += now() - t0;
     chain_rows_[ci] = 1;
@@ -550,7 +573,39 @@ class TxCall {
       news();
     }
   }
+  // A statements call: ONE pass per chunk -- the records parsed, the MuSig jobs run unless the device forms the coefficients --
+  // and no tape.  Per chunk the proofs are staged first (theirs is the longest chain, and a record holds all they need), then
+  // the key rows, then (a device that forms a_i and c) the signature rows; the IDs arrived with the records, so the signature
+  // transcripts of a chunk wait for its aggregated keys alone.
+  void parse_pass(Chunk& k) {
+    const double t0 = now();
+    chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) { tx_statements_many(p, l, &statement(k.lo + first), cnt, !musig_dev_); });
+    std::lock_guard<std::mutex> lk(hm_);
+    t_keys_host_ += now() - t0;
+  }
+  void staging_statements() {
+    for (size_t ci = 0; ci < chunks_.size(); ++ci) {
+      Chunk& k = *chunks_[ci];
+      parse_pass(k);
+      scan(k, seg_[ci]);
+      if (!gather(ci, k)) return;
+      key_rows_out(ci, seg_[ci]);
+      if (musig_dev_) chain_rows_out(ci);
+      std::unique_lock<std::mutex> lk(hm_);
+      hashed_upto_ = ids_upto_ = ci + 1;
+      if (!musig_dev_) make_sig_stages(lk, ids_upto_);
+      if (quit_) return;
+    }
+    if (musig_dev_) return;                              // (every stage was made beside its key rows)
+    std::unique_lock<std::mutex> lk(hm_);
+    for (;;) {
+      make_sig_stages(lk, ids_upto_);
+      if (quit_ || all_sigs_made_) return;
+      hcv_.wait(lk, [&] { return quit_ || keys_back(sig_plan_[sig_next_]); });
+    }
+  }
   void staging_main() {
+    if (statements_) { staging_statements(); return; }
     if (precompute_) { staging_precompute(); return; }
     for (const Span& run : runs_) {                     // a run of chunks: keys and proofs of each on their way, then their IDs
       for (size_t ci = run.first; ci < run.last; ++ci) {
@@ -710,7 +765,7 @@ class TxCall {
     if (next_stage_ < n) r.staged = staged_[next_stage_] != 0;
     if (next_stage_ >= RING) r.ring_free = arena_free_[next_stage_ - RING] != 0;
     if (hashes_ && next_hash_ < n) r.tape = tape_ready_[next_hash_] != 0;
-    if (chains_ && next_sig_ < n) r.sig_rows = chain_rows_[next_sig_] != 0;
+    if ((chains_ || musig_dev_) && next_sig_ < n) r.sig_rows = chain_rows_[next_sig_] != 0;
     if (tape_failed_) note(EINVAL_, "a transaction's hash plan does not fit the device's tape");
     return true;
   }
@@ -723,7 +778,9 @@ class TxCall {
     mark("key rows ready, segment", next_key_);
     const double t0 = now();
     if (sg.g_hi > sg.g_lo) {
-      const int rc = dev_.keys_enqueue((int)(next_key_ % n_slots_), sg.ksc.data(), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo);
+      // (a statements call whose device forms the coefficients: points and offsets alone -- the scalars are the device's to write)
+      const int rc = musig_dev_ ? dev_.keys_enqueue_formed((int)(next_key_ % n_slots_), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo)
+                                : dev_.keys_enqueue((int)(next_key_ % n_slots_), sg.ksc.data(), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo);
       if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
     }
     t_keys_ += now() - t0;
@@ -781,13 +838,22 @@ class TxCall {
     // without asking rc_: this order always has queued them in the step in which a tape failed; finish() collects the stage)
     progress |= queue_keys(r, next_kcollect_ + n_slots_ > next_key_);
     progress |= proofs_turn(r, proofs_first_ || next_stage_ < next_key_);      // (a chunk's proofs after its keys, unless the call is one chunk)
-    if (rc_ == OK && next_kcollect_ < next_key_ && (!seg_[next_kcollect_].pending || dev_.keys_done((int)(next_kcollect_ % n_slots_)))) {
-      keys_collect(next_kcollect_);
-      { std::lock_guard<std::mutex> lk(hm_); keys_arrived_[next_kcollect_] = 1; }
-      hcv_.notify_all();
-      ++next_kcollect_;
-      progress = true;
-    }
+    progress |= keys_turn();
+    progress |= sigs_turn(r);
+    return end_step(progress);
+  }
+  // the aggregated keys of segment next_kcollect_, if the device is through with them: collected, and the staging thread is told
+  bool keys_turn() {
+    if (rc_ != OK || next_kcollect_ >= next_key_ || (seg_[next_kcollect_].pending && !dev_.keys_done((int)(next_kcollect_ % n_slots_)))) return false;
+    keys_collect(next_kcollect_);
+    { std::lock_guard<std::mutex> lk(hm_); keys_arrived_[next_kcollect_] = 1; }
+    hcv_.notify_all();
+    ++next_kcollect_;
+    return true;
+  }
+  // the signature stages the staging thread has made (host transcripts), as far as their slots are free
+  bool sigs_turn(const Ready& r) {
+    bool progress = false;
     while (rc_ == OK && next_sig_ < r.sig_avail) {
       const double t0 = now();
       if (next_sig_ >= n_slots_) {                                            // the stage that used this slot last: collected once it is done
@@ -803,6 +869,38 @@ class TxCall {
       t_sigs_ += now() - t0;
       mark("signatures queued, stage", next_sig_);
       ++next_sig_;
+      progress = true;
+    }
+    return progress;
+  }
+  // A statements call (tx_statements.hpp): the same sub-steps in a fourth order.  A chunk's proofs go out first, as soon as the
+  // staging thread has staged them -- a record holds all they need, and nothing is hashed before them --; then its key stage;
+  // then its signature stage.  No tape is ever asked for, and nothing waits for an ID.  With the host's transcripts the
+  // signature stages are the staging thread's runs, made when their keys are back (step_host_signed's last two sub-steps);
+  // on a device that forms a_i and c a chunk's signature stage is queued right behind its key stage (the device orders the
+  // two), and both are collected together, oldest chunk first, which frees their slot (step_chained's, without the tape).
+  bool step_statements(const Ready& r) {
+    const size_t n = chunks_.size();
+    if (musig_dev_ ? (next_chain_ == n && next_stage_ == n) : (next_kcollect_ == n && next_stage_ == n && r.sigs_all && next_sig_ == r.sig_avail)) { finished_ = true; return true; }
+    bool progress = proofs_turn(r, true);
+    progress |= queue_keys(r, rc_ == OK && (musig_dev_ ? next_chain_ : next_kcollect_) + n_slots_ > next_key_);
+    if (!musig_dev_) {
+      progress |= keys_turn();
+      progress |= sigs_turn(r);
+      return end_step(progress);
+    }
+    if (rc_ == OK && r.sig_rows && next_sig_ < next_key_) {
+      const double t0 = now();
+      chain_enqueue_host_ids(next_sig_);
+      t_sigs_ += now() - t0;
+      mark("signatures queued, stage", next_sig_);
+      ++next_sig_;
+      progress = true;
+    }
+    if (rc_ == OK && next_chain_ < next_sig_ && (!sig_stages_[next_chain_]->pending || dev_.sigs_done((int)(next_chain_ % n_slots_)))) {
+      sigs_collect(next_chain_);
+      keys_collect(next_chain_);
+      next_kcollect_ = ++next_chain_;
       progress = true;
     }
     return end_step(progress);
@@ -858,9 +956,21 @@ class TxCall {
     if (rc_ != OK) { finished_ = true; return true; }
     Ready r;
     if (!snapshot(r)) return true;
-    return precompute_ ? step_precompute(r) : chains_ ? step_chained(r) : step_host_signed(r);
+    return statements_ ? step_statements(r) : precompute_ ? step_precompute(r) : chains_ ? step_chained(r) : step_host_signed(r);
   }
  private:
+  // (a statements call whose device forms a_i and c) chunk c's signature stage behind its key stage (queued, or empty like the
+  // stage itself); the rows' IDs go up with them
+  void chain_enqueue_host_ids(size_t c) {
+    SigStage& sg = *sig_stages_[c];
+    const size_t ns = sg.keyed.size();
+    if (ns == 0) return;
+    if (!seg_[c].pending || sg.ids.size() != 32 * ns) { note(EINVAL_, "a signature stage without its key stage or its IDs"); return; }
+    const int slot = (int)(c % n_slots_);
+    const SigChain chain{slot, -1, nullptr, sg.ids.data()};
+    const int rc = dev_.sigs_enqueue(slot, ns, sg.ssc.data(), sg.spt.data(), sg.soff.data(), sg.sst.data(), &chain);
+    if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
+  }
   // chunk c's signature stage behind its key stage and its tape (both queued, or empty like the stage itself)
   void chain_enqueue(size_t c) {
     const Chunk& k = *chunks_[c];
@@ -972,6 +1082,8 @@ class TxCall {
   const bool hashes_;                                    // the device hashes the transaction IDs (tapes instead of the host's second-pass hashing)
   const bool chains_;                                    // ... and forms the signature's challenge: a chunk's three stages are one chain on the device
   const bool precompute_;                                // nothing is verified: one pass, the tapes, and PRECOMPUTED beside IDs and records (no keys, proofs or signatures)
+  const bool statements_;                                // the pieces hold records of what the caller's VM left (tx_statements.hpp): one parsing pass, no tape, no second pass
+  const bool musig_dev_;                                 // ... and the device forms a_i and c: a chunk's key stage and signature stage are a chain, as for chains_, without a tape
   const bool ids_;                                       // the IDs of accepted transactions go out (the device says so, and a piece has room for them)
   std::vector<uint8_t*> id_out_;                         // ... per transaction of the call, where its 32 bytes go (NULL: its caller has no room)
   const size_t log_k_;                                   // the log's entries go out too, at most so many per transaction (0: no)

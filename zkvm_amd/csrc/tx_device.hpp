@@ -168,7 +168,19 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, const zk::zkvm::TxFormat& format = zk::zkvm::TxFormat())
       : v_(v), sb_(slot_base), ab_(arena_base), reasons_(format.reasons()), hashes_(format.hash_on_device), chains_(format.hash_on_device && format.sign_on_device),
         ids_(format.out.ids), precompute_(format.precompute_only && format.out.ids && !chains_), levels_(precompute_ && levels_asked()),
-        log_k_(format.out.ids ? format.out.log_k : 0) {}
+        log_k_(format.out.ids ? format.out.log_k : 0), statements_(format.statements()), forms_musig_(format.statements() && format.sign_on_device) {}
+  //   statements(): ZKGPU_TXFORMAT_STATEMENTS_V1 -- the call's pieces are records (tx_statements.hpp); nothing is hashed for an ID
+  //   ... with sign_on_device: the MuSig coefficients come from k_musig_rows (tx_musig_rows.hpp) in both stages' rows, the
+  //     challenge from k_tx_sig_rows over the IDs the host uploads; no host fallback: an error of a launch is the call's
+  bool statements() const override { return statements_; }
+  bool forms_musig() const override { return forms_musig_; }
+  // points and offsets up, the coefficients written where the rows lie (skip 0), then the stage as msm_values_enqueue queues it
+  int keys_enqueue_formed(int slot, const uint8_t* points, const uint64_t* offsets, size_t rows) override {
+    zkgpu_ctx* c = keys(slot);
+    if (!forms_musig_) { err_ = "a key stage without scalars on a device that does not form them"; return ZKGPU_EINVAL; }
+    TRY(reasons_room(c, rows, true));
+    return reasons_behind(c, seen(formed_keys_queue(c, points, offsets, rows), c, "key coefficient stage: "), ZKGPU_TXSTATUS_KEY);
+  }
   bool precompute() const override { return precompute_; }
   bool reasons() const override { return reasons_; }
   bool hashes() const override { return hashes_; }
@@ -270,7 +282,8 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     // the stage is collected, and here on every error, after which sigs_collect is not asked)
     bool profiled = false;
     { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); profiled = v_->root->profiling; }
-    int rc = seen(chain_queue(slot, *chain, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, profiled), c, "signature challenge stage: ");
+    int rc = seen(chain->txids ? host_ids_chain_queue(slot, *chain, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, profiled)
+                               : chain_queue(slot, *chain, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, profiled), c, "signature challenge stage: ");
     if (rc == ZKGPU_OK) {
       std::lock_guard<std::recursive_mutex> lk(c->mu);
       DeviceGuard g(c->device);
@@ -284,11 +297,11 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   bool sigs_done(int slot) override { return split_done(sigs(slot)); }
   int sigs_collect(int slot, uint8_t* bits, uint8_t* why) override {
     const int rc = seen(split_collect_why(sigs(slot), bits, nullptr, reasons_ ? why : nullptr), sigs(slot));
-    if (chains_) {
+    if (chains_ || forms_musig_) {
       zkgpu_ctx* c = sigs(slot);
       const size_t rows = sig(slot).rows;
       sig(slot).rows = 0;
-      if (rc == ZKGPU_OK) { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_signed_on_device += rows; }
+      if (rc == ZKGPU_OK) { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_signed_on_device += rows; if (forms_musig_) v_->root->tx_musig_on_device += rows; }
       bool profiled = false;
       { std::lock_guard<std::recursive_mutex> lk(c->mu); profiled = c->profiling; }
       if (profiled) profile_to_root(c);                  // (only a call made with zkgpu_profile_enable on: nothing of it otherwise)
@@ -358,6 +371,90 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     }
     c->profiling = profiled;
     SigRowsView view{(const SigScript*)v_->tx_sig_const.p, (const uint32_t*)hs.d_txid.p, (const uint32_t*)ss.d_pos.p, (const uint32_t*)kc->values.p,
+                     (const uint64_t*)c->in_offsets.p, (const uint32_t*)c->in_points.p, (uint32_t*)c->in_scalars.p, (uint32_t)rows};
+    {
+      Launch l(c, "k_tx_sig_rows", c->stream);
+      hipLaunchKernelGGL(zk::k_tx_sig_rows, dim3(blocks_for(rows, 64)), dim3(64), 0, c->stream, view);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return ZKGPU_OK;
+  }
+  // ---- a statements call whose device forms the MuSig coefficients (tx_musig_rows.hpp)
+  // once per verifier: what the key aggregation hashes, written down by running the host's own recipe over a recorder
+  int musig_const(zkgpu_ctx* c) {
+    if (v_->tx_musig_const.p) return ZKGPU_OK;
+    zk::zkvm::MusigScript sc;
+    if (!zk::zkvm::musig_script(sc)) { c->last_error = "the key-aggregation transcripts do not fit the device's script"; return ZKGPU_EINVAL; }
+    return const_upload(c, v_->tx_musig_const, &sc, sizeof sc);
+  }
+  // what k_musig_rows indexes blindly: the offsets rise, every row has its `skip` leading terms and at least one key
+  static bool musig_rows_fit(const uint64_t* offsets, size_t rows, uint32_t skip) {
+    if (rows == 0 || rows >= (1ull << 31)) return false;
+    for (size_t r = 0; r < rows; ++r) if (offsets[r + 1] < offsets[r] + skip + 1) return false;
+    return true;
+  }
+  // the coefficients of the rows that lie in c's input buffers (points, offsets; in_scalars has room for every term), on c's
+  // stream (c->mu held, the device set)
+  int musig_launch(zkgpu_ctx* c, size_t rows, uint32_t skip) {
+    const zk::zkvm::MusigRowsView view{(const zk::zkvm::MusigScript*)v_->tx_musig_const.p, (const uint64_t*)c->in_offsets.p, (const uint32_t*)c->in_points.p,
+                                       (uint32_t*)c->in_scalars.p, (uint32_t)rows, skip, nullptr};
+    {
+      Launch l(c, "k_musig_rows", c->stream);
+      hipLaunchKernelGGL(zk::k_musig_rows, dim3(blocks_for(rows, 64)), dim3(64), 0, c->stream, view);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return ZKGPU_OK;
+  }
+  int formed_keys_queue(zkgpu_ctx* c, const uint8_t* points, const uint64_t* offsets, size_t rows) {
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    TRY(refuse_if_pending(c));
+    DeviceGuard g(c->device);
+    if (!musig_rows_fit(offsets, rows, 0) || offsets[0] != 0) { c->last_error = "a key row without a key"; return ZKGPU_EINVAL; }
+    const uint64_t n = offsets[rows];
+    TRY(musig_const(c));
+    TRY(ensure(c, c->in_scalars, std::max<size_t>(n * 32, 16)));
+    TRY(upload(c, c->in_points, points, n * 32));
+    TRY(upload(c, c->in_offsets, offsets, (rows + 1) * 8));
+    TRY(musig_launch(c, rows, 0));
+    Job job;
+    resident_rows(c, job, rows, n, longest_row(offsets, rows));
+    return stage_queued(c, batch_device_enqueue(c, job, true), rows);
+  }
+  // the rows of a signature stage up with their IDs; k_musig_rows (skip 1: term 0 is R) at once, k_tx_sig_rows behind the
+  // slot's key stage (the event chain_queue uses); nothing is waited for, and there is no hashing stage to order behind
+  int host_ids_chain_queue(int slot, const zk::zkvm::SigChain& chain, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points,
+                           const uint64_t* dyn_offsets, const uint8_t* base_scalars, bool profiled) {
+    using namespace zk::zkvm;
+    zkgpu_ctx* c = sigs(slot);
+    zkgpu_ctx* kc = keys(chain.key_slot);
+    zkgpu_verifier::TxSigStage& ss = sig(slot);
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    TRY(refuse_if_pending(c));
+    DeviceGuard g(c->device);
+    if (!forms_musig_) { c->last_error = "a signature stage with the host's IDs on a device that does not form the coefficients"; return ZKGPU_EINVAL; }
+    hipStream_t key_stream = nullptr;
+    {
+      std::lock_guard<std::recursive_mutex> kl(kc->mu);
+      if (!kc->pending || kc->split.kind != 1 || !kc->split.values || kc->split.batch != rows) { c->last_error = "no key stage of these rows in flight in the slot"; return ZKGPU_EINVAL; }
+      key_stream = kc->split.stream;
+    }
+    if (!musig_rows_fit(dyn_offsets, rows, 1) || dyn_offsets[0] != 0) { c->last_error = "a signature row without its R or a key"; return ZKGPU_EINVAL; }
+    TRY(musig_const(c));
+    if (!v_->tx_sig_const.p) {                           // once per verifier: what tx_finish_signature hashes, written down
+      SigScript sc;
+      if (!sig_script(sc)) { c->last_error = "the signature transcript does not fit the device's script"; return ZKGPU_EINVAL; }
+      TRY(const_upload(c, v_->tx_sig_const, &sc, sizeof sc));
+    }
+    if (!ss.ev_keys) HIP_TRY(c, hipEventCreateWithFlags(&ss.ev_keys, hipEventDisableTiming));
+    TRY(verify_ps_upload(c, rows, dyn_scalars, dyn_points, dyn_offsets, base_scalars, sidx_[slot].data(), soff_[slot].data()));
+    TRY(upload(c, ss.d_ids, chain.txids, rows * 32));
+    if (ss.h_pos.size() < rows) { const size_t old = ss.h_pos.size(); ss.h_pos.resize(rows); for (size_t r = old; r < rows; ++r) ss.h_pos[r] = (uint32_t)r; }
+    TRY(upload(c, ss.d_pos, ss.h_pos.data(), rows * 4));  // (a row's ID is its own: the identity)
+    c->profiling = profiled;
+    TRY(musig_launch(c, rows, 1));
+    HIP_TRY(c, hipEventRecord(ss.ev_keys, key_stream));
+    HIP_TRY(c, hipStreamWaitEvent(c->stream, ss.ev_keys, 0));
+    SigRowsView view{(const SigScript*)v_->tx_sig_const.p, (const uint32_t*)ss.d_ids.p, (const uint32_t*)ss.d_pos.p, (const uint32_t*)kc->values.p,
                      (const uint64_t*)c->in_offsets.p, (const uint32_t*)c->in_points.p, (uint32_t*)c->in_scalars.p, (uint32_t)rows};
     {
       Launch l(c, "k_tx_sig_rows", c->stream);
@@ -503,6 +600,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   const bool reasons_, hashes_, chains_, ids_;
   const bool precompute_, levels_;                       // a precompute-only call | ... whose tapes are walked by level
   const size_t log_k_;
+  const bool statements_, forms_musig_;                  // the call's pieces are records | ... and the device forms a_i and c
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];
   std::string err_;

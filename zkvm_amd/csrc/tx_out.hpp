@@ -18,7 +18,7 @@ namespace zk {
 namespace zkvm {
 
 // (ZKGPU_TXFORMAT_*, ZKGPU_TXSTATUS_REJECTED / _OUTSIDE_SUBSET / _PRECOMPUTED)
-constexpr int TXFORMAT_V1 = 1, TXFORMAT_V1_REASONS = 2, TXFORMAT_HASH_ON_DEVICE = 256, TXFORMAT_SIGN_ON_DEVICE = 512, TXFORMAT_RETURN_IDS = 1024,
+constexpr int TXFORMAT_V1 = 1, TXFORMAT_V1_REASONS = 2, TXFORMAT_STATEMENTS_V1 = 4, TXFORMAT_HASH_ON_DEVICE = 256, TXFORMAT_SIGN_ON_DEVICE = 512, TXFORMAT_RETURN_IDS = 1024,
               TXFORMAT_RETURN_LOG = 2048, TXFORMAT_PRECOMPUTE_ONLY = 8192, TXFORMAT_LOG_SHIFT = 16;
 constexpr uint8_t TXOUT_REJECTED = 1, TXOUT_OUTSIDE_SUBSET = 2, TXOUT_PRECOMPUTED = 3;
 inline size_t tx_log_record_bytes(size_t K) { return 1 + 33 * K; }
@@ -61,8 +61,12 @@ struct TxOutLayout {
 // window K in bits 16 .. 23 or a window without the flag; the log without the IDs; signing on the device without hashing
 // there; flags (or any stray bit) without one of the two base formats; precompute-only without the IDs (it has nothing else
 // to hand out) or beside signing on the device (it checks no signature).  0 alone is valid: no format enabled.
+// The statements format (base 4: tx_statements.hpp) takes ONE flag, signing on the device, and takes it without hashing there:
+// the ID arrives in the record, and there is nothing to hash for it.  Beside any other flag or a window it is refused.
 struct TxFormat {
-  int base = 0;                                           // 0 none, 1, 2 (the same bytes and bits as 1; the status bytes carry a reason)
+  int base = 0;                                           // 0 none, 1, 2 (the same bytes and bits as 1; the status bytes carry a reason),
+                                                          // 4 (records of what the caller's own VM left; status bytes as those of 2)
+  bool mute = false;                                      // (base 4 of a caller without a status argument: no reason byte is brought back)
   bool hash_on_device = false, sign_on_device = false;
   bool precompute_only = false;                           // the VM, the ID and the log alone: nothing is verified, nothing accepted (status 3)
   TxOutLayout out;
@@ -71,17 +75,20 @@ struct TxFormat {
     const bool log = (word & TXFORMAT_RETURN_LOG) != 0, ids = (word & TXFORMAT_RETURN_IDS) != 0;
     const bool hash = (word & TXFORMAT_HASH_ON_DEVICE) != 0, sign = (word & TXFORMAT_SIGN_ON_DEVICE) != 0;
     const bool pre = (word & TXFORMAT_PRECOMPUTE_ONLY) != 0;
-    if (word < 0 || log != (log_k != 0) || (log && !ids) || (sign && !hash) || (pre && (!ids || sign))) return false;
+    if (word < 0 || log != (log_k != 0) || (log && !ids) || (pre && (!ids || sign))) return false;
     const int base = word & ~(TXFORMAT_HASH_ON_DEVICE | TXFORMAT_SIGN_ON_DEVICE | TXFORMAT_RETURN_IDS | TXFORMAT_RETURN_LOG | TXFORMAT_PRECOMPUTE_ONLY | (255 << TXFORMAT_LOG_SHIFT));
-    if (word != 0 && base != TXFORMAT_V1 && base != TXFORMAT_V1_REASONS) return false;
-    f->base = base; f->hash_on_device = hash; f->sign_on_device = sign; f->precompute_only = pre;
+    if (base == TXFORMAT_STATEMENTS_V1 ? (hash || ids || log || pre) : (sign && !hash)) return false;
+    if (word != 0 && base != TXFORMAT_V1 && base != TXFORMAT_V1_REASONS && base != TXFORMAT_STATEMENTS_V1) return false;
+    f->base = base; f->mute = false; f->hash_on_device = hash; f->sign_on_device = sign; f->precompute_only = pre;
     f->out.ids = ids; f->out.log_k = (size_t)log_k;
     return true;
   }
   static TxFormat of_valid(int word) { TxFormat f; if (!of(word, &f)) f = TxFormat(); return f; }     // (of a word validated when it was stored)
-  bool reasons() const { return base == TXFORMAT_V1_REASONS; }
+  bool statements() const { return base == TXFORMAT_STATEMENTS_V1; }
+  bool reasons() const { return base == TXFORMAT_V1_REASONS || (statements() && !mute); }
   // the same for a caller that passed no status argument: nowhere to say a reason or to put an ID or a record -- the format-1 call
-  TxFormat without_status() const { TxFormat f = *this; f.base = reasons() ? TXFORMAT_V1 : base; f.out = TxOutLayout(); return f; }
+  // (`mute` is read by reasons() for base 4 alone, which has no reasonless twin to fall back to; formats 1 / 2 never read it)
+  TxFormat without_status() const { TxFormat f = *this; f.base = base == TXFORMAT_V1_REASONS ? TXFORMAT_V1 : base; f.mute = true; f.out = TxOutLayout(); return f; }
 };
 
 // One call of a merged round (zkgpu_tx_verify_submit): its own bitmap ((batch + 7) / 8 bytes) and its own area of

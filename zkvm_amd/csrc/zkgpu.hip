@@ -159,7 +159,7 @@ struct zkgpu_ctx {
          RT_TABLES_SMALL, RT_TABLES_BUCKET, RT_HOST_COUNTERS };
   uint64_t msm_routes[RT_HOST_COUNTERS] = {};
   DecodeRoutes decode_routes; uint8_t r_seed[32] = {0};  // DECODE launches and points by form (kernels.hpp; zkgpu_debug_read "decode_routes") | the seed of the last draw into r_draw or a lane's coal_r ("r_seed"); zero when the last batch brought its own r
-  uint8_t prover_seed[32] = {0}; uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0, tx_logged_on_device = 0, tx_precomputed = 0;   // hooks enabled only: the seed the last prover call on this context drew for itself (prover_seed.hpp; "prover_seed") | root context of a verifier: transaction IDs / signature challenges its device produced (tx_device.hpp: GpuTxDevice)
+  uint8_t prover_seed[32] = {0}; uint64_t last_adds = 0, tx_hashed_on_device = 0, tx_signed_on_device = 0, tx_logged_on_device = 0, tx_precomputed = 0, tx_musig_on_device = 0;   // hooks enabled only: the seed the last prover call on this context drew for itself (prover_seed.hpp; "prover_seed") | root context of a verifier: transaction IDs / signature challenges its device produced (tx_device.hpp: GpuTxDevice)
 };
 
 namespace {
@@ -3713,6 +3713,12 @@ long long zkgpu_debug_read(zkgpu_ctx* c, const char* what, void* out, size_t byt
     if (bytes < sizeof(uint64_t)) return ZKGPU_EINVAL;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     memcpy(out, &c->tx_precomputed, sizeof(uint64_t));
+    return (long long)sizeof(uint64_t);
+  }
+  if (strcmp(what, "tx_musig_on_device") == 0) {       // ... signature rows whose MuSig coefficients it formed (ZKGPU_TXFORMAT_STATEMENTS_V1 | ZKGPU_TXFORMAT_SIGN_ON_DEVICE)
+    if (bytes < sizeof(uint64_t)) return ZKGPU_EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    memcpy(out, &c->tx_musig_on_device, sizeof(uint64_t));
     return (long long)sizeof(uint64_t);
   }
   if (strcmp(what, "r_seed") == 0) {                   // the seed of the last draw of verifier randomness on this context (draw_r.hpp);

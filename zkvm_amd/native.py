@@ -220,9 +220,29 @@ TXFORMAT_RETURN_LOG = 0x800            # a fourth, only beside the third and wit
 TXFORMAT_LOG_SHIFT = 16                # the IDs, a record count | kind[K] | id[K][32] per transaction: its log's Input / Output entries
 TXFORMAT_PRECOMPUTE_ONLY = 0x2000      # a fifth, only beside the third and never beside the second: the VM, the IDs and the log ALONE -- nothing is verified,
 TXSTATUS_PRECOMPUTED = 3               # no bit is set, and a transaction the VM ran to the end reads 3 beside its ID and record: NOT a verdict
+TXFORMAT_STATEMENTS_V1 = 4             # a third base format: records of what the caller's OWN VM left (pack_statement); alone or beside the second flag
 TXLOG_INPUT, TXLOG_OUTPUT = 1, 2
 TXSTATUS_ACCEPTED, TXSTATUS_REJECTED, TXSTATUS_OUTSIDE_SUBSET = 0, 1, 2
 TXSTATUS_TX_INVALID, TXSTATUS_PROOF_FORMAT, TXSTATUS_PROOF_POINT, TXSTATUS_PROOF_EQUATION, TXSTATUS_KEY, TXSTATUS_SIGNATURE = 16, 17, 18, 19, 20, 21
+
+
+def pack_statement(txid: bytes, R: bytes, s: bytes, keys, n_in: int, n_out: int, commitments: bytes, proof: bytes) -> bytes:
+    """One record of TXFORMAT_STATEMENTS_V1 (include/zkgpu.h; the framing is this library's own):
+    txid:32 | R:32 s:32 | k:u32 keys[k]:32 each | n_in:u32 n_out:u32 | commitments: 64*(n_in+n_out) | p:u32 R1CSProof[p],
+    little endian.  keys: the verification keys in the order the program's signtx instructions met them; commitments:
+    (quantity, flavor) per value, inputs first.  The library cannot know whether txid belongs to anything: it is the message
+    the signature is checked over, no more.  Refuses what cannot be a record; what the library answers with a status
+    (k = 0, counts above 64, a scalar that is not canonical) is packed as it is."""
+    keys = [bytes(k) for k in keys]
+    txid, R, s, commitments, proof = bytes(txid), bytes(R), bytes(s), bytes(commitments), bytes(proof)
+    if len(txid) != 32 or len(R) != 32 or len(s) != 32 or any(len(k) != 32 for k in keys):
+        raise ValueError("txid, R, s and every key are 32 bytes")
+    if not (0 <= n_in < 1 << 32 and 0 <= n_out < 1 << 32 and len(keys) < 1 << 32 and len(proof) < 1 << 32):
+        raise ValueError("a count that does not fit 32 bits")
+    if len(commitments) != 64 * (n_in + n_out):
+        raise ValueError("commitments: 64 bytes per value, %d values" % (n_in + n_out))
+    u32 = lambda x: int(x).to_bytes(4, "little")
+    return b"".join([txid, R, s, u32(len(keys))] + keys + [u32(n_in), u32(n_out), commitments, u32(len(proof)), proof])
 
 
 def runtime_hint(apply: bool = True) -> Tuple[int, str]:

@@ -330,6 +330,7 @@ class BlockVerifier:
     TXFORMAT_RETURN_LOG = 0x800            # a flag only beside the one above, with a window K << TXFORMAT_LOG_SHIFT: the log's entries too
     TXFORMAT_LOG_SHIFT = 16                # bits 16 .. 23 of the format: K, the log entries kept per transaction, 1 .. 255
     TXFORMAT_PRECOMPUTE_ONLY = 0x2000      # a flag only beside TXFORMAT_RETURN_IDS, never beside TXFORMAT_SIGN_ON_DEVICE: NOTHING is verified (precompute_txs)
+    TXFORMAT_STATEMENTS_V1 = 4             # a third base format: records of what the caller's own VM left (verify_statements); alone or beside TXFORMAT_SIGN_ON_DEVICE
     TXLOG_INPUT, TXLOG_OUTPUT = 1, 2       # kind bytes of a log record (include/zkgpu.h: ZKGPU_TXLOG_*)
     # status bytes (include/zkgpu.h: ZKGPU_TXSTATUS_*); 16 .. 21 only with TXFORMAT_RECOLLECTED_V1_REASONS, lowest code first
     TXSTATUS_ACCEPTED = 0
@@ -371,10 +372,12 @@ class BlockVerifier:
         self._tx_return_ids = bool(fmt & self.TXFORMAT_RETURN_IDS)
         self._tx_log_k = (fmt >> self.TXFORMAT_LOG_SHIFT) & 255 if fmt & self.TXFORMAT_RETURN_LOG else 0
         self._tx_precompute = bool(fmt & self.TXFORMAT_PRECOMPUTE_ONLY)
+        self._tx_word = fmt
 
     _tx_return_ids = False
     _tx_log_k = 0
     _tx_precompute = False
+    _tx_word = 0                           # the word set_tx_format was given last (verify_statements puts it back)
 
     class _TxLayout(NamedTuple):
         """the layout of a call's status array -- status[batch] | id[batch][32] | record[batch][1 + 33 K] -- as a value: what a
@@ -537,6 +540,59 @@ class BlockVerifier:
         finally:
             del self.__dict__["_tx_calls"][call_id]
         return self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
+
+    @staticmethod
+    def _statement_records(records) -> list:
+        """the record list of a statements call, refused here when it cannot be one: the library would read a str's or an int's
+        bytes as a record and answer 16, which hides a caller's mistake"""
+        if isinstance(records, (bytes, bytearray, memoryview, str)) or not hasattr(records, "__iter__"):
+            raise TypeError("records: a sequence of bytes objects (zkvm_amd.pack_statement), one per transaction")
+        out = []
+        for i, r in enumerate(records):
+            if not isinstance(r, (bytes, bytearray, memoryview)):
+                raise TypeError("records[%d] is %s, not bytes (zkvm_amd.pack_statement)" % (i, type(r).__name__))
+            out.append(bytes(r))
+        if len(out) >= 1 << 31:
+            raise ValueError("too many records for one call")
+        return out
+
+    def _statements_format(self, on_device: bool) -> None:
+        self.set_tx_format(self.TXFORMAT_STATEMENTS_V1 | (self.TXFORMAT_SIGN_ON_DEVICE if on_device else 0))
+
+    def verify_statements(self, records: Sequence[bytes], host_threads: int = 0, on_device: bool = False):
+        """upstream's PrecomputedTx::verify behind the CALLER'S OWN VM: records of what that VM left (zkvm_amd.pack_statement) ->
+        (accept bitmap, status bytes).  Sets the format to TXFORMAT_STATEMENTS_V1 -- with on_device=True beside
+        TXFORMAT_SIGN_ON_DEVICE: the MuSig coefficients and the challenge are then formed on the device, same verdicts --, makes
+        one zkgpu_tx_verify_batch call and PUTS BACK the format set_tx_format was given last, whichever way the call ends: a
+        verify_txs afterwards reads transactions under the format it was set up with, never as records.  (The format is the
+        verifier's: not to be raced with another thread's calls on the same BlockVerifier.)  bit = every key decodes and s B = R + c X and the cloak proof verifies; the status bytes
+        are always reason codes (tx_errors): 0, 16 (record malformed), 17 .. 19 (proof), 20 (key), 21 (signature), 2 (more keys
+        or values than the library serves: the caller's own verifier must).  The library cannot know whether a record's txid
+        belongs to anything: it is the message the signature is checked over."""
+        recs = self._statement_records(records)
+        before = self._tx_word
+        self._statements_format(on_device)
+        try:
+            bm, st = self._tx_call(b"".join(recs), [len(r) for r in recs], host_threads)
+            return self._tx_result(bm, st, len(recs), False, False)
+        finally:
+            self.set_tx_format(before)
+
+    def submit_statements(self, records: Sequence[bytes], host_threads: int = 0, on_device: bool = False) -> int:
+        """the same through zkgpu_tx_verify_submit -> call id for wait_statements.  The call keeps the format it was queued under,
+        whatever is set afterwards, and its round holds no transaction call and no statements call of the other mode.  The format
+        set_tx_format was given last is put back before this returns."""
+        recs = self._statement_records(records)
+        before = self._tx_word
+        self._statements_format(on_device)
+        try:
+            return self.submit_txs_packed(b"".join(recs), [len(r) for r in recs], host_threads)
+        finally:
+            self.set_tx_format(before)
+
+    def wait_statements(self, call_id: int):
+        """zkgpu_tx_verify_wait for a call made by submit_statements -> (accept bitmap, status bytes) as verify_statements"""
+        return self.wait_txs(call_id)
 
     def tx_stats(self):
         """zkgpu_tx_verify_stats -> (rounds the engine has run, calls they held in all)"""
