@@ -171,3 +171,42 @@ def test_a_rounds_hand_out(host, calls, ok):
         else:
             assert got == bytes(OUTSIDE if s == OUTSIDE else REJECTED for s in status[at: at + b]) + bytes(size - b)
         at, at_bits, at_area = at + b, at_bits + len(want_bits), at_area + size
+
+
+PRE, STATEMENTS = 0x2000, 4
+ROUND_WORDS = [0, 1, 2, 1 | HASH, 2 | HASH | SIGN, 1 | IDS, 2 | HASH | IDS | PRE, 1 | IDS | PRE, STATEMENTS, STATEMENTS | SIGN]
+
+
+def model_round_key(word):
+    """a submitted call's kind and what it is keyed by: precompute-only by (base, hashing), statements by (signing), anything
+    else verifies -- one key whatever its word"""
+    if word & PRE:
+        return ("precompute", word & 7, bool(word & HASH))
+    if word & 7 == STATEMENTS:
+        return ("statements", bool(word & SIGN))
+    return ("verify",)
+
+
+def model_round_format(first, now):
+    """-> [base, hash, sign, precompute-only, reasons] of the round whose first call was submitted under `first`, started under `now`"""
+    kind = model_round_key(first)[0]
+    if kind == "precompute":                                # as its calls were queued; never signs on the device
+        return [first & 7, int(bool(first & HASH)), 0, 1, int(first & 7 == 2)]
+    if kind == "statements":                                # base 4 and the signing switch its calls were queued under
+        return [STATEMENTS, 0, int(bool(first & SIGN)), 0, 1]
+    word = first if now & 7 == STATEMENTS else now          # the format in force now -- its bytes are transactions, though
+    return [word & 7, int(bool(word & HASH)), int(bool(word & SIGN)), 0, int(word & 7 == 2)]
+
+
+def test_the_round_rule_of_calls_in_flight(host):
+    """tx_round_mates / tx_round_format (what the engine of zkgpu_tx_verify_submit asks) over every triple of words -- the round's
+    first call's, the one in force when the round starts, a candidate's -- against the rule written out above"""
+    assert all(model_valid(w & ~PRE) for w in ROUND_WORDS if w & 7 != STATEMENTS)
+    for first in ROUND_WORDS:
+        for now in ROUND_WORDS:
+            for candidate in ROUND_WORDS:
+                rc, out = call(host, 6, [first, now, candidate])
+                assert rc == 0, (hex(first), hex(now), hex(candidate))
+                assert out[0] == int(model_round_key(candidate) == model_round_key(first)), (hex(first), hex(candidate))
+                assert out[1:6] == model_round_format(first, now), (hex(first), hex(now))
+    assert call(host, 6, [1, 2, SIGN | 1])[0] == -1         # (a word the format refuses)

@@ -1090,11 +1090,10 @@ bool add_terms(ge& acc, const uint8_t* sc, const uint8_t* pt, uint64_t lo, uint6
 
 class HostTxDevice : public TxDevice {
  public:
-  // format: of it the stand-ins read what the caller is handed (out: the IDs, the log's window); whether a stand-in hashes
-  // or chains is its class
-  HostTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int fail_at,
-               const TxFormat& format = TxFormat())
-      : txs_(txs), offs_(offs), batch_(batch), proof_ok_(proof_ok), rng_(seed), fail_at_(fail_at), out_(format.out) {
+  // format: the mode of the call the stand-in serves, handed to TxCall as it is (format()); a stand-in answers no question about
+  // the mode itself.  Its CLASS must be the one the format calls for: this one neither hashes nor chains (stand_in_format)
+  HostTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int fail_at, const TxFormat& format)
+      : txs_(txs), offs_(offs), batch_(batch), proof_ok_(proof_ok), rng_(seed), fail_at_(fail_at), format_(format) {
     ge B;
     B.X = fe_BASE_X(); B.Y = fe_BASE_Y(); B.Z = fe_one(); B.T = fe_BASE_T();
     encode_point(base_, B);
@@ -1205,10 +1204,7 @@ class HostTxDevice : public TxDevice {
     return 0;
   }
   std::string last_error() override { return err_.empty() ? "injected device fault" : err_; }
-  // a caller that is handed the transaction IDs (ZKGPU_TXFORMAT_RETURN_IDS), and the log's entries, at most log_k() per
-  // transaction (ZKGPU_TXFORMAT_RETURN_LOG; only with ids)
-  bool ids() const override { return out_.ids; }
-  size_t log_k() const override { return out_.ids ? out_.log_k : 0; }
+  const TxFormat& format() const override { return format_; }
   size_t leaked() { std::lock_guard<std::mutex> lk(mu_); return staged_total_ - released_total_; }
 
  protected:
@@ -1239,8 +1235,15 @@ class HostTxDevice : public TxDevice {
   size_t staged_total_ = 0, released_total_ = 0;
   uint8_t base_[32];
   std::string err_;
-  const TxOutLayout out_;
+  const TxFormat format_;
 };
+// the format of a verifying call for the stand-in of `kind` -- 0 HostTxDevice, 1 hashing, 2 chaining: base 1 and the device
+// switches that class serves; out: what the caller is handed
+TxFormat stand_in_format(int kind, const TxOutLayout& out = TxOutLayout()) {
+  TxFormat f;
+  f.base = TXFORMAT_V1; f.hash_on_device = kind >= 1; f.sign_on_device = kind >= 2; f.out = out;
+  return f;
+}
 }  // namespace
 
 // One call over a stand-in device, fail-closed in both outputs.  -> the call's return code; *n_chunks, *n_sig_stages: what was
@@ -1266,7 +1269,7 @@ int txcall_selftest(HostTxDevice& dev, size_t batch, const uint8_t* txs, const u
 extern "C" int zkhost_txcall_selftest(size_t batch, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok, int host_threads,
                                       size_t chunk, uint32_t delay_seed, int fail_at, uint8_t* accept_bitmap, uint8_t* status,
                                       size_t* n_chunks, size_t* n_sig_stages, size_t* leaked) {
-  HostTxDevice dev(txs, offs, batch, proof_ok, delay_seed, fail_at);
+  HostTxDevice dev(txs, offs, batch, proof_ok, delay_seed, fail_at, stand_in_format(0));
   return txcall_selftest(dev, batch, txs, offs, host_threads, chunk, 2, accept_bitmap, status, n_chunks, n_sig_stages, leaked);
 }
 
@@ -1286,7 +1289,7 @@ extern "C" int zkhost_txcall_pair_selftest(size_t batch, size_t split, const uin
   int rc_all = 0;
   size_t leaked_all = 0;
   {
-    HostTxDevice dev0(txs, offs, batch, proof_ok, delay_seed, -1), dev1(txs, offs, batch, proof_ok, delay_seed + 1, -1);
+    HostTxDevice dev0(txs, offs, batch, proof_ok, delay_seed, -1, stand_in_format(0)), dev1(txs, offs, batch, proof_ok, delay_seed + 1, -1, stand_in_format(0));
     std::vector<TxCall::Piece> p0{{txs, offs, split}}, p1{{txs, offs + split, batch - split}};
     // (the second call's offsets are still relative to `txs`: Piece = base pointer + its own offsets)
     TxCall c0(dev0, store[0], (size_t)1 << 17, p0, host_threads, chunk, bits[0].data(), status, 1);
@@ -1380,17 +1383,15 @@ extern "C" long long zkhost_tx_hash_tape(const uint8_t* txs, const uint64_t* off
   return (long long)tape.n_tx();
 }
 
-// ---- the scheduling of a FLAGGED call (a device that hashes: TxDevice::hashes) on the CPU: the stand-in above, and the
+// ---- the scheduling of a FLAGGED call (a format that hashes: TxFormat::hashes) on the CPU: the stand-in above, and the
 // ---- tapes of the chunks interpreted by tx_hash_run on a thread of their own after a random delay.  hash_fail_at: the
 // ---- n-th hash_enqueue / hash_collect reports an error (-1: none).  *hashed: transaction IDs the stand-in produced.
 namespace {
 class HostHashingTxDevice : public HostTxDevice {
  public:
-  HostHashingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int hash_fail_at,
-                      int fail_at = -1, const TxFormat& format = TxFormat())
+  HostHashingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int hash_fail_at, int fail_at, const TxFormat& format)
       : HostTxDevice(txs, offs, batch, proof_ok, seed, fail_at, format), hrng_(seed ^ 0x9e3779b9u), hash_fail_at_(hash_fail_at) { hash_tape_constants(protos_, labels_); }
   ~HostHashingTxDevice() override { for (auto& s : h_) if (s.th.joinable()) s.th.join(); }
-  bool hashes() const override { return true; }
   TxHashTape* hash_tape(int slot) override { return &h_[slot].tape; }
   int hash_enqueue(int slot, const TxHashTape& tape) override {
     HashStage& s = h_[slot];
@@ -1403,7 +1404,7 @@ class HostHashingTxDevice : public HostTxDevice {
       std::this_thread::sleep_for(std::chrono::microseconds(us));
       hash_tape_run_host(s.tape.block(), protos_, labels_, s.slots, s.ids);
       // (the caller is handed the log: what k_tx_log_gather does, lane by lane, with the table the device would be sent)
-      const size_t K = log_k();
+      const size_t K = format_.log_k();
       s.log_ok = true;
       if (K && s.tape.n_tx()) {
         std::vector<uint32_t> table;
@@ -1430,7 +1431,7 @@ class HostHashingTxDevice : public HostTxDevice {
   std::string last_error() override { return herr_.empty() ? HostTxDevice::last_error() : herr_; }
   uint64_t hashed() const { return hashed_; }
   uint64_t id_asks() const { return id_asks_; }           // collects that were given a host buffer for the IDs
-  const uint8_t* hash_log(int slot) override { return log_k() && h_[slot].log_ok ? (const uint8_t*)h_[slot].log.data() : nullptr; }
+  const uint8_t* hash_log(int slot) override { return format_.log_k() && h_[slot].log_ok ? (const uint8_t*)h_[slot].log.data() : nullptr; }
   uint64_t logged() const { return logged_; }             // log entries the stand-in's gather handed back
 
  protected:
@@ -1451,7 +1452,7 @@ class HostHashingTxDevice : public HostTxDevice {
 extern "C" int zkhost_txcall_hashing_selftest(size_t batch, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok, int host_threads,
                                               size_t chunk, uint32_t delay_seed, int hash_fail_at, int n_slots, uint8_t* accept_bitmap,
                                               uint8_t* status, size_t* n_chunks, size_t* leaked, uint64_t* hashed) {
-  HostHashingTxDevice dev(txs, offs, batch, proof_ok, delay_seed, hash_fail_at);
+  HostHashingTxDevice dev(txs, offs, batch, proof_ok, delay_seed, hash_fail_at, -1, stand_in_format(1));
   size_t n_sig_stages;
   const int rc = txcall_selftest(dev, batch, txs, offs, host_threads, chunk, n_slots, accept_bitmap, status, n_chunks, &n_sig_stages, leaked);
   *hashed = dev.hashed();
@@ -1523,17 +1524,16 @@ extern "C" long long zkhost_tx_sig_rows(const uint8_t* txs, const uint64_t* offs
   return (long long)live.size();
 }
 
-// ---- the scheduling of a call that CHAINS (TxDevice::chains) on the CPU: the hashing stand-in above, plus a signature stage
+// ---- the scheduling of a call that CHAINS (TxFormat::chains) on the CPU: the hashing stand-in above, plus a signature stage
 // ---- that waits -- on its own thread, as the device waits on events -- for the key stage of key_slot and the tape of hash_slot,
 // ---- forms the challenges with tx_sig_row and then checks the rows like the unchained stage.  sig_fail_at: the n-th
 // ---- chained sigs_enqueue / sigs_collect reports an error (-1: none).  *signed_rows: rows whose challenge the stand-in produced.
 namespace {
 class HostChainingTxDevice : public HostHashingTxDevice {
  public:
-  HostChainingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int sig_fail_at,
-                       int hash_fail_at = -1, int fail_at = -1, const TxFormat& format = TxFormat())
+  HostChainingTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int sig_fail_at, int hash_fail_at, int fail_at,
+                       const TxFormat& format)
       : HostHashingTxDevice(txs, offs, batch, proof_ok, seed, hash_fail_at, fail_at, format), crng_(seed ^ 0x51ed270bu), sig_fail_at_(sig_fail_at) { have_script_ = sig_script(script_); }
-  bool chains() const override { return true; }
   int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc, const SigChain* chain) override {
     if (!chain) { cerr_ = "an unchained signature stage on a device that chains"; return -1; }
     const uint32_t* tape_pos = chain->tape_pos;
@@ -1590,15 +1590,15 @@ extern "C" int zkhost_txcall_chaining_selftest(size_t batch, const uint8_t* txs,
                                                size_t chunk, uint32_t delay_seed, int sig_fail_at, int n_slots, uint8_t* accept_bitmap,
                                                uint8_t* status, size_t* n_chunks, size_t* n_sig_stages, size_t* leaked, uint64_t* hashed,
                                                uint64_t* signed_rows) {
-  HostChainingTxDevice dev(txs, offs, batch, proof_ok, delay_seed, sig_fail_at);
+  HostChainingTxDevice dev(txs, offs, batch, proof_ok, delay_seed, sig_fail_at, -1, -1, stand_in_format(2));
   const int rc = txcall_selftest(dev, batch, txs, offs, host_threads, chunk, n_slots, accept_bitmap, status, n_chunks, n_sig_stages, leaked);
   *hashed = dev.hashed();
   *signed_rows = dev.signed_rows();
   return rc;
 }
 
-// ---- a call whose caller is handed more than bits and status bytes -- the transaction IDs (TxDevice::ids: ZKGPU_TXFORMAT_RETURN_IDS),
-// ---- the log's entries (TxDevice::log_k: ZKGPU_TXFORMAT_RETURN_LOG) -- on the CPU, over any of the three stand-ins above, with the
+// ---- a call whose caller is handed more than bits and status bytes -- the transaction IDs (TxFormat::ids: ZKGPU_TXFORMAT_RETURN_IDS),
+// ---- the log's entries (TxFormat::log_k: ZKGPU_TXFORMAT_RETURN_LOG) -- on the CPU, over any of the three stand-ins above, with the
 // ---- LIBRARY's own layout code (tx_out.hpp): begin, piece, the round's hand-out and the fail-closed clean-up are the functions
 // ---- session.hpp calls.  kind 0: HostTxDevice, 1: hashing, 2: chaining.  fail_at: the n-th operation of stage fail_stage fails
 // ---- (-1: none) -- 0 keys / proofs / unchained signatures, 1 the hashing stage, 2 the chained signature stage.
@@ -1620,7 +1620,7 @@ int tx_out_selftest(int kind, TxOutLayout la, TxOutLayout lb, size_t batch, size
                     uint8_t* status_a, uint8_t* status_b, TxOutSelftest& t) {
   if (kind < 0 || kind > 2 || fail_stage < 0 || fail_stage > kind || !status_a || (split && (split >= batch || split % 8 || !status_b))) return -1;
   const size_t na = split ? split : batch, nb = split ? batch - split : 0;
-  TxFormat format;                                       // (the round's device brings back what the wider of its calls asks for)
+  TxFormat format = stand_in_format(kind);               // (the round's device brings back what the wider of its calls asks for)
   format.out.ids = la.ids || (nb && lb.ids);
   format.out.log_k = std::max(la.log_k, nb ? lb.log_k : 0);
   const std::unique_ptr<HostTxDevice> dev = tx_stand_in(kind, fail_stage, fail_at, txs, offs, batch, proof_ok, delay_seed, format);
@@ -1700,14 +1700,25 @@ extern "C" int zkhost_txcall_log_selftest(int kind, size_t K, size_t k_b, size_t
 // ---- byte / ID / record of transaction in[3] and of a piece's ID / record areas (-1: not there), the piece's window; op 2 begin,
 // ---- 3 nothing-in-the-subset, 4 fail-closed over bitmap and area (either may be NULL).  op 5, a round's hand-out: in[0] calls,
 // ---- in[1] ok, then (ids, K, batch) per call; bitmap / area hold the ROUND's bits / status bytes, out_bits / out_area the
-// ---- calls' bitmaps ((batch + 7) / 8 bytes each) and areas one behind the other.  -> 0, -1 on bad arguments
+// ---- calls' bitmaps ((batch + 7) / 8 bytes each) and areas one behind the other.  op 6, the round rule (tx_round_mates,
+// ---- tx_round_format): in[0] the word the round's first call was submitted under, in[1] the word in force now, in[2] the word a
+// ---- candidate was submitted under (all three valid) -> out: does the candidate share the round, then the round format's base,
+// ---- hash, sign, precompute-only, reasons.  -> 0, -1 on bad arguments
 extern "C" int zkhost_tx_out_layout(int op, const int64_t* in, uint8_t* bitmap, uint8_t* area, uint8_t* out_bits, uint8_t* out_area, int64_t* out) {
-  if (!in || op < 0 || op > 5 || (op <= 1 && !out)) return -1;
+  if (!in || op < 0 || op > 6 || ((op <= 1 || op == 6) && !out)) return -1;
   const auto layout = [](const int64_t* q) { TxOutLayout l; l.ids = q[0] != 0; l.log_k = (size_t)q[1]; return l; };
   if (op == 0) {
     TxFormat f;
     const int64_t r[7] = {TxFormat::of((int)in[0], &f), f.base, f.hash_on_device, f.sign_on_device, f.out.ids, (int64_t)f.out.log_k, f.precompute_only};
     std::copy(r, r + 7, out);
+    return 0;
+  }
+  if (op == 6) {
+    TxFormat first, now, candidate;
+    if (!TxFormat::of((int)in[0], &first) || !TxFormat::of((int)in[1], &now) || !TxFormat::of((int)in[2], &candidate)) return -1;
+    const TxFormat f = tx_round_format(first, now);
+    const int64_t r[6] = {tx_round_mates(candidate, first), f.base, f.hash_on_device, f.sign_on_device, f.precompute_only, f.reasons()};
+    std::copy(r, r + 6, out);
     return 0;
   }
   if (op == 5) {
@@ -1824,7 +1835,7 @@ extern "C" long long zkhost_tx_hash_levels(const uint8_t* txs, const uint64_t* o
   return (long long)tape.n_tx();
 }
 
-// ---- a PRECOMPUTE-ONLY call (TxDevice::precompute: ZKGPU_TXFORMAT_PRECOMPUTE_ONLY) on the CPU: TxCall over a stand-in that
+// ---- a PRECOMPUTE-ONLY call (TxFormat::precompute: ZKGPU_TXFORMAT_PRECOMPUTE_ONLY) on the CPU: TxCall over a stand-in that
 // ---- hashes (hashing = 1: the tapes interpreted as above, hash_fail_at as there) or not, with reasons (format 2) or without, the
 // ---- caller handed IDs and, K > 0, the log -- and that COUNTS every key, proof and signature operation it is asked for: there
 // ---- must be none.  status is laid out by tx_out.hpp (33 + (K ? 1 + 33 K : 0) bytes per transaction), begun and fail-closed as
@@ -1834,11 +1845,8 @@ extern "C" long long zkhost_tx_hash_levels(const uint8_t* txs, const uint64_t* o
 namespace {
 class HostPrecomputeTxDevice : public HostHashingTxDevice {
  public:
-  HostPrecomputeTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, uint32_t seed, bool hashing, bool reasons, int hash_fail_at, const TxFormat& format)
-      : HostHashingTxDevice(txs, offs, batch, nullptr, seed, hash_fail_at, -1, format), hashing_(hashing), reasons_(reasons) {}
-  bool precompute() const override { return true; }
-  bool hashes() const override { return hashing_; }
-  bool reasons() const override { return reasons_; }
+  HostPrecomputeTxDevice(const uint8_t* txs, const uint64_t* offs, size_t batch, uint32_t seed, int hash_fail_at, const TxFormat& format)
+      : HostHashingTxDevice(txs, offs, batch, nullptr, seed, hash_fail_at, -1, format) {}
   int keys_enqueue(int, const uint8_t*, const uint8_t*, const uint64_t*, size_t) override { return asked(); }
   int keys_collect(int, uint8_t*, uint8_t*, uint8_t*) override { return asked(); }
   int proofs_stage(size_t, size_t, const TxProofSource*, int, void**, std::string*) override { return asked(); }
@@ -1851,7 +1859,6 @@ class HostPrecomputeTxDevice : public HostHashingTxDevice {
 
  private:
   int asked() { ++stage_ops_; return -1; }
-  const bool hashing_, reasons_;
   std::atomic<uint64_t> stage_ops_{0};
 };
 }  // namespace
@@ -1865,7 +1872,7 @@ extern "C" int zkhost_txcall_precompute_selftest(int hashing, int reasons, size_
   format.base = reasons ? TXFORMAT_V1_REASONS : TXFORMAT_V1;
   format.hash_on_device = hashing != 0; format.precompute_only = true;
   format.out.ids = true; format.out.log_k = K;
-  HostPrecomputeTxDevice dev(txs, offs, batch, delay_seed, hashing != 0, reasons != 0, hash_fail_at, format);
+  HostPrecomputeTxDevice dev(txs, offs, batch, delay_seed, hash_fail_at, format);
   format.out.begin(accept_bitmap, status, batch);
   std::vector<TxStatement> store;
   int rc;
@@ -1971,29 +1978,26 @@ extern "C" long long zkhost_musig_recipe_compare(const uint8_t* tx, size_t len) 
   return at == rec.jobs.size() && at == k ? (long long)at : -1;
 }
 
-// ---- the scheduling of a statements call (TxCall::step_statements) on the CPU: the stand-in of zkhost_txcall_selftest that
-// ---- says statements(), refuses every hashing operation, and -- on_device -- forms the coefficients itself: a key stage that
+// ---- the scheduling of a statements call (TxCall::step_statements) on the CPU: the stand-in of zkhost_txcall_selftest under a
+// ---- statements format, which refuses every hashing operation and -- forms_musig() -- forms the coefficients itself: a key stage that
 // ---- arrives as points alone (musig_row with skip 0, then the stage), a signature stage that arrives as a chain with the host's
 // ---- IDs (musig_row with skip 1, tx_sig_row over those IDs once the slot's key stage is through, then the equations).
 namespace {
 class HostStatementsTxDevice : public HostTxDevice {
  public:
-  HostStatementsTxDevice(const uint8_t* recs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int fail_at, bool on_device, bool reasons)
-      : HostTxDevice(recs, offs, batch, proof_ok, seed, fail_at), on_device_(on_device), reasons_(reasons), srng_(seed ^ 0x3c6ef372u) {
+  HostStatementsTxDevice(const uint8_t* recs, const uint64_t* offs, size_t batch, const uint8_t* proof_ok, uint32_t seed, int fail_at, const TxFormat& format)
+      : HostTxDevice(recs, offs, batch, proof_ok, seed, fail_at, format), srng_(seed ^ 0x3c6ef372u) {
     have_scripts_ = musig_script(musig_) && sig_script(script_);
   }
-  bool statements() const override { return true; }
-  bool forms_musig() const override { return on_device_; }
-  bool reasons() const override { return reasons_; }
   TxHashTape* hash_tape(int) override { ++hash_asks_; return nullptr; }
   int hash_enqueue(int, const TxHashTape&) override { ++hash_asks_; return -1; }
   int hash_collect(int, uint8_t*) override { ++hash_asks_; return -1; }
   int keys_enqueue(int slot, const uint8_t* sc, const uint8_t* pt, const uint64_t* off, size_t rows) override {
-    if (on_device_) { err_ = "a key stage with scalars on a device that forms them"; return -1; }
+    if (format_.forms_musig()) { err_ = "a key stage with scalars on a device that forms them"; return -1; }
     return HostTxDevice::keys_enqueue(slot, sc, pt, off, rows);
   }
   int keys_enqueue_formed(int slot, const uint8_t* pt, const uint64_t* off, size_t rows) override {
-    if (!on_device_ || !have_scripts_) { err_ = "a key stage without scalars on a device that does not form them"; return -1; }
+    if (!format_.forms_musig() || !have_scripts_) { err_ = "a key stage without scalars on a device that does not form them"; return -1; }
     std::vector<uint8_t>& sc = formed_[slot];
     sc.assign(32 * off[rows], 0);
     if (zkhost_musig_rows(sc.data(), pt, off, rows, 0, nullptr) != 0) { err_ = "a key row without a key"; return -1; }
@@ -2012,7 +2016,7 @@ class HostStatementsTxDevice : public HostTxDevice {
   }
   int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc, const SigChain* chain) override {
     sig_rows_[slot] = rows;
-    if (!on_device_) return HostTxDevice::sigs_enqueue(slot, rows, dsc, dpt, doff, bsc, chain);
+    if (!format_.forms_musig()) return HostTxDevice::sigs_enqueue(slot, rows, dsc, dpt, doff, bsc, chain);
     if (!chain || !chain->txids || !have_scripts_) { err_ = "a signature stage of a device that forms the coefficients without the host's IDs"; return -1; }
     if (failing()) return -3;
     Stage& s = sigs_[slot];
@@ -2052,7 +2056,6 @@ class HostStatementsTxDevice : public HostTxDevice {
   uint64_t formed_rows() const { return formed_rows_; }
 
  private:
-  const bool on_device_, reasons_;
   std::mt19937 srng_;
   MusigScript musig_;
   SigScript script_;
@@ -2072,7 +2075,9 @@ extern "C" int zkhost_txcall_statements_selftest(int on_device, int reasons, siz
                                                  uint8_t* status, uint64_t* out) {
   for (int q = 0; q < 5; ++q) out[q] = 0;
   if (!accept_bitmap || !recs || !offs || !proof_ok) return -1;
-  HostStatementsTxDevice dev(recs, offs, batch, proof_ok, delay_seed, fail_at, on_device != 0, reasons != 0);
+  TxFormat format;
+  format.base = TXFORMAT_STATEMENTS_V1; format.sign_on_device = on_device != 0; format.mute = reasons == 0;
+  HostStatementsTxDevice dev(recs, offs, batch, proof_ok, delay_seed, fail_at, format);
   TxOutLayout().begin(accept_bitmap, status, batch);
   std::vector<TxStatement> store;
   int rc;
@@ -2085,4 +2090,105 @@ extern "C" int zkhost_txcall_statements_selftest(int on_device, int reasons, siz
   out[1] = dev.leaked(); out[2] = dev.hash_asks(); out[4] = dev.formed_rows();
   if (rc != 0) TxOutLayout().fail_closed(accept_bitmap, status, batch);
   return rc;
+}
+
+// ---- WHAT THE DEVICE IS ASKED, recorded (tests/test_tx_call_sequences.py holds it against tests/golden/tx_call_sequences.json):
+// ---- a wrapper that forwards every call of TxCall to a stand-in and notes, in the order they arrive, (operation, slot or ring
+// ---- slot, rows, detail).  rows of a collect: those of the stage that was queued in the slot; detail: the terms of a key stage,
+// ---- 0 / 1 / 2 for a signature stage with final scalars / chained to a tape / chained with the host's IDs, 1 for a hash_collect
+// ---- that was given a host buffer.  (proofs_stage comes from the staging thread: the list has a lock of its own.)
+#include <map>
+namespace {
+class TracingTxDevice : public TxDevice {
+ public:
+  enum Op : int64_t { KEYS_ENQUEUE, KEYS_ENQUEUE_FORMED, KEYS_COLLECT, PROOFS_STAGE, PROOFS_START, PROOFS_FINISH, SIGS_ENQUEUE, SIGS_COLLECT, HASH_ENQUEUE, HASH_COLLECT };
+  explicit TracingTxDevice(TxDevice& in) : in_(in) {}
+  const std::vector<int64_t>& trace() const { return trace_; }
+  const uint8_t* basepoint() override { return in_.basepoint(); }
+  int keys_enqueue(int slot, const uint8_t* sc, const uint8_t* pt, const uint64_t* off, size_t rows) override {
+    key_rows_[slot] = rows;
+    saw(KEYS_ENQUEUE, slot, rows, off[rows]);
+    return in_.keys_enqueue(slot, sc, pt, off, rows);
+  }
+  int keys_enqueue_formed(int slot, const uint8_t* pt, const uint64_t* off, size_t rows) override {
+    key_rows_[slot] = rows;
+    saw(KEYS_ENQUEUE_FORMED, slot, rows, off[rows]);
+    return in_.keys_enqueue_formed(slot, pt, off, rows);
+  }
+  bool keys_done(int slot) override { return in_.keys_done(slot); }
+  int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values, uint8_t* why) override {
+    saw(KEYS_COLLECT, slot, key_rows_[slot], 0);
+    return in_.keys_collect(slot, ok_bits, values, why);
+  }
+  int proofs_stage(size_t ring_slot, size_t n, const TxProofSource* src, int host_threads, void** handle, std::string* err) override {
+    const int rc = in_.proofs_stage(ring_slot, n, src, host_threads, handle, err);
+    std::lock_guard<std::mutex> lk(mu_);
+    if (rc == 0) staged_[*handle] = {ring_slot, n};
+    note(PROOFS_STAGE, ring_slot, n, 0);
+    return rc;
+  }
+  int proofs_start(size_t ring_slot, void* handle) override { saw(PROOFS_START, ring_slot, staged(handle).second, 0); return in_.proofs_start(ring_slot, handle); }
+  bool proofs_done(void* handle) override { return in_.proofs_done(handle); }
+  int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t* why) override {
+    const auto at = staged(handle);
+    saw(PROOFS_FINISH, at.first, at.second, 0);
+    return in_.proofs_finish(handle, accept_bits, why);
+  }
+  void proofs_release(void* handle) override { in_.proofs_release(handle); }
+  int sigs_enqueue(int slot, size_t rows, const uint8_t* dsc, const uint8_t* dpt, const uint64_t* doff, const uint8_t* bsc, const SigChain* chain) override {
+    sig_rows_[slot] = rows;
+    saw(SIGS_ENQUEUE, slot, rows, !chain ? 0 : chain->txids ? 2 : 1);
+    return in_.sigs_enqueue(slot, rows, dsc, dpt, doff, bsc, chain);
+  }
+  bool sigs_done(int slot) override { return in_.sigs_done(slot); }
+  int sigs_collect(int slot, uint8_t* bits, uint8_t* why) override { saw(SIGS_COLLECT, slot, sig_rows_[slot], 0); return in_.sigs_collect(slot, bits, why); }
+  std::string last_error() override { return in_.last_error(); }
+  TxHashTape* hash_tape(int slot) override { return in_.hash_tape(slot); }
+  int hash_enqueue(int slot, const TxHashTape& tape) override {
+    hash_rows_[slot] = tape.n_tx();
+    saw(HASH_ENQUEUE, slot, tape.n_tx(), 0);
+    return in_.hash_enqueue(slot, tape);
+  }
+  bool hash_done(int slot) override { return in_.hash_done(slot); }
+  int hash_collect(int slot, uint8_t* txids) override { saw(HASH_COLLECT, slot, hash_rows_[slot], txids != nullptr); return in_.hash_collect(slot, txids); }
+  const uint8_t* hash_log(int slot) override { return in_.hash_log(slot); }
+  const TxFormat& format() const override { return in_.format(); }
+
+ private:
+  void note(int64_t op, size_t slot, size_t rows, uint64_t detail) { const int64_t e[4] = {op, (int64_t)slot, (int64_t)rows, (int64_t)detail}; trace_.insert(trace_.end(), e, e + 4); }     // (mu_ held)
+  void saw(int64_t op, size_t slot, size_t rows, uint64_t detail) { std::lock_guard<std::mutex> lk(mu_); note(op, slot, rows, detail); }
+  std::pair<size_t, size_t> staged(void* handle) { std::lock_guard<std::mutex> lk(mu_); return staged_[handle]; }
+  TxDevice& in_;
+  std::mutex mu_;
+  std::vector<int64_t> trace_;
+  std::map<void*, std::pair<size_t, size_t>> staged_;      // a staged chunk's ring slot and proofs
+  size_t key_rows_[2] = {0, 0}, sig_rows_[2] = {0, 0}, hash_rows_[2] = {0, 0};
+};
+}  // namespace
+
+// One CLEAN call (no injected fault) under the format word `word` over the stand-in the word calls for -- transactions, or for
+// the statements words their records -- and what the device was asked.  out: the trace, four values per operation, `cap`
+// operations of room; plan[0] chunks, plan[1] signature stages planned.  -> operations noted, or -1 bad arguments (a word that
+// is refused or enables nothing among them), -2 the call failed, -3 more than `cap` operations
+extern "C" long long zkhost_txcall_trace(int word, int n_slots, size_t chunk, size_t batch, const uint8_t* txs, const uint64_t* offs, const uint8_t* proof_ok,
+                                         int host_threads, uint32_t delay_seed, int64_t* out, size_t cap, uint64_t* plan) {
+  TxFormat format;
+  if (!TxFormat::of(word, &format) || format.base == 0 || !txs || !offs || !proof_ok || !out || !plan) return -1;
+  std::unique_ptr<HostTxDevice> dev;
+  if (format.statements()) dev.reset(new HostStatementsTxDevice(txs, offs, batch, proof_ok, delay_seed, -1, format));
+  else if (format.precompute()) dev.reset(new HostPrecomputeTxDevice(txs, offs, batch, delay_seed, -1, format));
+  else dev = tx_stand_in(format.chains() ? 2 : format.hashes() ? 1 : 0, 0, -1, txs, offs, batch, proof_ok, delay_seed, format);
+  TracingTxDevice traced(*dev);
+  std::vector<uint8_t> bitmap((batch + 7) / 8 + 1), status(format.out.bytes(batch));
+  format.out.begin(bitmap.data(), status.data(), batch);
+  std::vector<TxStatement> store;
+  {
+    TxCall call(traced, store, (size_t)1 << 17, batch, txs, offs, host_threads, chunk, bitmap.data(), status.data(), n_slots);
+    plan[0] = call.n_chunks(); plan[1] = call.n_sig_stages_planned();
+    if (call.run() != 0) return -2;
+  }
+  const size_t n = traced.trace().size() / 4;
+  if (n > cap) return -3;
+  std::copy(traced.trace().begin(), traced.trace().end(), out);
+  return (long long)n;
 }

@@ -169,16 +169,10 @@ struct zkgpu_verifier {
     int host_threads = 0;
     int state = 0, rc = 0;                              // 0 queued, 1 in a round, 2 done
     std::chrono::steady_clock::time_point arrived;      // (the engine lets a small queue wait a little while a round is running)
-    zk::zkvm::TxOutLayout layout;                       // of its status argument, as the format said when it was SUBMITTED
-    // ... and its KIND: 0 a verifying call (base format and device switches are the round's, read when it starts, as they always
-    // were); a precompute-only call: ZKGPU_TXFORMAT_PRECOMPUTE_ONLY | the base format | ZKGPU_TXFORMAT_HASH_ON_DEVICE as the
-    // format said them when it was submitted.  A round holds calls of ONE kind and, precompute-only, runs under it
-    // a statements call (ZKGPU_TXFORMAT_STATEMENTS_V1): the word it was submitted under, 4 or 4 | ZKGPU_TXFORMAT_SIGN_ON_DEVICE -- a
-    // round never holds statements calls beside transaction calls, nor calls queued under the one word beside the other's.
-    // word: the whole format word at submit time (read for a verifying call only when the statements format is in force by
-    // the time its round starts)
-    int kind = 0, word = 0;
-    std::vector<uint8_t> bits, area;                   // its bitmap; its status argument, layout.bytes(batch), as wait will copy it out
+    // the format in force when the call was SUBMITTED: submitted.out lays out its status argument, and tx_round_mates /
+    // tx_round_format (tx_out.hpp) say from it which calls share its round and what that round runs under
+    zk::zkvm::TxFormat submitted;
+    std::vector<uint8_t> bits, area;                   // its bitmap; its status argument, submitted.out.bytes(batch), as wait will copy it out
   };
   std::mutex tx_mu;
   std::condition_variable tx_cv;
@@ -1959,7 +1953,7 @@ void tx_engine_main(zkgpu_verifier* v) {
         TxRound& r = *fresh[set];
         // (a round holds calls of ONE kind: a precompute-only call never shares a round with a verifying one)
         while (!v->tx_queue.empty() && (r.calls.empty() || (r.total + v->tx_queue.front()->batch <= v->tx_merge_max &&
-                                                            v->tx_queue.front()->kind == r.calls.front()->kind))) {
+                                                            tx_round_mates(v->tx_queue.front()->submitted, r.calls.front()->submitted)))) {
           r.calls.push_back(v->tx_queue.front());
           r.total += r.calls.back()->batch;
           r.calls.back()->state = 1;
@@ -1976,27 +1970,18 @@ void tx_engine_main(zkgpu_verifier* v) {
       int threads = 0;
       // (every call has its own area, laid out as the format said when it was submitted and "nothing accepted" until verdicts()
       // writes beside a set bit; the round's device brings back what the widest of them asks for)
-      TxFormat format = TxFormat::of_valid(v->tx_format.load());
-      format.out = TxOutLayout();
-      // (the kind is the calls', as the layout is: a precompute-only round runs under the base format and the hashing switch its
-      // calls were queued under, whatever the format says by now, and never chains)
-      // (a statements round likewise runs under what its calls were QUEUED under -- the base and the signing switch; and a round of
-      // transaction calls that finds the statements format in force by now runs under the word its first call was queued under:
-      // its bytes are transactions, whatever the format says meanwhile)
-      const int kind = r.calls.front()->kind;
-      const bool kind_statements = kind != 0 && (kind & TXFORMAT_PRECOMPUTE_ONLY) == 0;
-      if (kind == 0 && format.statements()) { format = TxFormat::of_valid(r.calls.front()->word); format.out = TxOutLayout(); }
-      format.precompute_only = kind != 0 && !kind_statements;
-      if (kind_statements) { format = TxFormat::of_valid(kind); format.out = TxOutLayout(); }
-      else if (kind) { format.base = kind & 3; format.hash_on_device = (kind & TXFORMAT_HASH_ON_DEVICE) != 0; format.sign_on_device = false; }
+      // (the kind is the calls', as the layout is -- tx_round_format: a precompute-only or a statements round runs under what its
+      // calls were QUEUED under, a verifying round under the format in force now)
+      TxFormat format = tx_round_format(r.calls.front()->submitted, TxFormat::of_valid(v->tx_format.load()));
       for (auto* p : r.calls) {
         p->bits.resize((p->batch + 7) / 8);
-        p->area.resize(p->layout.bytes(p->batch));
-        p->layout.begin(p->bits.data(), p->area.data(), p->batch);
-        r.pieces.push_back(p->layout.piece(p->txs, p->offsets, p->batch, p->area.data()));
-        r.hand_out.push_back({p->batch, p->layout, p->bits.data(), p->area.data()});
-        format.out.ids |= p->layout.ids;
-        format.out.log_k = std::max(format.out.log_k, p->layout.log_k);
+        const TxOutLayout& layout = p->submitted.out;
+        p->area.resize(layout.bytes(p->batch));
+        layout.begin(p->bits.data(), p->area.data(), p->batch);
+        r.pieces.push_back(layout.piece(p->txs, p->offsets, p->batch, p->area.data()));
+        r.hand_out.push_back({p->batch, layout, p->bits.data(), p->area.data()});
+        format.out.ids |= layout.ids;
+        format.out.log_k = std::max(format.out.log_k, layout.log_k);
         threads = std::max(threads, p->host_threads);
       }
       r.bits.assign((r.total + 7) / 8 + 1, 0);
@@ -2064,12 +2049,7 @@ int zkgpu_tx_verify_submit(zkgpu_verifier* v, size_t batch, const uint8_t* txs, 
   std::unique_ptr<zkgpu_verifier::TxPending> p(new zkgpu_verifier::TxPending());
   p->batch = batch; p->txs = txs; p->offsets = tx_offsets; p->host_threads = host_threads;
   p->arrived = std::chrono::steady_clock::now();
-  const int word_now = v->tx_format.load();
-  const zk::zkvm::TxFormat submitted = zk::zkvm::TxFormat::of_valid(word_now);
-  p->layout = submitted.out;                             // (the layout wait will write: the one in force now; so with the call's kind)
-  if (submitted.precompute_only) p->kind = zk::zkvm::TXFORMAT_PRECOMPUTE_ONLY | submitted.base | (submitted.hash_on_device ? zk::zkvm::TXFORMAT_HASH_ON_DEVICE : 0);
-  if (submitted.statements()) p->kind = zk::zkvm::TXFORMAT_STATEMENTS_V1 | (submitted.sign_on_device ? zk::zkvm::TXFORMAT_SIGN_ON_DEVICE : 0);
-  p->word = word_now;
+  p->submitted = zk::zkvm::TxFormat::of_valid(v->tx_format.load());     // (the layout wait will write is the one in force now; so with the call's kind)
   std::lock_guard<std::mutex> lk(v->tx_mu);
   if (v->tx_engine_quit) return ZKGPU_EINVAL;
   if (!v->tx_engine.joinable()) {

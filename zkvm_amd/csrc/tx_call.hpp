@@ -21,19 +21,23 @@
 //     key stages (two slots, alternating), proofs (a ring of RING staging areas), signature stages (two slots).
 // accept = the VM accepted & the keys decode & the signature holds & the proof verifies; fail-closed in both outputs.
 //
-// A device that brings back REASONS (TxDevice::reasons(): the verifier's format 2) hands every stage's rows one byte each
-// beside the bit; verdicts() then writes, beside every clear bit, the LOWEST code that applies to the transaction -- the
-// order upstream would meet the faults in: decoding and the VM (16, host), r1cs::Verifier::verify (17 .. 19), the keys the
-// signature covers (20), the deferred signature check (21).  The bits are formed exactly as without reasons.
+// THE MODE of a call is one value, the device's TxFormat (tx_out.hpp: dev.format(), the verifier's format word decoded or a
+// stand-in's filled in by hand), and its predicates are the only place that says which flag counts beside which.  TxCall keeps
+// the value (fmt_) and asks it; what also depends on the call's own arguments stays here: reasons_ needs a status array to
+// write to, ids_ / log_k_ a piece with room.  None of the switches has a host fallback: an error of a stage is an error of the call.
 //
-// ONE scheduler, two switches the device sets (format flags of the verifier; neither has a host fallback: an error of a stage is an
-// error of the call):
-//   TxDevice::hashes() (ZKGPU_TXFORMAT_HASH_ON_DEVICE) takes the contract IDs, the anchor ratchets and the transaction-ID tree of
-//     every chunk off the staging thread: the second pass writes the chunk's plans into a tape (tx_hash_tape.hpp) instead of
-//     running them, the calling thread queues the tape (hash_enqueue: one copy up, one launch, one copy of the IDs down) and
-//     hands the IDs to the statements when they are back; the signature transcripts of a chunk then wait for its IDs as they
-//     wait for its keys.  Two tapes may be in flight (one when two calls share the stage contexts).
-//   TxDevice::chains() (ZKGPU_TXFORMAT_SIGN_ON_DEVICE, only beside hashes()) also leaves the signature's challenge to the device
+// format().reasons() (format 2, or a statements call with a status argument): every stage hands its rows one byte each beside
+// the bit; verdicts() then writes, beside every clear bit, the LOWEST code that applies to the transaction -- the order
+// upstream would meet the faults in: decoding and the VM (16, host), r1cs::Verifier::verify (17 .. 19), the keys the signature
+// covers (20), the deferred signature check (21).  The bits are formed exactly as without reasons.
+//
+// ONE scheduler; two predicates change what the device does:
+//   format().hashes() (ZKGPU_TXFORMAT_HASH_ON_DEVICE, never in a statements call) takes the contract IDs, the anchor ratchets and
+//     the transaction-ID tree of every chunk off the staging thread: the second pass writes the chunk's plans into a tape
+//     (tx_hash_tape.hpp) instead of running them, the calling thread queues the tape (hash_enqueue: one copy up, one launch, one
+//     copy of the IDs down) and hands the IDs to the statements when they are back; the signature transcripts of a chunk then
+//     wait for its IDs as they wait for its keys.  Two tapes may be in flight (one when two calls share the stage contexts).
+//   format().chains() (hashes() and ZKGPU_TXFORMAT_SIGN_ON_DEVICE) also leaves the signature's challenge to the device
 //     (tx_sig_rows.hpp), formed from the IDs and the aggregated keys where the two stages left them: a chunk's key stage, its
 //     tape and its signature stage are then ONE chain on the device, ordered by events, and nothing between keys_enqueue and
 //     sigs_collect of a chunk waits for the host.  The staging thread makes a chunk's signature rows in the FIRST pass, beside
@@ -43,30 +47,31 @@
 //     free again (the IDs are not brought down: nothing on the host reads them).  A row whose key did not decode runs through
 //     all the same: its bit is ANDed with the key's.
 // What the caller is handed beside the bits changes nothing of the schedule, and its layout is tx_out.hpp's (TxOutLayout, TxPiece):
-//   TxDevice::ids() (ZKGPU_TXFORMAT_RETURN_IDS): the transaction ID of every ACCEPTED transaction, written by verdicts() where it
+//   format().ids() (ZKGPU_TXFORMAT_RETURN_IDS): the transaction ID of every ACCEPTED transaction, written by verdicts() where it
 //     writes TX_OK and nowhere else (Piece::ids), from the statement's txid: the one the VM's second pass hashed for the
 //     signature, or the one the device's tape produced.  Nothing is hashed for it; all it adds is that a device that chains
 //     copies its IDs down after all (hash_collect with a host buffer).
-//   TxDevice::log_k() (ZKGPU_TXFORMAT_RETURN_LOG, only beside ids()): also the Input / Output entries of every accepted
+//   format().log_k() (ZKGPU_TXFORMAT_RETURN_LOG, only beside ids()): also the Input / Output entries of every accepted
 //     transaction's log (tx_log.hpp), one record each (Piece::log), written by verdicts() where it writes the ID.  The records
 //     of the whole call are kept in a side array of the call until then: the host's second pass fills them from the slots its
 //     plans wrote (tx_prepare_many_logged); a device that hashes brings the entries' contract IDs down with the transaction IDs
 //     (hash_log) and the host adds counts and kinds from the tape's shape table.  Nothing is hashed for it either.
-//   TxDevice::precompute() (ZKGPU_TXFORMAT_PRECOMPUTE_ONLY, only beside ids() and never beside chains()): the call VERIFIES NOTHING.
-//     The staging thread makes ONE pass per chunk -- the VM and the plans of what the ID and the log need, run on the host or,
-//     on a device that hashes, written to the chunk's tape with no job run at all -- and the calling thread queues and
-//     collects tapes (step_precompute: the first two sub-steps of step_host_signed) or, without such a device, only waits for
-//     the staging thread.  No key stage, no proofs, no signature stage is planned, staged or queued.  verdicts() sets no bit
-//     and writes PRECOMPUTED (3), never 0, beside the ID and the record of every transaction the VM ran to the end.
-//   TxDevice::statements() (ZKGPU_TXFORMAT_STATEMENTS_V1): the pieces hold RECORDS of what the caller's own VM left
+// Two predicates pick another kind of call altogether:
+//   format().precompute() (ZKGPU_TXFORMAT_PRECOMPUTE_ONLY, only beside ids(), never with chains() or statements()): the call
+//     VERIFIES NOTHING.  The staging thread makes ONE pass per chunk -- the VM and the plans of what the ID and the log need, run
+//     on the host or, with hashes(), written to the chunk's tape with no job run at all -- and the calling thread queues and
+//     collects tapes (step_precompute: the first two sub-steps of step_host_signed) or, without hashes(), only waits for the
+//     staging thread.  No key stage, no proofs, no signature stage is planned, staged or queued.  verdicts() sets no bit and
+//     writes PRECOMPUTED (3), never 0, beside the ID and the record of every transaction the VM ran to the end.
+//   format().statements() (ZKGPU_TXFORMAT_STATEMENTS_V1): the pieces hold RECORDS of what the caller's own VM left
 //     (tx_statements.hpp), not transactions.  The staging thread makes ONE pass per chunk -- the records parsed, the MuSig jobs run
 //     on the host -- and no tape is ever written; the ID arrived in the record, so a chunk's signature rows wait for its keys
-//     alone.  With TxDevice::forms_musig() (ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it) no transcript runs on the host at all: a key
+//     alone.  With format().forms_musig() (ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it) no transcript runs on the host at all: a key
 //     stage goes out as points and offsets (keys_enqueue_formed), a chunk's signature stage right behind it as a chain whose IDs
 //     the host uploads (SigChain::txids), and both are collected together.  verdicts() is the verifying call's.
-// The calling thread's sub-steps (snapshot, queue_keys, queue_tape, proofs_turn, keys_turn, sigs_turn, the collects, end_step)
-// are the same whatever the switches say; what differs is when a slot counts as free and the ORDER in which the sub-steps run:
-// step_host_signed(), step_chained(), step_precompute() and step_statements(), which say why.
+// The calling thread's sub-steps (snapshot, queue_keys, queue_tape, tape_turn, proofs_turn, keys_turn, sigs_turn, queue_chain,
+// chain_turn, end_step) are the same whatever the mode; what differs is when a slot counts as free and the ORDER in which the
+// sub-steps run: step_host_signed(), step_chained(), step_precompute() and step_statements(), which say why.
 #pragma once
 #include "host_pool.hpp"
 #include "tx_hash_tape.hpp"
@@ -95,7 +100,7 @@ namespace zkvm {
 struct TxProofSource { uint32_t n_in, n_out; const uint8_t* com; const uint8_t* proof; uint64_t proof_len; };
 // What a signature stage of a device that chains waits for ON THE DEVICE: the key stage queued last in key_slot (its row r holds
 // the aggregated key of row r) and the tape queued last in hash_slot (tape_pos[r]: which of its transactions row r signs).
-// txids (a statements call whose device forms the coefficients: TxDevice::forms_musig): THE IDS COME FROM THE HOST -- 32 bytes
+// txids (a statements call whose device forms the coefficients: TxFormat::forms_musig): THE IDS COME FROM THE HOST -- 32 bytes
 // per row, uploaded with the rows; there is no hash slot (hash_slot and tape_pos are not read: a row's ID is its own)
 struct SigChain { int key_slot, hash_slot; const uint32_t* tape_pos; const uint8_t* txids = nullptr; };
 
@@ -121,7 +126,7 @@ class TxDevice {
   // aggregated keys: rows of (a_i, X_i) -> per row the encoding of sum a_i X_i (values) and "every key decodes" (ok bits)
   virtual int keys_enqueue(int slot, const uint8_t* scalars, const uint8_t* points, const uint64_t* offsets, size_t rows) = 0;
   virtual bool keys_done(int slot) = 0;                                     // never blocks
-  // why (here and below; may be NULL, and is ignored by a device without reasons): one reason byte per row, 0 beside a set bit
+  // why (here and below; may be NULL, and is ignored unless format().reasons()): one reason byte per row, 0 beside a set bit
   virtual int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values, uint8_t* why) = 0;
   // cloak proofs of one chunk.  proofs_stage runs on the STAGING thread (host work: grouping by shape, gathering into the
   // ring slot's staging area); start / finish / release on the calling thread.  A handle that was staged is released
@@ -132,44 +137,30 @@ class TxDevice {
   virtual int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t* why) = 0;
   virtual void proofs_release(void* handle) = 0;
   // signature equations: per row dynamic terms (scalars, points) + one term on the basepoint's table -> "is the identity".
-  // chain (NULL: the scalars are final; otherwise only to a device that chains()): the rows of ONE chunk in the order of its key
-  // stage's rows, with the coefficients a_i in place of -c a_i -- the device forms c behind what `chain` names
+  // chain (NULL: the scalars are final; otherwise only under a format that chains() or forms_musig()): the rows of ONE chunk in
+  // the order of its key stage's rows, with the coefficients a_i in place of -c a_i -- the device forms c behind what `chain` names
   virtual int sigs_enqueue(int slot, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points, const uint64_t* dyn_offsets,
                            const uint8_t* base_scalars, const SigChain* chain) = 0;
   virtual bool sigs_done(int slot) = 0;                                     // never blocks
   virtual int sigs_collect(int slot, uint8_t* bits, uint8_t* why) = 0;
   virtual std::string last_error() = 0;
-  virtual bool reasons() const { return false; }                            // does every stage bring back reason bytes?
-  // transaction IDs on the device.  hashes(): does the device take them?  hash_tape(slot): the flattener of that slot, kept
-  // by the device between calls (the staging thread fills it).  hash_enqueue queues the finished tape; hash_collect waits
-  // and writes 32 bytes per transaction of the tape, in the tape's order -- nowhere when the pointer is null: a device that
-  // chains is only waited for, its IDs stay where its signature stage read them.  A device that does not hash is never asked.
-  virtual bool hashes() const { return false; }
+  // the mode of the call the device was made for (tx_out.hpp): one value; TxCall reads it once
+  virtual const TxFormat& format() const = 0;
+  // transaction IDs on the device (format().hashes(); a device whose format does not say so is never asked).  hash_tape(slot):
+  // the flattener of that slot, kept by the device between calls (the staging thread fills it).  hash_enqueue queues the
+  // finished tape; hash_collect waits and writes 32 bytes per transaction of the tape, in the tape's order -- nowhere when the
+  // pointer is null: a device that chains is only waited for, its IDs stay where its signature stage read them (with
+  // format().ids() it brings them down like one that only hashes: hash_collect is given a host buffer).
   virtual TxHashTape* hash_tape(int) { return nullptr; }
   virtual int hash_enqueue(int, const TxHashTape&) { return -1; }
   virtual bool hash_done(int) { return true; }                              // never blocks
   virtual int hash_collect(int, uint8_t*) { return -1; }
-  // the signature's challenge on the device.  chains(): does the device form it?  (Asked only of a device that hashes.)
-  virtual bool chains() const { return false; }
-  // does the caller want the transaction IDs of what was accepted?  (A device that chains then brings its IDs down like one
-  // that only hashes: hash_collect is given a host buffer.)
-  virtual bool ids() const { return false; }
-  // ... and the log's entries, at most log_k() of them per transaction (0: no; only beside ids())?  A device that hashes then
-  // gathers the entries' contract IDs behind every tape: hash_log(slot), valid from a hash_collect that returned 0 until the
-  // slot's next hash_enqueue, is n_tx x log_k() x 32 bytes in the tape's order, entry j of a transaction whose shape logs
-  // count <= log_k() entries at [t][j], zeros elsewhere.
-  virtual size_t log_k() const { return 0; }
+  // (format().log_k() > 0) the entries' contract IDs the device gathered behind a tape: hash_log(slot), valid from a
+  // hash_collect that returned 0 until the slot's next hash_enqueue, is n_tx x log_k() x 32 bytes in the tape's order, entry j
+  // of a transaction whose shape logs count <= log_k() entries at [t][j], zeros elsewhere.
   virtual const uint8_t* hash_log(int) { return nullptr; }
-  // is the call a precompute-only one: the VM, the IDs and the log, nothing verified?  (Only of a device with ids() that does
-  // not chain.)  Such a call asks for nothing above but the hash_* functions, and those only of a device that hashes.
-  virtual bool precompute() const { return false; }
-  // is the call one over RECORDS of what the caller's own VM left (ZKGPU_TXFORMAT_STATEMENTS_V1: tx_statements.hpp)?  Such a
-  // call asks for keys, proofs and signatures alone: nothing is hashed for an ID, no tape is written.
-  virtual bool statements() const { return false; }
-  // ... and does the device form the MuSig coefficients a_i and the challenge c itself (ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside
-  // it)?  Then a key stage arrives as points and offsets alone (keys_enqueue_formed: the device writes the scalars), and a
-  // signature stage as a chain whose IDs come from the host (SigChain::txids), its key terms' scalars unset.
-  virtual bool forms_musig() const { return false; }
+  // (format().forms_musig()) a key stage as points and offsets alone: the device writes the scalars; the signature stage then
+  // arrives as a chain whose IDs come from the host (SigChain::txids), its key terms' scalars unset.
   virtual int keys_enqueue_formed(int, const uint8_t*, const uint64_t*, size_t) { return -1; }
 };
 
@@ -183,21 +174,21 @@ class TxCall {
 
   // several callers' transactions as ONE call (zkgpu_tx_verify_submit: calls in flight are merged as tickets are): the
   // pieces in order, transaction i of the merged call = the i-th transaction counted through them.  ids / log are written only
-  // for a device with ids() / with log_k() >= the piece's log_k
+  // under a format with ids() / with log_k() >= the piece's log_k
   using Piece = TxPiece;
   static_assert(TX_INVALID == TXOUT_REJECTED && TX_UNSUPPORTED == TXOUT_OUTSIDE_SUBSET, "tx_out.hpp restates two status bytes");
   // store: what the VM leaves per transaction, kept by the caller between calls (fresh memory costs a page fault per 4 KB);
   // at most `kept` entries of it are used, the rest of a longer call lives in the call.
-  // A lone call: `status` (may be NULL) is the caller's whole status argument, laid out as the device's ids() and log_k() say
+  // A lone call: `status` (may be NULL) is the caller's whole status argument, laid out as the format's ids() and log_k() say
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
-      : TxCall(dev, store, kept, std::vector<Piece>{TxOutLayout{dev.ids(), dev.ids() ? dev.log_k() : 0}.piece(txs, tx_offsets, batch, status)}, host_threads,
+      : TxCall(dev, store, kept, std::vector<Piece>{TxOutLayout{dev.format().ids(), dev.format().log_k()}.piece(txs, tx_offsets, batch, status)}, host_threads,
                chunk_override, accept_bitmap, status, n_slots) {}
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
-        reasons_(dev.reasons() && status != nullptr), hashes_(dev.hashes() && !dev.statements()), chains_(hashes_ && dev.chains()), precompute_(dev.precompute() && dev.ids() && !chains_ && !dev.statements()),
-        statements_(dev.statements()), musig_dev_(statements_ && dev.forms_musig()), ids_(dev.ids() && any_ids(pieces)), log_k_(ids_ && any_log(pieces, dev.log_k()) ? dev.log_k() : 0), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        fmt_(dev.format()), reasons_(fmt_.reasons() && status != nullptr), ids_(fmt_.ids() && any_ids(pieces)), log_k_(ids_ && any_log(pieces, fmt_.log_k()) ? fmt_.log_k() : 0),
+        timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
     if (ids_) id_out_.reserve(batch_);
     if (log_k_) { log_out_.reserve(batch_); log_rec_.assign(batch_ * tx_log_record_bytes(log_k_), 0); }
@@ -282,7 +273,7 @@ class TxCall {
     }
     // (after an error: nothing is left pending on the device)
     for (size_t s = 0; s < seg_.size(); ++s) keys_collect(s);
-    while (next_hcollect_ < next_hash_) hash_collect(next_hcollect_++, !chains_ || ids_);
+    while (next_hcollect_ < next_hash_) hash_collect(next_hcollect_++, !fmt_.chains() || ids_);
     for (size_t s = 0; s < n_sig_made_locked(); ++s) sigs_collect(s);
     for (size_t c = 0; c < chunks_.size(); ++c) proofs_collect(*chunks_[c]);
     report();
@@ -365,8 +356,8 @@ class TxCall {
       if (c == n && c - first > 1) { sig_plan_.push_back({first, c - 1}); sig_plan_.push_back({c - 1, c}); }
       else sig_plan_.push_back({first, c});
     }
-    if (precompute_) { sig_plan_.clear(); all_sigs_made_ = true; }     // (no signature is looked at)
-    if (chains_ || musig_dev_) {                         // one stage per chunk, all of them there from the start: chain_rows_[c] publishes c's rows
+    if (fmt_.precompute()) { sig_plan_.clear(); all_sigs_made_ = true; }     // (no signature is looked at)
+    if (fmt_.chains() || fmt_.forms_musig()) {           // one stage per chunk, all of them there from the start: chain_rows_[c] publishes c's rows
       sig_plan_.clear();
       for (size_t c = 0; c < n; ++c) { sig_plan_.push_back({c, c + 1}); sig_stages_.emplace_back(new SigStage()); sig_stages_[c]->first = c; sig_stages_[c]->last = c + 1; }
       n_sig_stages_ = sig_next_ = n; all_sigs_made_ = true;
@@ -406,7 +397,7 @@ class TxCall {
     if (only == ALL_PROTOS) n_host_hashed_ += k.n;
   }
   // the second pass of a chunk on a device that hashes: the plans into the slot's tape, the MuSig jobs alone on the host
-  void vm_pass_taped(Chunk& k, TxHashTape& tape, uint8_t host_only = P_MUSIG) {
+  void vm_pass_taped(Chunk& k, TxHashTape& tape, uint8_t host_only) {
     const double t0 = now();
     std::atomic<int> bad{0};
     tape.reset(k.n);
@@ -489,7 +480,7 @@ class TxCall {
     sg.keyed.resize(k.live.size());
     for (size_t q = 0; q < k.live.size(); ++q) sg.keyed[q] = k.g0 + q;
     lay_rows(sg, [&](size_t q) -> TxStatement& { return statement(k.lo + k.live[q]); }, [](size_t, size_t) {});
-    if (musig_dev_) {                                    // (the IDs the records brought go up with the rows)
+    if (fmt_.forms_musig()) {                            // (the IDs the records brought go up with the rows)
       sg.ids.resize(32 * k.live.size());
       for (size_t q = 0; q < k.live.size(); ++q) memcpy(&sg.ids[32 * q], statement(k.lo + k.live[q]).txid, 32);
     }
@@ -555,21 +546,45 @@ class TxCall {
       news();
     }
   }
-  // A precompute-only call: one pass per chunk and nothing else.  On a device that hashes the pass writes the chunk's tape (its
-  // slot is free once chunk ci - n_slots has been collected) and runs no job; otherwise it runs what the IDs and the log need.
+  // the stages that are due, until all of them are made (or the call is over): how a staging loop that makes them ends
+  void make_sig_stages_to_the_end() {
+    std::unique_lock<std::mutex> lk(hm_);
+    for (;;) {
+      make_sig_stages(lk, ids_upto_);
+      if (quit_ || all_sigs_made_) return;
+      hcv_.wait(lk, [&] { return quit_ || (keys_back(sig_plan_[sig_next_]) && sig_plan_[sig_next_].last <= ids_upto_); });
+    }
+  }
+  // (hashes()) chunk ci's tape: wait for its slot -- free once chunk ci - n_slots has been collected --, write it (the jobs of
+  // host_only alone run on the host), publish it; false: the call is over.  scanned (a precompute-only call, whose ONE pass
+  // this is): which transactions the VM accepted, found before the tape is published
+  bool tape_out(size_t ci, uint8_t host_only, Segment* scanned = nullptr) {
+    {
+      std::unique_lock<std::mutex> lk(hm_);
+      hcv_.wait(lk, [&] { return quit_ || ids_upto_ + n_slots_ > ci; });
+      if (quit_) return false;
+    }
+    vm_pass_taped(*chunks_[ci], *dev_.hash_tape((int)(ci % n_slots_)), host_only);
+    if (scanned) scan(*chunks_[ci], *scanned);
+    std::lock_guard<std::mutex> lk(hm_);
+    if (quit_) return false;
+    tape_ready_[ci] = 1;
+    news();
+    return true;
+  }
+  // A precompute-only call: one pass per chunk and nothing else.  With hashes() the pass writes the chunk's tape and runs no
+  // job; otherwise it runs what the IDs and the log need.
   void staging_precompute() {
     for (size_t ci = 0; ci < chunks_.size(); ++ci) {
-      Chunk& k = *chunks_[ci];
-      if (hashes_) {
-        std::unique_lock<std::mutex> lk(hm_);
-        hcv_.wait(lk, [&] { return quit_ || ids_upto_ + n_slots_ > ci; });
-        if (quit_) return;
+      if (fmt_.hashes()) {
+        if (!tape_out(ci, NO_PROTO, &seg_[ci])) return;
+        continue;
       }
-      if (hashes_) vm_pass_taped(k, *dev_.hash_tape((int)(ci % n_slots_)), NO_PROTO); else vm_pass_ids(k);
-      scan(k, seg_[ci]);
+      vm_pass_ids(*chunks_[ci]);
+      scan(*chunks_[ci], seg_[ci]);
       std::lock_guard<std::mutex> lk(hm_);
       if (quit_) return;
-      if (hashes_) tape_ready_[ci] = 1; else hashed_upto_ = ids_upto_ = ci + 1;
+      hashed_upto_ = ids_upto_ = ci + 1;
       news();
     }
   }
@@ -579,7 +594,7 @@ class TxCall {
   // transcripts of a chunk wait for its aggregated keys alone.
   void parse_pass(Chunk& k) {
     const double t0 = now();
-    chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) { tx_statements_many(p, l, &statement(k.lo + first), cnt, !musig_dev_); });
+    chunk_groups(k, [&](const uint8_t** p, const size_t* l, size_t first, size_t cnt) { tx_statements_many(p, l, &statement(k.lo + first), cnt, !fmt_.forms_musig()); });
     std::lock_guard<std::mutex> lk(hm_);
     t_keys_host_ += now() - t0;
   }
@@ -590,23 +605,17 @@ class TxCall {
       scan(k, seg_[ci]);
       if (!gather(ci, k)) return;
       key_rows_out(ci, seg_[ci]);
-      if (musig_dev_) chain_rows_out(ci);
+      if (fmt_.forms_musig()) chain_rows_out(ci);
       std::unique_lock<std::mutex> lk(hm_);
       hashed_upto_ = ids_upto_ = ci + 1;
-      if (!musig_dev_) make_sig_stages(lk, ids_upto_);
+      if (!fmt_.forms_musig()) make_sig_stages(lk, ids_upto_);
       if (quit_) return;
     }
-    if (musig_dev_) return;                              // (every stage was made beside its key rows)
-    std::unique_lock<std::mutex> lk(hm_);
-    for (;;) {
-      make_sig_stages(lk, ids_upto_);
-      if (quit_ || all_sigs_made_) return;
-      hcv_.wait(lk, [&] { return quit_ || keys_back(sig_plan_[sig_next_]); });
-    }
+    if (!fmt_.forms_musig()) make_sig_stages_to_the_end();  // (else every stage was made beside its key rows)
   }
   void staging_main() {
-    if (statements_) { staging_statements(); return; }
-    if (precompute_) { staging_precompute(); return; }
+    if (fmt_.statements()) { staging_statements(); return; }
+    if (fmt_.precompute()) { staging_precompute(); return; }
     for (const Span& run : runs_) {                     // a run of chunks: keys and proofs of each on their way, then their IDs
       for (size_t ci = run.first; ci < run.last; ++ci) {
         Chunk& k = *chunks_[ci];
@@ -620,12 +629,12 @@ class TxCall {
           if (!gather(ci, k)) return;
           vm_pass(k, P_MUSIG);
           key_rows_out(ci, sg);
-          if (chains_) chain_rows_out(ci);
+          if (fmt_.chains()) chain_rows_out(ci);
         } else {
           vm_pass(k, P_MUSIG);
           scan(k, sg);
           key_rows_out(ci, sg);
-          if (chains_) chain_rows_out(ci);
+          if (fmt_.chains()) chain_rows_out(ci);
           if (!gather(ci, k)) return;
         }
       }
@@ -635,16 +644,8 @@ class TxCall {
           make_sig_stages(lk, std::min(ci, ids_upto_));
           if (quit_) return;
         }
-        if (hashes_) {                                   // the chunk's tape: its slot is free once chunk ci - n_slots has been collected
-          {
-            std::unique_lock<std::mutex> lk(hm_);
-            hcv_.wait(lk, [&] { return quit_ || ids_upto_ + n_slots_ > ci; });
-            if (quit_) return;
-          }
-          vm_pass_taped(*chunks_[ci], *dev_.hash_tape((int)(ci % n_slots_)));
-          std::lock_guard<std::mutex> lk(hm_);
-          tape_ready_[ci] = 1;
-          news();
+        if (fmt_.hashes()) {                               // the chunk's plans go to its tape, the MuSig jobs alone run here
+          if (!tape_out(ci, P_MUSIG)) return;
           continue;
         }
         vm_pass(*chunks_[ci], ALL_PROTOS);
@@ -652,13 +653,7 @@ class TxCall {
         hashed_upto_ = ids_upto_ = ci + 1;
       }
     }
-    if (chains_) return;                                 // (every stage was made in the first pass)
-    std::unique_lock<std::mutex> lk(hm_);
-    for (;;) {
-      make_sig_stages(lk, ids_upto_);
-      if (quit_ || all_sigs_made_) return;
-      hcv_.wait(lk, [&] { return quit_ || (keys_back(sig_plan_[sig_next_]) && sig_plan_[sig_next_].last <= ids_upto_); });
-    }
+    if (!fmt_.chains()) make_sig_stages_to_the_end();       // (else every stage was made in the first pass)
   }
   void stop_stager() {
     { std::lock_guard<std::mutex> lk(hm_); quit_ = true; }
@@ -764,8 +759,8 @@ class TxCall {
     if (next_key_ < n) r.rows = key_rows_[next_key_] != 0;
     if (next_stage_ < n) r.staged = staged_[next_stage_] != 0;
     if (next_stage_ >= RING) r.ring_free = arena_free_[next_stage_ - RING] != 0;
-    if (hashes_ && next_hash_ < n) r.tape = tape_ready_[next_hash_] != 0;
-    if ((chains_ || musig_dev_) && next_sig_ < n) r.sig_rows = chain_rows_[next_sig_] != 0;
+    if (fmt_.hashes() && next_hash_ < n) r.tape = tape_ready_[next_hash_] != 0;
+    if ((fmt_.chains() || fmt_.forms_musig()) && next_sig_ < n) r.sig_rows = chain_rows_[next_sig_] != 0;
     if (tape_failed_) note(EINVAL_, "a transaction's hash plan does not fit the device's tape");
     return true;
   }
@@ -779,7 +774,7 @@ class TxCall {
     const double t0 = now();
     if (sg.g_hi > sg.g_lo) {
       // (a statements call whose device forms the coefficients: points and offsets alone -- the scalars are the device's to write)
-      const int rc = musig_dev_ ? dev_.keys_enqueue_formed((int)(next_key_ % n_slots_), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo)
+      const int rc = fmt_.forms_musig() ? dev_.keys_enqueue_formed((int)(next_key_ % n_slots_), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo)
                                 : dev_.keys_enqueue((int)(next_key_ % n_slots_), sg.ksc.data(), sg.kpt.data(), sg.koff.data(), sg.g_hi - sg.g_lo);
       if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
     }
@@ -828,12 +823,9 @@ class TxCall {
   // the IDs that are back come first of all: the transcripts wait for them.
   bool step_host_signed(const Ready& r) {
     const size_t n = chunks_.size();
-    if (next_kcollect_ == n && next_stage_ == n && r.sigs_all && next_sig_ == r.sig_avail && (!hashes_ || next_hcollect_ == n)) { finished_ = true; return true; }
+    if (next_kcollect_ == n && next_stage_ == n && r.sigs_all && next_sig_ == r.sig_avail && (!fmt_.hashes() || next_hcollect_ == n)) { finished_ = true; return true; }
     bool progress = queue_tape(r, next_hcollect_ + n_slots_ > next_hash_);     // (its slot is free once chunk next_hash - n_slots is collected)
-    if (rc_ == OK && next_hcollect_ < next_hash_ && (!hash_pending_[next_hcollect_] || dev_.hash_done((int)(next_hcollect_ % n_slots_)))) {
-      hash_collect(next_hcollect_++);
-      progress = true;
-    }
+    progress |= tape_turn();
     // (... once segment next_key - n_slots is collected.  Unlike its siblings, and unlike step_chained(), the keys are queued
     // without asking rc_: this order always has queued them in the step in which a tape failed; finish() collects the stage)
     progress |= queue_keys(r, next_kcollect_ + n_slots_ > next_key_);
@@ -841,6 +833,12 @@ class TxCall {
     progress |= keys_turn();
     progress |= sigs_turn(r);
     return end_step(progress);
+  }
+  // the oldest tape in flight, if the device is through with it: its IDs collected into the statements, and the staging thread is told
+  bool tape_turn() {
+    if (rc_ != OK || next_hcollect_ >= next_hash_ || (hash_pending_[next_hcollect_] && !dev_.hash_done((int)(next_hcollect_ % n_slots_)))) return false;
+    hash_collect(next_hcollect_++);
+    return true;
   }
   // the aggregated keys of segment next_kcollect_, if the device is through with them: collected, and the staging thread is told
   bool keys_turn() {
@@ -873,6 +871,27 @@ class TxCall {
     }
     return progress;
   }
+  // (chains() or forms_musig()) the signature stage of chunk next_sig_, a chain behind what the chunk queued before it.
+  // stages_queued: those are queued -- its key stage, and its tape where the mode has one (the device orders them)
+  bool queue_chain(const Ready& r, bool stages_queued) {
+    if (rc_ != OK || !r.sig_rows || !stages_queued) return false;
+    const double t0 = now();
+    chain_enqueue(next_sig_);
+    t_sigs_ += now() - t0;
+    mark("signatures queued, stage", next_sig_);
+    ++next_sig_;
+    return true;
+  }
+  // ... and what the oldest chain in flight brought back, once its signature stage is through: signature bits, key bits and --
+  // where the mode has one -- its tape (the IDs themselves only for a caller that is handed them).  That frees the chunk's slot.
+  bool chain_turn() {
+    if (rc_ != OK || next_chain_ >= next_sig_ || (sig_stages_[next_chain_]->pending && !dev_.sigs_done((int)(next_chain_ % n_slots_)))) return false;
+    sigs_collect(next_chain_);
+    keys_collect(next_chain_);
+    if (fmt_.chains()) { hash_collect(next_chain_, ids_); next_hcollect_ = next_chain_ + 1; }
+    next_kcollect_ = ++next_chain_;
+    return true;
+  }
   // A statements call (tx_statements.hpp): the same sub-steps in a fourth order.  A chunk's proofs go out first, as soon as the
   // staging thread has staged them -- a record holds all they need, and nothing is hashed before them --; then its key stage;
   // then its signature stage.  No tape is ever asked for, and nothing waits for an ID.  With the host's transcripts the
@@ -881,28 +900,11 @@ class TxCall {
   // two), and both are collected together, oldest chunk first, which frees their slot (step_chained's, without the tape).
   bool step_statements(const Ready& r) {
     const size_t n = chunks_.size();
-    if (musig_dev_ ? (next_chain_ == n && next_stage_ == n) : (next_kcollect_ == n && next_stage_ == n && r.sigs_all && next_sig_ == r.sig_avail)) { finished_ = true; return true; }
+    if (fmt_.forms_musig() ? (next_chain_ == n && next_stage_ == n) : (next_kcollect_ == n && next_stage_ == n && r.sigs_all && next_sig_ == r.sig_avail)) { finished_ = true; return true; }
     bool progress = proofs_turn(r, true);
-    progress |= queue_keys(r, rc_ == OK && (musig_dev_ ? next_chain_ : next_kcollect_) + n_slots_ > next_key_);
-    if (!musig_dev_) {
-      progress |= keys_turn();
-      progress |= sigs_turn(r);
-      return end_step(progress);
-    }
-    if (rc_ == OK && r.sig_rows && next_sig_ < next_key_) {
-      const double t0 = now();
-      chain_enqueue_host_ids(next_sig_);
-      t_sigs_ += now() - t0;
-      mark("signatures queued, stage", next_sig_);
-      ++next_sig_;
-      progress = true;
-    }
-    if (rc_ == OK && next_chain_ < next_sig_ && (!sig_stages_[next_chain_]->pending || dev_.sigs_done((int)(next_chain_ % n_slots_)))) {
-      sigs_collect(next_chain_);
-      keys_collect(next_chain_);
-      next_kcollect_ = ++next_chain_;
-      progress = true;
-    }
+    progress |= queue_keys(r, rc_ == OK && (fmt_.forms_musig() ? next_chain_ : next_kcollect_) + n_slots_ > next_key_);
+    if (fmt_.forms_musig()) { progress |= queue_chain(r, next_sig_ < next_key_); progress |= chain_turn(); }
+    else { progress |= keys_turn(); progress |= sigs_turn(r); }
     return end_step(progress);
   }
   // The same for a device that chains.  Per chunk, in order: its key stage and its tape go out when the staging thread has
@@ -915,25 +917,12 @@ class TxCall {
     if (next_chain_ == n && next_stage_ == n) { finished_ = true; return true; }
     bool progress = queue_keys(r, rc_ == OK && next_chain_ + n_slots_ > next_key_);
     progress |= queue_tape(r, next_chain_ + n_slots_ > next_hash_);
-    if (rc_ == OK && r.sig_rows && next_sig_ < next_key_ && next_sig_ < next_hash_) {
-      const double t0 = now();
-      chain_enqueue(next_sig_);
-      t_sigs_ += now() - t0;
-      mark("signatures queued, stage", next_sig_);
-      ++next_sig_;
-      progress = true;
-    }
+    progress |= queue_chain(r, next_sig_ < next_key_ && next_sig_ < next_hash_);
     // (a chunk's proofs after its keys -- unless its keys wait for a slot: a slot is free again only when a whole chain has been
     // collected, the first chain needs the first tape, and the staging thread writes tapes after it has gathered every chunk of
     // the run, for which the ring's areas must come free -- the proofs must not wait for keys that wait for them)
     progress |= proofs_turn(r, proofs_first_ || next_stage_ < next_key_ || next_key_ >= next_chain_ + n_slots_);
-    if (rc_ == OK && next_chain_ < next_sig_ && (!sig_stages_[next_chain_]->pending || dev_.sigs_done((int)(next_chain_ % n_slots_)))) {
-      sigs_collect(next_chain_);
-      keys_collect(next_chain_);
-      hash_collect(next_chain_, ids_);
-      next_kcollect_ = next_hcollect_ = ++next_chain_;
-      progress = true;
-    }
+    progress |= chain_turn();
     return end_step(progress);
   }
   // A precompute-only call: the tapes and nothing else, in the order of step_host_signed() -- a chunk's tape goes out when the
@@ -941,13 +930,10 @@ class TxCall {
   // is nothing to queue: the call is through when the staging thread has passed the last chunk.
   bool step_precompute(const Ready& r) {
     const size_t n = chunks_.size();
-    if (hashes_ ? next_hcollect_ == n : r.ids_upto == n) { finished_ = true; return true; }
-    if (!hashes_) return end_step(false);
+    if (fmt_.hashes() ? next_hcollect_ == n : r.ids_upto == n) { finished_ = true; return true; }
+    if (!fmt_.hashes()) return end_step(false);
     bool progress = queue_tape(r, next_hcollect_ + n_slots_ > next_hash_);
-    if (rc_ == OK && next_hcollect_ < next_hash_ && (!hash_pending_[next_hcollect_] || dev_.hash_done((int)(next_hcollect_ % n_slots_)))) {
-      hash_collect(next_hcollect_++);
-      progress = true;
-    }
+    progress |= tape_turn();
     return end_step(progress);
   }
  public:
@@ -956,38 +942,33 @@ class TxCall {
     if (rc_ != OK) { finished_ = true; return true; }
     Ready r;
     if (!snapshot(r)) return true;
-    return statements_ ? step_statements(r) : precompute_ ? step_precompute(r) : chains_ ? step_chained(r) : step_host_signed(r);
+    return fmt_.statements() ? step_statements(r) : fmt_.precompute() ? step_precompute(r) : fmt_.chains() ? step_chained(r) : step_host_signed(r);
   }
  private:
-  // (a statements call whose device forms a_i and c) chunk c's signature stage behind its key stage (queued, or empty like the
-  // stage itself); the rows' IDs go up with them
-  void chain_enqueue_host_ids(size_t c) {
-    SigStage& sg = *sig_stages_[c];
-    const size_t ns = sg.keyed.size();
-    if (ns == 0) return;
-    if (!seg_[c].pending || sg.ids.size() != 32 * ns) { note(EINVAL_, "a signature stage without its key stage or its IDs"); return; }
-    const int slot = (int)(c % n_slots_);
-    const SigChain chain{slot, -1, nullptr, sg.ids.data()};
-    const int rc = dev_.sigs_enqueue(slot, ns, sg.ssc.data(), sg.spt.data(), sg.soff.data(), sg.sst.data(), &chain);
-    if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
-  }
-  // chunk c's signature stage behind its key stage and its tape (both queued, or empty like the stage itself)
+  // chunk c's signature stage as a chain behind its key stage and -- chains() -- its tape (both queued, or empty like the stage
+  // itself); forms_musig(): there is no tape, the rows' IDs go up with them
   void chain_enqueue(size_t c) {
     const Chunk& k = *chunks_[c];
     SigStage& sg = *sig_stages_[c];
     const size_t ns = sg.keyed.size();
     if (ns == 0) return;
-    const TxHashTape& tape = *dev_.hash_tape((int)(c % n_slots_));
-    std::vector<uint32_t> at(k.n, TAPE_IDLE);
-    for (size_t t = 0; t < tape.n_tx(); ++t) if (tape.position(t) < k.n) at[tape.position(t)] = (uint32_t)t;
-    sg.pos.resize(ns);
-    for (size_t q = 0; q < ns; ++q) {
-      sg.pos[q] = at[k.live[q]];
-      if (sg.pos[q] == TAPE_IDLE) { note(EINVAL_, "a transaction the VM accepted has no ID on its chunk's tape"); return; }
-    }
-    if (!seg_[c].pending || !hash_pending_[c]) { note(EINVAL_, "a signature stage without its key stage or its tape"); return; }
     const int slot = (int)(c % n_slots_);
-    const SigChain chain{slot, slot, sg.pos.data()};
+    SigChain chain{slot, -1, nullptr};
+    if (fmt_.forms_musig()) {
+      if (!seg_[c].pending || sg.ids.size() != 32 * ns) { note(EINVAL_, "a signature stage without its key stage or its IDs"); return; }
+      chain.txids = sg.ids.data();
+    } else {
+      const TxHashTape& tape = *dev_.hash_tape(slot);
+      std::vector<uint32_t> at(k.n, TAPE_IDLE);
+      for (size_t t = 0; t < tape.n_tx(); ++t) if (tape.position(t) < k.n) at[tape.position(t)] = (uint32_t)t;
+      sg.pos.resize(ns);
+      for (size_t q = 0; q < ns; ++q) {
+        sg.pos[q] = at[k.live[q]];
+        if (sg.pos[q] == TAPE_IDLE) { note(EINVAL_, "a transaction the VM accepted has no ID on its chunk's tape"); return; }
+      }
+      if (!seg_[c].pending || !hash_pending_[c]) { note(EINVAL_, "a signature stage without its key stage or its tape"); return; }
+      chain.hash_slot = slot; chain.tape_pos = sg.pos.data();
+    }
     const int rc = dev_.sigs_enqueue(slot, ns, sg.ssc.data(), sg.spt.data(), sg.soff.data(), sg.sst.data(), &chain);
     if (rc != OK) note(rc, dev_.last_error()); else sg.pending = true;
   }
@@ -1007,16 +988,19 @@ class TxCall {
       for (size_t j = 0; j < k.live.size(); ++j) {
         const size_t i = k.lo + k.live[j];
         if (status_) status_[i] = PRECOMPUTED;
-        if (ids_ && id_out_[i]) memcpy(id_out_[i], statement(i).txid, 32);
-        if (log_k_ && log_out_[i].first) tx_log_record_copy(log_out_[i].first, log_out_[i].second, &log_rec_[i * tx_log_record_bytes(log_k_)], log_k_);
+        hand_out(i);
         ++n_precomputed_;
       }
     }
-    for (size_t i = 0; reasons_ && i < batch_; ++i)
-      if (statement(i).status == TX_INVALID) status_[i] = host_reason(statement(i));
+    if (reasons_) host_reasons_out();
+  }
+  // transaction i's ID and record to its caller, where that caller has room for them
+  void hand_out(size_t i) {
+    if (ids_ && id_out_[i]) memcpy(id_out_[i], statement(i).txid, 32);
+    if (log_k_ && log_out_[i].first) tx_log_record_copy(log_out_[i].first, log_out_[i].second, &log_rec_[i * tx_log_record_bytes(log_k_)], log_k_);
   }
   void verdicts() {
-    if (precompute_) { precomputed_out(); return; }
+    if (fmt_.precompute()) { precomputed_out(); return; }
     std::vector<uint8_t> sig_ok(live_all_.size(), 0);
     // (key_ok_ matters for a chained stage alone, whose rows include those with an undecodable key; an unchained stage's
     // `keyed` holds only rows whose keys decoded, and the test is always true there)
@@ -1029,8 +1013,7 @@ class TxCall {
         const size_t i = k.lo + k.live[j];
         accept_[i / 8] |= (uint8_t)(1u << (i % 8));
         if (status_) status_[i] = TX_OK;
-        if (ids_ && id_out_[i]) memcpy(id_out_[i], statement(i).txid, 32);   // (here alone: an ID leaves only beside a set bit)
-        if (log_k_ && log_out_[i].first) tx_log_record_copy(log_out_[i].first, log_out_[i].second, &log_rec_[i * tx_log_record_bytes(log_k_)], log_k_);   // (and a record)
+        hand_out(i);                                         // (here alone: an ID or a record leaves only beside a set bit)
       }
     }
     if (reasons_) reasons_out();
@@ -1042,9 +1025,9 @@ class TxCall {
   }
   // Beside every clear bit of a transaction inside the subset, the lowest code that applies; 0 stays where verdicts() wrote it,
   // beside a set bit, and nowhere else.  A transaction no stage gave a reason for (cannot happen) reads "rejected" alone.
+  void host_reasons_out() { for (size_t i = 0; i < batch_; ++i) if (statement(i).status == TX_INVALID) status_[i] = host_reason(statement(i)); }
   void reasons_out() {
-    for (size_t i = 0; i < batch_; ++i)
-      if (statement(i).status == TX_INVALID) status_[i] = host_reason(statement(i));
+    host_reasons_out();
     std::vector<uint8_t> sig_why(live_all_.size(), 0);
     for (const auto& sg : sig_stages_)
       for (size_t q = 0; q < sg->keyed.size(); ++q) sig_why[sg->keyed[q]] = sg->why[q];
@@ -1078,12 +1061,8 @@ class TxCall {
   const int threads_;
   uint8_t* const accept_;
   uint8_t* const status_;
-  const bool reasons_;                                   // the device brings back reason bytes, and there is a status array to write them to
-  const bool hashes_;                                    // the device hashes the transaction IDs (tapes instead of the host's second-pass hashing)
-  const bool chains_;                                    // ... and forms the signature's challenge: a chunk's three stages are one chain on the device
-  const bool precompute_;                                // nothing is verified: one pass, the tapes, and PRECOMPUTED beside IDs and records (no keys, proofs or signatures)
-  const bool statements_;                                // the pieces hold records of what the caller's VM left (tx_statements.hpp): one parsing pass, no tape, no second pass
-  const bool musig_dev_;                                 // ... and the device forms a_i and c: a chunk's key stage and signature stage are a chain, as for chains_, without a tape
+  const TxFormat fmt_;                                   // the mode of the call: the device's format, read once (tx_out.hpp says what each predicate means)
+  const bool reasons_;                                   // the format brings back reason bytes, and there is a status array to write them to
   const bool ids_;                                       // the IDs of accepted transactions go out (the device says so, and a piece has room for them)
   std::vector<uint8_t*> id_out_;                         // ... per transaction of the call, where its 32 bytes go (NULL: its caller has no room)
   const size_t log_k_;                                   // the log's entries go out too, at most so many per transaction (0: no)

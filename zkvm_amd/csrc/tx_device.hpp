@@ -151,43 +151,35 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
  public:
   // slot_base / arena_base: which of the verifier's stage contexts and staging areas this call uses (a call alone: slots 0
   // and 1, areas 0 .. RING - 1; two rounds in flight: one slot and one set of areas each)
-  // format (tx_out.hpp: TxFormat, the verifier's format word decoded; of it the base format 0 never gets here):
+  // format (tx_out.hpp: TxFormat, the verifier's format word decoded; of it the base format 0 never gets here) is kept as it
+  // is, and its predicates are asked where they matter:
   //   reasons(): a format-2 call -- every stage also brings back one reason byte per row (tx_reason_kernels.hpp)
-  //   hash_on_device: ZKGPU_TXFORMAT_HASH_ON_DEVICE -- the transaction IDs of every chunk come from k_tx_hash
-  //   sign_on_device: ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the signature's challenge comes from k_tx_sig_rows
-  //   out.ids: ZKGPU_TXFORMAT_RETURN_IDS -- the caller is handed the IDs of what it accepted; all it changes HERE is that a chained
+  //   hashes(): ZKGPU_TXFORMAT_HASH_ON_DEVICE -- the transaction IDs of every chunk come from k_tx_hash
+  //   chains(): ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the signature's challenge comes from k_tx_sig_rows
+  //   ids(): ZKGPU_TXFORMAT_RETURN_IDS -- the caller is handed the IDs of what it accepted; all it changes HERE is that a chained
   //     stage copies its IDs down as an unchained one does (one copy on the hashing stream, no launch)
-  //   out.log_k: ZKGPU_TXFORMAT_RETURN_LOG beside it -- K, the log entries kept per transaction (0: no).  Here: behind k_tx_hash, on
+  //   log_k(): ZKGPU_TXFORMAT_RETURN_LOG beside it -- K, the log entries kept per transaction (0: no).  Here: behind k_tx_hash, on
   //     its stream, k_tx_log_gather and one more copy down (hash_queue); a call without it queues exactly what it queued before
-  //   precompute_only: ZKGPU_TXFORMAT_PRECOMPUTE_ONLY -- the call asks for the hashing stage alone (tx_call.hpp), and that stage
+  //   precompute(): ZKGPU_TXFORMAT_PRECOMPUTE_ONLY -- the call asks for the hashing stage alone (tx_call.hpp), and that stage
   //     walks the tape by dependency level (tx_hash_levels.hpp: k_tx_hash_levels) because that kernel, timed alone on the tapes of
   //     1024 and of 8192 payments, was faster in every process than k_tx_hash in any (median 250 / 255 us against a minimum of
   //     359 / 360 us: DESIGN.md sec 4.5, profiles/r14a_tx_precompute.txt); ZKGPU_TX_HASH_LEVELS=0 / 1 picks the kernel for the
-  //     tests and for measuring.  A verifying call's stage never does: its launches are as they were
+  //     tests and for measuring (levels_).  A verifying call's stage never does: its launches are as they were
+  //   statements(): ZKGPU_TXFORMAT_STATEMENTS_V1 -- the call's pieces are records (tx_statements.hpp); nothing is hashed for an ID
+  //   forms_musig(): ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the MuSig coefficients come from k_musig_rows (tx_musig_rows.hpp) in
+  //     both stages' rows, the challenge from k_tx_sig_rows over the IDs the host uploads; no host fallback: an error of a launch is the call's
   static constexpr bool TX_HASH_LEVELS_SERVE = true;
   explicit GpuTxDevice(zkgpu_verifier* v, int slot_base = 0, size_t arena_base = 0, const zk::zkvm::TxFormat& format = zk::zkvm::TxFormat())
-      : v_(v), sb_(slot_base), ab_(arena_base), reasons_(format.reasons()), hashes_(format.hash_on_device), chains_(format.hash_on_device && format.sign_on_device),
-        ids_(format.out.ids), precompute_(format.precompute_only && format.out.ids && !chains_), levels_(precompute_ && levels_asked()),
-        log_k_(format.out.ids ? format.out.log_k : 0), statements_(format.statements()), forms_musig_(format.statements() && format.sign_on_device) {}
-  //   statements(): ZKGPU_TXFORMAT_STATEMENTS_V1 -- the call's pieces are records (tx_statements.hpp); nothing is hashed for an ID
-  //   ... with sign_on_device: the MuSig coefficients come from k_musig_rows (tx_musig_rows.hpp) in both stages' rows, the
-  //     challenge from k_tx_sig_rows over the IDs the host uploads; no host fallback: an error of a launch is the call's
-  bool statements() const override { return statements_; }
-  bool forms_musig() const override { return forms_musig_; }
+      : v_(v), sb_(slot_base), ab_(arena_base), format_(format), levels_(format.precompute() && levels_asked()) {}
+  const zk::zkvm::TxFormat& format() const override { return format_; }
   // points and offsets up, the coefficients written where the rows lie (skip 0), then the stage as msm_values_enqueue queues it
   int keys_enqueue_formed(int slot, const uint8_t* points, const uint64_t* offsets, size_t rows) override {
     zkgpu_ctx* c = keys(slot);
-    if (!forms_musig_) { err_ = "a key stage without scalars on a device that does not form them"; return ZKGPU_EINVAL; }
+    if (!format_.forms_musig()) { err_ = "a key stage without scalars on a device that does not form them"; return ZKGPU_EINVAL; }
     TRY(reasons_room(c, rows, true));
     return reasons_behind(c, seen(formed_keys_queue(c, points, offsets, rows), c, "key coefficient stage: "), ZKGPU_TXSTATUS_KEY);
   }
-  bool precompute() const override { return precompute_; }
-  bool reasons() const override { return reasons_; }
-  bool hashes() const override { return hashes_; }
-  bool chains() const override { return chains_; }
-  bool ids() const override { return ids_; }
-  size_t log_k() const override { return log_k_; }
-  const uint8_t* hash_log(int slot) override { return hashes_ && log_k_ ? (const uint8_t*)hash(slot).h_log : nullptr; }
+  const uint8_t* hash_log(int slot) override { return format_.hashes() && format_.log_k() ? (const uint8_t*)hash(slot).h_log : nullptr; }
   zk::zkvm::TxHashTape* hash_tape(int slot) override { return &hash(slot).tape; }
   // one copy up, one launch, one copy of the IDs down, on the stage's own high-priority stream
   int hash_enqueue(int slot, const zk::zkvm::TxHashTape& tape) override {
@@ -210,7 +202,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   }
   bool keys_done(int slot) override { return split_done(keys(slot)); }
   int keys_collect(int slot, uint8_t* ok_bits, uint8_t* values, uint8_t* why) override {
-    return seen(split_collect_why(keys(slot), ok_bits, values, reasons_ ? why : nullptr), keys(slot));
+    return seen(split_collect_why(keys(slot), ok_bits, values, format_.reasons() ? why : nullptr), keys(slot));
   }
   // (staging thread: touches the plans -- plans_mu -- the given arena and nothing else of the verifier)
   int proofs_stage(size_t ring_slot, size_t n, const zk::zkvm::TxProofSource* src, int host_threads, void** handle, std::string* err) override {
@@ -231,7 +223,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     // the one-wavefront-per-transaction transcript, or cut in two, does not shorten the tail of the call)
     const size_t saved_chunk = v_->chunk;
     v_->chunk = std::max<size_t>(saved_chunk, 4096);
-    st->run = block_start(v_, st->blk, true, reasons_);
+    st->run = block_start(v_, st->blk, true, format_.reasons());
     v_->chunk = saved_chunk;
     if (!st->run) { err_ = v_->last_error; return ZKGPU_ENOMEM; }
     if (st->run->rc != ZKGPU_OK) {
@@ -256,7 +248,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   int proofs_finish(void* handle, uint8_t* accept_bits, uint8_t* why) override {
     Staged* st = (Staged*)handle;
     int rc = ZKGPU_OK;
-    if (st->run) { rc = block_finish(v_, st->run, accept_bits, reasons_ ? why : nullptr); if (rc != ZKGPU_OK) err_ = v_->last_error; }
+    if (st->run) { rc = block_finish(v_, st->run, accept_bits, format_.reasons() ? why : nullptr); if (rc != ZKGPU_OK) err_ = v_->last_error; }
     proofs_release(handle);
     return rc;
   }
@@ -296,12 +288,12 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   }
   bool sigs_done(int slot) override { return split_done(sigs(slot)); }
   int sigs_collect(int slot, uint8_t* bits, uint8_t* why) override {
-    const int rc = seen(split_collect_why(sigs(slot), bits, nullptr, reasons_ ? why : nullptr), sigs(slot));
-    if (chains_ || forms_musig_) {
+    const int rc = seen(split_collect_why(sigs(slot), bits, nullptr, format_.reasons() ? why : nullptr), sigs(slot));
+    if (format_.chains() || format_.forms_musig()) {
       zkgpu_ctx* c = sigs(slot);
       const size_t rows = sig(slot).rows;
       sig(slot).rows = 0;
-      if (rc == ZKGPU_OK) { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_signed_on_device += rows; if (forms_musig_) v_->root->tx_musig_on_device += rows; }
+      if (rc == ZKGPU_OK) { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_signed_on_device += rows; if (format_.forms_musig()) v_->root->tx_musig_on_device += rows; }
       bool profiled = false;
       { std::lock_guard<std::recursive_mutex> lk(c->mu); profiled = c->profiling; }
       if (profiled) profile_to_root(c);                  // (only a call made with zkgpu_profile_enable on: nothing of it otherwise)
@@ -325,9 +317,9 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   }
   // what a device with reasons adds around a key or signature stage of `rows` on c (stage_reasons_*): room for the reason bytes
   // before the stage is queued; behind it -- rc: what queueing it gave -- their kernel and copy
-  int reasons_room(zkgpu_ctx* c, size_t rows, bool values) { return reasons_ ? seen(stage_reasons_reserve(c, rows, values), c) : ZKGPU_OK; }
+  int reasons_room(zkgpu_ctx* c, size_t rows, bool values) { return format_.reasons() ? seen(stage_reasons_reserve(c, rows, values), c) : ZKGPU_OK; }
   int reasons_behind(zkgpu_ctx* c, int rc, uint8_t code_when_clear) {
-    return (rc == ZKGPU_OK && reasons_) ? seen(stage_reasons_enqueue(c, code_when_clear), c) : rc;
+    return (rc == ZKGPU_OK && format_.reasons()) ? seen(stage_reasons_enqueue(c, code_when_clear), c) : rc;
   }
   // the rows of a chained stage up and the challenge kernel queued behind what `chain` names
   int chain_queue(int slot, const zk::zkvm::SigChain& chain, size_t rows, const uint8_t* dyn_scalars, const uint8_t* dyn_points,
@@ -431,7 +423,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     TRY(refuse_if_pending(c));
     DeviceGuard g(c->device);
-    if (!forms_musig_) { c->last_error = "a signature stage with the host's IDs on a device that does not form the coefficients"; return ZKGPU_EINVAL; }
+    if (!format_.forms_musig()) { c->last_error = "a signature stage with the host's IDs on a device that does not form the coefficients"; return ZKGPU_EINVAL; }
     hipStream_t key_stream = nullptr;
     {
       std::lock_guard<std::recursive_mutex> kl(kc->mu);
@@ -517,18 +509,18 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     // (a chain beside ZKGPU_TXFORMAT_RETURN_LOG: its challenge kernel waits for the IDs, not for the gather and the copies queued
     // below -- the event it waits for is recorded here; without the flag chain_queue records its own, as it always has)
     hs.ids_marked = false;
-    if (chains_ && log_k_ && h.n_tx) {
+    if (format_.chains() && format_.log_k() && h.n_tx) {
       if (!hs.ev_ids) HIP_TRY(c, hipEventCreateWithFlags(&hs.ev_ids, hipEventDisableTiming));
       HIP_TRY(c, hipEventRecord(hs.ev_ids, hs.stream));
       hs.ids_marked = true;
     }
     // (a chain reads them on the device: they come down only for a caller that is handed them)
-    if (!chains_ || ids_) HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));
+    if (!format_.chains() || format_.ids()) HIP_TRY(c, hipMemcpyAsync(hs.h_out, hs.d_txid.p, id_bytes, hipMemcpyDeviceToHost, hs.stream));
     // (the caller is handed the log: the contract IDs its entries name, gathered from the slots into n_tx x K x 32 dense bytes)
     hs.logged = false;
-    if (log_k_ && h.n_tx) {
-      if (!tx_log_table(tape.block(), hs.log_table) || !tx_log_lanes_fit(h.n_tx, log_k_)) { c->last_error = "a log entry outside its transaction's slots"; return ZKGPU_EINVAL; }
-      const size_t tab_bytes = 4 * hs.log_table.size(), log_bytes = 32 * log_k_ * (size_t)h.n_tx;
+    if (format_.log_k() && h.n_tx) {
+      if (!tx_log_table(tape.block(), hs.log_table) || !tx_log_lanes_fit(h.n_tx, format_.log_k())) { c->last_error = "a log entry outside its transaction's slots"; return ZKGPU_EINVAL; }
+      const size_t tab_bytes = 4 * hs.log_table.size(), log_bytes = 32 * format_.log_k() * (size_t)h.n_tx;
       TRY(pinned_grow(c, hs.h_tab, hs.h_tab_cap, tab_bytes));
       TRY(pinned_grow(c, hs.h_log, hs.h_log_cap, log_bytes));
       TRY(ensure(c, hs.d_tab, tab_bytes));
@@ -538,13 +530,13 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
       c->profiling = profiled;
       {
         Launch l(c, "k_tx_log_gather", hs.stream);
-        hipLaunchKernelGGL(zk::k_tx_log_gather, dim3(blocks_for((uint64_t)h.n_tx * log_k_, 64)), dim3(64), 0, hs.stream, (const uint32_t*)hs.d_tape.p,
-                           (const uint32_t*)hs.d_tab.p, (const uint32_t*)hs.d_slots.p, (uint32_t*)hs.d_log.p, h.n_tx, (uint32_t)log_k_);
+        hipLaunchKernelGGL(zk::k_tx_log_gather, dim3(blocks_for((uint64_t)h.n_tx * format_.log_k(), 64)), dim3(64), 0, hs.stream, (const uint32_t*)hs.d_tape.p,
+                           (const uint32_t*)hs.d_tab.p, (const uint32_t*)hs.d_slots.p, (uint32_t*)hs.d_log.p, h.n_tx, (uint32_t)format_.log_k());
       }
       c->profiling = false;
       HIP_TRY(c, hipGetLastError());
       HIP_TRY(c, hipMemcpyAsync(hs.h_log, hs.d_log.p, log_bytes, hipMemcpyDeviceToHost, hs.stream));
-      hs.n_logged = tx_log_handed_back(tape.block(), hs.log_table, log_k_);
+      hs.n_logged = tx_log_handed_back(tape.block(), hs.log_table, format_.log_k());
       hs.logged = true;
     }
     hs.n_tx = h.n_tx;
@@ -585,7 +577,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     hs.n_tx = 0;
     if (n == 0) return ZKGPU_OK;
     HIP_TRY(c, hipStreamSynchronize(hs.stream));
-    if (txids && (!chains_ || ids_)) memcpy(txids, hs.h_out, 32 * n);
+    if (txids && (!format_.chains() || format_.ids())) memcpy(txids, hs.h_out, 32 * n);
     if (!c->ev_used.empty()) { prof_collect(c); profile_to_root(c); }     // (a profiled stage: its launches have run)
     { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); v_->root->tx_hashed_on_device += n; if (hs.logged) v_->root->tx_logged_on_device += hs.n_logged; }
     return ZKGPU_OK;
@@ -597,10 +589,8 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   zkgpu_verifier* v_;
   const int sb_;
   const size_t ab_;
-  const bool reasons_, hashes_, chains_, ids_;
-  const bool precompute_, levels_;                       // a precompute-only call | ... whose tapes are walked by level
-  const size_t log_k_;
-  const bool statements_, forms_musig_;                  // the call's pieces are records | ... and the device forms a_i and c
+  const zk::zkvm::TxFormat format_;                      // the mode of the call (tx_out.hpp): its predicates are asked where they matter
+  const bool levels_;                                    // (a precompute-only call) its tapes are walked by level: the environment may say otherwise
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];
   std::string err_;

@@ -1,6 +1,7 @@
 // tx_out.hpp -- what a transaction call hands its caller, laid out ONCE: the format word of zkgpu_verifier_set_tx_format decoded
-// and validated (TxFormat), the layout of a call's status argument as a value (TxOutLayout), and the hand-out of a merged round
-// to its calls (tx_round_hand_out).  Host-only, no HIP and no zkgpu.h (its constants are restated; session.hpp asserts them), so
+// and validated (TxFormat) -- with it the MODE of a call, as predicates every layer asks --, the layout of a call's status
+// argument as a value (TxOutLayout), which calls in flight share a round and under what format (tx_round_mates,
+// tx_round_format), and the hand-out of a merged round to its calls (tx_round_hand_out).  Host-only, no HIP and no zkgpu.h (its constants are restated; session.hpp asserts them), so
 // that libzkgpu and libzkhost -- the CPU self-tests of hostlib.cpp -- compile the SAME code, like pipe_plan.hpp or msm_route.hpp.
 //
 // The status argument of a call over `batch` transactions:   status[batch] | id[batch][32] | record[batch][1 + 33 K]
@@ -84,12 +85,47 @@ struct TxFormat {
     return true;
   }
   static TxFormat of_valid(int word) { TxFormat f; if (!of(word, &f)) f = TxFormat(); return f; }     // (of a word validated when it was stored)
-  bool statements() const { return base == TXFORMAT_STATEMENTS_V1; }
-  bool reasons() const { return base == TXFORMAT_V1_REASONS || (statements() && !mute); }
+  // What a call under the format IS, said here once -- for a decoded word and for a format filled in by hand alike; the scheduler
+  // (tx_call.hpp), the device (tx_device.hpp) and the CPU stand-ins (hostlib.cpp) ask these and narrow nothing themselves.
+  bool statements() const { return base == TXFORMAT_STATEMENTS_V1; }                      // the pieces are records of the caller's own VM: nothing is hashed for an ID
+  bool reasons() const { return base == TXFORMAT_V1_REASONS || (statements() && !mute); } // every stage brings back a reason byte per row
+  bool hashes() const { return hash_on_device && !statements(); }                         // the transaction IDs come from the device: tapes, no host second pass
+  bool chains() const { return hashes() && sign_on_device; }                              // ... and the signature's challenge: keys, tape and signatures are one chain
+  bool precompute() const { return precompute_only && out.ids && !chains() && !statements(); }   // the VM, the IDs and the log alone: nothing is verified
+  bool forms_musig() const { return statements() && sign_on_device; }                     // a statements call whose device forms a_i and c
+  bool ids() const { return out.ids; }                                                    // the caller is handed the IDs of what it accepted
+  size_t log_k() const { return out.ids ? out.log_k : 0; }                                // ... and at most so many log entries per transaction (only beside the IDs)
   // the same for a caller that passed no status argument: nowhere to say a reason or to put an ID or a record -- the format-1 call
   // (`mute` is read by reasons() for base 4 alone, which has no reasonless twin to fall back to; formats 1 / 2 never read it)
   TxFormat without_status() const { TxFormat f = *this; f.base = base == TXFORMAT_V1_REASONS ? TXFORMAT_V1 : base; f.mute = true; f.out = TxOutLayout(); return f; }
 };
+
+// Which calls of zkgpu_tx_verify_submit share a round, and the format the round runs under -- from the format each call was
+// SUBMITTED under.  A call's kind: PRECOMPUTE, keyed by (base, hash_on_device); STATEMENTS, keyed by (sign_on_device); anything
+// else VERIFY, one key whatever word the calls were submitted under (base format and device switches are read when the round
+// starts, as they always were).  A round holds calls of one kind and one key.
+enum class TxRoundKind { VERIFY, PRECOMPUTE, STATEMENTS };
+inline TxRoundKind tx_round_kind(const TxFormat& f) { return f.precompute_only ? TxRoundKind::PRECOMPUTE : f.statements() ? TxRoundKind::STATEMENTS : TxRoundKind::VERIFY; }
+inline bool tx_round_mates(const TxFormat& a, const TxFormat& b) {
+  const TxRoundKind kind = tx_round_kind(a);
+  if (kind != tx_round_kind(b)) return false;
+  if (kind == TxRoundKind::PRECOMPUTE) return a.base == b.base && a.hash_on_device == b.hash_on_device;
+  return kind != TxRoundKind::STATEMENTS || a.sign_on_device == b.sign_on_device;
+}
+// first: what the round's first call was submitted under; now: the verifier's format as the round starts.  A precompute-only
+// round runs under the base format and the hashing switch its calls were queued under, whatever the format says by now, and
+// never chains; a statements round under base 4 and the signing switch of its calls; a verifying round under the format in
+// force now -- unless that is the statements format: its bytes are transactions, and it runs under its first call's word.
+// `out` comes back empty (the caller ORs in the calls' layouts) and `mute` false; base 0 still means "nothing inside the subset".
+inline TxFormat tx_round_format(const TxFormat& first, const TxFormat& now) {
+  const TxRoundKind kind = tx_round_kind(first);
+  TxFormat f;
+  if (kind == TxRoundKind::PRECOMPUTE) { f.base = first.base; f.hash_on_device = first.hash_on_device; f.precompute_only = true; return f; }
+  if (kind == TxRoundKind::STATEMENTS) { f.base = TXFORMAT_STATEMENTS_V1; f.sign_on_device = first.sign_on_device; return f; }
+  f = now.statements() ? first : now;
+  f.precompute_only = false; f.mute = false; f.out = TxOutLayout();
+  return f;
+}
 
 // One call of a merged round (zkgpu_tx_verify_submit): its own bitmap ((batch + 7) / 8 bytes) and its own area of
 // layout.bytes(batch), whose ID and record parts the round's TxCall wrote through the call's TxPiece.  tx_round_hand_out gives
