@@ -681,6 +681,31 @@ int zkgpu_verifier_wait(zkgpu_verifier *v, uint64_t ticket, uint8_t *accept_bitm
  * queued under different base formats or hashing switches.  (A submitted VERIFYING call keeps its layout alone, as it always
  * has: base format and device switches are those in force when its round starts.) */
 #define ZKGPU_TXFORMAT_PRECOMPUTE_ONLY 8192   /* 0x2000; only together with ZKGPU_TXFORMAT_RETURN_IDS, never with ..._SIGN_ON_DEVICE */
+/* A sixth FLAG, only TOGETHER WITH ZKGPU_TXFORMAT_RETURN_IDS (valid: any word that is valid without it and has 0x400, or-ed with
+ * 16 -- every base-1 / base-2 combination with the IDs, the log window and precompute-only included; ZKGPU_EINVAL: 16 without
+ * 0x400, 16 beside base 0 or base 4, 16 alone; everything invalid without it stays invalid): the call's TRANSACTION ROOT comes
+ * back with the IDs -- upstream's MerkleTree::root over the transaction IDs of the call in call order, what a node compares
+ * with a block header's `txroot`.
+ *
+ *   !!  WITH THIS FLAG SET, THE `status` ARGUMENT OF zkgpu_tx_verify_batch AND zkgpu_tx_verify_wait POINTS AT 32 BYTES    !!
+ *   !!  MORE THAN THE SAME FORMAT WITHOUT IT: old_bytes(batch) + 32, ALSO WHEN batch IS 0.  A caller that sets the flag   !!
+ *   !!  and passes old_bytes(batch) bytes IS OVERRUN BY 32 BYTES.                                                         !!
+ *
+ * Bytes [0, old_bytes(batch)) are byte for byte what the same format writes without the flag -- status bytes, IDs, log records;
+ * nothing moves.  The 32 bytes behind them are the root.  It is the transaction ID's own tree (RFC 6962 split, one Merlin
+ * transcript per node) under the domain label "ZkVM.txroot": a node hashes the messages "L" and "R" into the challenge
+ * "merkle.node", a leaf the message ("txid", id) into "merkle.leaf", the empty tree nothing into "merkle.empty".  (Label and
+ * leaf message are a recollection like the rest of the format: INTEGRATION.md sec 3d'.)
+ * The root is written ONLY IF EVERY transaction of the call reads status 0 (3 under ZKGPU_TXFORMAT_PRECOMPUTE_ONLY); otherwise
+ * the 32 bytes are zero -- a block with one bad transaction has no root worth comparing.  Fail-closed like the rest: the area
+ * is zeroed before the call starts and again on any error, and the root is written last, after the last ID.  batch == 0: the
+ * empty tree's hash.  status == NULL stays legal: then there is no root.  A submitted call keeps the layout it was QUEUED
+ * under; every call of a merged round gets the root of ITS OWN transactions, and its bitmap, status bytes, IDs and records are
+ * byte for byte those of the same word without 16.  With ZKGPU_TXFORMAT_HASH_ON_DEVICE the IDs are in device memory when the
+ * call ends and the tree is folded there (one leaf launch per chunk, a few fold launches behind the last chunk, 32 bytes
+ * down; no host fallback: an error of a launch or copy is an error of the call); without it the host threads fold the host
+ * VM's IDs, and a precompute-only call still never touches the device. */
+#define ZKGPU_TXFORMAT_RETURN_ROOT 16   /* 0x10; only together with ZKGPU_TXFORMAT_RETURN_IDS */
 /* A third BASE FORMAT (3 stays invalid): the SECOND HALF of upstream's Tx::verify alone -- PrecomputedTx::verify -- for a
  * caller that ran ITS OWN VM (Tx::precompute()) and hands over what that VM left, not serialized transactions.  `txs` /
  * `tx_offsets` are then a CSR of RECORDS.  The framing is THIS LIBRARY'S OWN, not a recollection of anything upstream; of the
@@ -787,6 +812,7 @@ int zkgpu_verifier_verify_sharded(zkgpu_verifier *v, zkgpu_comm *comm, size_t ba
  *   ZKGPU_TIMELINE=<file>     with profiling on, every launch as "ctx kernel start_ms end_ms"
  *   ZKGPU_PROVER_TIMING=1     the provers and zkgpu_tx_verify_batch print per-phase host / device times to stderr
  *   ZKGPU_PROVER_SLICES=n     slices of a prover call in flight together (default: 2 from 1024 statements on)
+ *   ZKGPU_TX_ROOT_SPAN=s      tree levels one fold launch of ZKGPU_TXFORMAT_RETURN_ROOT walks, 1 .. 7 (default 7; read once, at load)
  * and GPU_MAX_HW_QUEUES (a HIP runtime variable, READ only: the host exports it on zkgpu_runtime_hint's advice before its
  * first HIP call; batches in flight need a hardware queue per context). */
 const void *zkgpu_hook(const char *name);

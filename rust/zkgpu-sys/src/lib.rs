@@ -29,6 +29,7 @@ pub const ZKGPU_TXFORMAT_RETURN_IDS: c_int = 1024;
 pub const ZKGPU_TXFORMAT_RETURN_LOG: c_int = 2048;
 pub const ZKGPU_TXFORMAT_LOG_SHIFT: c_int = 16;
 pub const ZKGPU_TXFORMAT_PRECOMPUTE_ONLY: c_int = 8192;
+pub const ZKGPU_TXFORMAT_RETURN_ROOT: c_int = 16;
 pub const ZKGPU_TXFORMAT_STATEMENTS_V1: c_int = 4;
 pub const ZKGPU_TXLOG_INPUT: c_int = 1;
 pub const ZKGPU_TXLOG_OUTPUT: c_int = 2;

@@ -173,6 +173,8 @@ pub struct TxCall<'v> {
     ids: bool,
     /// ... and under `ZKGPU_TXFORMAT_RETURN_LOG` with this window (0: no): `(33 + 1 + 33 * log_k) * n` bytes
     log_k: usize,
+    /// ... and under `ZKGPU_TXFORMAT_RETURN_ROOT`: 32 more bytes behind everything else
+    root: bool,
     waited: bool,
     _blob: Vec<u8>,
     _offsets: Vec<u64>,
@@ -205,6 +207,8 @@ pub struct GpuVerifier {
     return_ids: AtomicBool,
     /// ... and `ZKGPU_TXFORMAT_RETURN_LOG` with this window K (0: no): 33 + 1 + 33 K bytes per transaction
     log_k: AtomicUsize,
+    /// ... and `ZKGPU_TXFORMAT_RETURN_ROOT`: 32 more bytes behind everything else, the root over the call's IDs
+    return_root: AtomicBool,
     /// ... and `ZKGPU_TXFORMAT_PRECOMPUTE_ONLY`: calls verify nothing, and only `precompute` makes them
     precompute_only: AtomicBool,
 }
@@ -291,7 +295,7 @@ impl GpuVerifier {
         match built {
             Ok((ps, v, warned)) => {
                 let warning = if warned { Some(text(unsafe { sys::zkgpu_verifier_last_error(v) })) } else { None };
-                Ok(GpuVerifier { ctx, gens: Generators { ps, capacity: gens_capacity }, v, warning, return_ids: AtomicBool::new(false), log_k: AtomicUsize::new(0), precompute_only: AtomicBool::new(false) })
+                Ok(GpuVerifier { ctx, gens: Generators { ps, capacity: gens_capacity }, v, warning, return_ids: AtomicBool::new(false), log_k: AtomicUsize::new(0), return_root: AtomicBool::new(false), precompute_only: AtomicBool::new(false) })
             }
             Err(e) => {
                 unsafe { sys::zkgpu_destroy(ctx) };
@@ -388,6 +392,7 @@ impl GpuVerifier {
         self.return_ids.store(format & sys::ZKGPU_TXFORMAT_RETURN_IDS != 0, Ordering::SeqCst);
         let k = if format & sys::ZKGPU_TXFORMAT_RETURN_LOG != 0 { ((format >> sys::ZKGPU_TXFORMAT_LOG_SHIFT) & 255) as usize } else { 0 };
         self.log_k.store(k, Ordering::SeqCst);
+        self.return_root.store(format & sys::ZKGPU_TXFORMAT_RETURN_IDS != 0 && format & sys::ZKGPU_TXFORMAT_RETURN_ROOT != 0, Ordering::SeqCst);
         self.precompute_only.store(format & sys::ZKGPU_TXFORMAT_PRECOMPUTE_ONLY != 0, Ordering::SeqCst);
         Ok(())
     }
@@ -445,6 +450,24 @@ impl GpuVerifier {
         self.set_tx_format(base | hash | sign | sys::ZKGPU_TXFORMAT_RETURN_IDS | log)
     }
 
+    /// `enable_recollected_tx_format_returning_ids` (`k` = 0) or `..._returning_log` (`k` = 1 ..= 255) with
+    /// `ZKGPU_TXFORMAT_RETURN_ROOT` beside it: `verify_txs_with_root` then also hands back the Merkle root over the call's
+    /// transaction IDs in call order -- what a node compares with a block header's `txroot` -- if EVERY transaction of the
+    /// call was accepted.  Same verdicts, same IDs, same log.
+    pub fn enable_recollected_tx_format_returning_root(&self, k: usize, with_reasons: bool, hash_on_device: bool, sign_on_device: bool) -> Result<(), Error> {
+        if k > 255 {
+            return Err(Error::InvalidArgument("the log window is 0 (no log) or 1 ..= 255 entries".into()));
+        }
+        if sign_on_device && !hash_on_device {
+            return Err(Error::InvalidArgument("signing on the device needs hashing on the device".into()));
+        }
+        let base = if with_reasons { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1_REASONS } else { sys::ZKGPU_TXFORMAT_RECOLLECTED_V1 };
+        let hash = if hash_on_device { sys::ZKGPU_TXFORMAT_HASH_ON_DEVICE } else { 0 };
+        let sign = if sign_on_device { sys::ZKGPU_TXFORMAT_SIGN_ON_DEVICE } else { 0 };
+        let log = if k > 0 { sys::ZKGPU_TXFORMAT_RETURN_LOG | ((k as c_int) << sys::ZKGPU_TXFORMAT_LOG_SHIFT) } else { 0 };
+        self.set_tx_format(base | hash | sign | sys::ZKGPU_TXFORMAT_RETURN_IDS | log | sys::ZKGPU_TXFORMAT_RETURN_ROOT)
+    }
+
     /// `ZKGPU_TXFORMAT_PRECOMPUTE_ONLY` beside `ZKGPU_TXFORMAT_RETURN_IDS` (and, `k` > 0, `ZKGPU_TXFORMAT_RETURN_LOG` with that
     /// window): from here on the verifier's transaction calls VERIFY NOTHING and are made through `precompute`, the
     /// reference's `Tx::precompute()`; `verify_txs` and `submit_txs` refuse until a verifying format is enabled again.
@@ -480,7 +503,7 @@ impl GpuVerifier {
         }
         let log_k = self.log_k.load(Ordering::SeqCst);
         let mut bitmap = vec![0u8; (n + 7) / 8];
-        let mut status = vec![1u8; Self::tx_status_len(n, true, log_k)];
+        let mut status = vec![1u8; Self::tx_status_len(n, true, log_k) + Self::tx_root_len(self.return_root.load(Ordering::SeqCst))];
         check(
             unsafe {
                 sys::zkgpu_tx_verify_batch(self.v, n, blob.as_ptr(), offs.as_ptr(), host_threads as c_int, bitmap.as_mut_ptr(), status.as_mut_ptr())
@@ -549,6 +572,11 @@ impl GpuVerifier {
         }
     }
 
+    /// the 32 bytes `ZKGPU_TXFORMAT_RETURN_ROOT` adds behind a status array
+    fn tx_root_len(root: bool) -> usize {
+        if root { 32 } else { 0 }
+    }
+
     /// the log records behind the ID area -> beside every `Accepted` its entries
     fn tx_logs(n: usize, log_k: usize, verdicts: &[(TxVerdict, Option<[u8; 32]>)], status: &[u8]) -> Vec<Option<TxLog>> {
         let per = 1 + 33 * log_k;
@@ -608,10 +636,25 @@ impl GpuVerifier {
         Ok(self.verify_txs_with_log(txs, host_threads)?.into_iter().map(|(verdict, id, _)| (verdict, id)).collect())
     }
 
+    /// `verify_txs_with_log`, and the call's transaction root: `Some` only after `enable_recollected_tx_format_returning_root`
+    /// and only if EVERY transaction of the call was accepted -- the Merkle root over their IDs in call order; of no
+    /// transaction, the empty tree's hash is the library's to give and this wrapper returns `None`.
+    pub fn verify_txs_with_root(&self, txs: &[&[u8]], host_threads: i32) -> Result<(Vec<(TxVerdict, Option<[u8; 32]>, Option<TxLog>)>, Option<[u8; 32]>), Error> {
+        let mut root = None;
+        let out = self.verify_txs_into(txs, host_threads, &mut root)?;
+        Ok((out, root))
+    }
+
     /// `verify_txs_with_ids`, and beside every `Accepted` the `Input` / `Output` entries of its log -- `Some` only after
     /// `enable_recollected_tx_format_returning_log`, `None` beside every other verdict: the `VerifiedTx.log` of the reference
     /// without its header entry.
     pub fn verify_txs_with_log(&self, txs: &[&[u8]], host_threads: i32) -> Result<Vec<(TxVerdict, Option<[u8; 32]>, Option<TxLog>)>, Error> {
+        let mut root = None;
+        self.verify_txs_into(txs, host_threads, &mut root)
+    }
+
+    /// the one call behind `verify_txs*`; `root`: set if the format carries the root and the library wrote one (not all zero)
+    fn verify_txs_into(&self, txs: &[&[u8]], host_threads: i32, root: &mut Option<[u8; 32]>) -> Result<Vec<(TxVerdict, Option<[u8; 32]>, Option<TxLog>)>, Error> {
         if self.precompute_only.load(Ordering::SeqCst) {
             return Err(Error::InvalidArgument("verify_txs: the format in force is precompute-only, nothing would be verified".into()));
         }
@@ -628,8 +671,9 @@ impl GpuVerifier {
         }
         let ids = self.return_ids.load(Ordering::SeqCst);
         let log_k = if ids { self.log_k.load(Ordering::SeqCst) } else { 0 };
+        let has_root = ids && self.return_root.load(Ordering::SeqCst);
         let mut bitmap = vec![0u8; (n + 7) / 8];
-        let mut status = vec![1u8; Self::tx_status_len(n, ids, log_k)];
+        let mut status = vec![1u8; Self::tx_status_len(n, ids, log_k) + Self::tx_root_len(has_root)];
         check(
             unsafe {
                 sys::zkgpu_tx_verify_batch(self.v, n, blob.as_ptr(), offs.as_ptr(), host_threads as c_int, bitmap.as_mut_ptr(), status.as_mut_ptr())
@@ -638,6 +682,14 @@ impl GpuVerifier {
         )?;
         let verdicts = Self::tx_verdicts_with_ids(n, ids, &bitmap, &status);
         let logs = Self::tx_logs(n, log_k, &verdicts, &status);
+        if has_root {
+            let at = Self::tx_status_len(n, ids, log_k);
+            if status[at..at + 32].iter().any(|b| *b != 0) {
+                let mut r = [0u8; 32];
+                r.copy_from_slice(&status[at..at + 32]);
+                *root = Some(r);
+            }
+        }
         Ok(verdicts.into_iter().zip(logs).map(|((verdict, id), log)| (verdict, id, log)).collect())
     }
 
@@ -662,9 +714,10 @@ impl GpuVerifier {
         let mut id = 0u64;
         let ids = self.return_ids.load(Ordering::SeqCst); // (the layout of the call's status array is the one in force now)
         let log_k = if ids { self.log_k.load(Ordering::SeqCst) } else { 0 };
+        let root = ids && self.return_root.load(Ordering::SeqCst);
         // (the heap buffers of `blob` and `offsets` do not move when the vectors are moved into the handle)
         check(unsafe { sys::zkgpu_tx_verify_submit(self.v, n, blob.as_ptr(), offsets.as_ptr(), host_threads as c_int, &mut id) }, self.err())?;
-        Ok(TxCall { verifier: self, id, n, ids, log_k, waited: false, _blob: blob, _offsets: offsets })
+        Ok(TxCall { verifier: self, id, n, ids, log_k, root, waited: false, _blob: blob, _offsets: offsets })
     }
 
     /// Blocks until the call's round is done: one verdict per transaction of THAT call.
@@ -680,7 +733,7 @@ impl GpuVerifier {
         }
         let n = call.n;
         let mut bitmap = vec![0u8; (n + 7) / 8];
-        let mut status = vec![1u8; Self::tx_status_len(n, call.ids, call.log_k)];
+        let mut status = vec![1u8; Self::tx_status_len(n, call.ids, call.log_k) + Self::tx_root_len(call.root)];
         let rc = unsafe { sys::zkgpu_tx_verify_wait(self.v, call.id, bitmap.as_mut_ptr(), status.as_mut_ptr()) };
         call.waited = true; // (whatever it returned, the library is done with the call's bytes)
         check(rc, self.err())?;

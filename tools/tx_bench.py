@@ -1,6 +1,6 @@
 """zkgpu_tx_verify_batch on the committed 1024 transactions (per-stage times with ZKGPU_PROVER_TIMING=1).
 usage: tx_bench.py [--device-hashing] [--device-signing] [--host-threads N] [--calls N] [--in-flight K] [copies of the fixture per call] [block chunk] [tx chunk]
-(TX_BENCH_FORMAT=2: the format with reason codes; --device-hashing: or-ed with ZKGPU_TXFORMAT_HASH_ON_DEVICE; --device-signing: with
+(TX_BENCH_FORMAT=<word>: the base format and the layout flags, e.g. 2 for reason codes or 1042 = 2 | 0x400 | 16 for the IDs and the root; --device-hashing: or-ed with ZKGPU_TXFORMAT_HASH_ON_DEVICE; --device-signing: with
 that flag and ZKGPU_TXFORMAT_SIGN_ON_DEVICE; --calls N: library calls timed alone (3); --host-threads N: the
 host_threads of every call, 0 = the CPUs the process may use; --in-flight K: also K calls of that size through submit / wait)"""
 import os as _os; _os.environ.setdefault("ZKGPU_TEST_HOOKS", "1")   # the profile / mode hooks (include/zkgpu_hooks.h) are not exports
@@ -53,8 +53,9 @@ assert os.environ.get("ZKGPU_TEST_TX_FREE_HASHING") == "1" or not any(st)      #
 # the library call alone (offsets and output buffers made beforehand)
 offs = np.zeros(len(lens) + 1, dtype=np.uint64)
 np.cumsum(np.asarray(lens, dtype=np.uint64), out=offs[1:])
-# (TX_BENCH_FORMAT may carry ZKGPU_TXFORMAT_RETURN_IDS / _RETURN_LOG | K << 16: the library then writes 33, or 33 + 1 + 33 K, bytes per transaction)
-bmb, stb = C.create_string_buffer((len(lens) + 7) // 8), C.create_string_buffer(bv._tx_status_bytes(len(lens), *bv._tx_layout))
+# (TX_BENCH_FORMAT may carry ZKGPU_TXFORMAT_RETURN_IDS / _RETURN_LOG | K << 16: the library then writes 33, or 33 + 1 + 33 K, bytes per transaction;
+# with ZKGPU_TXFORMAT_RETURN_ROOT, 16, 32 more bytes behind them)
+bmb, stb = C.create_string_buffer((len(lens) + 7) // 8), C.create_string_buffer(bv._tx_status_bytes(len(lens), *bv._tx_layout, bv._tx_root))
 for _ in range(CALLS):
     t0 = time.perf_counter()
     rc = bv.lib.zkgpu_tx_verify_batch(bv.h, len(lens), blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), HT, bmb, stb)

@@ -13,7 +13,7 @@ built library or without a GPU raises.
 # itself, before that (bench.py does, at its very top).
 
 from .native import TXFORMAT_HASH_ON_DEVICE, TXFORMAT_LOG_SHIFT, TXFORMAT_PRECOMPUTE_ONLY, TXFORMAT_RETURN_IDS, TXFORMAT_RETURN_LOG, TXFORMAT_SIGN_ON_DEVICE, TXLOG_INPUT, TXLOG_OUTPUT, TXSTATUS_PRECOMPUTED, Context, PointSet, ZkGpuError, lib_path, load_library, runtime_hint  # noqa: F401
-from .native import TXFORMAT_STATEMENTS_V1, pack_statement  # noqa: F401
+from .native import TXFORMAT_RETURN_ROOT, TXFORMAT_STATEMENTS_V1, pack_statement  # noqa: F401
 
 __all__ = ["Context", "PointSet", "ZkGpuError", "lib_path", "load_library", "runtime_hint", "TXFORMAT_HASH_ON_DEVICE", "TXFORMAT_SIGN_ON_DEVICE", "TXFORMAT_RETURN_IDS", "TXFORMAT_RETURN_LOG",
-           "TXFORMAT_LOG_SHIFT", "TXLOG_INPUT", "TXLOG_OUTPUT", "TXFORMAT_PRECOMPUTE_ONLY", "TXSTATUS_PRECOMPUTED", "TXFORMAT_STATEMENTS_V1", "pack_statement"]
+           "TXFORMAT_LOG_SHIFT", "TXLOG_INPUT", "TXLOG_OUTPUT", "TXFORMAT_PRECOMPUTE_ONLY", "TXSTATUS_PRECOMPUTED", "TXFORMAT_STATEMENTS_V1", "pack_statement", "TXFORMAT_RETURN_ROOT"]

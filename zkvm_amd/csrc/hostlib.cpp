@@ -2192,3 +2192,51 @@ extern "C" long long zkhost_txcall_trace(int word, int n_slots, size_t chunk, si
   std::copy(traced.trace().begin(), traced.trace().end(), out);
   return (long long)n;
 }
+
+// ---- ZKGPU_TXFORMAT_RETURN_ROOT on the CPU (tx_out.hpp with the flag, tx_root.hpp), for tests/test_tx_root_host.py.  op 0: the
+// ---- format word in[0] -> out: valid, base, hash, sign, ids, K, precompute-only, root.  Ops 1 .. 4 take a layout in[0] = ids,
+// ---- in[1] = K, in[2] = root and a batch in[3]: op 1 -> out: bytes(batch), the offset of the root and of a piece's root (-1: not
+// ---- there); op 2 begin, 3 nothing-in-the-subset, 4 fail-closed over bitmap and area (either may be NULL).  op 5, a round's
+// ---- hand-out: in[0] calls, in[1] ok, then (ids, K, root, batch) per call; bitmap / area hold the ROUND's bits / status bytes,
+// ---- data the round's roots (32 bytes per call), out_bits / out_area the calls' bitmaps and areas one behind the other.
+// ---- op 6, the host fold: in[0] = n IDs at data, in[1] = the span (levels per pass; anything outside 1 .. 7: the default),
+// ---- in[2] = host threads -> 32 bytes at out_area; out[0] = passes.  -> 0, -1 on bad arguments
+#include "tx_root.hpp"
+extern "C" int zkhost_tx_root(int op, const int64_t* in, const uint8_t* data, uint8_t* bitmap, uint8_t* area, uint8_t* out_bits, uint8_t* out_area, int64_t* out) {
+  if (!in || op < 0 || op > 6 || ((op <= 1 || op == 6) && !out)) return -1;
+  const auto layout = [](const int64_t* q) { TxOutLayout l; l.ids = q[0] != 0; l.log_k = (size_t)q[1]; l.root = q[2] != 0; return l; };
+  if (op == 0) {
+    TxFormat f;
+    const int64_t r[8] = {TxFormat::of((int)in[0], &f), f.base, f.hash_on_device, f.sign_on_device, f.out.ids, (int64_t)f.out.log_k, f.precompute_only, f.out.root};
+    std::copy(r, r + 8, out);
+    return 0;
+  }
+  if (op == 6) {
+    if (in[0] < 0 || (in[0] > 0 && !data) || !out_area) return -1;
+    tx_root_fold_host(data, (size_t)in[0], (uint32_t)std::max<int64_t>(0, std::min<int64_t>(in[1], 64)), (int)in[2], out_area);
+    out[0] = tx_root_passes((uint64_t)in[0], tx_root_span(in[1]));
+    return 0;
+  }
+  if (op == 5) {
+    if (!data) return -1;
+    std::vector<TxHandOut> to;
+    for (int64_t c = 0; c < in[0]; ++c) {
+      to.push_back({(size_t)in[5 + 4 * c], layout(in + 2 + 4 * c), out_bits, out_area, data + 32 * c});
+      out_bits += (to.back().batch + 7) / 8; out_area += to.back().layout.bytes(to.back().batch);
+    }
+    tx_round_hand_out(bitmap, area, in[1] != 0, to.data(), to.size());
+    return 0;
+  }
+  const TxOutLayout lay = layout(in);
+  const size_t batch = (size_t)in[3];
+  if (op == 2) lay.begin(bitmap, area, batch);
+  if (op == 3) lay.nothing_in_subset(area, batch);
+  if (op == 4) lay.fail_closed(bitmap, area, batch);
+  if (op != 1) return 0;
+  uint8_t* const base = (uint8_t*)(uintptr_t)4096;        // (offsets only: nothing is read or written)
+  const auto at = [&](const uint8_t* p) { return p ? (int64_t)(p - base) : (int64_t)-1; };
+  const TxPiece pc = lay.piece(nullptr, nullptr, batch, base);
+  const int64_t r[3] = {(int64_t)lay.bytes(batch), at(lay.root_of(base, batch)), at(pc.root)};
+  std::copy(r, r + 3, out);
+  return 0;
+}

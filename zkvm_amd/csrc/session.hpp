@@ -16,6 +16,7 @@
 #include "tx_call.hpp"
 #include "tx_hash_kernels.hpp"
 #include "tx_hash_levels.hpp"
+#include "tx_root_kernels.hpp"
 #include "tx_sig_rows.hpp"
 #include "tx_musig_rows.hpp"
 #include "zkvm_tx.hpp"
@@ -130,9 +131,30 @@ struct zkgpu_verifier {
     size_t h_levels_cap = 0;
     std::vector<uint32_t> levels_table;
     Buffer d_levels;
+    // ZKGPU_TXFORMAT_RETURN_ROOT: where in the call the slot's next tape starts, its transactions' places in the call on their
+    // way up, and the event recorded behind the slot's latest leaf kernel (what the folds on the other slot's stream wait for)
+    size_t place = 0;
+    void* h_root_pos = nullptr;
+    size_t h_root_pos_cap = 0;
+    Buffer d_root_pos;
+    hipEvent_t ev_leaves = nullptr;
   };
   TxHashStage tx_hash[2];
   Buffer tx_hash_const;
+  // the roots of ONE call in flight (tx_root_kernels.hpp; a lone call uses [0], a round of the engine the one of its set): the
+  // call-wide leaves, zeroed when the call starts (ev_zeroed, recorded on zero_stream, orders the other slot's stream behind
+  // that), the two node arrays the passes alternate between, the roots of the asking pieces (device, pinned); marked[slot]:
+  // the call has queued leaves on that hashing slot.  Once per verifier: the tree's initial transcript (tx_root_const).
+  struct TxRootStage {
+    Buffer d_leaves, d_nodes[2], d_roots;
+    void* h_roots = nullptr;
+    size_t h_roots_cap = 0, total = 0, n_ranges = 0;
+    hipEvent_t ev_zeroed = nullptr;
+    hipStream_t zero_stream = nullptr;
+    bool marked[2] = {false, false};
+  };
+  TxRootStage tx_root[2];
+  Buffer tx_root_const;
   // what the signature's challenge needs beside its slot's signature context (tx_sig_rows.hpp): the rows' places on the tape,
   // the events that order it behind the slot's key stage and hashing stage; once per verifier, the script of the transcript
   // (d_ids, h_pos: a statements call whose device forms a_i and c -- the rows' IDs as the host uploaded them, and the identity
@@ -500,10 +522,18 @@ void zkgpu_verifier_destroy(zkgpu_verifier* v) {
       if (hs.h_tab) (void)hipHostFree(hs.h_tab);
       if (hs.h_log) (void)hipHostFree(hs.h_log);
       if (hs.h_levels) (void)hipHostFree(hs.h_levels);
+      if (hs.h_root_pos) (void)hipHostFree(hs.h_root_pos);
       if (hs.ev_ids) (void)hipEventDestroy(hs.ev_ids);
-      for (Buffer* b : {&hs.d_tape, &hs.d_slots, &hs.d_txid, &hs.d_tab, &hs.d_log, &hs.d_levels}) if (b->p) (void)hipFree(b->p);
+      if (hs.ev_leaves) (void)hipEventDestroy(hs.ev_leaves);
+      for (Buffer* b : {&hs.d_tape, &hs.d_slots, &hs.d_txid, &hs.d_tab, &hs.d_log, &hs.d_levels, &hs.d_root_pos}) if (b->p) (void)hipFree(b->p);
     }
     if (v->tx_hash_const.p) (void)hipFree(v->tx_hash_const.p);
+    for (auto& rs : v->tx_root) {
+      if (rs.h_roots) (void)hipHostFree(rs.h_roots);
+      if (rs.ev_zeroed) (void)hipEventDestroy(rs.ev_zeroed);
+      for (Buffer* b : {&rs.d_leaves, &rs.d_nodes[0], &rs.d_nodes[1], &rs.d_roots}) if (b->p) (void)hipFree(b->p);
+    }
+    if (v->tx_root_const.p) (void)hipFree(v->tx_root_const.p);
     for (auto& ss : v->tx_sig) {
       if (ss.ev_keys) (void)hipEventDestroy(ss.ev_keys);
       if (ss.ev_ids) (void)hipEventDestroy(ss.ev_ids);
@@ -1750,7 +1780,8 @@ static_assert(zk::zkvm::TXFORMAT_V1 == ZKGPU_TXFORMAT_RECOLLECTED_V1 && zk::zkvm
               zk::zkvm::TXFORMAT_RETURN_IDS == ZKGPU_TXFORMAT_RETURN_IDS && zk::zkvm::TXFORMAT_RETURN_LOG == ZKGPU_TXFORMAT_RETURN_LOG &&
               zk::zkvm::TXFORMAT_LOG_SHIFT == ZKGPU_TXFORMAT_LOG_SHIFT && zk::zkvm::TXOUT_REJECTED == ZKGPU_TXSTATUS_REJECTED &&
               zk::zkvm::TXOUT_OUTSIDE_SUBSET == ZKGPU_TXSTATUS_OUTSIDE_SUBSET && zk::zkvm::TXFORMAT_PRECOMPUTE_ONLY == ZKGPU_TXFORMAT_PRECOMPUTE_ONLY &&
-              zk::zkvm::TXOUT_PRECOMPUTED == ZKGPU_TXSTATUS_PRECOMPUTED && zk::zkvm::TXFORMAT_STATEMENTS_V1 == ZKGPU_TXFORMAT_STATEMENTS_V1,
+              zk::zkvm::TXOUT_PRECOMPUTED == ZKGPU_TXSTATUS_PRECOMPUTED && zk::zkvm::TXFORMAT_STATEMENTS_V1 == ZKGPU_TXFORMAT_STATEMENTS_V1 &&
+              zk::zkvm::TXFORMAT_RETURN_ROOT == ZKGPU_TXFORMAT_RETURN_ROOT,
               "tx_out.hpp restates the format's flags and three status bytes");
 int zkgpu_verifier_set_tx_format(zkgpu_verifier* v, int format) {
   zk::zkvm::TxFormat f;
@@ -1846,7 +1877,8 @@ int zkgpu_tx_verify_batch(zkgpu_verifier* v, size_t batch, const uint8_t* txs, c
   // leaves: TxCall::verdicts writes beside the bits it sets, and an error closes it again below)
   const TxOutLayout out = TxFormat::of_valid(v->tx_format.load()).out;
   out.begin(accept_bitmap, status, batch);
-  if (batch == 0) return ZKGPU_OK;
+  // (a call over no transaction: every one of them reads 0, and the root is the empty tree's -- one transcript on the host)
+  if (batch == 0) { if (uint8_t* root = out.root_of(status, 0)) tx_root_fold_host(nullptr, 0, TX_ROOT_SPAN, 1, root); return ZKGPU_OK; }
   if (!txs || !tx_offsets || batch >= (1ull << 31)) return ZKGPU_EINVAL;
   for (size_t i = 0; i < batch; ++i) if (tx_offsets[i + 1] < tx_offsets[i]) return ZKGPU_EINVAL;
   std::lock_guard<std::mutex> vlk(v->mu);
@@ -1896,7 +1928,7 @@ struct TxRound {
   std::vector<zkgpu_verifier::TxPending*> calls;
   std::vector<zk::zkvm::TxCall::Piece> pieces;
   std::vector<zk::zkvm::TxHandOut> hand_out;              // per call: its own bitmap and area
-  std::vector<uint8_t> bits, status;
+  std::vector<uint8_t> bits, status, roots;               // (roots: 32 bytes per call, written by the round's TxCall through the call's piece)
   std::unique_ptr<GpuTxDevice> dev;
   std::unique_ptr<zk::zkvm::TxCall> call;
   size_t total = 0;
@@ -1973,14 +2005,19 @@ void tx_engine_main(zkgpu_verifier* v) {
       // (the kind is the calls', as the layout is -- tx_round_format: a precompute-only or a statements round runs under what its
       // calls were QUEUED under, a verifying round under the format in force now)
       TxFormat format = tx_round_format(r.calls.front()->submitted, TxFormat::of_valid(v->tx_format.load()));
+      r.roots.assign(32 * r.calls.size(), 0);
       for (auto* p : r.calls) {
         p->bits.resize((p->batch + 7) / 8);
         const TxOutLayout& layout = p->submitted.out;
         p->area.resize(layout.bytes(p->batch));
         layout.begin(p->bits.data(), p->area.data(), p->batch);
         r.pieces.push_back(layout.piece(p->txs, p->offsets, p->batch, p->area.data()));
-        r.hand_out.push_back({p->batch, layout, p->bits.data(), p->area.data()});
+        // (a call's root goes through the round: tx_round_hand_out passes it on only beside status bytes that all read 0 / 3)
+        uint8_t* const root = layout.root ? &r.roots[32 * r.hand_out.size()] : nullptr;
+        r.pieces.back().root = root;
+        r.hand_out.push_back({p->batch, layout, p->bits.data(), p->area.data(), root});
         format.out.ids |= layout.ids;
+        format.out.root |= layout.root;
         format.out.log_k = std::max(format.out.log_k, layout.log_k);
         threads = std::max(threads, p->host_threads);
       }

@@ -56,6 +56,12 @@
 //     of the whole call are kept in a side array of the call until then: the host's second pass fills them from the slots its
 //     plans wrote (tx_prepare_many_logged); a device that hashes brings the entries' contract IDs down with the transaction IDs
 //     (hash_log) and the host adds counts and kinds from the tape's shape table.  Nothing is hashed for it either.
+//   format().root() (ZKGPU_TXFORMAT_RETURN_ROOT, only beside ids()): also the Merkle root over the IDs of a caller's transactions in
+//     call order (tx_root.hpp; Piece::root), written by verdicts() LAST and only for a piece every transaction of which was
+//     handed its ID -- zeros stay otherwise.  Without hashes() the IDs are the host VM's and verdicts() folds them on the host
+//     threads; with it the device hashes a leaf per transaction behind every tape (hash_place says where in the call the tape
+//     starts) and, behind the LAST tape, folds every asking piece's range and copies the roots down (root_enqueue) on that
+//     tape's stream -- finish() collects them where it collects the tape, and no step waits for them.
 // Two predicates pick another kind of call altogether:
 //   format().precompute() (ZKGPU_TXFORMAT_PRECOMPUTE_ONLY, only beside ids(), never with chains() or statements()): the call
 //     VERIFIES NOTHING.  The staging thread makes ONE pass per chunk -- the VM and the plans of what the ID and the log need, run
@@ -77,6 +83,7 @@
 #include "tx_hash_tape.hpp"
 #include "tx_log.hpp"
 #include "tx_out.hpp"
+#include "tx_root.hpp"
 #include "tx_statements.hpp"
 #include "zkvm_tx.hpp"
 
@@ -162,6 +169,17 @@ class TxDevice {
   // (format().forms_musig()) a key stage as points and offsets alone: the device writes the scalars; the signature stage then
   // arrives as a chain whose IDs come from the host (SigChain::txids), its key terms' scalars unset.
   virtual int keys_enqueue_formed(int, const uint8_t*, const uint64_t*, size_t) { return -1; }
+  // (format().root() beside format().hashes()) the roots of a call on the device.  root_begin(total), before the call's first
+  // tape: a call of `total` transactions starts -- its leaves read zero.  hash_place(slot, lo), before every hash_enqueue: the
+  // slot's next tape holds transactions of the call from lo on, and transaction t of it lies at lo + tape.position(t).
+  // root_enqueue(slot, ranges, n), once, after the call's last tape was queued (or found empty) in `slot`: behind every tape
+  // queued so far, the root over the leaves [ranges[2 r], ranges[2 r] + ranges[2 r + 1]) for r < n, and their way down.
+  // root_collect waits and writes 32 bytes per range; root_done never blocks.  No host fallback: an error is the call's.
+  virtual int root_begin(size_t) { return -1; }
+  virtual void hash_place(int, size_t) {}
+  virtual int root_enqueue(int, const uint64_t*, size_t) { return -1; }
+  virtual bool root_done(int) { return true; }
+  virtual int root_collect(int, uint8_t*) { return -1; }
 };
 
 class TxCall {
@@ -182,14 +200,20 @@ class TxCall {
   // A lone call: `status` (may be NULL) is the caller's whole status argument, laid out as the format's ids() and log_k() say
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, size_t batch, const uint8_t* txs, const uint64_t* tx_offsets,
          int host_threads, size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
-      : TxCall(dev, store, kept, std::vector<Piece>{TxOutLayout{dev.format().ids(), dev.format().log_k()}.piece(txs, tx_offsets, batch, status)}, host_threads,
+      : TxCall(dev, store, kept, std::vector<Piece>{TxOutLayout{dev.format().ids(), dev.format().log_k(), dev.format().root()}.piece(txs, tx_offsets, batch, status)}, host_threads,
                chunk_override, accept_bitmap, status, n_slots) {}
   TxCall(TxDevice& dev, std::vector<TxStatement>& store, size_t kept, const std::vector<Piece>& pieces, int host_threads,
          size_t chunk_override, uint8_t* accept_bitmap, uint8_t* status, int n_slots = 2)
       : dev_(dev), store_(store), batch_(total_of(pieces)), threads_(host_threads), accept_(accept_bitmap), status_(status),
         fmt_(dev.format()), reasons_(fmt_.reasons() && status != nullptr), ids_(fmt_.ids() && any_ids(pieces)), log_k_(ids_ && any_log(pieces, fmt_.log_k()) ? fmt_.log_k() : 0),
-        timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
+        root_(ids_ && fmt_.root() && any_root(pieces)), timing_(getenv("ZKGPU_PROVER_TIMING") != nullptr), t00_(now()), n_slots_((size_t)std::max(1, std::min(2, n_slots))) {
     ptr_.reserve(batch_); len_.reserve(batch_);
+    if (root_) {
+      handed_.assign(batch_, 0);
+      size_t at = 0;
+      for (const Piece& pc : pieces) { if (pc.root && pc.ids) { root_out_.push_back(pc.root); root_ranges_.push_back(at); root_ranges_.push_back(pc.batch); } at += pc.batch; }
+      root_dev_.assign(32 * root_out_.size(), 0);
+    }
     if (ids_) id_out_.reserve(batch_);
     if (log_k_) { log_out_.reserve(batch_); log_rec_.assign(batch_ * tx_log_record_bytes(log_k_), 0); }
     for (const Piece& pc : pieces) {
@@ -257,6 +281,7 @@ class TxCall {
     for (size_t s = 0; s < n_sig; ++s) if (sig_stages_[s]->pending && !dev_.sigs_done((int)(s % n_slots_))) return false;
     for (const auto& k : chunks_) if (k->handle && k->started && !dev_.proofs_done(k->handle)) return false;
     for (size_t c = next_hcollect_; c < next_hash_; ++c) if (hash_pending_[c] && !dev_.hash_done((int)(c % n_slots_))) return false;
+    if (root_pending_ && !dev_.root_done(root_slot_)) return false;
     return true;
   }
   int finish() {
@@ -274,6 +299,11 @@ class TxCall {
     // (after an error: nothing is left pending on the device)
     for (size_t s = 0; s < seg_.size(); ++s) keys_collect(s);
     while (next_hcollect_ < next_hash_) hash_collect(next_hcollect_++, !fmt_.chains() || ids_);
+    if (root_pending_) {                                 // (queued behind the last tape on its stream: that tape's collect has waited for it)
+      root_pending_ = false;
+      const int rc = dev_.root_collect(root_slot_, root_dev_.data());
+      if (rc != OK) note(rc, dev_.last_error());
+    }
     for (size_t s = 0; s < n_sig_made_locked(); ++s) sigs_collect(s);
     for (size_t c = 0; c < chunks_.size(); ++c) proofs_collect(*chunks_[c]);
     report();
@@ -319,6 +349,7 @@ class TxCall {
 
   static size_t total_of(const std::vector<Piece>& pieces) { size_t n = 0; for (const Piece& p : pieces) n += p.batch; return n; }
   static bool any_ids(const std::vector<Piece>& pieces) { for (const Piece& p : pieces) if (p.ids && p.batch) return true; return false; }
+  static bool any_root(const std::vector<Piece>& pieces) { for (const Piece& p : pieces) if (p.root && p.ids && p.batch) return true; return false; }
   // (a piece's window is at most the device's: the round's device is made for the widest of its calls)
   static bool log_fits(const Piece& p, size_t k) { return p.log && p.ids && p.log_k >= 1 && p.log_k <= k; }
   static bool any_log(const std::vector<Piece>& pieces, size_t k) { for (const Piece& p : pieces) if (log_fits(p, k) && p.batch) return true; return false; }
@@ -786,15 +817,24 @@ class TxCall {
   // the tape of chunk next_hash_ (a device that hashes).  slot_free: as for the keys
   bool queue_tape(const Ready& r, bool slot_free) {
     if (rc_ != OK || !r.tape || !slot_free) return false;
-    const TxHashTape& tape = *dev_.hash_tape((int)(next_hash_ % n_slots_));
+    const int slot = (int)(next_hash_ % n_slots_);
+    const TxHashTape& tape = *dev_.hash_tape(slot);
     const double t0 = now();
-    if (tape.n_tx()) {
-      const int rc = dev_.hash_enqueue((int)(next_hash_ % n_slots_), tape);
+    // (a call whose pieces ask for their roots: the leaves are zeroed before the first tape, every tape is told where it starts)
+    if (root_ && next_hash_ == 0) { const int rc = dev_.root_begin(batch_); if (rc != OK) note(rc, dev_.last_error()); }
+    if (root_) dev_.hash_place(slot, chunks_[next_hash_]->lo);
+    if (tape.n_tx() && rc_ == OK) {
+      const int rc = dev_.hash_enqueue(slot, tape);
       if (rc != OK) note(rc, dev_.last_error()); else hash_pending_[next_hash_] = 1;
     }
     t_keys_ += now() - t0;
     mark("transaction-ID tape queued, chunk", next_hash_);
     ++next_hash_;
+    // (... and behind the last tape the folds and the roots' way down, on its stream)
+    if (root_ && next_hash_ == chunks_.size() && rc_ == OK) {
+      const int rc = dev_.root_enqueue(slot, root_ranges_.data(), root_out_.size());
+      if (rc != OK) note(rc, dev_.last_error()); else { root_pending_ = true; root_slot_ = slot; }
+    }
     return true;
   }
   // the proofs of chunk next_stage_, if the mode lets them start now: the ring slot's last chunk is collected as soon as the
@@ -996,11 +1036,12 @@ class TxCall {
   }
   // transaction i's ID and record to its caller, where that caller has room for them
   void hand_out(size_t i) {
+    if (root_) handed_[i] = 1;
     if (ids_ && id_out_[i]) memcpy(id_out_[i], statement(i).txid, 32);
     if (log_k_ && log_out_[i].first) tx_log_record_copy(log_out_[i].first, log_out_[i].second, &log_rec_[i * tx_log_record_bytes(log_k_)], log_k_);
   }
   void verdicts() {
-    if (fmt_.precompute()) { precomputed_out(); return; }
+    if (fmt_.precompute()) { precomputed_out(); roots_out(); return; }
     std::vector<uint8_t> sig_ok(live_all_.size(), 0);
     // (key_ok_ matters for a chained stage alone, whose rows include those with an undecodable key; an unchained stage's
     // `keyed` holds only rows whose keys decoded, and the test is always true there)
@@ -1017,6 +1058,24 @@ class TxCall {
       }
     }
     if (reasons_) reasons_out();
+    roots_out();
+  }
+  // The root of every piece that asked for one and whose transactions were ALL handed their IDs (a piece's root area is zero
+  // until here, and stays zero otherwise): the device's where it hashed the IDs, else the fold of the statements' IDs on the
+  // host threads (tx_root_fold_host).  Last of all: after the last ID.
+  void roots_out() {
+    if (!root_) return;
+    std::vector<uint8_t> ids;
+    for (size_t r = 0; r < root_out_.size(); ++r) {
+      const size_t lo = (size_t)root_ranges_[2 * r], n = (size_t)root_ranges_[2 * r + 1];
+      bool whole = true;
+      for (size_t i = lo; i < lo + n && whole; ++i) whole = handed_[i] != 0;
+      if (!whole) continue;
+      if (fmt_.hashes() && n) { memcpy(root_out_[r], &root_dev_[32 * r], 32); continue; }
+      ids.resize(32 * n);
+      for (size_t i = 0; i < n; ++i) memcpy(&ids[32 * i], statement(lo + i).txid, 32);
+      tx_root_fold_host(ids.data(), n, TX_ROOT_SPAN, threads_, root_out_[r]);
+    }
   }
   // what the host itself rejected: the transaction (16) -- except the one check of the SIGNATURE the VM makes on the host, a
   // scalar s that is not canonical, which is the signature's reason (the text is zkvm_tx.hpp's, which keeps one status for both)
@@ -1069,6 +1128,13 @@ class TxCall {
   std::vector<std::pair<uint8_t*, size_t>> log_out_;     // ... per transaction, where its record goes (NULL: no room) and its caller's window
   std::vector<uint8_t> log_rec_;                         // ... the records of the whole call, window log_k_, until verdicts() hands them out
   std::vector<uint32_t> log_table_;                      // (calling thread: the shape table of the tape being collected)
+  const bool root_;                                      // the roots of pieces that kept every transaction go out too (only beside ids_)
+  std::vector<uint8_t*> root_out_;                       // ... per asking piece, where its 32 bytes go,
+  std::vector<uint64_t> root_ranges_;                    // ... and (first transaction of the call, transactions) of it
+  std::vector<uint8_t> root_dev_;                        // ... what a device that hashes brought down, 32 bytes per asking piece
+  std::vector<char> handed_;                             // ... per transaction: verdicts() handed its ID out
+  bool root_pending_ = false;                            // (calling thread) the folds are queued and not yet collected, in
+  int root_slot_ = 0;                                    // ... this slot
   const bool timing_;
   const double t00_;
   const size_t n_slots_;                                 // key / signature stages in flight at once (2; 1 when two calls share the stage contexts)

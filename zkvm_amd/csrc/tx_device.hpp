@@ -147,6 +147,8 @@ int const_upload(zkgpu_ctx* c, Buffer& kept, const void* a, size_t na, const voi
 // mixed shapes on the lanes, staged through the verifier's ring of pinned / device areas.  v->mu is held by the call.
 static_assert(zk::zkvm::TxCall::OK == ZKGPU_OK && zk::zkvm::TxCall::ENOMEM_ == ZKGPU_ENOMEM && zk::zkvm::TxCall::EINVAL_ == ZKGPU_EINVAL, "tx_call.hpp restates three status codes");
 static_assert(zk::zkvm::TXLOG_INPUT == ZKGPU_TXLOG_INPUT && zk::zkvm::TXLOG_OUTPUT == ZKGPU_TXLOG_OUTPUT, "tx_log.hpp restates the two entry kinds");
+uint32_t tx_root_span_from_env() { const char* e = getenv("ZKGPU_TX_ROOT_SPAN"); return zk::zkvm::tx_root_span(e ? atoll(e) : 0); }
+const uint32_t g_tx_root_span = tx_root_span_from_env();   // (once, at load: no call reads the environment)
 class GpuTxDevice : public zk::zkvm::TxDevice {
  public:
   // slot_base / arena_base: which of the verifier's stage contexts and staging areas this call uses (a call alone: slots 0
@@ -166,6 +168,11 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   //     359 / 360 us: DESIGN.md sec 4.5, profiles/r14a_tx_precompute.txt); ZKGPU_TX_HASH_LEVELS=0 / 1 picks the kernel for the
   //     tests and for measuring (levels_).  A verifying call's stage never does: its launches are as they were
   //   statements(): ZKGPU_TXFORMAT_STATEMENTS_V1 -- the call's pieces are records (tx_statements.hpp); nothing is hashed for an ID
+  //   root(): ZKGPU_TXFORMAT_RETURN_ROOT beside ids() -- asked only beside hashes() (tx_call.hpp folds the host VM's IDs itself).  Behind
+  //     every tape, on its stream, one more copy up (the transactions' places in the call) and k_tx_root_leaves; behind the call's
+  //     LAST tape k_tx_root_fold once per pass and asking piece, and 32 bytes per piece down (tx_root_kernels.hpp).  The folds wait
+  //     ON THE DEVICE for the leaves the other slot's stream wrote (an event per slot); the host waits where it waited for the tape.
+  //     ZKGPU_TX_ROOT_SPAN=1 .. 7 sets the levels per pass for the tests (root_span_).  A call without the flag queues what it queued before
   //   forms_musig(): ZKGPU_TXFORMAT_SIGN_ON_DEVICE beside it -- the MuSig coefficients come from k_musig_rows (tx_musig_rows.hpp) in
   //     both stages' rows, the challenge from k_tx_sig_rows over the IDs the host uploads; no host fallback: an error of a launch is the call's
   static constexpr bool TX_HASH_LEVELS_SERVE = true;
@@ -301,6 +308,16 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     return rc;
   }
   std::string last_error() override { return err_; }
+  int root_begin(size_t total) override { return seen(root_zero(total), keys(0), "transaction root stage: "); }
+  void hash_place(int slot, size_t lo) override { hash(slot).place = lo; }
+  int root_enqueue(int slot, const uint64_t* ranges, size_t n) override { return seen(root_queue(slot, ranges, n), keys(slot), "transaction root stage: "); }
+  bool root_done(int slot) override {
+    zkgpu_verifier::TxHashStage& hs = hash(slot);
+    if (!hs.stream) return true;
+    DeviceGuard g(v_->root->device);
+    return hipStreamQuery(hs.stream) != hipErrorNotReady;
+  }
+  int root_collect(int slot, uint8_t* roots) override { return seen(root_wait(slot, roots), keys(slot), "transaction root stage: "); }
 
  private:
   struct Staged { zkgpu_txblock* blk = nullptr; zkgpu_verifier::BlockRun* run = nullptr; };
@@ -471,17 +488,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceGuard g(c->device);
     hs.n_tx = 0;
-    if (!hs.stream) {
-      int least = 0, greatest = 0;
-      HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-      HIP_TRY(c, hipStreamCreateWithPriority(&hs.stream, hipStreamNonBlocking, greatest));
-    }
-    if (!v_->tx_hash_const.p) {                          // once per verifier: the protocols' initial transcripts, the label table
-      std::vector<uint32_t> protos;
-      std::vector<uint8_t> labels;
-      hash_tape_constants(protos, labels);
-      TRY(const_upload(c, v_->tx_hash_const, protos.data(), 4 * protos.size(), labels.data(), labels.size()));
-    }
+    TRY(hash_stream_and_const(c, hs));
     const HashTapeHead& h = tape.head();
     const size_t bytes = tape.bytes(), id_bytes = 32 * (size_t)h.n_tx;
     TRY(pinned_grow(c, hs.h_in, hs.h_in_cap, bytes));
@@ -509,7 +516,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
     // (a chain beside ZKGPU_TXFORMAT_RETURN_LOG: its challenge kernel waits for the IDs, not for the gather and the copies queued
     // below -- the event it waits for is recorded here; without the flag chain_queue records its own, as it always has)
     hs.ids_marked = false;
-    if (format_.chains() && format_.log_k() && h.n_tx) {
+    if (format_.chains() && (format_.log_k() || format_.root()) && h.n_tx) {     // (... nor for the leaves and the folds of a call that returns its root)
       if (!hs.ev_ids) HIP_TRY(c, hipEventCreateWithFlags(&hs.ev_ids, hipEventDisableTiming));
       HIP_TRY(c, hipEventRecord(hs.ev_ids, hs.stream));
       hs.ids_marked = true;
@@ -539,7 +546,147 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
       hs.n_logged = tx_log_handed_back(tape.block(), hs.log_table, format_.log_k());
       hs.logged = true;
     }
+    if (format_.root() && h.n_tx) TRY(root_leaves_queue(c, hs, tape, profiled));
     hs.n_tx = h.n_tx;
+    return ZKGPU_OK;
+  }
+  // the slot's stream, and once per verifier the protocols' initial transcripts and the label table (c->mu held, the device set)
+  int hash_stream_and_const(zkgpu_ctx* c, zkgpu_verifier::TxHashStage& hs) {
+    if (!hs.stream) {
+      int least = 0, greatest = 0;
+      HIP_TRY(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+      HIP_TRY(c, hipStreamCreateWithPriority(&hs.stream, hipStreamNonBlocking, greatest));
+    }
+    if (!v_->tx_hash_const.p) {
+      std::vector<uint32_t> protos;
+      std::vector<uint8_t> labels;
+      zk::zkvm::hash_tape_constants(protos, labels);
+      TRY(const_upload(c, v_->tx_hash_const, protos.data(), 4 * protos.size(), labels.data(), labels.size()));
+    }
+    return ZKGPU_OK;
+  }
+  // ---- the roots of a call (tx_root_kernels.hpp).  The call's stage: a lone call's is [0], a round's its set's
+  zkgpu_verifier::TxRootStage& root_stage() const { return v_->tx_root[sb_ & 1]; }
+  int slot_index(int slot) const { return (sb_ + slot) & 1; }
+  zk::zkvm::TxRootView root_view() const {
+    return zk::zkvm::TxRootView{(const uint32_t*)v_->tx_root_const.p, (const uint8_t*)v_->tx_hash_const.p + 4 * (size_t)zk::zkvm::N_PROTO * zk::zkvm::TAPE_PROTO_WORDS};
+  }
+  // a call of `total` transactions starts: its leaves read zero, on slot 0's stream; the event says when
+  int root_zero(size_t total) {
+    zkgpu_ctx* c = keys(0);
+    zkgpu_verifier::TxHashStage& hs = hash(0);
+    zkgpu_verifier::TxRootStage& rs = root_stage();
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    rs.total = 0; rs.n_ranges = 0; rs.marked[0] = rs.marked[1] = false;
+    if (total == 0 || total >= (1ull << 31)) { c->last_error = "a call without transactions has no leaves"; return ZKGPU_EINVAL; }
+    TRY(hash_stream_and_const(c, hs));
+    if (!v_->tx_root_const.p) {                          // once per verifier: the tree's freshly initialised transcript
+      uint32_t init[zk::zkvm::TAPE_PROTO_WORDS];
+      zk::zkvm::tx_root_init(init);
+      TRY(const_upload(c, v_->tx_root_const, init, sizeof init));
+    }
+    if (!rs.ev_zeroed) HIP_TRY(c, hipEventCreateWithFlags(&rs.ev_zeroed, hipEventDisableTiming));
+    TRY(ensure(c, rs.d_leaves, 32 * total));
+    for (Buffer& b : rs.d_nodes) TRY(ensure(c, b, 32 * ((total + 1) / 2)));
+    HIP_TRY(c, hipMemsetAsync(rs.d_leaves.p, 0, 32 * total, hs.stream));
+    HIP_TRY(c, hipEventRecord(rs.ev_zeroed, hs.stream));
+    rs.zero_stream = hs.stream;
+    rs.total = total;
+    return ZKGPU_OK;
+  }
+  // the stream behind the zeroing of the call's leaves (its own stream already is)
+  int root_behind_zeroing(zkgpu_ctx* c, zkgpu_verifier::TxHashStage& hs, zkgpu_verifier::TxRootStage& rs) {
+    if (hs.stream != rs.zero_stream) HIP_TRY(c, hipStreamWaitEvent(hs.stream, rs.ev_zeroed, 0));
+    return ZKGPU_OK;
+  }
+  // behind the tape just queued on hs.stream: its transactions' places in the call up, a leaf per transaction, the slot's event
+  // (c->mu held, the device set)
+  int root_leaves_queue(zkgpu_ctx* c, zkgpu_verifier::TxHashStage& hs, const zk::zkvm::TxHashTape& tape, bool profiled) {
+    zkgpu_verifier::TxRootStage& rs = root_stage();
+    const size_t n = tape.n_tx();
+    if (rs.total == 0 || !v_->tx_root_const.p) { c->last_error = "a tape of a call whose leaves were never zeroed"; return ZKGPU_EINVAL; }
+    TRY(pinned_grow(c, hs.h_root_pos, hs.h_root_pos_cap, 4 * n));
+    TRY(ensure(c, hs.d_root_pos, 4 * n));
+    uint32_t* pos = (uint32_t*)hs.h_root_pos;
+    for (size_t t = 0; t < n; ++t) {
+      const size_t at = hs.place + tape.position(t);
+      if (at >= rs.total) { c->last_error = "a transaction of the tape lies outside its call"; return ZKGPU_EINVAL; }
+      pos[t] = (uint32_t)at;
+    }
+    if (!hs.ev_leaves) HIP_TRY(c, hipEventCreateWithFlags(&hs.ev_leaves, hipEventDisableTiming));
+    HIP_TRY(c, hipMemcpyAsync(hs.d_root_pos.p, hs.h_root_pos, 4 * n, hipMemcpyHostToDevice, hs.stream));
+    TRY(root_behind_zeroing(c, hs, rs));
+    c->profiling = profiled;
+    {
+      Launch l(c, "k_tx_root_leaves", hs.stream);
+      hipLaunchKernelGGL(zk::k_tx_root_leaves, dim3(blocks_for(n, 64)), dim3(64), 0, hs.stream, root_view(), (const uint32_t*)hs.d_txid.p,
+                         (const uint32_t*)hs.d_root_pos.p, (uint32_t)n, (uint32_t*)rs.d_leaves.p, (uint32_t)rs.total);
+    }
+    c->profiling = false;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(hs.ev_leaves, hs.stream));
+    rs.marked[&hs == &v_->tx_hash[0] ? 0 : 1] = true;
+    return ZKGPU_OK;
+  }
+  // behind the call's last tape, on its slot's stream: the other slot's leaves waited for (on the device), every range folded
+  // pass by pass between the two node arrays, its root copied beside the others, all of them down in one copy
+  int root_queue(int slot, const uint64_t* ranges, size_t n_ranges) {
+    using namespace zk::zkvm;
+    zkgpu_ctx* c = keys(slot);
+    zkgpu_verifier::TxHashStage& hs = hash(slot);
+    zkgpu_verifier::TxHashStage& other = hash(slot ^ 1);
+    zkgpu_verifier::TxRootStage& rs = root_stage();
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    rs.n_ranges = 0;
+    if (rs.total == 0 || n_ranges == 0) { c->last_error = "no call whose roots could be folded"; return ZKGPU_EINVAL; }
+    for (size_t r = 0; r < n_ranges; ++r)
+      if (ranges[2 * r] > rs.total || ranges[2 * r + 1] > rs.total - ranges[2 * r]) { c->last_error = "a root over transactions outside the call"; return ZKGPU_EINVAL; }
+    TRY(hash_stream_and_const(c, hs));
+    TRY(pinned_grow(c, rs.h_roots, rs.h_roots_cap, 32 * n_ranges));
+    TRY(ensure(c, rs.d_roots, 32 * n_ranges));
+    TRY(root_behind_zeroing(c, hs, rs));
+    if (rs.marked[slot_index(slot ^ 1)] && other.ev_leaves && other.stream != hs.stream) HIP_TRY(c, hipStreamWaitEvent(hs.stream, other.ev_leaves, 0));
+    bool profiled = false;
+    { std::lock_guard<std::recursive_mutex> rl(v_->root->mu); profiled = v_->root->profiling; }
+    const uint32_t s = root_span_;
+    const TxRootView view = root_view();
+    HIP_TRY(c, hipMemsetAsync(rs.d_roots.p, 0, 32 * n_ranges, hs.stream));     // (a range of no transaction keeps zeros: the empty tree's hash is the host's)
+    for (size_t r = 0; r < n_ranges; ++r) {
+      const uint32_t* in = (const uint32_t*)rs.d_leaves.p + TX_ROOT_NODE_WORDS * (size_t)ranges[2 * r];
+      uint64_t count = ranges[2 * r + 1];
+      if (count == 0) continue;
+      for (uint32_t pass = 0; count > 1; ++pass) {
+        const uint64_t next = tx_root_after_pass(count, s);
+        uint32_t* out = (uint32_t*)rs.d_nodes[pass & 1].p;
+        c->profiling = profiled;
+        {
+          Launch l(c, "k_tx_root_fold", hs.stream);
+          hipLaunchKernelGGL(zk::k_tx_root_fold, dim3((uint32_t)next), dim3(TX_ROOT_LANES), 0, hs.stream, view, in, (uint32_t)count, out, s);
+        }
+        c->profiling = false;
+        HIP_TRY(c, hipGetLastError());
+        in = out; count = next;
+      }
+      HIP_TRY(c, hipMemcpyAsync((char*)rs.d_roots.p + 32 * r, in, 32, hipMemcpyDeviceToDevice, hs.stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(rs.h_roots, rs.d_roots.p, 32 * n_ranges, hipMemcpyDeviceToHost, hs.stream));
+    rs.n_ranges = n_ranges;
+    return ZKGPU_OK;
+  }
+  int root_wait(int slot, uint8_t* roots) {
+    zkgpu_ctx* c = keys(slot);
+    zkgpu_verifier::TxHashStage& hs = hash(slot);
+    zkgpu_verifier::TxRootStage& rs = root_stage();
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceGuard g(c->device);
+    const size_t n = rs.n_ranges;
+    rs.n_ranges = 0;
+    if (n == 0 || !hs.stream) { c->last_error = "no roots in flight in the slot"; return ZKGPU_EINVAL; }
+    HIP_TRY(c, hipStreamSynchronize(hs.stream));
+    memcpy(roots, rs.h_roots, 32 * n);
+    if (!c->ev_used.empty()) { prof_collect(c); profile_to_root(c); }     // (a profiled call: the folds have run)
     return ZKGPU_OK;
   }
   static bool levels_asked() {
@@ -591,6 +738,7 @@ class GpuTxDevice : public zk::zkvm::TxDevice {
   const size_t ab_;
   const zk::zkvm::TxFormat format_;                      // the mode of the call (tx_out.hpp): its predicates are asked where they matter
   const bool levels_;                                    // (a precompute-only call) its tapes are walked by level: the environment may say otherwise
+  const uint32_t root_span_ = g_tx_root_span;            // levels per pass of the root's folds (ZKGPU_TX_ROOT_SPAN, read when the library was loaded)
   std::vector<uint32_t> sidx_[2];
   std::vector<uint64_t> soff_[2];
   std::string err_;

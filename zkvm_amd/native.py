@@ -220,6 +220,7 @@ TXFORMAT_RETURN_LOG = 0x800            # a fourth, only beside the third and wit
 TXFORMAT_LOG_SHIFT = 16                # the IDs, a record count | kind[K] | id[K][32] per transaction: its log's Input / Output entries
 TXFORMAT_PRECOMPUTE_ONLY = 0x2000      # a fifth, only beside the third and never beside the second: the VM, the IDs and the log ALONE -- nothing is verified,
 TXSTATUS_PRECOMPUTED = 3               # no bit is set, and a transaction the VM ran to the end reads 3 beside its ID and record: NOT a verdict
+TXFORMAT_RETURN_ROOT = 0x10            # a sixth, only beside the third: 32 more bytes behind everything else, the Merkle root over the call's transaction IDs
 TXFORMAT_STATEMENTS_V1 = 4             # a third base format: records of what the caller's OWN VM left (pack_statement); alone or beside the second flag
 TXLOG_INPUT, TXLOG_OUTPUT = 1, 2
 TXSTATUS_ACCEPTED, TXSTATUS_REJECTED, TXSTATUS_OUTSIDE_SUBSET = 0, 1, 2

@@ -330,6 +330,7 @@ class BlockVerifier:
     TXFORMAT_RETURN_LOG = 0x800            # a flag only beside the one above, with a window K << TXFORMAT_LOG_SHIFT: the log's entries too
     TXFORMAT_LOG_SHIFT = 16                # bits 16 .. 23 of the format: K, the log entries kept per transaction, 1 .. 255
     TXFORMAT_PRECOMPUTE_ONLY = 0x2000      # a flag only beside TXFORMAT_RETURN_IDS, never beside TXFORMAT_SIGN_ON_DEVICE: NOTHING is verified (precompute_txs)
+    TXFORMAT_RETURN_ROOT = 0x10            # a flag only beside TXFORMAT_RETURN_IDS: the Merkle root over the call's transaction IDs comes back too (root=True)
     TXFORMAT_STATEMENTS_V1 = 4             # a third base format: records of what the caller's own VM left (verify_statements); alone or beside TXFORMAT_SIGN_ON_DEVICE
     TXLOG_INPUT, TXLOG_OUTPUT = 1, 2       # kind bytes of a log record (include/zkgpu.h: ZKGPU_TXLOG_*)
     # status bytes (include/zkgpu.h: ZKGPU_TXSTATUS_*); 16 .. 21 only with TXFORMAT_RECOLLECTED_V1_REASONS, lowest code first
@@ -361,7 +362,11 @@ class BlockVerifier:
         Output entries of every accepted transaction's log (the library writes 33 + 1 + 33 K bytes per transaction).
         A format with TXFORMAT_RETURN_IDS and without TXFORMAT_SIGN_ON_DEVICE may carry TXFORMAT_PRECOMPUTE_ONLY: the calls
         then VERIFY NOTHING -- upstream's Tx::precompute alone -- and are made through precompute_txs / submit_txs and
-        wait_precomputed; verify_txs and wait_txs refuse, so that a status of 3 is never read as a verdict."""
+        wait_precomputed; verify_txs and wait_txs refuse, so that a status of 3 is never read as a verdict.
+        A format with TXFORMAT_RETURN_IDS may carry TXFORMAT_RETURN_ROOT: the library then writes 32 more bytes behind everything
+        else, and verify_txs / wait_txs / precompute_txs / wait_precomputed called with root=True return them as a last element --
+        the Merkle root over the call's transaction IDs in call order if EVERY transaction of the call reads 0 (3 under
+        precompute-only), 32 zero bytes otherwise."""
         if log_k:
             if not 1 <= log_k <= 255:
                 raise ValueError("log_k is 1 .. 255")
@@ -372,8 +377,10 @@ class BlockVerifier:
         self._tx_return_ids = bool(fmt & self.TXFORMAT_RETURN_IDS)
         self._tx_log_k = (fmt >> self.TXFORMAT_LOG_SHIFT) & 255 if fmt & self.TXFORMAT_RETURN_LOG else 0
         self._tx_precompute = bool(fmt & self.TXFORMAT_PRECOMPUTE_ONLY)
+        self._tx_root = bool(fmt & self.TXFORMAT_RETURN_ROOT) and self._tx_return_ids
         self._tx_word = fmt
 
+    _tx_root = False                       # the format carries TXFORMAT_RETURN_ROOT: 32 more bytes behind a call's status array
     _tx_return_ids = False
     _tx_log_k = 0
     _tx_precompute = False
@@ -391,9 +398,16 @@ class BlockVerifier:
         return self._TxLayout(self._tx_return_ids, self._tx_log_k)
 
     @staticmethod
-    def _tx_status_bytes(batch: int, has_ids: bool, log_k: int) -> int:
-        """bytes the library writes into a call's status array under that layout"""
-        return ((33 if has_ids else 1) + (1 + 33 * log_k if has_ids and log_k else 0)) * batch
+    def _tx_status_bytes(batch: int, has_ids: bool, log_k: int, has_root: bool = False) -> int:
+        """bytes the library writes into a call's status array under that layout (has_root: and the 32 bytes of the root behind)"""
+        return ((33 if has_ids else 1) + (1 + 33 * log_k if has_ids and log_k else 0)) * batch + (32 if has_ids and has_root else 0)
+
+    def _tx_root_of(self, st, batch: int, log_k: int, has_root: bool) -> bytes:
+        """the last 32 bytes of a call's status array under a layout with the root"""
+        if not has_root:
+            raise ValueError("root=True needs a format with TXFORMAT_RETURN_ROOT (set_tx_format)")
+        at = self._tx_status_bytes(batch, True, log_k)
+        return st.raw[at: at + 32]
 
     def _tx_result(self, bm, st, batch: int, has_ids: bool, ids: bool, log_k: int = 0, log: bool = False, beside: int = 0):
         """(bitmap, status bytes) of a transaction call, and with ids=True the call's ID area: 32 bytes per transaction, the ID
@@ -432,7 +446,7 @@ class BlockVerifier:
         """zkgpu_verifier_set_tx_statements_kept: how many transactions' VM results (700 B each) the verifier keeps between calls"""
         self._check(self.lib.zkgpu_verifier_set_tx_statements_kept(self.h, transactions))
 
-    def verify_txs(self, txs: Sequence[bytes], host_threads: int = 0, ids: bool = False, log: bool = False):
+    def verify_txs(self, txs: Sequence[bytes], host_threads: int = 0, ids: bool = False, log: bool = False, root: bool = False):
         """zkgpu_tx_verify_batch: serialized ZkVM transactions (payment subset) -> (accept bitmap, status bytes:
         0 accepted, 1 rejected, 2 outside the subset).  Inert until set_tx_format names a format.  With
         TXFORMAT_RECOLLECTED_V1_REASONS the bitmap is the same and a rejected transaction reads one of TXSTATUS_TX_INVALID ..
@@ -441,10 +455,12 @@ class BlockVerifier:
         status bytes, ids) with ids[i] the transaction ID beside status 0 and 32 zero bytes beside everything else.  log=True
         (only under a format with TXFORMAT_RETURN_LOG): -> (bitmap, status bytes, ids, log) with log[i] None beside everything
         but status 0, else the transaction's Input / Output log entries as a list of ("input" | "output", contract ID) in
-        the order the program logged them -- or, when there are more than the window K holds, their number as an int."""
-        return self.verify_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads, ids=ids, log=log)
+        the order the program logged them -- or, when there are more than the window K holds, their number as an int.
+        root=True (only under a format with TXFORMAT_RETURN_ROOT): one more element at the end, the 32-byte Merkle root over the
+        call's transaction IDs -- zeros unless every transaction of the call was accepted."""
+        return self.verify_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads, ids=ids, log=log, root=root)
 
-    def verify_txs_packed(self, blob: bytes, lengths, host_threads: int = 0, ids: bool = False, log: bool = False):
+    def verify_txs_packed(self, blob: bytes, lengths, host_threads: int = 0, ids: bool = False, log: bool = False, root: bool = False):
         """the same over one buffer of concatenated transactions and their lengths (same status bytes, reasons included)"""
         batch = len(lengths)
         has_ids, log_k = self._tx_layout
@@ -454,8 +470,11 @@ class BlockVerifier:
             raise ValueError("ids=True needs a format with TXFORMAT_RETURN_IDS (set_tx_format)")
         if log and not (has_ids and log_k):
             raise ValueError("log=True needs a format with TXFORMAT_RETURN_LOG (set_tx_format)")
+        if root and not self._tx_root:
+            raise ValueError("root=True needs a format with TXFORMAT_RETURN_ROOT (set_tx_format)")
         bm, st = self._tx_call(blob, lengths, host_threads)
-        return self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
+        out = self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
+        return out + (self._tx_root_of(st, batch, log_k, self._tx_root),) if root else out
 
     def _tx_call(self, blob: bytes, lengths, host_threads: int):
         """zkgpu_tx_verify_batch under the layout in force -> (bitmap buffer, status buffer)"""
@@ -466,7 +485,7 @@ class BlockVerifier:
         if int(offs[-1]) != len(blob):
             raise ValueError("the lengths add up to %d bytes, the buffer holds %d" % (int(offs[-1]), len(blob)))
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
-        st = C.create_string_buffer(max(self._tx_status_bytes(batch, has_ids, log_k), 1))      # (with the flags the library writes more than a byte per transaction)
+        st = C.create_string_buffer(max(self._tx_status_bytes(batch, has_ids, log_k, self._tx_root), 1))      # (with the flags the library writes more than a byte per transaction)
         self._check(self.lib.zkgpu_tx_verify_batch(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, bm, st))
         return bm, st
 
@@ -476,32 +495,40 @@ class BlockVerifier:
         out = self._tx_result(bm, st, batch, True, True, log_k, bool(log_k), beside=self.TXSTATUS_PRECOMPUTED)
         return out[1], out[2], (out[3] if log_k else None)
 
-    def precompute_txs(self, txs: Sequence[bytes], host_threads: int = 0):
+    def precompute_txs(self, txs: Sequence[bytes], host_threads: int = 0, root: bool = False):
         """upstream's Tx::precompute over serialized transactions, under a format with TXFORMAT_PRECOMPUTE_ONLY: the VM runs, NOTHING
         is verified.  -> (status bytes, ids, logs).  status[i] is TXSTATUS_PRECOMPUTED (3) where the VM ran to the end -- beside
         it ids[i] is the transaction ID and, under TXFORMAT_RETURN_LOG, logs[i] the Input / Output entries as verify_txs lists
         them (or their number, when the window is too small) --, 2 outside the subset, otherwise what the host VM alone finds
         (1, or 16 / 21 with reasons), with ids[i] 32 zero bytes and logs[i] None.  logs is None without TXFORMAT_RETURN_LOG.
-        A 3 is NOT a verdict: signature, keys, proof and commitments were not looked at -- never treat it as accepted."""
+        A 3 is NOT a verdict: signature, keys, proof and commitments were not looked at -- never treat it as accepted.
+        root=True (only under a format with TXFORMAT_RETURN_ROOT): -> (status bytes, ids, logs, root), the root over the IDs if
+        every transaction reads 3, else 32 zero bytes."""
         if not (self._tx_precompute and self._tx_return_ids):
             raise ValueError("precompute_txs needs a format with TXFORMAT_PRECOMPUTE_ONLY (set_tx_format)")
+        if root and not self._tx_root:
+            raise ValueError("root=True needs a format with TXFORMAT_RETURN_ROOT (set_tx_format)")
         bm, st = self._tx_call(b"".join(txs), [len(t) for t in txs], host_threads)
-        return self._precomputed(bm, st, len(txs), self._tx_log_k)
+        out = self._precomputed(bm, st, len(txs), self._tx_log_k)
+        return out + (self._tx_root_of(st, len(txs), self._tx_log_k, self._tx_root),) if root else out
 
-    def wait_precomputed(self, call_id: int):
+    def wait_precomputed(self, call_id: int, root: bool = False):
         """zkgpu_tx_verify_wait for a call submitted under a format with TXFORMAT_PRECOMPUTE_ONLY -> (status bytes, ids, logs) as
-        precompute_txs"""
+        precompute_txs (root=True: and the root, if the call was submitted under a format with TXFORMAT_RETURN_ROOT)"""
         queued = self.__dict__["_tx_calls"][call_id]
         if not (len(queued) > 5 and queued[5]):
             raise ValueError("the call was not submitted under a format with TXFORMAT_PRECOMPUTE_ONLY")
-        batch, log_k = queued[2], queued[4]
+        batch, log_k, has_root = queued[2], queued[4], len(queued) > 6 and queued[6]
+        if root and not has_root:
+            raise ValueError("root=True: the call was not submitted under a format with TXFORMAT_RETURN_ROOT")
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
-        st = C.create_string_buffer(max(self._tx_status_bytes(batch, True, log_k), 1))
+        st = C.create_string_buffer(max(self._tx_status_bytes(batch, True, log_k, has_root), 1))
         try:
             self._check(self.lib.zkgpu_tx_verify_wait(self.h, call_id, bm, st))
         finally:
             del self.__dict__["_tx_calls"][call_id]
-        return self._precomputed(bm, st, batch, log_k)
+        out = self._precomputed(bm, st, batch, log_k)
+        return out + (self._tx_root_of(st, batch, log_k, has_root),) if root else out
 
     def submit_txs_packed(self, blob: bytes, lengths, host_threads: int = 0) -> int:
         """zkgpu_tx_verify_submit: the call is queued (calls in flight are merged into rounds); -> call id for wait_txs.  The
@@ -514,19 +541,23 @@ class BlockVerifier:
         cid = C.c_uint64(0)
         self._check(self.lib.zkgpu_tx_verify_submit(self.h, batch, blob, offs.ctypes.data_as(C.POINTER(C.c_uint64)), host_threads, C.byref(cid)))
         # (the layout of the call's status array is the one in force when it was queued: remembered with the call)
-        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch) + self._tx_layout + (self._tx_precompute,)
+        self.__dict__.setdefault("_tx_calls", {})[int(cid.value)] = (blob, offs, batch) + self._tx_layout + (self._tx_precompute, self._tx_root)
         return int(cid.value)
 
     def submit_txs(self, txs: Sequence[bytes], host_threads: int = 0) -> int:
         return self.submit_txs_packed(b"".join(txs), [len(t) for t in txs], host_threads)
 
-    def wait_txs(self, call_id: int, ids: bool = False, log: bool = False):
+    def wait_txs(self, call_id: int, ids: bool = False, log: bool = False, root: bool = False):
         """zkgpu_tx_verify_wait -> (accept bitmap, status bytes) of that call; the status bytes are those verify_txs gives for
         the same transactions -- with TXFORMAT_RECOLLECTED_V1_REASONS the same reason codes, whatever round the call was merged into.
         ids=True (the call was submitted under a format with TXFORMAT_RETURN_IDS): -> (bitmap, status bytes, ids) as verify_txs;
-        log=True (... with TXFORMAT_RETURN_LOG): -> (bitmap, status bytes, ids, log) as verify_txs"""
+        log=True (... with TXFORMAT_RETURN_LOG): -> (bitmap, status bytes, ids, log) as verify_txs; root=True (... with
+        TXFORMAT_RETURN_ROOT): one more element at the end, the root over THIS call's IDs, as verify_txs"""
         queued = self.__dict__["_tx_calls"][call_id]
         batch, (has_ids, log_k) = queued[2], self._TxLayout(*queued[3:5])
+        has_root = len(queued) > 6 and queued[6]
+        if root and not has_root:
+            raise ValueError("root=True: the call was not submitted under a format with TXFORMAT_RETURN_ROOT")
         if len(queued) > 5 and queued[5]:
             raise ValueError("the call was submitted under TXFORMAT_PRECOMPUTE_ONLY: nothing was verified (wait_precomputed)")
         if ids and not has_ids:
@@ -534,12 +565,13 @@ class BlockVerifier:
         if log and not (has_ids and log_k):
             raise ValueError("log=True: the call was not submitted under a format with TXFORMAT_RETURN_LOG")
         bm = C.create_string_buffer(max((batch + 7) // 8, 1))
-        st = C.create_string_buffer(max(self._tx_status_bytes(batch, has_ids, log_k), 1))
+        st = C.create_string_buffer(max(self._tx_status_bytes(batch, has_ids, log_k, has_root), 1))
         try:
             self._check(self.lib.zkgpu_tx_verify_wait(self.h, call_id, bm, st))
         finally:
             del self.__dict__["_tx_calls"][call_id]
-        return self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
+        out = self._tx_result(bm, st, batch, has_ids, ids, log_k, log)
+        return out + (self._tx_root_of(st, batch, log_k, has_root),) if root else out
 
     @staticmethod
     def _statement_records(records) -> list:
