@@ -314,8 +314,8 @@ k_decompress_post(const uint32_t* __restrict__ pts, const uint32_t* __restrict__
 
 // ---- digits ----------------------------------------------------------------
 // Signed radix-2^w recoding, digits in (-2^(w-1), 2^(w-1)], least significant
-// window first.  `f(t, d)` is called for every non-zero digit.
-template <typename F>
+// window first.  `f(t, d)` is called for every non-zero digit (kZeros: for every digit).
+template <bool kZeros = false, typename F>
 __device__ __forceinline__ void for_each_digit(const uint32_t* __restrict__ sc, int w, int n_windows, F f) {
   uint32_t s[8];
   const uint4* s4 = reinterpret_cast<const uint4*>(sc);
@@ -339,7 +339,7 @@ __device__ __forceinline__ void for_each_digit(const uint32_t* __restrict__ sc, 
     int d;
     if (v > half) { d = (int)v - (int)(mask + 1); carry = 1; }
     else { d = (int)v; carry = 0; }
-    if (d != 0) f(t, d);
+    if (kZeros || d != 0) f(t, d);
   }
 }
 
@@ -1034,6 +1034,34 @@ __device__ __forceinline__ void ge_add_cached(ge& r, const ge& p, const ge_cache
   fe_mul(r.T, e, h);
 }
 
+// A sum that starts from its first term instead of adding it to the identity: the table row q (negate: -q) as an extended
+// point scaled by two -- an affine Niels row gives (2x : 2y : 2 : 2xy) with 2xy = (2d xy) / d, a cached row
+// (Y+X, Y-X, 2Z, 2dT) gives (2X : 2Y : 2Z : 2T) -- ONE product by a constant where the addition costs seven or eight.
+// Limbs carried.
+__device__ __forceinline__ fe fe_INV_D() {      // 1 / d mod 2^255 - 19
+  const fe c = {{0x1c9f843u, 0x03c9db3u, 0x285c4bcu, 0x0c213cau, 0x02d775au, 0x1b9cf66u, 0x3108a66u, 0x1c86562u, 0x1214d5cu, 0x10241fbu}};
+  return c;
+}
+__device__ __forceinline__ void ge_from_rows(ge& r, const fe& ypx, const fe& ymx, const fe& t2d, bool negate) {
+  fe qa = ymx, qb = ypx, t, nt;
+  fe_cswap(qa, qb, negate);         // -q = (ymx, ypx, -t2d)
+  fe_sub_c(r.X, qb, qa);
+  fe_add_c(r.Y, qb, qa);
+  fe_mul(t, t2d, fe_INV_D());
+  fe_neg(nt, t);
+  fe_cmov(t, nt, negate);
+  r.T = t;
+}
+__device__ __forceinline__ void ge_from_niels(ge& r, const ge_niels& q, bool negate) {
+  ge_from_rows(r, q.ypx, q.ymx, q.xy2d, negate);
+  r.Z = fe_zero();
+  r.Z.v[0] = 2;
+}
+__device__ __forceinline__ void ge_from_cached(ge& r, const ge_cached& q, bool negate) {
+  ge_from_rows(r, q.YpX, q.YmX, q.T2d, negate);
+  r.Z = q.Z2;
+}
+
 constexpr int SMALL_TBL = 8;   // multiples per point (signed 4-bit digits)
 
 __device__ __forceinline__ void store_cached(uint32_t* row, const ge& p) {
@@ -1070,10 +1098,11 @@ k_small_tables(const uint32_t* __restrict__ dyn_scalars, const uint32_t* __restr
   ge_niels nq;
   load_niels(nq, dyn_rows + k * NIELS_WORDS);
   ge cur;
-  ge_identity(cur);
+  ge_from_niels(cur, nq, false);      // P itself: loaded, not added to the identity
   uint32_t* row = tbl + k * (SMALL_TBL * EXT_WORDS);
+  store_cached(row, cur);
 #pragma unroll 1
-  for (int e = 0; e < SMALL_TBL; ++e) {
+  for (int e = 1; e < SMALL_TBL; ++e) {
     ge_madd(cur, cur, nq, false);
     store_cached(row + e * EXT_WORDS, cur);
   }
@@ -1099,8 +1128,8 @@ k_small_accumulate(const uint32_t* __restrict__ recoded, const uint64_t* __restr
       load_ext(c4, tbl + (k * SMALL_TBL + (uint64_t)((d < 0 ? -d : d) - 1)) * EXT_WORDS);
       ge_cached c;
       c.YpX = c4.X; c.YmX = c4.Y; c.Z2 = c4.Z; c.T2d = c4.T;
-      if (!total_set) { ge_identity(total); total_set = true; }
-      ge_add_cached(total, total, c, d < 0);
+      if (total_set) ge_add_cached(total, total, c, d < 0);
+      else { ge_from_cached(total, c, d < 0); total_set = true; }      // a lane's first term: loaded, not added to the identity
     }
   }
   if (part > 0) {
@@ -1428,36 +1457,89 @@ k_static_accumulate(const int16_t* __restrict__ digits, const uint64_t* __restri
   store_ext(partials + (((uint64_t)slot * W + t) * P + part) * EXT_WORDS, acc);
 }
 
-// one wave per tx: sum the W*P static partials and the dynamic-term sum, then
-// the ristretto identity test.  Lane sums are folded with wavefront shuffles.
-// With row_map / n_active (the per-transaction re-check of failed groups) block b handles
-// MSM row_map[b]; its partials sit at slot b.
-// (one wavefront; `lane` = its lane)
-__device__ inline void static_combine_slot(const uint32_t* __restrict__ partials, uint32_t n_partials, const uint32_t* __restrict__ dyn_sum,
-                                           const uint8_t* __restrict__ dyn_ok, uint32_t slot, uint32_t tx, int lane,
-                                           uint8_t* __restrict__ accept, uint32_t* __restrict__ out_points) {
-  ge acc;
-  ge_identity(acc);
-  for (uint32_t c = lane; c < n_partials; c += 64) {
-    ge p;
-    load_ext(p, partials + ((uint64_t)slot * n_partials + c) * EXT_WORDS);
-    ge_add(acc, acc, p);
-  }
-  if (lane == 0 && dyn_sum) {
-    ge p;
-    load_ext(p, dyn_sum + (uint64_t)tx * EXT_WORDS);
-    ge_add(acc, acc, p);
-  }
+// Per-section clocks of the failed-group tail (build variant -DZK_TAIL_STAMPS only: tools/tail_stamps.py), on the model of
+// PREP_STAMP: the first lane of wavefront 0 and of the last two wavefronts of the first TAIL_STAMP_WGS workgroups (failed
+// groups / queued rows) of k_locate_fused (kernel 0), k_recheck_fused (1) and k_group_combine (2) note the cycle counter.
+// Slots, the same meaning in every kernel (one that a kernel or a wavefront does not pass stays 0):
+//   0 start   1 own share summed   2 past the barrier   3 partial sums gathered (the unfused form's loop)
+//   4 suffix scan of the proof-point sums   5 the row's sum is one point   6 prefix scan of S1 (the candidates)
+//   7 verdict / culprit named   8 digits (k_group_combine: locating scalars and digits) written
+#ifdef ZK_TAIL_STAMPS
+constexpr int TAIL_STAMP_SLOTS = 10, TAIL_STAMP_WGS = 16, TAIL_STAMP_WHO = 3;
+__device__ unsigned long long g_tail_stamps[3 * TAIL_STAMP_WGS * TAIL_STAMP_WHO * TAIL_STAMP_SLOTS];
+__device__ __forceinline__ int tail_stamp_who() {
+  return threadIdx.x == 0 ? 0 : threadIdx.x == blockDim.x - 128 ? 1 : threadIdx.x == blockDim.x - 64 ? 2 : -1;
+}
+#define TAIL_STAMP_AT(kern, wg, i, clk) do { const int who_ = tail_stamp_who(); if ((wg) < (uint32_t)TAIL_STAMP_WGS && who_ >= 0) \
+  g_tail_stamps[(((kern) * TAIL_STAMP_WGS + (wg)) * TAIL_STAMP_WHO + who_) * TAIL_STAMP_SLOTS + (i)] = (clk); } while (0)
+#define TAIL_CLOCK(var) const unsigned long long var = __builtin_readcyclecounter()
+inline long long tail_stamps_read(void* out, size_t bytes) {      // zkgpu_debug_read "tail_stamps": bytes copied, or < 0
+  const size_t n = bytes < sizeof(g_tail_stamps) ? bytes : sizeof(g_tail_stamps);
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tail_stamps), n) != hipSuccess) return -3;      // (ZKGPU_EHIP)
+  return (long long)n;
+}
+#else
+inline long long tail_stamps_read(void*, size_t) { return -1; }      // (ZKGPU_EINVAL: this build has no stamps)
+#define TAIL_STAMP_AT(kern, wg, i, clk) do { } while (0)
+#define TAIL_CLOCK(var) do { } while (0)
+#endif
+#define TAIL_STAMP(kern, wg, i) TAIL_STAMP_AT(kern, wg, i, __builtin_readcyclecounter())
+
+// ---- pieces of the failed-group tail (k_recheck_fused, k_locate_fused) ----------------------------------------------------
+// one wavefront's sums -> lane 0, by shuffled additions from `from` lanes apart down
+__device__ __forceinline__ void wave_fold(ge& acc, int lane, int from = 32) {
 #pragma unroll 1
-  for (int delta = 32; delta >= 1; delta >>= 1) {
+  for (int delta = from; delta >= 1; delta >>= 1) {
     ge other;
     shfl_down_ge(other, acc, delta);
     if (lane < delta) ge_add(acc, acc, other);
   }
-  if (lane == 0) {
-    accept[tx] = (ge_is_identity(acc) && (!dyn_ok || dyn_ok[tx])) ? 1 : 0;
-    if (out_points) store_ext(out_points + (uint64_t)slot * EXT_WORDS, acc);
+}
+
+// a point per thread in LDS, word-major (sh[word][n]: the lanes of a wavefront side by side, no bank conflicts)
+__device__ __forceinline__ void lds_park(uint32_t* sh, uint32_t n, uint32_t idx, const ge& p) {
+#pragma unroll
+  for (int q = 0; q < 10; ++q) {
+    sh[q * n + idx] = p.X.v[q]; sh[(10 + q) * n + idx] = p.Y.v[q];
+    sh[(20 + q) * n + idx] = p.Z.v[q]; sh[(30 + q) * n + idx] = p.T.v[q];
   }
+}
+__device__ __forceinline__ void lds_take(ge& p, const uint32_t* sh, uint32_t n, uint32_t idx) {
+#pragma unroll
+  for (int q = 0; q < 10; ++q) {
+    p.X.v[q] = sh[q * n + idx]; p.Y.v[q] = sh[(10 + q) * n + idx];
+    p.Z.v[q] = sh[(20 + q) * n + idx]; p.T.v[q] = sh[(30 + q) * n + idx];
+  }
+}
+
+// The sums of ALL threads of a workgroup (blockDim a power of two, 128 .. 512) -> one point in lane 0 of wavefront 0, called
+// by every thread.  While more than one wavefront holds sums the upper half parks them in LDS and the lower half adds them:
+// every lane of an adding wavefront has an addition to do, and from the first halving on no two of them share a SIMD.  The
+// last 64 sums are folded by shuffles.  Nine dependent additions for 512 sums, where one wavefront gathering 512 partial sums
+// from memory walked fourteen (eight gathered, six folded) -- and a point addition is bound by the SIMD's 64-bit multiplier,
+// so that eight wavefronts folding side by side, two to a SIMD, take as long as one doing it alone
+// (profiles/r17a_tail_fold.txt).
+constexpr uint32_t FOLD_SLOTS = 256;      // LDS: EXT_WORDS x FOLD_SLOTS words
+__device__ inline void block_fold(ge& acc, uint32_t* sh /*[EXT_WORDS][FOLD_SLOTS]*/) {
+  const uint32_t t = threadIdx.x;
+  for (uint32_t half = blockDim.x >> 1; half >= 64; half >>= 1) {
+    if (t >= half && t < 2 * half) lds_park(sh, FOLD_SLOTS, t - half, acc);
+    __syncthreads();
+    if (t < half) {
+      ge other;
+      lds_take(other, sh, FOLD_SLOTS, t);
+      ge_add(acc, acc, other);
+    }
+    __syncthreads();                       // (the next halving parks where this one read)
+  }
+  if (t < 64) wave_fold(acc, (int)t);
+}
+
+// the whole sum of row `tx` (generator terms + proof points), queued at `slot`, in ONE lane: its verdict
+__device__ __forceinline__ void slot_verdict(const ge& acc, const uint8_t* __restrict__ dyn_ok, uint32_t slot, uint32_t tx,
+                                             uint8_t* __restrict__ accept, uint32_t* __restrict__ out_points) {
+  accept[tx] = (ge_is_identity(acc) && (!dyn_ok || dyn_ok[tx])) ? 1 : 0;
+  if (out_points) store_ext(out_points + (uint64_t)slot * EXT_WORDS, acc);
 }
 
 // COMBINE_LANES lanes per slot, eight slots per wavefront: a slot's W x P partial sums (19 for a payment over 14-bit tables) are
@@ -1494,20 +1576,19 @@ k_static_combine(const uint32_t* __restrict__ partials, uint32_t n_partials, con
     shfl_down_ge(other, acc, delta);
     if (sub < (uint32_t)delta) ge_add(acc, acc, other);
   }
-  if (sub == 0 && mine < n) {
-    accept[tx] = (ge_is_identity(acc) && (!dyn_ok || dyn_ok[tx])) ? 1 : 0;
-    if (out_points) store_ext(out_points + (uint64_t)slot * EXT_WORDS, acc);
-  }
+  if (sub == 0 && mine < n) slot_verdict(acc, dyn_ok, slot, tx, accept, out_points);
 }
 
-// One thread's share of ONE row's fixed-base sum: the (window, term) pairs i = tid, tid + n_threads, .. of the W x ns
-// pairs of the row whose terms start at k0 -- the next table row is fetched while the current addition runs.  For the rows
-// that are summed on the tail of a batch by a single workgroup (k_locate_fused, k_recheck_fused), where a launch of its own
-// for the partial sums costs more than the sums.
+// One thread's share of ONE row's fixed-base sum: of the W x ns (window, term) pairs of the row whose terms start at k0, the
+// pairs first + c * stride + e (e < mine; c = 0, 1, ..) -- first = tid, mine = 1, stride = the threads for equal shares; a
+// thread with other work to do takes a smaller `mine` -- the next table row is fetched while the current addition runs.  The
+// sum starts from `start` (an extended point in memory) when there is one, else from its first term (ge_from_niels).  For
+// the rows that are summed on the tail of a batch by a single workgroup (k_locate_fused, k_recheck_fused), where a launch of
+// its own for the partial sums costs more than the sums.
 __device__ inline void static_row_share(ge& acc, const int16_t* __restrict__ digits, uint64_t n_static_total, uint64_t k0, uint32_t ns,
                                         const uint32_t* __restrict__ st_index, const uint32_t* __restrict__ table, uint32_t n_set,
-                                        uint32_t H, int W, uint32_t tid, uint32_t n_threads) {
-  ge_identity(acc);
+                                        uint32_t H, int W, uint32_t first, uint32_t mine, uint32_t stride,
+                                        const uint32_t* __restrict__ start = nullptr) {
   const uint32_t items = (uint32_t)W * ns;
   auto fetch = [&](uint32_t i, ge_niels& q, bool& neg) {
     const uint32_t t = i / ns, j = i - t * ns;
@@ -1520,38 +1601,52 @@ __device__ inline void static_row_share(ge& acc, const int16_t* __restrict__ dig
     if (d == 0) niels_identity(q);
     neg = d < 0;
   };
-  uint32_t i = tid;
+  uint32_t i = first, e = 0;
+  auto advance = [&]() { if (++e == mine) { e = 0; i += stride - (mine - 1); } else ++i; };      // (i only grows)
   ge_niels cur, nxt;
   bool cur_neg = false, nxt_neg = false;
   if (i < items) fetch(i, cur, cur_neg);
+  if (start) {
+    load_ext(acc, start);
+  } else if (i < items) {
+    ge_from_niels(acc, cur, cur_neg);
+    advance();
+    if (i < items) fetch(i, cur, cur_neg);
+  } else {
+    ge_identity(acc);
+  }
   while (i < items) {
-    const uint32_t in = i + n_threads;
-    if (in < items) fetch(in, nxt, nxt_neg);
+    advance();
+    if (i < items) fetch(i, nxt, nxt_neg);
     ge_madd(acc, acc, cur, cur_neg);
     cur = nxt; cur_neg = nxt_neg;
-    i = in;
   }
 }
 
 // The individual re-check of the queued transactions in ONE launch: workgroup `slot` sums the generator terms of
-// transaction row_map[slot] (256 shares), then its first wavefront adds the proof-point sum and tests for the identity --
-// k_static_accumulate (row_map) + k_static_combine in one, for the tail of a batch.
+// transaction row_map[slot] (blockDim shares; the last thread's starts from the proof-point sum), folds the shares in LDS
+// (block_fold) and tests for the identity -- k_static_accumulate (row_map) + k_static_combine in one, for the tail of a
+// batch.  (`partials` is the unfused tail's buffer: not used here.)
 __global__ void __launch_bounds__(512)
 k_recheck_fused(const int16_t* __restrict__ digits, const uint64_t* __restrict__ st_offsets, const uint32_t* __restrict__ st_index,
                 const uint32_t* __restrict__ table, uint32_t n_set, uint32_t H, int W, uint64_t n_static_total,
-                uint32_t* __restrict__ partials /*[slots][blockDim][40]*/, const uint32_t* __restrict__ dyn_sum,
+                uint32_t* __restrict__ partials, const uint32_t* __restrict__ dyn_sum,
                 const uint8_t* __restrict__ dyn_ok, const uint32_t* __restrict__ row_map, const uint32_t* __restrict__ n_active,
                 uint8_t* __restrict__ accept, uint32_t* __restrict__ out_points) {
+  __shared__ uint32_t sh_fold[EXT_WORDS * FOLD_SLOTS];
   const uint32_t slot = blockIdx.x;
   if (slot >= *n_active) return;
+  TAIL_STAMP(1, slot, 0);
   const uint32_t tx = row_map[slot];
   const uint64_t k0 = st_offsets[tx];
   ge acc;
-  static_row_share(acc, digits, n_static_total, k0, (uint32_t)(st_offsets[tx + 1] - k0), st_index, table, n_set, H, W, threadIdx.x, blockDim.x);
-  store_ext(partials + ((uint64_t)slot * blockDim.x + threadIdx.x) * EXT_WORDS, acc);
-  __threadfence_block();
-  __syncthreads();
-  if (threadIdx.x < 64) static_combine_slot(partials, blockDim.x, dyn_sum, dyn_ok, slot, tx, (int)threadIdx.x, accept, out_points);
+  static_row_share(acc, digits, n_static_total, k0, (uint32_t)(st_offsets[tx + 1] - k0), st_index, table, n_set, H, W, threadIdx.x, 1,
+                   blockDim.x, (dyn_sum && threadIdx.x == blockDim.x - 1) ? dyn_sum + (uint64_t)tx * EXT_WORDS : nullptr);
+  TAIL_STAMP(1, slot, 1);
+  block_fold(acc, sh_fold);
+  TAIL_STAMP(1, slot, 5);
+  if (threadIdx.x == 0) slot_verdict(acc, dyn_ok, slot, tx, accept, out_points);
+  TAIL_STAMP(1, slot, 7);
 }
 
 // one wave per MSM over the resident set: sum of its W*P table partials -> canonical ristretto
@@ -1783,10 +1878,11 @@ k_group_combine(const uint32_t* __restrict__ partials, uint32_t n_partials, cons
                 uint32_t* __restrict__ row_map, uint32_t* __restrict__ n_recheck, uint32_t* __restrict__ cand,
                 int16_t* __restrict__ rechk_digits /*locate == 2: [W][n_msm * n_static]*/) {
   __shared__ uint32_t sh_fail;           // 0: the group passed, else f + 1
-  __shared__ unsigned long long sh_queue;
+  __shared__ unsigned long long sh_queue, sh_live;      // sh_live bit i: member i of the group takes part (not left out)
   const uint32_t G = blockIdx.x;
   const int t = threadIdx.x, lane = t & 63;
   const uint32_t in_group = min(group, n_msm - G * group);
+  TAIL_CLOCK(clk_start);
   if (t < 64) {
     ge acc;
     ge_identity(acc);
@@ -1822,7 +1918,9 @@ k_group_combine(const uint32_t* __restrict__ partials, uint32_t n_partials, cons
       const uint32_t tx = G * group + i;
       accept[tx] = (ok && !tx_excluded(msm_fail, wellformed, tx)) ? 1 : 0;
     }
+    const unsigned long long lives = __ballot((uint32_t)lane < in_group && !tx_excluded(msm_fail, wellformed, G * group + (uint32_t)lane));
     if (lane == 0) {
+      sh_live = lives;                    // (a group has 64 members at most)
       uint32_t f1 = 0;
       if (!ok) {
         const uint32_t f = atomicAdd(n_fail, 1u);
@@ -1846,10 +1944,14 @@ k_group_combine(const uint32_t* __restrict__ partials, uint32_t n_partials, cons
       }
     }
   }
+  TAIL_CLOCK(clk_verdict);
   __syncthreads();
   const uint32_t f1 = sh_fail;
   if (f1 == 0) return;
   const uint32_t f = f1 - 1;
+  TAIL_STAMP_AT(2, f, 0, clk_start);
+  TAIL_STAMP_AT(2, f, 7, clk_verdict);
+  TAIL_STAMP(2, f, 2);
   if (!locate) { if (t == 0) cand[f] = LOCATE_NONE; return; }
   if (kSpec && locate == 2) {
     // the locating sums of ALL groups were formed beside the group sums (rows n_groups + G of the same multiplication):
@@ -1863,33 +1965,108 @@ k_group_combine(const uint32_t* __restrict__ partials, uint32_t n_partials, cons
   // group), and their digits, stored at the group's place in the failed list
   const uint32_t n_groups = (n_msm + group - 1) / group;
   const uint64_t stride = (uint64_t)n_groups * n_static;
+  // The members' scalars are loaded whether the member takes part or not (sh_live: a member left out counts as zero), eight
+  // loads in flight: with the two flag loads and the branch in front of every scalar load the sixteen members of a group
+  // were thirty-two memory latencies in a row, two thirds of this kernel's time for a failed group.  The digits are taken
+  // from the sum in registers, the zero ones with the others.
+  const unsigned long long lives = sh_live;
   for (uint32_t j = (uint32_t)t; j < n_static; j += blockDim.x) {
     scm run = scm_zero(), sum = scm_zero();
+#pragma unroll 8
     for (uint32_t i = in_group; i-- > 0;) {        // sum_k (sum_{t >= k} s_t) = sum_t (t + 1) s_t
       const uint32_t tx = G * group + i;
-      if (!tx_excluded(msm_fail, wellformed, tx)) {
-        const uint4* src = reinterpret_cast<const uint4*>(st_scalars + ((uint64_t)tx * n_static + j) * 8);
-        const uint4 a = src[0], b = src[1];
-        scm v;
-        v.v[0] = a.x; v.v[1] = a.y; v.v[2] = a.z; v.v[3] = a.w; v.v[4] = b.x; v.v[5] = b.y; v.v[6] = b.z; v.v[7] = b.w;
-        run = scm_add(run, v);
-      }
+      const uint4* src = reinterpret_cast<const uint4*>(st_scalars + ((uint64_t)tx * n_static + j) * 8);
+      const uint4 a = src[0], b = src[1];
+      const uint32_t keep = ((lives >> i) & 1) ? 0xffffffffu : 0u;
+      scm v;
+      v.v[0] = a.x & keep; v.v[1] = a.y & keep; v.v[2] = a.z & keep; v.v[3] = a.w & keep;
+      v.v[4] = b.x & keep; v.v[5] = b.y & keep; v.v[6] = b.z & keep; v.v[7] = b.w & keep;
+      run = scm_add(run, v);
       sum = scm_add(sum, run);
     }
-    uint32_t* o = loc_sc + ((uint64_t)f * n_static + j) * 8;
-    uint4* dst = reinterpret_cast<uint4*>(o);
+    uint4* dst = reinterpret_cast<uint4*>(loc_sc + ((uint64_t)f * n_static + j) * 8);
     dst[0] = make_uint4(sum.v[0], sum.v[1], sum.v[2], sum.v[3]);
     dst[1] = make_uint4(sum.v[4], sum.v[5], sum.v[6], sum.v[7]);
     const uint64_t g = (uint64_t)f * n_static + j;
-    for (int tt = 0; tt < W; ++tt) loc_digits[(uint64_t)tt * stride + g] = 0;
-    for_each_digit(o, w, W, [&](int tt, int d) { loc_digits[(uint64_t)tt * stride + g] = (int16_t)d; });
+    __attribute__((aligned(16))) uint32_t sv[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) sv[q] = sum.v[q];
+    for_each_digit<true>(sv, w, W, [&](int tt, int d) { loc_digits[(uint64_t)tt * stride + g] = (int16_t)d; });
+  }
+  TAIL_STAMP(2, f, 8);
+}
+
+// Naming the culprit of failed group f (= group G), one wavefront: S2 (the locating sum, in every lane) against the candidates
+// (lane k: M = (k + 1) S1).  The position that fits is the one bad transaction, which alone is queued for the individual check
+// (cand[f] = its slot in row_map); no such position: every transaction of the group is queued (cand[f] = LOCATE_NONE).
+// *sh_queue: bit i set for transaction i of the group queued.  Shared by the fused and the unfused tail.
+__device__ inline void locate_name(const ge& S2, const ge& M, bool live, uint32_t tx, int lane, uint32_t group, uint32_t G, uint32_t f,
+                                   uint32_t* __restrict__ row_map, uint32_t* __restrict__ n_recheck, uint32_t* __restrict__ cand,
+                                   unsigned long long* sh_queue) {
+  const bool match = live && ge_ristretto_eq(M, S2);
+  const unsigned long long hits = __ballot(match);
+  const unsigned long long lives = __ballot(live);
+  if (hits) {
+    const int b = __ffsll((long long)hits) - 1;
+    if (lane == 0) {
+      const uint32_t slot = atomicAdd(n_recheck, 1u);
+      row_map[slot] = G * group + (uint32_t)b;
+      cand[f] = slot;
+      *sh_queue = 1ull << b;
+    }
+  } else {
+    uint32_t base = 0;
+    if (lane == 0) { base = atomicAdd(n_recheck, (uint32_t)__popcll(lives)); cand[f] = LOCATE_NONE; *sh_queue = lives; }
+    base = __shfl(base, 0);
+    if (live) row_map[base + (uint32_t)__popcll(lives & ((1ull << lane) - 1))] = tx;
   }
 }
 
-// Failed group f (= group G): S2 = generator partials of the locating sum (`partials2`: its n_partials rows) + sum_t i_t dyn_t;
-// the position i with i S1 = S2 names the one bad transaction, which alone is queued for the individual check (cand[f] = its
-// slot in row_map); no such i: every transaction of the group is queued (cand[f] = LOCATE_NONE).  Called by all 256 threads of
-// a workgroup: wavefront 0 locates, then everybody writes the digits of the queued transactions' generator scalars.
+// ... then every thread of the workgroup writes digits of the queued transactions' generator scalars ([W][n_msm * n_static], as
+// k_static_digits writes them): a thread per scalar, all W digits of it, the zero ones too
+__device__ inline void queued_digits(unsigned long long queue, uint32_t G, uint32_t group, uint32_t n_msm,
+                                     const uint32_t* __restrict__ st_scalars, uint32_t n_static, int16_t* __restrict__ digits, int w, int W) {
+  for (uint32_t i = 0; i < group && i < 64; ++i) {
+    if (!((queue >> i) & 1)) continue;
+    const uint32_t ti = G * group + i;
+    for (uint32_t j = threadIdx.x; j < n_static; j += blockDim.x) {
+      const uint64_t g = (uint64_t)ti * n_static + j;
+      for_each_digit<true>(st_scalars + 8 * g, w, W, [&](int tt, int dd) { digits[(uint64_t)tt * n_msm * n_static + g] = (int16_t)dd; });
+    }
+  }
+}
+
+// group (1 .. 64) rounded up to a power of two: the lanes the scans of a group run over
+__device__ __forceinline__ int locate_span(uint32_t group) { return 1 << (31 - __clz((int)(2 * group - 1))); }
+
+// S2 = the locating sum's generator terms + sum_k k d_k (k = lane + 1, d_k the proof-point sum of transaction k of the group),
+// and the candidates M_k = k S1.  Neither needs a multiplication: sum_k k d_k = sum_j (sum_{k >= j} d_k) is the sum of the SUFFIX
+// sums, and k S1 is the PREFIX sum of S1 over the lanes -- log2(group) shuffled additions each, where round 3 ran a
+// five-step double-and-add on two chains per lane (seven points live at once: 1084 bytes of scratch).
+// One wavefront: the suffix sums of the members' proof-point sums (lanes >= span: the identity)
+__device__ inline void locate_suffix_sums(ge& suf, const uint32_t* __restrict__ dyn_sum, bool live, uint32_t tx, int lane, int span) {
+  ge_identity(suf);
+  if (live) load_ext(suf, dyn_sum + (uint64_t)tx * EXT_WORDS);
+#pragma unroll 1
+  for (int delta = 1; delta < span; delta <<= 1) {
+    ge other;
+    shfl_down_ge(other, suf, delta);           // (lanes >= group hold the identity)
+    if (lane + delta < span) ge_add(suf, suf, other);
+  }
+}
+// ... and the candidates: S1 in every lane -> (lane + 1) S1 by an inclusive scan
+__device__ inline void locate_candidates(ge& M, const uint32_t* __restrict__ S1, int lane, int span) {
+  load_ext(M, S1);
+#pragma unroll 1
+  for (int delta = 1; delta < span; delta <<= 1) {
+    ge other;
+    shfl_up_ge(other, M, delta);
+    if (lane >= delta) ge_add(M, M, other);
+  }
+}
+
+// Failed group f (= group G), the unfused form: S2 from the generator partials of the locating sum (`partials2`: its n_partials
+// rows).  Called by all 256 threads of a workgroup: wavefront 0 locates, then everybody writes the digits of the queued.
 __device__ inline void locate_group(const uint32_t* __restrict__ partials2, uint32_t n_partials, const uint32_t* __restrict__ dyn_sum,
                                     const uint32_t* __restrict__ msm_fail, const uint32_t* __restrict__ wellformed, uint32_t n_msm,
                                     uint32_t group, uint32_t G, uint32_t f, const uint32_t* __restrict__ fail_sum,
@@ -1907,69 +2084,21 @@ __device__ inline void locate_group(const uint32_t* __restrict__ partials2, uint
     }
     const uint32_t tx = G * group + (uint32_t)lane;
     const bool live = (uint32_t)lane < group && tx < n_msm && !tx_excluded(msm_fail, wellformed, tx);
-    // S2 = sum_lanes share + sum_k k d_k (k = lane + 1, d_k the proof-point sum of transaction k of the group), and the
-    // candidates M_k = k S1.  Neither needs a multiplication: sum_k k d_k = sum_j (sum_{k >= j} d_k) is the sum of the SUFFIX
-    // sums, and k S1 is the PREFIX sum of S1 over the lanes -- log2(group) shuffled additions each, where round 3 ran a
-    // five-step double-and-add on two chains per lane (seven points live at once: 1084 bytes of scratch in this function;
-    // the kernel sits on the tail of every batch that has a failed group).
-    const int span = 1 << (31 - __clz((int)(2 * group - 1)));      // group (1 .. 64) rounded up to a power of two
+    const int span = locate_span(group);
     {
       ge suf;
-      ge_identity(suf);
-      if (live) load_ext(suf, dyn_sum + (uint64_t)tx * EXT_WORDS);
-#pragma unroll 1
-      for (int delta = 1; delta < span; delta <<= 1) {
-        ge other;
-        shfl_down_ge(other, suf, delta);           // (lanes >= group hold the identity)
-        if (lane + delta < span) ge_add(suf, suf, other);
-      }
+      locate_suffix_sums(suf, dyn_sum, live, tx, lane, span);
       if (lane < span) ge_add(acc, acc, suf);
     }
-#pragma unroll 1
-    for (int delta = 32; delta >= 1; delta >>= 1) {
-      ge other;
-      shfl_down_ge(other, acc, delta);
-      if (lane < delta) ge_add(acc, acc, other);
-    }
+    wave_fold(acc, lane);
     ge M;
-    load_ext(M, fail_sum + (uint64_t)f * EXT_WORDS);  // S1 in every lane -> (lane + 1) S1 by an inclusive scan
-#pragma unroll 1
-    for (int delta = 1; delta < span; delta <<= 1) {
-      ge other;
-      shfl_up_ge(other, M, delta);
-      if (lane >= delta) ge_add(M, M, other);
-    }
+    locate_candidates(M, fail_sum + (uint64_t)f * EXT_WORDS, lane, span);
     ge S2;
     shfl_ge(S2, acc, 0);
-    const bool match = live && ge_ristretto_eq(M, S2);
-    const unsigned long long hits = __ballot(match);
-    const unsigned long long lives = __ballot(live);
-    if (hits) {
-      const int b = __ffsll((long long)hits) - 1;
-      if (lane == 0) {
-        const uint32_t slot = atomicAdd(n_recheck, 1u);
-        row_map[slot] = G * group + (uint32_t)b;
-        cand[f] = slot;
-        *sh_queue = 1ull << b;
-      }
-    } else {
-      uint32_t base = 0;
-      if (lane == 0) { base = atomicAdd(n_recheck, (uint32_t)__popcll(lives)); cand[f] = LOCATE_NONE; *sh_queue = lives; }
-      base = __shfl(base, 0);
-      if (live) row_map[base + (uint32_t)__popcll(lives & ((1ull << lane) - 1))] = tx;
-    }
+    locate_name(S2, M, live, tx, lane, group, G, f, row_map, n_recheck, cand, sh_queue);
   }
   __syncthreads();
-  const unsigned long long queue = *sh_queue;
-  for (uint32_t i = 0; i < group && i < 64; ++i) {
-    if (!((queue >> i) & 1)) continue;
-    const uint32_t ti = G * group + i;
-    for (uint32_t j = (uint32_t)t; j < n_static; j += blockDim.x) {
-      const uint64_t g = (uint64_t)ti * n_static + j;
-      for (int tt = 0; tt < W; ++tt) digits[(uint64_t)tt * n_msm * n_static + g] = 0;
-      for_each_digit(st_scalars + 8 * g, w, W, [&](int tt, int dd) { digits[(uint64_t)tt * n_msm * n_static + g] = (int16_t)dd; });
-    }
-  }
+  queued_digits(*sh_queue, G, group, n_msm, st_scalars, n_static, digits, w, W);
 }
 
 // one workgroup per failed group f, after the locating multiscalar multiplication (rows indexed by f)
@@ -1987,29 +2116,80 @@ k_locate_combine(const uint32_t* __restrict__ partials, uint32_t n_partials, con
                fail_sum, row_map, n_recheck, cand, st_scalars, n_static, digits, w, W, &sh_queue);
 }
 
-// The locating multiplication and k_locate_combine in ONE launch: workgroup f sums the locating scalars' generator terms
-// itself (256 shares, digits at the group's place f in the failed list) and goes on to name the culprit.
+// The locating multiplication and k_locate_combine in ONE launch: workgroup f (LOCATE_THREADS = 512 threads) sums the locating
+// scalars' generator terms itself (digits at the group's place f in the failed list), folds the shares in LDS (block_fold) and
+// goes on to name the culprit.  What does not depend on the shares runs beside them: the last wavefront forms the suffix sums
+// of the members' proof-point sums first and adds them to its shares before the fold, the last but one forms the candidates
+// k S1 and leaves them in LDS; both take a smaller part of the row (LOCATE_SHARE_SCAN pairs where the others take
+// LOCATE_SHARE_WORK: they sit on different SIMDs, each beside a wavefront with a full part, and the scans of a group of 16
+// cost about what the difference does).  Behind the shares: nine additions of the fold and the comparison.
+#ifndef ZK_LOCATE_SHARE_WORK
+#define ZK_LOCATE_SHARE_WORK 3
+#endif
+#ifndef ZK_LOCATE_SHARE_SCAN
+#define ZK_LOCATE_SHARE_SCAN 2
+#endif
+constexpr uint32_t LOCATE_SHARE_WORK = ZK_LOCATE_SHARE_WORK, LOCATE_SHARE_SCAN = ZK_LOCATE_SHARE_SCAN;
+
 __global__ void __launch_bounds__(512)
 k_locate_fused(const int16_t* __restrict__ loc_digits, const uint64_t* __restrict__ st_offsets, const uint32_t* __restrict__ st_index,
                const uint32_t* __restrict__ table, uint32_t n_set, uint32_t H, uint32_t n_groups,
-               uint32_t* __restrict__ partials /*[n_groups][blockDim][40]*/, const uint32_t* __restrict__ dyn_sum,
+               uint32_t* __restrict__ partials /*the unfused tail's buffer: not used here*/, const uint32_t* __restrict__ dyn_sum,
                const uint32_t* __restrict__ msm_fail, const uint32_t* __restrict__ wellformed, uint32_t n_msm,
                uint32_t group, const uint32_t* __restrict__ fail_list, const uint32_t* __restrict__ n_fail,
                const uint32_t* __restrict__ fail_sum, uint32_t* __restrict__ row_map, uint32_t* __restrict__ n_recheck,
                uint32_t* __restrict__ cand, const uint32_t* __restrict__ st_scalars, uint32_t n_static,
                int16_t* __restrict__ digits, int w, int W) {
   __shared__ unsigned long long sh_queue;
+  __shared__ uint32_t sh_fold[EXT_WORDS * FOLD_SLOTS];
+  __shared__ uint32_t sh_suf[EXT_WORDS * 64], sh_cand[EXT_WORDS * 64];
   const uint32_t f = blockIdx.x;
   if (f >= *n_fail) return;
-  {
-    ge acc;
-    static_row_share(acc, loc_digits, (uint64_t)n_groups * n_static, st_offsets[f], n_static, st_index, table, n_set, H, W, threadIdx.x, blockDim.x);
-    store_ext(partials + ((uint64_t)f * blockDim.x + threadIdx.x) * EXT_WORDS, acc);
+  TAIL_STAMP(0, f, 0);
+  const uint32_t G = fail_list[f];
+  const uint32_t t = threadIdx.x, n_scan = 128, n_work = blockDim.x - n_scan;
+  const int lane = (int)(t & 63);
+  const bool suffix_wave = t >= blockDim.x - 64, prefix_wave = !suffix_wave && t >= n_work;
+  const uint32_t tx = G * group + (uint32_t)lane;
+  const bool live = (uint32_t)lane < group && tx < n_msm && !tx_excluded(msm_fail, wellformed, tx);
+  const int span = locate_span(group);
+  if (suffix_wave) {
+    ge suf;
+    locate_suffix_sums(suf, dyn_sum, live, tx, lane, span);
+    lds_park(sh_suf, 64, (uint32_t)lane, suf);
+    TAIL_STAMP(0, f, 4);
   }
-  __threadfence_block();
+  if (prefix_wave) {
+    ge M;
+    locate_candidates(M, fail_sum + (uint64_t)f * EXT_WORDS, lane, span);
+    lds_park(sh_cand, 64, (uint32_t)lane, M);
+    TAIL_STAMP(0, f, 6);
+  }
+  ge acc;
+  {
+    const bool scans = t >= n_work;
+    const uint32_t first = scans ? n_work * LOCATE_SHARE_WORK + (t - n_work) * LOCATE_SHARE_SCAN : t * LOCATE_SHARE_WORK;
+    static_row_share(acc, loc_digits, (uint64_t)n_groups * n_static, st_offsets[f], n_static, st_index, table, n_set, H, W, first,
+                     scans ? LOCATE_SHARE_SCAN : LOCATE_SHARE_WORK, n_work * LOCATE_SHARE_WORK + n_scan * LOCATE_SHARE_SCAN);
+  }
+  TAIL_STAMP(0, f, 1);
+  if (suffix_wave && lane < span) {          // + sum_k k d_k: the sum of the suffix sums joins the fold
+    ge suf;
+    lds_take(suf, sh_suf, 64, (uint32_t)lane);
+    ge_add(acc, acc, suf);
+  }
+  block_fold(acc, sh_fold);
+  TAIL_STAMP(0, f, 5);
+  if (t < 64) {
+    ge S2, M;
+    shfl_ge(S2, acc, 0);
+    lds_take(M, sh_cand, 64, (uint32_t)lane);
+    locate_name(S2, M, live, tx, lane, group, G, f, row_map, n_recheck, cand, &sh_queue);
+    TAIL_STAMP(0, f, 7);
+  }
   __syncthreads();
-  locate_group(partials + (uint64_t)f * blockDim.x * EXT_WORDS, blockDim.x, dyn_sum, msm_fail, wellformed, n_msm, group, fail_list[f], f,
-               fail_sum, row_map, n_recheck, cand, st_scalars, n_static, digits, w, W, &sh_queue);
+  queued_digits(sh_queue, G, group, n_msm, st_scalars, n_static, digits, w, W);
+  TAIL_STAMP(0, f, 8);
 }
 
 // Final verdicts of a batch checked in groups, packed into the bitmap (byte i / 8, bit i % 8):

@@ -1090,10 +1090,11 @@ k_points_tables(PrepShape sh, const uint32_t* __restrict__ com, const uint32_t* 
     atomicOr(&msm_fail[tx], 1u);
   }
   ge cur;
-  ge_identity(cur);
+  ge_from_niels(cur, nq, false);      // P itself: loaded, not added to the identity
   uint32_t* row = tbl + g * (SMALL_TBL * EXT_WORDS);
+  store_cached(row, cur);
 #pragma unroll 1
-  for (int e = 0; e < SMALL_TBL; ++e) {
+  for (int e = 1; e < SMALL_TBL; ++e) {
     ge_madd(cur, cur, nq, false);
     store_cached(row + e * EXT_WORDS, cur);
   }

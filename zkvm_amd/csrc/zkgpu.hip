@@ -1726,7 +1726,7 @@ static long long debug_read_buffers(zkgpu_ctx* c, const char* what, void* out, s
   if (!c || !what || !out) return ZKGPU_EINVAL;
   std::lock_guard<std::recursive_mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  const std::string w(what);
+  const std::string w(what); if (w == "tail_stamps") return zk::tail_stamps_read(out, bytes);      // (-DZK_TAIL_STAMPS builds: kernels.hpp)
 #ifdef ZK_PREP_STAMPS
   if (w == "prep_stamps") {
     const size_t n = std::min(bytes, sizeof(unsigned long long) * 256 * 2 * zk::PREP_STAMP_SLOTS);
